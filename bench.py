@@ -17,6 +17,14 @@ HBM when the timed region starts.
 (python -m torch.distributed.run, one per GPU) BEFORE anything in this process touches the GPU,
 and exits with their status.
 
+A plain run sets up, warms up, times `--steps` steps and prints the result line.  `--dump-outputs DIR`
+then writes what the last timed step handed back (DIR/<name>.npy, float64): the chains' parameters
+`theta` [chains, P], their score estimates `grad` [chains, h] and log-likelihood estimates `loglik`
+[chains] (g1: `grad` / `loglik` of every window).  Inputs are seeded: the same arguments give the same
+inputs on every run.  `--full` adds the legs that need runs of their own: one chain alone, the
+replay-arithmetic kernel, the parity checks against the reference fixtures, the CPU baseline and
+(g1) the per-timestep kernel times with their roofline.
+
 The JSON line also carries
   roofline      the binding resource of the dominant kernel.  The LDS-resident kernels stream no
                 particle state through HBM, so the bound is VALU issue: achieved = (per-class VALU
@@ -26,8 +34,8 @@ The JSON line also carries
                 timed launches).  The SURVEY 8(d) HBM model (2*(n+1+h)*8 B per particle-timestep)
                 is kept as `hbm_model`, explicitly non-binding.  The large-N kernel (c5) does stream
                 its state: there bound = "hbm" and the algorithmic bytes are real traffic.
-  cpu_baseline  the CPU oracle (NumPy restatement of the reference, bit-identical to it) timed
-                on this box's host, 1 core, on a bounded sample of the same workload
+  cpu_baseline  (--full) the CPU oracle (NumPy restatement of the reference, bit-identical to it)
+                timed on this box's host, 1 core, on a bounded sample of the same workload
 """
 import argparse
 import json
@@ -162,31 +170,21 @@ def run_giant(args, rank, world, dev_index, n_distinct):
     if not (np.all(np.isfinite(g)) and np.all(np.isfinite(ll))):
         raise SystemExit("non-finite gradients after the run")
     elapsed, _ = rank_epilogue(torch.from_numpy(g).to(dev), elapsed, device=dev)
-    # the dominant kernel's launch duration: HIP events around every timestep launch of a few more repetitions
-    kern = []
-    for _ in range(min(args.steps, 5)):
-        ev = rw.launch_timed()
-        torch.cuda.synchronize(dev)
-        kern += [a.elapsed_time(b) for a, b in ev]
-    kern_ms = float(np.mean(kern))
+    if args.dump_outputs:
+        out = gather_rows(np.concatenate([g, ll[:, None]], axis=1), dev)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, grad=out[:, :-1], loglik=out[:, -1])
+    variant = rw.ctx.last_variant()
+    if args.full:
+        # the dominant kernel's launch duration: HIP events around every timestep launch of a few more repetitions
+        kern = []
+        for _ in range(min(args.steps, 5)):
+            ev = rw.launch_timed()
+            torch.cuda.synchronize(dev)
+            kern += [a.elapsed_time(b) for a, b in ev]
+        kern_ms = float(np.mean(kern))
     if rank != 0:
         return
-    n, h = STATE_STAT[model]
-    wsize = 8 if args.dtype == "f64" else 4
-    alg_bytes = float(reps) * N * 2 * (n + 1 + h) * wsize           # per timestep launch
-    alg_gbs = alg_bytes / (kern_ms * 1e-3) / 1e9
-    variant = rw.ctx.last_variant()
-    key = "{0}_{1}_{2}".format(args.config, args.dtype, variant)
-    trec = (_load_json("hbm_traffic.json") or {}).get(key)
-    traffic = trec["bytes_per_launch"] * (float(reps) / trec["chains"]) if trec else None
-    roof = {"bound": "hbm", "achieved": alg_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg_gbs / HBM_PEAK_GBS,
-            "traffic": traffic, "kernel_ms": kern_ms, "kernel": "pfg_grid_step_dev_kernel (one launch = one timestep of all {0} windows)".format(reps),
-            "whole_window_ms": elapsed / args.steps * 1e3, "launches_per_step": T + 2,
-            "frac_whole_window": float(reps) * N * T * 2 * (n + 1 + h) * wsize / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
-            "note": "whole-GPU windows: particle state streams through HBM every timestep (scan + record read, record + scan "
-                    "write = the algorithmic 2 (n + 1 + h) w bytes per particle-step); kernel_ms = HIP events around the "
-                    "timestep launches, frac_whole_window = the same bytes over the wall time of the 50-launch sequence",
-            "stale": profile_is_stale()}
     line = {"metric": "ground-truth gradient estimates/sec (SVM 48-step buffered window, N=1000000 particles)",
             "value": float(reps) * world * args.steps / elapsed, "unit": "windows/s", "n_gpus": n_distinct, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -195,11 +193,27 @@ def run_giant(args, rank, world, dev_index, n_distinct):
                        "window_T": T, "rng": "device", "kernel_variant": variant, "rng_precision": RNG_PRECISION +
                        "; whole-GPU windows resample with sorted uniforms (exponential spacings)",
                        "parallelism": "independent windows, {0} rank(s) x {1} windows".format(world, reps)},
-            "particle_steps_per_s": float(reps) * world * args.steps * N * T / elapsed,
-            "us_per_pf_timestep": kern_ms * 1e3, "roofline": roof}
-    if world == 1 and not args.no_single_chain:
+            "particle_steps_per_s": float(reps) * world * args.steps * N * T / elapsed}
+    if args.full:
+        n, h = STATE_STAT[model]
+        wsize = 8 if args.dtype == "f64" else 4
+        alg_bytes = float(reps) * N * 2 * (n + 1 + h) * wsize           # per timestep launch
+        alg_gbs = alg_bytes / (kern_ms * 1e-3) / 1e9
+        key = "{0}_{1}_{2}".format(args.config, args.dtype, variant)
+        trec = (_load_json("hbm_traffic.json") or {}).get(key)
+        traffic = trec["bytes_per_launch"] * (float(reps) / trec["chains"]) if trec else None
+        line["us_per_pf_timestep"] = kern_ms * 1e3
+        line["roofline"] = {"bound": "hbm", "achieved": alg_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg_gbs / HBM_PEAK_GBS,
+                            "traffic": traffic, "kernel_ms": kern_ms, "kernel": "pfg_grid_step_dev_kernel (one launch = one timestep of all {0} windows)".format(reps),
+                            "whole_window_ms": elapsed / args.steps * 1e3, "launches_per_step": T + 2,
+                            "frac_whole_window": float(reps) * N * T * 2 * (n + 1 + h) * wsize / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
+                            "note": "whole-GPU windows: particle state streams through HBM every timestep (scan + record read, record + scan "
+                                    "write = the algorithmic 2 (n + 1 + h) w bytes per particle-step); kernel_ms = HIP events around the "
+                                    "timestep launches, frac_whole_window = the same bytes over the wall time of the 50-launch sequence",
+                            "stale": profile_is_stale()}
+    if args.full and world == 1 and not args.no_single_chain:
         line["parity"] = giant_grad_error_vs_reference(dev_index)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import pf_oracle as po
         Ts = 24
         t_c = time.perf_counter()
@@ -515,6 +529,31 @@ def rank_epilogue(local_theta, elapsed, device=None):
     return elapsed, samples
 
 
+def gather_rows(local, device):
+    """[C, X] float64 rows of every rank -> [world*C, X] ndarray in global chain order (a collective: every rank calls it)."""
+    import torch
+    from sgmcmc_ssm_amd import distributed
+    t = torch.as_tensor(np.ascontiguousarray(local, dtype=np.float64), device=device)
+    return distributed.gather_samples(t).cpu().numpy()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, **arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in float64.  All arrays share their leading (chain / window)
+    axis; if together they exceed 64 MB, the same fixed, seeded sample of rows is kept from each."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    keep = None
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.RandomState(0).choice(rows, size=int(rows * DUMP_LIMIT_BYTES // total), replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a if keep is None else a[keep])
+
+
 def cpu_rehearsal(args):
     """No GPU: the rank logic alone under gloo (spawn, chain ranges, barrier, max-over-ranks,
     gather in global chain order) with ChainEnsemble-shaped [C, P] tensors."""
@@ -560,6 +599,11 @@ def main():
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow more ranks than GPUs (ranks fold onto devices; the line is labelled, n_gpus = distinct devices)")
     ap.add_argument("--cpu-rehearsal", action="store_true", help="no GPU: exercise the multi-rank logic under gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: one chain alone, replay arithmetic, parity, CPU "
+                         "baseline, g1's per-timestep kernel times and roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's theta / grad / loglik as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.model is not None:
         args.config = {"svm": "c2", "garch": "c3"}[args.model]
@@ -649,6 +693,11 @@ def main():
     if not np.all(np.isfinite(theta)) and not os.environ.get("PFG_BENCH_KNOCKOUT"):
         # (PFG_BENCH_KNOCKOUT: timing / counter runs of knock-out builds that are no valid samplers, tools/lds_split.sh)
         raise SystemExit("non-finite parameters after the run")
+    if args.dump_outputs:
+        grad, loglik = ens.last_gradient_statistics()
+        out = gather_rows(np.concatenate([grad, loglik[:, None]], axis=1), dev)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, theta=theta, grad=out[:, :-1], loglik=out[:, -1])
 
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     variant = ens.ctx.last_variant()                      # the PF kernel the timed launches ran
@@ -656,7 +705,7 @@ def main():
 
     # latency of ONE chain alone on the GPU (the reference's unit: one chain, one step at a time)
     single = None
-    if rank == 0 and not args.no_single_chain:
+    if rank == 0 and args.full and not args.no_single_chain:
         one = make_ensemble(1, 7, 10 ** 6)
         one.step(2)
         torch.cuda.synchronize(dev)
@@ -747,11 +796,11 @@ def main():
         }
         if world != n_distinct:
             line["rehearsal"] = "{0} ranks folded onto {1} GPU(s): NOT a multi-GPU measurement".format(world, n_distinct)
-        if world == 1 and not args.no_single_chain:
+        if args.full and world == 1 and not args.no_single_chain:
             if args.config == "c2":
                 line["parity"] = grad_error_vs_reference()
             line["replay_arithmetic"] = replay_arithmetic_leg(w, dev_index)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(w, budget_s=args.cpu_budget)
             line["speedup_vs_cpu_1core"] = line["value"] / line["cpu_baseline"]["value"]
             if single:

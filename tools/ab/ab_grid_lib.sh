@@ -9,7 +9,7 @@ for l in sys.stdin:
     try: r=json.loads(l)
     except Exception: continue
     if r['model']=='svm': print(r['N'], r['B'], '%.2f us/step frac %.3f'%(r['us_per_step'], r['frac_of_8TBps']), r['grad'][:2])"
-  PFGRAD_LIB=$L/$lib timeout -k 10 100 python bench.py --config g1 --no-cpu-baseline 2>/dev/null | python -c "
+  PFGRAD_LIB=$L/$lib timeout -k 10 100 python bench.py --config g1 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('g1', r['value'], r['roofline']['frac'], r['config']['kernel_variant'])"
 done

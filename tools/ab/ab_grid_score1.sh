@@ -2,7 +2,7 @@
 cd /root/repo
 for rep in 1 2; do
 for off in 0 1; do
-  PFGRAD_NO_SCORE1=$off timeout -k 10 120 python bench.py --config g1 --no-cpu-baseline 2>/dev/null | python -c "
+  PFGRAD_NO_SCORE1=$off timeout -k 10 120 python bench.py --config g1 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('g1 no_score1=$off rep$rep', r['value'], r['roofline']['frac'], r['config']['kernel_variant'])"
   PFGRAD_NO_SCORE1=$off GRID_TIME_REPLAY=0 timeout -k 10 200 python tools/grid_time.py 100000 400000 1000000 2>/dev/null | python -c "

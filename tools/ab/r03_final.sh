@@ -8,9 +8,9 @@ tools/calib/valu_calib 100000 > $OUT/valu_calibration.txt 2>&1
 CS=/root/repo/stochastic-gradient-mcmc-for-non-linear-state-models---mth422_amd/csrc
 PFGRAD_LIB=$CS/libpfgrad_stamps.so python tools/phase_profile.py svm 12288 2>&1 | grep -v amdgpu.ids > $OUT/phase_stamps_svm.txt
 PFGRAD_LIB=$CS/libpfgrad_stamps.so python tools/phase_profile.py svm 256 2>&1 | grep -v amdgpu.ids > $OUT/phase_stamps_svm_lone_workgroup.txt
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 for c in c1 c3 c4 c5; do
-  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --cpu-budget 5 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || echo "bench $c failed"
+  timeout -k 10 300 python bench.py --config $c --full --steps 20 --warmup 3 --cpu-budget 5 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || echo "bench $c failed"
 done
 python tools/config_perf.py dropin 2>&1 | grep -v amdgpu.ids > $OUT/dropin.txt
 python tools/pcie_rate.py 2>&1 | grep -v amdgpu.ids > $OUT/pcie_inclusive.txt

@@ -6,10 +6,10 @@ cd /root/repo
 OUT=gpurun_out/r04_final
 rm -rf $OUT; mkdir -p $OUT
 CS=/root/repo/stochastic-gradient-mcmc-for-non-linear-state-models---mth422_amd/csrc
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "default done"
 for c in c1 c3 c4 c5 g1; do
-  timeout -k 10 300 python bench.py --config $c --cpu-budget 5 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || echo "bench $c failed"
+  timeout -k 10 300 python bench.py --config $c --full --cpu-budget 5 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || echo "bench $c failed"
   echo "$c done"
 done
 for m in dropin dropin_fit dropin_large; do
