@@ -1,7 +1,7 @@
 // Host-side declarations shared by the translation units of libpfgrad.so: the context, error
-// plumbing, the kernel-variant table and the per-(model, kernel) launch entry the instantiation
-// units (pfg_inst_*.hip) define.  Splitting the ~250 kernel instantiations over five units lets
-// the build compile them in parallel.
+// plumbing, the launch plan and the per-(model, proposal kernel, generator) launch entry the ten
+// instantiation units (pfg_inst_*.hip) define.  Splitting the kernel instantiations over those
+// units lets the build compile them in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -64,7 +64,6 @@ struct pfg_ctx {
     std::vector<pfg_dev_problem> h_desc;
     const char *last_variant = "none";   // tag of the kernel variant the latest dispatch launched
     bool last_traced = false;            // ... and whether that was a trace-honouring instantiation
-    bool score1 = false;                 // the dispatch in flight is a PFG_SMOOTHER_POYIADJIS_N launch (see launch_one)
     // largest dynamic-LDS size hipFuncAttributeMaxDynamicSharedMemorySize has been set to, per kernel: the
     // attribute is per (function, device) and a context is bound to one device
     std::unordered_map<const void *, size_t> lds_set;
@@ -86,19 +85,59 @@ inline int fail(pfg_ctx *ctx, int code, const std::string &msg) {
     } while (0)
 
 constexpr size_t kLdsLimit = 160 * 1024;
-// variant ids below zero: kernels other than the LDS-resident table entries
-constexpr int kVariantMem = -2;     // large-N kernel (state in an HBM scratch)
-constexpr int kVariantParis = -3, kVariantSystematic = -4, kVariantN2 = -5, kVariantBig = -6;
-constexpr int kVariantMemLw4 = -8;  // large-N kernel, N <= 4096, no predictive statistic: log-weights in registers
-constexpr int kVariantGrid = -7;    // whole-GPU window for N above the one-workgroup kernels' maximum (pfg_grid_kernel.hpp)
 
-// Launch of every kernel of one (model, proposal kernel, generator): defined (and explicitly
-// instantiated) in pfg_inst_*.hip via pfg_launch.hpp, declared here for the dispatcher in pfgrad.hip.
-template <int MODEL, int KERNEL, int RNG>
-int launch_mkr(pfg_ctx *ctx, int dtype, int v, int n_max, int B, const pfg_dev_problem *dp, hipStream_t st, bool traced);
+// What runs a batch: filled by make_plan (pfgrad.hip), the one place where a kernel is chosen; launch_mkr only maps it
+// onto an instantiation.
+enum class Family {
+    None,
+    Reg,           // LDS-resident kernel, entry (nt, ppt, pp)
+    Paris, N2,     // its PaRIS / O(N^2) Poyiadjis instantiations, 256 x ppt; nt = MEM_NT: the large-N kernel's PaRIS one
+    Systematic,    // its systematic-resampling instantiation (device generator), 256 x 4
+    Mem,           // large-N kernel (state in an HBM scratch); lw4: N <= 4096, log-weights in registers
+    Big,           // large-N kernel, device-generator fast path for np2 particle slots
+    Grid,          // whole-GPU window above the one-workgroup kernels' maximum (pfg_grid_kernel.hpp), tile class (ppt, kmax)
+};
 
-// the whole-GPU window of one (model, kernel, generator): T_max + 2 (REPLAY: 5 T_max + 2) launches, see pfg_launch.hpp
+struct LaunchPlan {
+    Family family = Family::None;
+    bool f64 = true;
+    int n_max = 0;
+    int nt = 0, ppt = 0;
+    bool pp = true;
+    bool traced = true;          // the TRACE instantiation (pfg_last_traced)
+    bool score1 = false;         // the score-only twin (PFG_SMOOTHER_POYIADJIS_N, see SCORE1 in pfg_reg_kernel.hpp)
+    bool lw4 = false;
+    int np2 = 0;                 // Big
+    int kmax = 0, tiles = 0, t_max = 0, phase = -1;   // Grid
+    bool cdf_single = false;     // Grid, REPLAY: the lone-workgroup CDF kernel
+    size_t lds = 0;              // dynamic LDS of the kernel (Grid: of its timestep kernel)
+    size_t scratch = 0;          // per-window HBM scratch, bytes (0: none)
+    const char *name = nullptr;  // pfg_last_variant once the kernel is chosen
+    int rc = PFG_OK;             // an error found once the kernel is chosen (name set) or before (name NULL)
+    std::string err;
+};
+
+// The LDS-resident (nt, ppt, pp) entries built for a unit, and those with a score-only twin.  (Twins measured per unit,
+// whole library built with -DPFG_EXP_PLAIN=1 -- device generator: 1024 x 4 -4.7 %, one wave x 2 -2.8 %, 256 x 4 -0.6 %,
+// 512 x 2 +2.1 %, large-N kernel 0; REPLAY arithmetic legs: SVM 256 x 4 -5.8 %, LGSSM one wave -6.5 %, GARCH 256 x 4
+// +8 %: profiles/r04_ab_score1_twin.txt; the 1024 x 1 latency variant, one window alone, SVM T = N = 1000: device
+// 1.957 -> 1.814 ms, REPLAY 2.768 -> 2.623.)
+constexpr bool reg_entry_built(int model, int rng, bool f64, int nt, int ppt, bool pp) {
+    if ((nt == 256 && (ppt == 1 ? pp : ppt == 4)) || (pp && ((nt == 1024 && ppt == 1) || (nt == 64 && ppt == 2)))) return true;
+    if (rng != PFG_RNG_DEVICE) return false;
+    if (nt == 512) return ppt == 2 && !pp && model == PFG_MODEL_GARCH && f64;
+    return (nt == 1024 && ppt == 4 && !pp) || (nt == 64 && (ppt == 4 || ppt == 2));
+}
+constexpr bool reg_score1_twin(int model, int rng, bool f64, int nt, int ppt, bool pp) {
+    const bool lat = model != PFG_MODEL_GARCH && nt == 1024 && ppt == 1 && pp;
+    const bool dev = rng == PFG_RNG_DEVICE && !pp && ((nt == 1024 && ppt == 4) || (nt == 64 && ppt == 2));
+    const bool rep = rng == PFG_RNG_REPLAY && model != PFG_MODEL_GARCH && ((nt == 256 && ppt == 4) || (nt == 64 && ppt == 2));
+    return f64 && (lat || dev || rep);
+}
+
+// Launch of the planned kernel of one (model, proposal kernel, generator): defined (and explicitly instantiated) in
+// pfg_inst_*.hip via pfg_launch.hpp, declared here for the dispatcher in pfgrad.hip.
 template <int MODEL, int KERNEL, int RNG>
-int launch_grid_mkr(pfg_ctx *ctx, int dtype, int n_max, int t_max, int B, const pfg_dev_problem *dp, hipStream_t st, int phase);
+int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st);
 
 }  // namespace pfg_host

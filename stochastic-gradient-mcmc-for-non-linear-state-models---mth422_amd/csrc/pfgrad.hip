@@ -11,62 +11,71 @@
 using namespace pfg_host;
 
 namespace pfg_host {
-extern template int launch_mkr<PFG_MODEL_SVM, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_SVM, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, bool);
-
-extern template int launch_grid_mkr<PFG_MODEL_SVM, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_SVM, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL, PFG_RNG_REPLAY>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-extern template int launch_grid_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL, PFG_RNG_DEVICE>(pfg_ctx *, int, int, int, int, const pfg_dev_problem *, hipStream_t, int);
-
-template <int MODEL, int KERNEL>
-int launch_grid_mk(pfg_ctx *ctx, int dtype, int rng, int n_max, int t_max, int B, const pfg_dev_problem *dp, hipStream_t st, int phase) {
-    if (rng == PFG_RNG_REPLAY) return launch_grid_mkr<MODEL, KERNEL, PFG_RNG_REPLAY>(ctx, dtype, n_max, t_max, B, dp, st, phase);
-    return launch_grid_mkr<MODEL, KERNEL, PFG_RNG_DEVICE>(ctx, dtype, n_max, t_max, B, dp, st, phase);
-}
-
-template <int MODEL, int KERNEL>
-int launch_mk(pfg_ctx *ctx, int dtype, int rng, int v, int n_max, int B, const pfg_dev_problem *dp, hipStream_t st, bool traced) {
-    if (rng == PFG_RNG_REPLAY) return launch_mkr<MODEL, KERNEL, PFG_RNG_REPLAY>(ctx, dtype, v, n_max, B, dp, st, traced);
-    return launch_mkr<MODEL, KERNEL, PFG_RNG_DEVICE>(ctx, dtype, v, n_max, B, dp, st, traced);
-}
+extern template int launch_mkr<PFG_MODEL_SVM, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_SVM, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL, PFG_RNG_REPLAY>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL, PFG_RNG_DEVICE>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR, PFG_RNG_REPLAY>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR, PFG_RNG_DEVICE>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL, PFG_RNG_REPLAY>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
+extern template int launch_mkr<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL, PFG_RNG_DEVICE>(pfg_ctx *, const LaunchPlan &, int, const pfg_dev_problem *, hipStream_t);
 }  // namespace pfg_host
 
 namespace {
 
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// runtime (model, kernel, dtype, rng) -> f(int_c<MODEL>, int_c<KERNEL>, REAL(), int_c<RNG>): the one place where the ids
+// become template arguments.  An id outside its enum takes the last branch (LGSSM, optimal, f32, REPLAY), which is what
+// the unchecked queries pfg_variant_name / pfg_scratch_bytes have always computed for it.
+template <typename F>
+auto with_types(int model, int kernel, int dtype, int rng, F &&f) {
+    auto g = [&](auto m, auto k, auto real) {
+        return rng == PFG_RNG_DEVICE ? f(m, k, real, int_c<PFG_RNG_DEVICE>()) : f(m, k, real, int_c<PFG_RNG_REPLAY>());
+    };
+    auto d = [&](auto m, auto k) { return dtype == PFG_F64 ? g(m, k, double()) : g(m, k, float()); };
+    auto kk = [&](auto m) { return kernel == PFG_KERNEL_PRIOR ? d(m, int_c<PFG_KERNEL_PRIOR>()) : d(m, int_c<PFG_KERNEL_OPTIMAL>()); };
+    return model == PFG_MODEL_SVM ? d(int_c<PFG_MODEL_SVM>(), int_c<PFG_KERNEL_PRIOR>())
+           : model == PFG_MODEL_GARCH ? kk(int_c<PFG_MODEL_GARCH>()) : kk(int_c<PFG_MODEL_LGSSM>());
+}
+// the same, where the proposal kernel does not matter (sizes)
+template <typename F>
+auto with_types(int model, int dtype, int rng, F &&f) { return with_types(model, PFG_KERNEL_PRIOR, dtype, rng, f); }
+
+// dynamic LDS of the LDS-resident kernel (NT, PPT, PP, MODE).  Evaluated in this unit, built without PFG_FAST_ALGEBRA:
+// the largest math tables any build of the kernel units carries.
+template <int NT, int PPT, bool PP, int MODE = pfg::MODE_PLAIN>
+size_t reg_lds(int model, int dtype, int rng, int N) {
+    return with_types(model, dtype, rng, [&](auto m, auto, auto real, auto g) {
+        return pfg::reg_kernel_lds_bytes<decltype(m)::value, decltype(real), NT, PPT, decltype(g)::value, PP, MODE>(N);
+    });
+}
+
 // ---- kernel variants ----------------------------------------------------------------
-// pp = ping-pong LDS state buffers (3 barriers/step); single buffer fits larger N (4 barriers).
-struct Variant { int NT, PPT; bool pp; const char *tag; };
-const Variant kVariants[] = { {256, 1, true, "wg256x1"}, {256, 4, true, "wg256x4"}, {256, 4, false, "wg256x4s"},
+// pp = ping-pong LDS state buffers (3 barriers/step); single buffer fits larger N (4 barriers).  tag1: the name of the
+// score-only twin, where a unit has one (reg_score1_twin).
+struct Variant { int NT, PPT; bool pp; const char *tag, *tag1; size_t (*lds)(int, int, int, int); };
+template <int NT, int PPT, bool PP>
+constexpr Variant entry(const char *tag, const char *tag1 = nullptr) { return {NT, PPT, PP, tag, tag1, reg_lds<NT, PPT, PP>}; }
+const Variant kVariants[] = { entry<256, 1, true>("wg256x1"), entry<256, 4, true>("wg256x4", "wg256x4_score1"),
+                              entry<256, 4, false>("wg256x4s", "wg256x4s_score1"),
                               // latency variant: one particle per thread, 16 waves on one CU; picked for
                               // small batches (fewer windows than a quarter of the CUs), never by order
-                              {1024, 1, true, "wg1024x1"},
+                              entry<1024, 1, true>("wg1024x1", "wg1024x1_score1"),
                               // 1024 < N <= 4096 with the device generator when the state fits LDS
                               // (32-bit CDF): SVM fp64, every model in f32
-                              {1024, 4, false, "wg1024x4s"},
+                              entry<1024, 4, false>("wg1024x4s", "wg1024x4s_score1"),
                               // N <= 128: one wave per window (barriers and cross-wave reductions degenerate)
-                              {64, 2, true, "wg64x2"},
+                              entry<64, 2, true>("wg64x2", "wg64x2_score1"),
                               // GARCH fp64: six LDS arrays allow two workgroups per CU; eight waves each
                               // put four waves on a SIMD (256x4: two)
-                              {512, 2, false, "wg512x2s"},
+                              entry<512, 2, false>("wg512x2s"),
                               // 128 < N <= 256, many windows: still one wave per window, four particles per lane
-                              {64, 4, true, "wg64x4"},
+                              entry<64, 4, true>("wg64x4"),
                               // one wave per window, single state buffer
-                              {64, 2, false, "wg64x2s"}, {64, 4, false, "wg64x4s"} };
+                              entry<64, 2, false>("wg64x2s", "wg64x2s_score1"), entry<64, 4, false>("wg64x4s") };
 // Measured and not kept (round 3, BASELINE config 4, 512 chains, ms per launch): the 4096 LDS slots of N <= 4096 in
 // fewer, wider threads -- 512 x 8 (2 waves per SIMD, 251 VGPRs, no spills) 12.99, 256 x 16 (1 wave per SIMD, 256 VGPRs +
 // 176 AGPRs) 16.14, against 12.73 for 1024 x 4 at its 128-VGPR cap (16 spilled VGPRs): LDS holds ONE such workgroup per
@@ -82,80 +91,183 @@ int state_dim(int model) { return model == PFG_MODEL_GARCH ? 2 : 1; }
 int stat_dim(int model) { return model == PFG_MODEL_SVM ? 3 : 4; }
 int theta_dim(int model) { return model == PFG_MODEL_SVM ? 3 : 4; }
 
-size_t lds_bytes(int model, int dtype, int rng, const Variant &v, int N) {
-    size_t rs = dtype == PFG_F64 ? 8 : 4;
-    const bool fast = pfg::fast_layout(v.NT, v.pp);
-    size_t NL = fast ? (size_t)v.NT * v.PPT : (size_t)(N + 63) / 64 * 64;
-    size_t NC = fast ? (size_t)v.NT * v.PPT + (size_t)v.NT * v.PPT / 32 : NL;
-    size_t red = (size_t)v.PPT * (v.NT / 64) + (v.NT / 64) + (size_t)PFG_MAX_STAT * (v.NT / 64) + 8;
-    size_t tab = (fast && dtype == PFG_F64)
-                     ? 8 * (size_t)(pfg::tab_doubles_exp(rng == PFG_RNG_DEVICE) + (rng == PFG_RNG_DEVICE ? pfg::TAB_DOUBLES_RNG : 0)) : 0;
-    const bool blk = fast && rng == PFG_RNG_DEVICE;        // 32-bit fixed-point CDF (pfg::pf_reg_kernel)
-    const size_t NLS = NL + ((fast && rng == PFG_RNG_DEVICE) ? (size_t)(PFG_OPT_PADSTATE ? 8 / rs : 0) : 0);      // pfg::state_pad
-    return (NC * (blk ? 4 : 8) + 15) / 16 * 16 + (v.pp ? 2 : 1) * NLS * (state_dim(model) + stat_dim(model)) * rs + red * 8 + tab;
-}
-
-// index into kVariants, or -1 when no LDS-resident variant fits.  PFGRAD_VARIANT=<tag> forces a
-// variant (tuning / tests) when it can hold n_max.
-int pick_variant(int model, int dtype, int rng, int n_max, int batch = 1 << 30) {
-    if (const char *force = std::getenv("PFGRAD_VARIANT")) {
-        if (!std::strcmp(force, "mem1024") && n_max <= pfg::MEM_MAX_N) return kVariantMem;
+// The kernel of a plain batch (no PaRIS / systematic / O(N^2)) of `batch` windows of up to n_max particles: Reg with the
+// kVariants index v, Mem, Grid, or None above every kernel.  force = PFGRAD_VARIANT: <tag> forces a variant (tuning /
+// tests) when it can hold n_max.
+Family pick_plain(int model, int dtype, int rng, int n_max, int batch, const char *force, int &v) {
+    auto fits = [&](int i) { return kVariants[i].lds(model, dtype, rng, n_max) <= kLdsLimit; };
+    auto holds = [&](int i) { return n_max <= kVariants[i].NT * kVariants[i].PPT && fits(i); };
+    auto reg = [&](int i) { v = i; return Family::Reg; };
+    if (force) {
+        if (!std::strcmp(force, "mem1024") && n_max <= pfg::MEM_MAX_N) return Family::Mem;
         // "big": the large-N kernels also where an LDS-resident variant would fit (A/B timing)
-        if (!std::strcmp(force, "big") && rng == PFG_RNG_DEVICE && n_max > 1024 && n_max <= pfg::MEM_MAX_N) return kVariantMem;
-        for (int v = 0; v < kNumVariants; ++v)
-            if (!std::strcmp(force, kVariants[v].tag) && n_max <= kVariants[v].NT * kVariants[v].PPT &&
-                lds_bytes(model, dtype, rng, kVariants[v], n_max) <= kLdsLimit)
-                return v;
+        if (!std::strcmp(force, "big") && rng == PFG_RNG_DEVICE && n_max > 1024 && n_max <= pfg::MEM_MAX_N) return Family::Mem;
+        for (int i = 0; i < kNumVariants; ++i)
+            if (!std::strcmp(force, kVariants[i].tag) && holds(i)) return reg(i);
     }
     // preference order: fp64 N<=1024 runs best on the single-buffer 256x4 variant at 3
     // workgroups per CU; f32 on ping-pong.  N > 1024 goes to the large-N kernel: 1024-thread
     // register-resident variants spill at the 128-VGPR cap and measured 3-5x slower than it.
     // N <= 128, many windows: one wave per window (2048 LGSSM N=100 T=200 chains: 1.07 -> 0.57 ms);
     // a lone window is quicker on the four waves of wg256x1 (0.34 vs 0.38 ms)
-    if (n_max <= 128 && batch > kLatencyBatch &&
-        lds_bytes(model, dtype, rng, kVariants[kTinyVariant], n_max) <= kLdsLimit)
-        return rng == PFG_RNG_DEVICE ? kTinySingleVariant : kTinyVariant;
-    if (n_max > 128 && n_max <= 256 && batch > kLatencyBatch && rng == PFG_RNG_DEVICE &&
-        lds_bytes(model, dtype, rng, kVariants[kTiny4Variant], n_max) <= kLdsLimit)
-        return kTiny4SingleVariant;
-    if (batch <= kLatencyBatch && n_max > 256 && n_max <= 1024 &&
-        lds_bytes(model, dtype, rng, kVariants[kLatencyVariant], n_max) <= kLdsLimit)
-        return kLatencyVariant;
+    if (n_max <= 128 && batch > kLatencyBatch && fits(kTinyVariant))
+        return reg(rng == PFG_RNG_DEVICE ? kTinySingleVariant : kTinyVariant);
+    if (n_max > 128 && n_max <= 256 && batch > kLatencyBatch && rng == PFG_RNG_DEVICE && fits(kTiny4Variant))
+        return reg(kTiny4SingleVariant);
+    if (batch <= kLatencyBatch && n_max > 256 && n_max <= 1024 && fits(kLatencyVariant)) return reg(kLatencyVariant);
     // GARCH fp64, device generator, 256 < N <= 1024: LDS holds two workgroups per CU either way; 512 threads x 2
     // particles put four waves on a SIMD instead of two (8192 windows of config 3: 1.99 -> 1.87 ms)
-    if (model == PFG_MODEL_GARCH && dtype == PFG_F64 && rng == PFG_RNG_DEVICE && n_max > 256 && n_max <= 1024 &&
-        lds_bytes(model, dtype, rng, kVariants[kGarchVariant], n_max) <= kLdsLimit)
-        return kGarchVariant;
+    if (model == PFG_MODEL_GARCH && dtype == PFG_F64 && rng == PFG_RNG_DEVICE && n_max > 256 && n_max <= 1024 && fits(kGarchVariant))
+        return reg(kGarchVariant);
     const int order_f64[] = {0, 2, 1}, order_f32[] = {0, 1, 2};
-    const int *order = dtype == PFG_F64 ? order_f64 : order_f32;
-    for (int oi = 0; oi < 3; ++oi) {
-        const int v = order[oi];
-        if (n_max <= kVariants[v].NT * kVariants[v].PPT && lds_bytes(model, dtype, rng, kVariants[v], n_max) <= kLdsLimit)
-            return v;
+    for (int i : dtype == PFG_F64 ? order_f64 : order_f32)
+        if (holds(i)) return reg(i);
+    if (rng == PFG_RNG_DEVICE && n_max <= 4096 && fits(kLds4096Variant)) return reg(kLds4096Variant);
+    if (n_max <= pfg::MEM_MAX_N) return Family::Mem;
+    if (n_max <= pfg::GRID_MAX_N) return Family::Grid;     // one window over the whole GPU (pfg_grid_kernel.hpp)
+    return Family::None;
+}
+
+// Who asks for a plan: the queries pfg_variant_name / pfg_scratch_bytes (a large batch of plain windows), pfg_run_batch
+// (N above the one-workgroup kernels, or PFGRAD_VARIANT=grid, runs as whole-GPU windows), pfg_launch_device* (one-workgroup
+// kernels only) and pfg_launch_device_grid* (whole-GPU windows).
+enum class Caller { Query, Batch, Device, Grid };
+
+LaunchPlan refuse(LaunchPlan &p, int rc, std::string msg) {
+    p.rc = rc;
+    p.err = std::move(msg);
+    return std::move(p);
+}
+
+// Which kernel runs a batch of B windows of up to n_max particles, with what LDS and scratch, under which name.  smoother
+// as the dispatcher receives it: PFG_SMOOTHER_POYIADJIS_N states that every window is (NEMETH, lambduh = 1, score) -- the
+// same kernels as NEMETH, except where a unit has a twin specialised to that estimator.  traced: the descriptors may carry
+// trace_* / rec_* buffers (the plain LDS-resident kernels exist as a production twin that ignores them, see
+// pfg_reg_kernel.hpp; every other kernel always honours them).  predictive: the windows ask for the predictive statistic,
+// which only the general large-N kernel computes.  The environment variables PFGRAD_VARIANT, PFGRAD_NO_SCORE1 and
+// PFGRAD_CDF_SINGLE are read here and nowhere else.
+LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B, bool traced,
+                     bool predictive = false, int t_max = 0, int phase = -1) {
+    LaunchPlan p;
+    p.f64 = dtype == PFG_F64;
+    p.n_max = n_max; p.t_max = t_max; p.phase = phase;
+    auto score1_on = [&] {          // PFGRAD_NO_SCORE1=1 (A/B timing): the general kernel for these launches too
+        if (smoother != PFG_SMOOTHER_POYIADJIS_N) return false;
+        const char *off = std::getenv("PFGRAD_NO_SCORE1");
+        return !(off && off[0] == '1');
+    };
+    auto mem_lds = [&] { return with_types(model, dtype, rng, [&](auto, auto, auto real, auto g) { return pfg::mem_kernel_lds_bytes<decltype(real), decltype(g)::value>(n_max); }); };
+    auto mem_scratch = [&](bool paris) {
+        return (with_types(model, dtype, rng, [&](auto m, auto, auto real, auto) {
+                    return pfg::mem_kernel_scratch_bytes<decltype(m)::value, decltype(real)>(n_max, paris);
+                }) + 255) / 256 * 256;
+    };
+    const char *force = std::getenv("PFGRAD_VARIANT");
+    int v = -1;
+    if (caller == Caller::Grid) p.family = Family::Grid;
+    else if (smoother == PFG_SMOOTHER_PARIS) p.family = Family::Paris;
+    else if (smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) p.family = Family::Systematic;
+    else if (smoother == PFG_SMOOTHER_POYIADJIS_N2) p.family = Family::N2;
+    else if (predictive && n_max <= pfg::MEM_MAX_N) p.family = Family::Mem;
+    else {
+        p.family = pick_plain(model, dtype, rng, n_max, B, force, v);
+        if (p.family == Family::None)
+            return refuse(p, PFG_ERR_UNSUPPORTED, "N = " + std::to_string(n_max) + " exceeds the supported maximum of " + std::to_string(pfg::GRID_MAX_N));
+        if (p.family == Family::Grid && caller == Caller::Device)
+            return refuse(p, PFG_ERR_UNSUPPORTED, "N = " + std::to_string(n_max) + " > " + std::to_string(pfg::MEM_MAX_N) +
+                                                      " runs as a whole-GPU window, one launch per timestep: use pfg_launch_device_grid (it needs T_max)");
+        // PFGRAD_VARIANT=grid: the whole-GPU window also where a one-workgroup kernel would serve (tests, A/B timing)
+        if (caller == Caller::Batch && !predictive && force && !std::strcmp(force, "grid")) p.family = Family::Grid;
+        // N > 1024 with the device generator: the fast large-N kernel, unless PFGRAD_VARIANT=mem1024 asks for the general
+        // one (A/B timing, tests; a predictive batch has taken the general one above)
+        if (p.family == Family::Mem && rng == PFG_RNG_DEVICE && !(force && !std::strcmp(force, "mem1024"))) p.family = Family::Big;
     }
-    if (rng == PFG_RNG_DEVICE && n_max <= 4096 &&
-        lds_bytes(model, dtype, rng, kVariants[kLds4096Variant], n_max) <= kLdsLimit)
-        return kLds4096Variant;
-    if (n_max <= pfg::MEM_MAX_N) return kVariantMem;
-    if (n_max <= pfg::GRID_MAX_N) return kVariantGrid;     // one window over the whole GPU (pfg_grid_kernel.hpp)
-    return -1;
-}
-
-size_t grid_scratch_bytes(int model, int dtype, int rng, int N) {
-    const bool rp = rng == PFG_RNG_REPLAY;
-    if (dtype == PFG_F64)
-        return model == PFG_MODEL_SVM ? pfg::grid_layout<PFG_MODEL_SVM, double>(N, rp).bytes
-               : model == PFG_MODEL_GARCH ? pfg::grid_layout<PFG_MODEL_GARCH, double>(N, rp).bytes
-                                          : pfg::grid_layout<PFG_MODEL_LGSSM, double>(N, rp).bytes;
-    return model == PFG_MODEL_SVM ? pfg::grid_layout<PFG_MODEL_SVM, float>(N, rp).bytes
-           : model == PFG_MODEL_GARCH ? pfg::grid_layout<PFG_MODEL_GARCH, float>(N, rp).bytes
-                                      : pfg::grid_layout<PFG_MODEL_LGSSM, float>(N, rp).bytes;
-}
-
-size_t scratch_bytes(int model, int dtype, int N, bool paris = false) {
-    const size_t rs = dtype == PFG_F64 ? 8 : 4, per = 16 / rs;
-    const size_t rec = (state_dim(model) + stat_dim(model) + per - 1) / per * per;   // pfg::mem_rec_len
-    return (size_t)N * rs * (1 + 2 * rec) + 16 + (paris ? (size_t)N * (2 * rs + 8) + 16 + 2 * (size_t)((N + 1023) / 1024 * 1024) * 4 : 0);   // pfg::mem_kernel_scratch_bytes
+    switch (p.family) {
+        case Family::Reg: {
+            const Variant &e = kVariants[v];
+            p.nt = e.NT; p.ppt = e.PPT; p.pp = e.pp;
+            p.traced = traced;
+            p.lds = e.lds(model, dtype, rng, n_max);
+            p.name = e.tag;
+            if (!reg_entry_built(model, rng, p.f64, e.NT, e.PPT, e.pp)) return refuse(p, PFG_ERR_UNSUPPORTED, "no kernel variant");
+            p.score1 = !traced && reg_score1_twin(model, rng, p.f64, e.NT, e.PPT, e.pp) && score1_on();
+            if (p.score1) p.name = e.tag1;
+            break;
+        }
+        case Family::Mem:
+            // the log-weights in registers: N <= 4096, and no window asks for the predictive statistic
+            p.lw4 = !predictive && n_max <= 4096;
+            // its score-only twin (GARCH: unmeasured here, +8 % in the LDS-resident REPLAY unit)
+            p.score1 = p.lw4 && !traced && p.f64 && model != PFG_MODEL_GARCH && score1_on();
+            p.name = p.score1 ? "mem1024_score1" : "mem1024";
+            p.lds = mem_lds();
+            p.scratch = mem_scratch(false);
+            break;
+        case Family::Big:
+            p.np2 = n_max <= 4096 ? 4096 : 16384;
+            p.name = p.np2 == 4096 ? "big4096" : "big16384";
+            p.lds = with_types(model, dtype, rng, [&](auto, auto, auto real, auto) { return pfg::big_kernel_lds_bytes<decltype(real)>(p.np2); });
+            p.scratch = mem_scratch(false);         // (what the general kernel needs: the fast path uses less)
+            break;
+        case Family::Paris:
+        case Family::N2: {
+            const bool paris = p.family == Family::Paris;
+            const std::string pf = paris ? "pf = 'paris'" : "pf = 'poyiadjis_N2'";
+            if (n_max <= 1024) {
+                p.nt = 256; p.ppt = n_max <= 256 ? 1 : 4;
+                p.name = paris ? (p.ppt == 1 ? "paris256x1" : "paris256x4") : (p.ppt == 1 ? "n2_256x1" : "n2_256x4");
+                p.lds = (paris ? (p.ppt == 1 ? reg_lds<256, 1, true, pfg::MODE_PARIS> : reg_lds<256, 4, true, pfg::MODE_PARIS>)
+                               : (p.ppt == 1 ? reg_lds<256, 1, true, pfg::MODE_N2> : reg_lds<256, 4, true, pfg::MODE_N2>))(model, dtype, rng, n_max);
+                if (p.lds > kLdsLimit)
+                    return refuse(p, PFG_ERR_UNSUPPORTED, pf + ": N = " + std::to_string(n_max) + " does not fit the LDS-resident variant");
+                break;
+            }
+            // the large-N kernel's PaRIS instantiation (also its O(N^2) sweep): state in the HBM scratch
+            p.name = paris ? "paris_mem1024" : "n2_mem1024";
+            p.scratch = mem_scratch(true);
+            if (n_max > pfg::MEM_MAX_N)
+                return refuse(p, PFG_ERR_UNSUPPORTED, pf + " is implemented for N <= 16384 (N = " + std::to_string(n_max) + ")");
+            p.nt = pfg::MEM_NT;
+            p.lds = mem_lds();
+            break;
+        }
+        case Family::Systematic:        // the 256 x 4 default variants of fp64 / f32
+            p.name = "systematic256x4";
+            p.nt = 256; p.ppt = 4; p.pp = !p.f64;
+            if (rng != PFG_RNG_DEVICE) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling needs the DEVICE rng");
+            if (n_max > 1024) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling is built for N <= 1024");
+            p.lds = (p.f64 ? reg_lds<256, 4, false, pfg::MODE_SYSTEMATIC> : reg_lds<256, 4, true, pfg::MODE_SYSTEMATIC>)(model, dtype, rng, n_max);
+            if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling: state does not fit LDS");
+            break;
+        case Family::Grid: {
+            // every window of the batch must fall into the same tile class; NEMETH / FILTER with the score, sufficient or
+            // no statistic
+            p.ppt = pfg::grid_ppt(n_max); p.kmax = pfg::grid_kmax(n_max);
+            p.score1 = rng == PFG_RNG_DEVICE && score1_on();
+            p.name = p.ppt == 8 ? (p.score1 ? "grid2048_score1" : "grid2048") : (p.score1 ? "grid1024_score1" : "grid1024");
+            if (n_max > pfg::GRID_MAX_N)
+                return refuse(p, PFG_ERR_UNSUPPORTED, "N = " + std::to_string(n_max) + " exceeds the supported maximum of " + std::to_string(pfg::GRID_MAX_N));
+            // REPLAY: PFGRAD_CDF_SINGLE=1 computes the reference's CDF with the lone-workgroup kernel (A/B and cross-check)
+            const char *single = std::getenv("PFGRAD_CDF_SINGLE");
+            p.cdf_single = single && single[0] == '1';
+            with_types(model, dtype, rng, [&](auto m, auto, auto real, auto g) {
+                using REAL = decltype(real);
+                const pfg::GridLayout L = pfg::grid_layout<decltype(m)::value, REAL>(n_max, rng == PFG_RNG_REPLAY);
+                p.tiles = L.G;
+                p.scratch = L.bytes;
+                if (rng == PFG_RNG_REPLAY)      // the timestep kernel's LDS
+                    p.lds = p.ppt == 4 ? pfg::grid_step_lds_bytes<pfg::GRID_NT, 4, REAL, decltype(g)::value>(L.C)
+                                       : pfg::grid_step_lds_bytes<pfg::GRID_NT, 8, REAL, decltype(g)::value>(L.C);
+                else
+                    p.lds = 8 * (p.ppt == 4 ? pfg::grid_dev_lds_doubles<pfg::GRID_NT, 4>(L.G) : pfg::grid_dev_lds_doubles<pfg::GRID_NT, 8>(L.G));
+                return 0;
+            });
+            break;
+        }
+        case Family::None:
+            break;
+    }
+    return p;
 }
 
 int check_combo(pfg_ctx *ctx, int model, int kernel, int dtype, int rng) {
@@ -169,84 +281,27 @@ int check_combo(pfg_ctx *ctx, int model, int kernel, int dtype, int rng) {
     return PFG_OK;
 }
 
-// traced: the descriptors may carry trace_* / rec_* buffers (the plain LDS-resident kernels, device generator and
-// REPLAY, exist as a production twin that ignores them, see pfg_reg_kernel.hpp; every other kernel always honours them)
-int dispatch(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int B,
-             const pfg_dev_problem *dp, hipStream_t st, int smoother = PFG_SMOOTHER_NEMETH,
-             bool force_mem = false, bool traced = true) {
-    int rc = check_combo(ctx, model, kernel, dtype, rng);
-    if (rc) return rc;
-    if (B <= 0) return PFG_OK;
-    if (n_max < 1) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
-    // PFG_SMOOTHER_POYIADJIS_N: the caller states that every descriptor is (NEMETH, lambduh = 1, score) -- same kernels as
-    // NEMETH, except where a unit has a twin specialised to that estimator (launch_one)
-    ctx->score1 = (smoother == PFG_SMOOTHER_POYIADJIS_N) && !traced;
-    if (ctx->score1) {
-        const char *off = std::getenv("PFGRAD_NO_SCORE1");      // A/B timing: the general kernel for these launches too
-        if (off && off[0] == '1') ctx->score1 = false;
+// B windows of the descriptors dp on st, as planned: the kernel's name becomes pfg_last_variant once it is chosen
+int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, int B, const pfg_dev_problem *dp, hipStream_t st) {
+    if (p.family == Family::Grid && B > 65535) return fail(ctx, PFG_ERR_INVALID, "at most 65535 whole-GPU windows per launch");
+    if (p.name) {
+        ctx->last_variant = p.name;
+        ctx->last_traced = p.traced;
     }
-    if (smoother == PFG_SMOOTHER_POYIADJIS_N) smoother = PFG_SMOOTHER_NEMETH;
-    int v = smoother == PFG_SMOOTHER_PARIS ? kVariantParis
-            : smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC ? kVariantSystematic
-            : smoother == PFG_SMOOTHER_POYIADJIS_N2 ? kVariantN2
-            : (force_mem && n_max <= pfg::MEM_MAX_N) ? kVariantMem
-            : pick_variant(model, dtype, rng, n_max, B);
-    if (v == -1)
-        return fail(ctx, PFG_ERR_UNSUPPORTED,
-                    "N = " + std::to_string(n_max) + " exceeds the supported maximum of " + std::to_string(pfg::GRID_MAX_N));
-    if (v == kVariantGrid)
-        return fail(ctx, PFG_ERR_UNSUPPORTED,
-                    "N = " + std::to_string(n_max) + " > " + std::to_string(pfg::MEM_MAX_N) +
-                    " runs as a whole-GPU window, one launch per timestep: use pfg_launch_device_grid (it needs T_max)");
-    // N > 1024 with the device generator: the fast large-N kernel, unless the statistic needs the
-    // general one (predictive) or PFGRAD_VARIANT=mem1024 asks for it (A/B timing, tests)
-    if (v == kVariantMem && rng == PFG_RNG_DEVICE && !force_mem) {
-        const char *force = std::getenv("PFGRAD_VARIANT");
-        if (!(force && !std::strcmp(force, "mem1024"))) v = kVariantBig;
-    }
-    // the large-N kernel with the log-weights in registers: N <= 4096, and the host knows that no window asks for the
-    // predictive statistic (pfg_run_batch routes those with force_mem; resident descriptors never carry it)
-    if (v == kVariantMem && !force_mem && n_max <= 4096) v = kVariantMemLw4;
-    ctx->last_variant = v >= 0 ? kVariants[v].tag
-                        : (v == kVariantMem || v == kVariantMemLw4) ? "mem1024"
-                        : v == kVariantBig ? (n_max <= 4096 ? "big4096" : "big16384")
-                        : v == kVariantParis ? (n_max <= 256 ? "paris256x1" : n_max <= 1024 ? "paris256x4" : "paris_mem1024")
-                        : v == kVariantSystematic ? "systematic256x4"
-                        : (n_max <= 256 ? "n2_256x1" : n_max <= 1024 ? "n2_256x4" : "n2_mem1024");
-    ctx->last_traced = traced || v < 0;
-    if (model == PFG_MODEL_SVM) return launch_mk<PFG_MODEL_SVM, PFG_KERNEL_PRIOR>(ctx, dtype, rng, v, n_max, B, dp, st, traced);
-    if (model == PFG_MODEL_GARCH) {
-        if (kernel == PFG_KERNEL_PRIOR) return launch_mk<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR>(ctx, dtype, rng, v, n_max, B, dp, st, traced);
-        return launch_mk<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL>(ctx, dtype, rng, v, n_max, B, dp, st, traced);
-    }
-    if (kernel == PFG_KERNEL_PRIOR) return launch_mk<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR>(ctx, dtype, rng, v, n_max, B, dp, st, traced);
-    return launch_mk<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL>(ctx, dtype, rng, v, n_max, B, dp, st, traced);
+    if (p.rc) return fail(ctx, p.rc, p.err);
+    return with_types(model, kernel, PFG_F64, rng, [&](auto m, auto k, auto, auto g) {
+        return launch_mkr<decltype(m)::value, decltype(k)::value, decltype(g)::value>(ctx, p, B, dp, st);
+    });
 }
 
-// whole-GPU windows (N above the one-workgroup kernels' maximum, or forced): NEMETH / FILTER with the score,
-// sufficient or no statistic
-int dispatch_grid(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int t_max, int B,
-                  const pfg_dev_problem *dp, hipStream_t st, int phase = -1, int smoother = PFG_SMOOTHER_NEMETH) {
+int dispatch(pfg_ctx *ctx, Caller caller, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
+             const pfg_dev_problem *dp, hipStream_t st, bool traced = false, int t_max = 0, int phase = -1) {
     int rc = check_combo(ctx, model, kernel, dtype, rng);
     if (rc) return rc;
     if (B <= 0) return PFG_OK;
     if (n_max < 1) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
-    if (t_max < 0) return fail(ctx, PFG_ERR_INVALID, "T_max must be >= 0");
-    if (B > 65535) return fail(ctx, PFG_ERR_INVALID, "at most 65535 whole-GPU windows per launch");
-    ctx->score1 = smoother == PFG_SMOOTHER_POYIADJIS_N && rng == PFG_RNG_DEVICE;
-    if (ctx->score1) {
-        const char *off = std::getenv("PFGRAD_NO_SCORE1");      // A/B timing: the general kernel for these launches too
-        if (off && off[0] == '1') ctx->score1 = false;
-    }
-    ctx->last_variant = pfg::grid_ppt(n_max) == 8 ? (ctx->score1 ? "grid2048_score1" : "grid2048") : (ctx->score1 ? "grid1024_score1" : "grid1024");
-    ctx->last_traced = true;
-    if (model == PFG_MODEL_SVM) return launch_grid_mk<PFG_MODEL_SVM, PFG_KERNEL_PRIOR>(ctx, dtype, rng, n_max, t_max, B, dp, st, phase);
-    if (model == PFG_MODEL_GARCH) {
-        if (kernel == PFG_KERNEL_PRIOR) return launch_grid_mk<PFG_MODEL_GARCH, PFG_KERNEL_PRIOR>(ctx, dtype, rng, n_max, t_max, B, dp, st, phase);
-        return launch_grid_mk<PFG_MODEL_GARCH, PFG_KERNEL_OPTIMAL>(ctx, dtype, rng, n_max, t_max, B, dp, st, phase);
-    }
-    if (kernel == PFG_KERNEL_PRIOR) return launch_grid_mk<PFG_MODEL_LGSSM, PFG_KERNEL_PRIOR>(ctx, dtype, rng, n_max, t_max, B, dp, st, phase);
-    return launch_grid_mk<PFG_MODEL_LGSSM, PFG_KERNEL_OPTIMAL>(ctx, dtype, rng, n_max, t_max, B, dp, st, phase);
+    if (caller == Caller::Grid && t_max < 0) return fail(ctx, PFG_ERR_INVALID, "T_max must be >= 0");
+    return launch(ctx, make_plan(caller, model, dtype, rng, smoother, n_max, B, traced, false, t_max, phase), model, kernel, rng, B, dp, st);
 }
 
 // ---- SGLD update for resident chains ---------------------------------------------------
@@ -527,24 +582,17 @@ int pfg_synchronize(pfg_ctx *ctx) {
     return PFG_OK;
 }
 
+// both for a large batch of plain windows: never the latency variant or a twin
 int64_t pfg_scratch_bytes(int model, int dtype, int rng, int N) {
     if (model < 0 || model > 2 || N < 1) return -1;
-    const int v = pick_variant(model, dtype, rng, N);
-    if (v >= 0) return 0;
-    if (v == kVariantMem) return (int64_t)((scratch_bytes(model, dtype, N) + 255) / 256 * 256);
-    if (v == kVariantGrid) return (int64_t)grid_scratch_bytes(model, dtype, rng, N);
-    return -1;
+    const LaunchPlan p = make_plan(Caller::Query, model, dtype, rng, PFG_SMOOTHER_NEMETH, N, 1 << 30, false);
+    return p.name ? (int64_t)p.scratch : -1;
 }
 
 const char *pfg_variant_name(int model, int kernel, int dtype, int rng, int n_max) {
-    (void)kernel; (void)rng;
-    int v = pick_variant(model, dtype, rng, n_max);
-    if (v == kVariantMem && rng == PFG_RNG_DEVICE) {
-        const char *force = std::getenv("PFGRAD_VARIANT");
-        if (!(force && !std::strcmp(force, "mem1024"))) return n_max <= 4096 ? "big4096" : "big16384";
-    }
-    if (v == kVariantGrid) return pfg::grid_ppt(n_max) == 8 ? "grid2048" : "grid1024";
-    return v == kVariantMem ? "mem1024" : (v < 0 ? "none" : kVariants[v].tag);
+    (void)kernel;
+    const LaunchPlan p = make_plan(Caller::Query, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, 1 << 30, false);
+    return p.name ? p.name : "none";
 }
 
 int pfg_launch_device(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int B,
@@ -552,7 +600,7 @@ int pfg_launch_device(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, i
     if (!ctx) return PFG_ERR_INVALID;
     if (!dev_probs && B > 0) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device: dev_probs is NULL");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    return dispatch(ctx, model, kernel, dtype, rng, n_max, B, dev_probs, (hipStream_t)hip_stream, PFG_SMOOTHER_NEMETH, false, false);
+    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B, dev_probs, (hipStream_t)hip_stream);
 }
 
 int pfg_launch_device_traced(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
@@ -562,7 +610,7 @@ int pfg_launch_device_traced(pfg_ctx *ctx, int model, int kernel, int dtype, int
     if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_POYIADJIS_N)
         return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    return dispatch(ctx, model, kernel, dtype, rng, n_max, B, dev_probs, (hipStream_t)hip_stream, smoother, false, true);
+    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream, true);
 }
 
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max,
@@ -572,7 +620,7 @@ int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, i
     if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_POYIADJIS_N)
         return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    return dispatch(ctx, model, kernel, dtype, rng, n_max, B, dev_probs, (hipStream_t)hip_stream, smoother, false, false);
+    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream);
 }
 
 int pfg_launch_device_grid(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int T_max, int B,
@@ -580,7 +628,7 @@ int pfg_launch_device_grid(pfg_ctx *ctx, int model, int kernel, int dtype, int r
     if (!ctx) return PFG_ERR_INVALID;
     if (!dev_probs && B > 0) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_grid: dev_probs is NULL");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    return dispatch_grid(ctx, model, kernel, dtype, rng, n_max, T_max, B, dev_probs, (hipStream_t)hip_stream);
+    return dispatch(ctx, Caller::Grid, model, kernel, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B, dev_probs, (hipStream_t)hip_stream, true, T_max);
 }
 
 int pfg_launch_device_grid_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max, int T_max,
@@ -591,7 +639,8 @@ int pfg_launch_device_grid_smoother(pfg_ctx *ctx, int model, int kernel, int dty
         return fail(ctx, PFG_ERR_UNSUPPORTED, "whole-GPU windows are built for NEMETH / FILTER / POYIADJIS_N");
     if (phase < PFG_GRID_PHASE_FINISH) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_grid_smoother: phase must be PFG_GRID_PHASE_ALL, a timestep >= 0, PFG_GRID_PHASE_INIT or PFG_GRID_PHASE_FINISH");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    return dispatch_grid(ctx, model, kernel, dtype, rng, n_max, phase == PFG_GRID_PHASE_ALL ? T_max : 0, B, dev_probs, (hipStream_t)hip_stream, phase, smoother);
+    return dispatch(ctx, Caller::Grid, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream, true,
+                    phase == PFG_GRID_PHASE_ALL ? T_max : 0, phase);
 }
 
 int pfg_launch_device_grid_phase(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int phase, int B,
@@ -601,7 +650,7 @@ int pfg_launch_device_grid_phase(pfg_ctx *ctx, int model, int kernel, int dtype,
     if (phase < PFG_GRID_PHASE_FINISH) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_grid_phase: phase must be a timestep >= 0, PFG_GRID_PHASE_INIT or PFG_GRID_PHASE_FINISH");
     if (phase == -1) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_grid_phase: use pfg_launch_device_grid for the whole window");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    return dispatch_grid(ctx, model, kernel, dtype, rng, n_max, 0, B, dev_probs, (hipStream_t)hip_stream, phase);
+    return dispatch(ctx, Caller::Grid, model, kernel, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B, dev_probs, (hipStream_t)hip_stream, true, 0, phase);
 }
 
 int pfg_sghmc_update_device(pfg_ctx *ctx, int model, int B, double *theta, double *momentum, const double *outs,
@@ -858,18 +907,12 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     const bool sysres = ps[0].smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC;
     const bool predictive = ps[0].stat == PFG_STAT_PREDICTIVE;   // large-N kernel only (any N)
     const bool n2 = ps[0].smoother == PFG_SMOOTHER_POYIADJIS_N2;
-    int variant = paris ? kVariantParis : sysres ? kVariantSystematic : n2 ? kVariantN2
-                  : predictive ? kVariantMem : pick_variant(model, dtype, rng, n_max);
-    if (variant == -1)
-        return fail(ctx, PFG_ERR_UNSUPPORTED,
-                    "N = " + std::to_string(n_max) + " exceeds the supported maximum of " + std::to_string(pfg::GRID_MAX_N));
-    // PFGRAD_VARIANT=grid: the whole-GPU window also where a one-workgroup kernel would serve (tests, A/B timing)
-    if (variant != kVariantGrid && !paris && !sysres && !n2 && !predictive) {
-        const char *force = std::getenv("PFGRAD_VARIANT");
-        if (force && !std::strcmp(force, "grid")) variant = kVariantGrid;
-    }
-    int t_max = 0;
-    if (variant == kVariantGrid) {
+    LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng,
+                                paris ? PFG_SMOOTHER_PARIS : sysres ? PFG_SMOOTHER_NEMETH_SYSTEMATIC : n2 ? PFG_SMOOTHER_POYIADJIS_N2
+                                : score1 ? PFG_SMOOTHER_POYIADJIS_N : PFG_SMOOTHER_NEMETH,
+                                n_max, B, traced, predictive);
+    if (plan.rc && !plan.name) return fail(ctx, plan.rc, plan.err);
+    if (plan.family == Family::Grid) {
         for (int b = 0; b < B; ++b) {
             const pfg_problem &q = ps[b];
             const std::string id = "problem " + std::to_string(b) + ": ";
@@ -878,16 +921,12 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
             if (q.elementwise) return fail(ctx, PFG_ERR_UNSUPPORTED, id + "elementwise statistics are built for N <= " + std::to_string(pfg::MEM_MAX_N));
             if (pfg::grid_ppt(q.N) != pfg::grid_ppt(n_max))
                 return fail(ctx, PFG_ERR_INVALID, id + "whole-GPU windows of one batch must all have N <= 524288 or all N > 524288");
-            t_max = q.T > t_max ? q.T : t_max;
+            plan.t_max = q.T > plan.t_max ? q.T : plan.t_max;
         }
     }
-    size_t n_scratch = 0;                  // bytes; every window of the batch gets n_max-sized state
+    // every window of the batch gets n_max-sized state (the predictive statistic's buffers after it)
     const size_t pred_each = predictive ? ((size_t)n_max * PFG_MAX_PRED * (dtype == PFG_F64 ? 8 : 4) + 255) / 256 * 256 : 0;
-    const bool paris_mem = (paris || n2) && n_max > 1024;       // the large-N kernel's PaRIS instantiation (also its O(N^2) sweep)
-    const size_t scratch_each = (scratch_bytes(model, dtype, n_max, paris_mem) + 255) / 256 * 256 + pred_each;
-    if (variant == kVariantMem || paris_mem) n_scratch = scratch_each * (size_t)B;
-    const size_t grid_each = variant == kVariantGrid ? grid_scratch_bytes(model, dtype, rng, n_max) : 0;
-    if (variant == kVariantGrid) n_scratch = grid_each * (size_t)B;
+    const size_t scratch_each = plan.scratch + pred_each, n_scratch = scratch_each * (size_t)B;
 
     PFG_HIP(ctx, hipSetDevice(ctx->device));
     PFG_HIP(ctx, ctx->in.ensure(n_in * 8));
@@ -1041,9 +1080,8 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
             std::memcpy(&slot, &q.step, sizeof slot);
             d.step_ctr = reinterpret_cast<const uint64_t *>(put(&slot, 1));
         }
-        d.scratch = n_scratch ? static_cast<void *>(static_cast<char *>(ctx->scratch.ptr) + (variant == kVariantGrid ? grid_each : scratch_each) * (size_t)b)
-                              : nullptr;
-        if (predictive) d.pred_scratch = static_cast<char *>(d.scratch) + (scratch_each - pred_each);
+        d.scratch = n_scratch ? static_cast<void *>(static_cast<char *>(ctx->scratch.ptr) + scratch_each * (size_t)b) : nullptr;
+        if (predictive) d.pred_scratch = static_cast<char *>(d.scratch) + plan.scratch;
         d.prior_mean = q.prior_mean; d.prior_var = q.prior_var; d.lambduh = q.lambduh;
         d.seed = q.seed; d.stream = q.stream;
         d.T = q.T; d.t1 = q.t1; d.tL = tL; d.N = q.N;
@@ -1058,14 +1096,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     PFG_HIP(ctx, hipMemcpyAsync(ctx->desc.ptr, ctx->h_desc.data(), (size_t)B * sizeof(pfg_dev_problem),
                                 hipMemcpyHostToDevice, ctx->stream));
     PFG_HIP(ctx, hipMemsetAsync(ctx->out.ptr, 0, oo * 8, ctx->stream));
-    if (variant == kVariantGrid)
-        rc = dispatch_grid(ctx, model, kernel, dtype, rng, n_max, t_max, B, static_cast<const pfg_dev_problem *>(ctx->desc.ptr), ctx->stream,
-                           -1, score1 ? PFG_SMOOTHER_POYIADJIS_N : PFG_SMOOTHER_NEMETH);
-    else
-        rc = dispatch(ctx, model, kernel, dtype, rng, n_max, B, static_cast<const pfg_dev_problem *>(ctx->desc.ptr),
-                      ctx->stream, paris ? PFG_SMOOTHER_PARIS : sysres ? PFG_SMOOTHER_NEMETH_SYSTEMATIC
-                                   : n2 ? PFG_SMOOTHER_POYIADJIS_N2 : score1 ? PFG_SMOOTHER_POYIADJIS_N : PFG_SMOOTHER_NEMETH,
-                      predictive, traced);
+    rc = launch(ctx, plan, model, kernel, rng, B, static_cast<const pfg_dev_problem *>(ctx->desc.ptr), ctx->stream);
     if (rc) return rc;
     for (int b = 0; b < B; ++b) {
         if (!ps[b].elementwise) continue;
