@@ -73,7 +73,19 @@ enum pfg_smoother { PFG_SMOOTHER_NEMETH = 0, PFG_SMOOTHER_FILTER = 1, PFG_SMOOTH
                      * 4: -3.9 %, config 1: -3.8 %; seed-compatible arithmetic -4.6 % / -6.2 %, bitwise the same numbers).
                      * A descriptor that breaks the statement gets out[0..7] = NaN from that twin.  pfg_run_batch
                      * chooses it by itself when every window of the batch qualifies. */
-                    PFG_SMOOTHER_POYIADJIS_N = 5 };
+                    PFG_SMOOTHER_POYIADJIS_N = 5,
+                    /* The EXACT score of the linear Gaussian model, no particles: the reference's kind = 'marginal'
+                     * gradient (sgmcmc_sampler.py:298-329; models/lgssm/helper.py:53-192, 312-420, include_init = True).
+                     * Valid in descriptors and launches; model LGSSM and dtype F64 only; kernel, rng, N, lambduh,
+                     * stat and the stream / seed fields are ignored.  Per window: forward Kalman messages over the
+                     * left buffer [0, t1) from the message of x_{-1} given by prior_mean = mean_precision / precision,
+                     * prior_var = 1 / precision (> 0), backward messages over the right buffer [tL, T) from the zero
+                     * message, then the smoothed score over [t1, tL) with `weights`.  out[0..3] = the gradient in the
+                     * LGSSM score column order, out[4] = sum_t w_t log Pr(y_t | y_{<t}) over [t1, tL) given the left
+                     * buffer (noisy_loglikelihood(kind = 'marginal'), sgmcmc_sampler.py:147-174), out[5..7] = 0.
+                     * `scratch`: 16 (tL - t1 + 1) bytes rounded up to 256 (pfg_run / pfg_run_batch allocate it;
+                     * resident callers supply it).  A batch is all-Kalman or Kalman-free; no trace / final outputs. */
+                    PFG_SMOOTHER_KALMAN = 6 };
 /* additive statistic: *_complete_data_loglike_gradient (score), *_sufficient_statistics, zero */
 enum pfg_stat { PFG_STAT_SCORE = 0, PFG_STAT_SUFF = 1, PFG_STAT_NONE = 2,
                 /* k-step-ahead predictive log-likelihoods accumulated with the filter's
@@ -277,7 +289,8 @@ int pfg_launch_device_traced(pfg_ctx *ctx, int model, int kernel, int dtype, int
 int pfg_last_traced(pfg_ctx *ctx);
 /* as pfg_launch_device for a batch whose descriptors all have smoother = `smoother`
  * (PFG_SMOOTHER_PARIS, _NEMETH_SYSTEMATIC and _POYIADJIS_N2 have their own kernel instantiations;
- * the plain entry point serves NEMETH / FILTER) */
+ * the plain entry point serves NEMETH / FILTER).  PFG_SMOOTHER_KALMAN: the exact-score kernel, one lane per
+ * descriptor (kernel, rng and n_max are ignored; every descriptor brings its scratch) */
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother,
                                int n_max, int B, const pfg_dev_problem *dev_probs, void *hip_stream);
 /* N above the one-workgroup kernels' maximum (16384 < N <= 4194304; the reference has no limit and its bias experiments

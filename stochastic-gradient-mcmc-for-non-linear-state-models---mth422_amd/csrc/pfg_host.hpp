@@ -96,6 +96,7 @@ enum class Family {
     Mem,           // large-N kernel (state in an HBM scratch); lw4: N <= 4096, log-weights in registers
     Big,           // large-N kernel, device-generator fast path for np2 particle slots
     Grid,          // whole-GPU window above the one-workgroup kernels' maximum (pfg_grid_kernel.hpp), tile class (ppt, kmax)
+    Kalman,        // exact Kalman score of LGSSM windows (PFG_SMOOTHER_KALMAN, pfg_kalman.hip): one lane per window
 };
 
 struct LaunchPlan {
@@ -111,7 +112,7 @@ struct LaunchPlan {
     int kmax = 0, tiles = 0, t_max = 0, phase = -1;   // Grid
     bool cdf_single = false;     // Grid, REPLAY: the lone-workgroup CDF kernel
     size_t lds = 0;              // dynamic LDS of the kernel (Grid: of its timestep kernel)
-    size_t scratch = 0;          // per-window HBM scratch, bytes (0: none)
+    size_t scratch = 0;          // per-window HBM scratch, bytes (0: none; Kalman: from the longest window, n_max)
     const char *name = nullptr;  // pfg_last_variant once the kernel is chosen
     int rc = PFG_OK;             // an error found once the kernel is chosen (name set) or before (name NULL)
     std::string err;
@@ -139,5 +140,8 @@ constexpr bool reg_score1_twin(int model, int rng, bool f64, int nt, int ppt, bo
 // pfg_inst_*.hip via pfg_launch.hpp, declared here for the dispatcher in pfgrad.hip.
 template <int MODEL, int KERNEL, int RNG>
 int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st);
+
+// Launch of the Kalman window kernel (Family::Kalman), defined in pfg_kalman.hip.
+int launch_kalman(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st);
 
 }  // namespace pfg_host

@@ -165,6 +165,7 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
     const char *force = std::getenv("PFGRAD_VARIANT");
     int v = -1;
     if (caller == Caller::Grid) p.family = Family::Grid;
+    else if (smoother == PFG_SMOOTHER_KALMAN) p.family = Family::Kalman;
     else if (smoother == PFG_SMOOTHER_PARIS) p.family = Family::Paris;
     else if (smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) p.family = Family::Systematic;
     else if (smoother == PFG_SMOOTHER_POYIADJIS_N2) p.family = Family::N2;
@@ -264,10 +265,23 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
             });
             break;
         }
+        case Family::Kalman:
+            // n_max = the longest window [t1, tL) of the batch: the backward messages stored per window
+            p.name = "kalman";
+            p.traced = false;
+            p.scratch = (16 * ((size_t)n_max + 1) + 255) / 256 * 256;
+            break;
         case Family::None:
             break;
     }
     return p;
+}
+
+// PFG_SMOOTHER_KALMAN ignores the proposal kernel and the generator
+int check_kalman(pfg_ctx *ctx, int model, int dtype) {
+    if (model != PFG_MODEL_LGSSM) return fail(ctx, PFG_ERR_UNSUPPORTED, "the exact Kalman score (kind = 'marginal') is built for LGSSM only");
+    if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, "the exact Kalman score (kind = 'marginal') is built for dtype f64 only");
+    return PFG_OK;
 }
 
 int check_combo(pfg_ctx *ctx, int model, int kernel, int dtype, int rng) {
@@ -289,6 +303,7 @@ int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, in
         ctx->last_traced = p.traced;
     }
     if (p.rc) return fail(ctx, p.rc, p.err);
+    if (p.family == Family::Kalman) return launch_kalman(ctx, p, B, dp, st);
     return with_types(model, kernel, PFG_F64, rng, [&](auto m, auto k, auto, auto g) {
         return launch_mkr<decltype(m)::value, decltype(k)::value, decltype(g)::value>(ctx, p, B, dp, st);
     });
@@ -296,10 +311,11 @@ int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, in
 
 int dispatch(pfg_ctx *ctx, Caller caller, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
              const pfg_dev_problem *dp, hipStream_t st, bool traced = false, int t_max = 0, int phase = -1) {
-    int rc = check_combo(ctx, model, kernel, dtype, rng);
+    const bool kalman = smoother == PFG_SMOOTHER_KALMAN;
+    int rc = kalman ? check_kalman(ctx, model, dtype) : check_combo(ctx, model, kernel, dtype, rng);
     if (rc) return rc;
     if (B <= 0) return PFG_OK;
-    if (n_max < 1) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
+    if (n_max < 1 && !kalman) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
     if (caller == Caller::Grid && t_max < 0) return fail(ctx, PFG_ERR_INVALID, "T_max must be >= 0");
     return launch(ctx, make_plan(caller, model, dtype, rng, smoother, n_max, B, traced, false, t_max, phase), model, kernel, rng, B, dp, st);
 }
@@ -617,7 +633,7 @@ int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, i
                                int B, const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (!ctx) return PFG_ERR_INVALID;
     if (!dev_probs && B > 0) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_smoother: dev_probs is NULL");
-    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_POYIADJIS_N)
+    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_KALMAN)
         return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
     return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream);
@@ -729,7 +745,8 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     if (B < 0 || (B > 0 && (!ps || !rs))) return fail(ctx, PFG_ERR_INVALID, "pfg_run_batch: NULL problems/results");
     if (B == 0) return PFG_OK;
     const int model = ps[0].model, kernel = ps[0].kernel, dtype = ps[0].dtype, rng = ps[0].rng;
-    int rc = check_combo(ctx, model, kernel, dtype, rng);
+    const bool kalman = ps[0].smoother == PFG_SMOOTHER_KALMAN;     // the exact score: no particles, no streams
+    int rc = kalman ? check_kalman(ctx, model, dtype) : check_combo(ctx, model, kernel, dtype, rng);
     if (rc) return rc;
     const int NS = state_dim(model), H = stat_dim(model), P = theta_dim(model);
 
@@ -757,11 +774,24 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         std::string id = "problem " + std::to_string(b) + ": ";
         if (q.model != model || q.kernel != kernel || q.dtype != dtype || q.rng != rng)
             return fail(ctx, PFG_ERR_INVALID, id + "model/kernel/dtype/rng must match across a batch");
-        if (q.N < 1) return fail(ctx, PFG_ERR_INVALID, id + "N must be >= 1");
+        if (q.N < 1 && !kalman) return fail(ctx, PFG_ERR_INVALID, id + "N must be >= 1");
         if (q.T < 0) return fail(ctx, PFG_ERR_INVALID, id + "T must be >= 0");
         if (q.t1 < 0 || q.tL < q.t1) return fail(ctx, PFG_ERR_INVALID, id + "need 0 <= t1 <= tL");
-        if (q.smoother < PFG_SMOOTHER_NEMETH || q.smoother > PFG_SMOOTHER_POYIADJIS_N2)
+        if ((q.smoother < PFG_SMOOTHER_NEMETH || q.smoother > PFG_SMOOTHER_POYIADJIS_N2) && q.smoother != PFG_SMOOTHER_KALMAN)
             return fail(ctx, PFG_ERR_INVALID, id + "Unrecognized pf (smoother id)");
+        if ((q.smoother == PFG_SMOOTHER_KALMAN) != kalman)
+            return fail(ctx, PFG_ERR_INVALID, id + "the exact Kalman score cannot share a batch with particle filters");
+        if (kalman) {
+            const pfg_result &r = rs[b];
+            if (q.t1 > q.T) return fail(ctx, PFG_ERR_INVALID, id + "need t1 <= T");
+            if (!(q.prior_var > 0.0) || !std::isfinite(q.prior_var) || !std::isfinite(q.prior_mean))
+                return fail(ctx, PFG_ERR_INVALID, id + "the forward message needs a finite precision > 0 (prior_var = 1 / precision)");
+            if (q.init_x || q.elementwise || q.stat == PFG_STAT_PREDICTIVE || q.paris_stream)
+                return fail(ctx, PFG_ERR_INVALID, id + "the exact Kalman score takes no warm start, elementwise or predictive statistic");
+            if (r.x_T || r.logw_T || r.stats_T || r.trace_x || r.trace_logw || r.trace_stats || r.trace_ll || r.trace_anc ||
+                r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats)
+                return fail(ctx, PFG_ERR_INVALID, id + "the exact Kalman score has no particles: only the result record");
+        }
         if ((q.smoother == PFG_SMOOTHER_POYIADJIS_N2) != (ps[0].smoother == PFG_SMOOTHER_POYIADJIS_N2))
             return fail(ctx, PFG_ERR_INVALID, id + "pf = 'poyiadjis_N2' cannot share a batch with other smoothers");
         if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.N > pfg::MEM_MAX_N)
@@ -817,8 +847,9 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         if (!q.theta) return fail(ctx, PFG_ERR_INVALID, id + "theta is NULL");
         if (q.T > 0 && !q.y) return fail(ctx, PFG_ERR_INVALID, id + "observations are NULL");
         const bool raw_stream = q.smoother == PFG_SMOOTHER_PARIS && (q.flags & PFG_FLAG_PARIS_RAW_STREAM) != 0;
-        if (rng == PFG_RNG_REPLAY && !raw_stream && !q.init_x && !q.z0) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs z0");
-        if (rng == PFG_RNG_REPLAY && !raw_stream && q.T > 0 && (!q.u || !q.z)) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs u and z");
+        const bool streams = rng == PFG_RNG_REPLAY && !raw_stream && !kalman;
+        if (streams && !q.init_x && !q.z0) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs z0");
+        if (streams && q.T > 0 && (!q.u || !q.z)) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs u and z");
         if (q.init_x && !q.init_logw) return fail(ctx, PFG_ERR_INVALID, id + "init_x needs init_logw");
         if ((q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) != (ps[0].smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC))
             return fail(ctx, PFG_ERR_INVALID, id + "systematic resampling cannot share a batch with other smoothers");
@@ -832,13 +863,18 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
                      std::fabs(q.theta[0]));
             return fail(ctx, PFG_ERR_NUMERIC, buf);                                   // svm/kernels.py:6-11
         }
-        n_max = q.N > n_max ? q.N : n_max;
+        if (kalman) {           // the plan sizes the scratch from the longest window
+            const int L = (q.tL < q.T ? q.tL : q.T) - q.t1;
+            n_max = L > n_max ? L : n_max;
+        } else {
+            n_max = q.N > n_max ? q.N : n_max;
+        }
         const int nw = q.weights ? (q.tL < q.T ? q.tL : q.T) - q.t1 : 0;
         size_shared(q.y, (size_t)q.T);
         size_shared(q.weights, nw > 0 ? (size_t)nw : 0);
         n_in += PFG_MAX_THETA + (q.step ? 1 : 0);
         n_host += PFG_MAX_THETA + (q.step ? 1 : 0);
-        if (rng == PFG_RNG_REPLAY) {
+        if (rng == PFG_RNG_REPLAY && !kalman) {
             size_in(q.z0, (size_t)q.N);
             size_in(q.u, (size_t)q.T * q.N);
             size_in(q.z, (size_t)q.T * q.N);
@@ -908,7 +944,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     const bool predictive = ps[0].stat == PFG_STAT_PREDICTIVE;   // large-N kernel only (any N)
     const bool n2 = ps[0].smoother == PFG_SMOOTHER_POYIADJIS_N2;
     LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng,
-                                paris ? PFG_SMOOTHER_PARIS : sysres ? PFG_SMOOTHER_NEMETH_SYSTEMATIC : n2 ? PFG_SMOOTHER_POYIADJIS_N2
+                                kalman ? PFG_SMOOTHER_KALMAN : paris ? PFG_SMOOTHER_PARIS : sysres ? PFG_SMOOTHER_NEMETH_SYSTEMATIC : n2 ? PFG_SMOOTHER_POYIADJIS_N2
                                 : score1 ? PFG_SMOOTHER_POYIADJIS_N : PFG_SMOOTHER_NEMETH,
                                 n_max, B, traced, predictive);
     if (plan.rc && !plan.name) return fail(ctx, plan.rc, plan.err);
@@ -1014,7 +1050,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
             for (int j = 0; j < P; ++j) th[j] = q.theta[j];
             d.theta = put(th, PFG_MAX_THETA);
         }
-        if (rng == PFG_RNG_REPLAY) {
+        if (rng == PFG_RNG_REPLAY && !kalman) {
             d.z0 = put(q.z0, q.z0 ? q.N : 0);
             d.u = put(q.u, (size_t)q.T * q.N);
             d.z = put(q.z, (size_t)q.T * q.N);

@@ -15,7 +15,8 @@ from . import _build
 MODEL = {"svm": 0, "garch": 1, "lgssm": 2}
 KERNEL = {"prior": 0, "optimal": 1}
 SMOOTHER = {"nemeth": 0, "filter": 1, "paris": 2, "nemeth_systematic": 3, "poyiadjis_n2": 4,
-            "poyiadjis_n": 5}       # launch-level id only (never in a descriptor): see include/pfgrad.h
+            "poyiadjis_n": 5,       # launch-level id only (never in a descriptor): see include/pfgrad.h
+            "kalman": 6}            # the exact LGSSM score (kind='marginal'), no particles: see include/pfgrad.h
 STAT = {"score": 0, "suff": 1, "none": 2, "predictive": 3}
 DTYPE = {"f64": 0, "f32": 1}
 RNG = {"replay": 0, "device": 1, "philox": 1}     # "philox" = alias of "device" (Philox-keyed lanes)
@@ -26,6 +27,11 @@ FLAG_PARIS_RAW_CARRY = 8         # ... whose first entry is the generator's pend
 MAX_STAT, MAX_THETA, OUT_DOUBLES, MAX_PRED, STAMP_WORDS = 4, 4, 8, 16, 16
 STATE_DIM = {"svm": 1, "garch": 2, "lgssm": 1}
 STAT_DIM = {"svm": 3, "garch": 4, "lgssm": 4}
+
+
+def kalman_scratch_bytes(L):
+    """pfg_dev_problem.scratch a PFG_SMOOTHER_KALMAN window of L = tL - t1 steps needs (include/pfgrad.h)."""
+    return (16 * (int(L) + 1) + 255) // 256 * 256
 THETA_DIM = {"svm": 3, "garch": 4, "lgssm": 4}
 
 PFG_OK, PFG_ERR_INVALID, PFG_ERR_UNSUPPORTED, PFG_ERR_DEVICE, PFG_ERR_NOMEM, PFG_ERR_NUMERIC = 0, -1, -2, -3, -4, -5

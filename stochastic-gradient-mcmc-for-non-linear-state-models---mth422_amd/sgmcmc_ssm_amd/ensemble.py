@@ -74,6 +74,9 @@ class ChainEnsemble(object):
       resampling: 'multinomial' (the reference's) | 'systematic' (extension, parity-unpinned)
       sampler: 'sgld' (sample_sgld + project_parameters) | 'sghmc' (extension: momentum with
                friction `friction` in (0,1]; friction = 1 is SGLD)
+      kind: 'pf' (the particle-filter score) | 'marginal' (LGSSM, dtype 'f64': the exact Kalman score of
+               every window, PFG_SMOOTHER_KALMAN -- the reference's kind='marginal', the KF baseline of its
+               LGSSM experiment; N, pf and resampling are ignored)
       window_sampling: 'host' (one window start per chain and step drawn on the host, keyed by
                (seed, global chain id, step) so that a chain's windows do not depend on the rank
                partition; descriptors are re-uploaded) | 'device' (a Philox-keyed kernel rewrites the descriptors in HBM: the
@@ -85,16 +88,21 @@ class ChainEnsemble(object):
                  lambduh=None, kernel=None, epsilon=0.1, prior=None, subsequence_length=-1,
                  buffer_length=-1, dtype="f64", seed=0, chain_offset=0, device=None,
                  forward_message=None, partition_style=None, resampling="multinomial",
-                 sampler="sgld", friction=0.1, window_sampling="host"):
+                 sampler="sgld", friction=0.1, window_sampling="host", kind="pf"):
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
+        if kind not in ("pf", "marginal"):
+            raise ValueError("kind must be 'pf' or 'marginal'")
+        if kind == "marginal" and (model != "lgssm" or dtype != "f64"):
+            raise NotImplementedError("kind='marginal' (the exact Kalman score) is built for model 'lgssm', dtype 'f64'")
+        self.kind = kind
         Parameters, Prior, Helper = _model_info(model)
         self.model, self.N, self.dtype, self.epsilon = model, int(N), dtype, float(epsilon)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.ctx = _capi.default_context(self.device.index)
         self.helper = Helper(n=1, m=1, forward_message=forward_message)
         self.kernel = self.helper._get_kernel(kernel)
-        if pf == "poyiadjis_N":
+        if pf == "poyiadjis_N" or kind == "marginal":
             self.lambduh = 1.0
         elif pf == "nemeth":
             self.lambduh = 0.95 if lambduh is None else float(lambduh)
@@ -182,7 +190,15 @@ class ChainEnsemble(object):
                 table[start] = self._weights_for(start)
             self._weights_table = table
             self.weights_dev = torch.from_numpy(table).to(dev)
-        pm, pv, _ = self._prior_x(proto, theta0[0])
+        if kind == "marginal":
+            # the message of x_{-1} itself: mean mean_precision / precision, variance 1 / precision
+            fm = self.helper.default_forward_message
+            prec = float(np.reshape(fm['precision'], -1)[0])
+            if not (0.0 < prec < np.inf):
+                raise ValueError("the forward message needs a finite precision > 0, got {0}".format(prec))
+            pm, pv = float(np.reshape(fm['mean_precision'], -1)[0]) / prec, 1.0 / prec
+        else:
+            pm, pv, _ = self._prior_x(proto, theta0[0])
         self._desc = np.zeros(self.C, dtype=_capi.DEV_PROBLEM_DTYPE)
         d = self._desc
         d["theta"] = self.theta_dev.data_ptr() + np.arange(self.C, dtype=np.uint64) * (8 * _capi.MAX_THETA)
@@ -195,17 +211,23 @@ class ChainEnsemble(object):
         d["smoother"], d["stat"] = _capi.SMOOTHER["nemeth"], _capi.STAT["score"]
         if model == "garch" and self.helper.default_forward_message is None:
             d["flags"] = _capi.FLAG_GARCH_STATIONARY_PRIOR
-        if resampling == "systematic":       # extension, see include/pfgrad.h
+        if kind == "marginal":
+            d["smoother"] = _capi.SMOOTHER["kalman"]
+        elif resampling == "systematic":       # extension, see include/pfgrad.h
             if self.N > 1024:
                 raise NotImplementedError("systematic resampling is built for N <= 1024")
             d["smoother"] = _capi.SMOOTHER["nemeth_systematic"]
         elif resampling != "multinomial":
             raise ValueError("Unrecognized resampling = {0}".format(resampling))
-        sb = self.ctx.scratch_bytes(model, dtype, "device", self.N)
+        if kind == "marginal":
+            # the backward messages of the longest window: S (segments: no window is longer), or the whole series
+            sb = _capi.kalman_scratch_bytes(S if S > 0 else self.T)
+        else:
+            sb = self.ctx.scratch_bytes(model, dtype, "device", self.N)
         if sb < 0:
             raise ValueError("N = {0} is above the supported maximum".format(self.N))
         self.scratch_dev = None
-        if sb > 0:       # large-N kernel: particle state lives in HBM (L2-resident), one slab per chain
+        if sb > 0:       # large-N kernel: particle state lives in HBM (L2-resident), one slab per chain (Kalman: messages)
             self.scratch_dev = torch.empty(self.C * sb, dtype=torch.uint8, device=dev)
             d["scratch"] = self.scratch_dev.data_ptr() + np.arange(self.C, dtype=np.uint64) * np.uint64(sb)
         self.steps_done = 0
@@ -307,11 +329,17 @@ class ChainEnsemble(object):
     # ------------------------------------------------------------------------------------
     def launch_pf(self, stream=None, traced=False):
         """Enqueue one particle-filter launch for all chains on `stream` (default: torch's
-        current stream).  Results land in self.out_dev[C, 8] (score columns, loglik).
+        current stream; kind='marginal': the exact Kalman score).  Results land in self.out_dev[C, 8]
+        (score columns, loglik).
         traced=True runs the twin instantiation that honours trace_* / rec_* buffers a caller put into
         the descriptors (tests, diagnostics); the production launch ignores them."""
         st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
-        if traced:
+        if self.kind == "marginal":
+            if traced:
+                raise ValueError("kind='marginal' has no particles to trace")
+            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman",
+                                            1, self.C, self.desc_dev.data_ptr(), st)
+        elif traced:
             self.ctx.launch_device_traced(self.model, self.kernel, self.dtype, "device",
                                           "nemeth_systematic" if self.resampling == "systematic" else "nemeth",
                                           self.N, self.C, self.desc_dev.data_ptr(), st)
@@ -474,7 +502,8 @@ class ChainEnsemble(object):
         return self.theta_dev[:, :self.P].cpu().numpy()
 
     def last_gradient_statistics(self):
-        """[C, h] score estimates and [C] log-likelihood estimates of the latest PF launch."""
+        """[C, h] score estimates and [C] log-likelihood estimates of the latest PF launch (kind='marginal':
+        the exact window scores and forward log-likelihoods)."""
         out = self.out_dev.cpu().numpy()
         return out[:, :_capi.STAT_DIM[self.model]], out[:, 4]
 

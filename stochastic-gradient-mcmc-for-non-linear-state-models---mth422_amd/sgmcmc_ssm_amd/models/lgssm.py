@@ -2,11 +2,17 @@
 
 Exports LGSSMParameters, LGSSMPrior, LGSSMHelper, LGSSMSampler, SeqLGSSMSampler,
 generate_lgssm_data (reference: models/lgssm/{parameters,helper,sampler}.py).  Particle-filter
-entries only: the "prior" and "optimal" proposals (models/lgssm/kernels.py:11-122) and the
-score (helper.py:1270-1277) are model id PFG_MODEL_LGSSM in libpfgrad.so.  The reference's
-Kalman (exact) code is not accelerated; its outputs serve as test fixtures."""
+entries: the "prior" and "optimal" proposals (models/lgssm/kernels.py:11-122) and the score
+(helper.py:1270-1277) are model id PFG_MODEL_LGSSM in libpfgrad.so.  The exact gradient of the
+reference's kind='marginal' -- buffered Kalman messages and the smoothed score
+(helper.py:53-192, 312-420) -- is PFG_SMOOTHER_KALMAN (csrc/pfg_kalman.hip): every sampler entry
+(noisy_gradient, noisy_loglikelihood, sample_sgld / sgrld / sgld_cv, fit*) accepts
+kind='marginal', and LGSSMHelper.gradient_marginal_loglikelihood / marginal_loglikelihood run
+one window on the GPU.  Not built: kind='complete', predictive_loglikelihood(kind='marginal'),
+non-zero backward messages, include_init=False."""
 import numpy as np
 
+from .. import particle_filters as _pf
 from ..base_parameters import (BaseParameters, BasePrior, MatrixVar, CholPrecisionVar,
                                WishartPrecisionPrior, MatrixNormalPrior, install_properties,
                                BasePreconditioner, MatrixPrecond, CholPrecisionPrecond)
@@ -64,11 +70,59 @@ def generate_lgssm_data(T, parameters, initial_message=None, tqdm=None):
 
 class LGSSMHelper(PFHelper):
     """pf_gradient_estimate -> dict(LRinv_vec, LQinv_vec, C, A)  (models/lgssm/helper.py:1136-1142);
-    default kernel 'optimal' for n*m = 1 (:1200-1214)."""
+    default kernel 'optimal' for n*m = 1 (:1200-1214).  The exact (Kalman) gradient and marginal
+    log-likelihood of a window: kalman_problem, gradient_marginal_loglikelihood, marginal_loglikelihood."""
     model = "lgssm"
+    exact = True
     default_kernel = "optimal"
     kernels = ("prior", "optimal")
     score_names = ("LRinv_vec", "LQinv_vec", "C", "A")
+
+    def kalman_problem(self, observations, parameters, subsequence_start=0, subsequence_end=None,
+                       weights=None, forward_message=None, backward_message=None):
+        """One buffered window as a PFG_SMOOTHER_KALMAN problem: forward messages over [0, subsequence_start) from
+        `forward_message` (the message of x_{-1}), backward messages over [subsequence_end, T) from
+        `backward_message`, the exact score and the forward log-likelihood over the window."""
+        if forward_message is None:
+            forward_message = self.default_forward_message
+        if backward_message is not None and (np.any(np.asarray(backward_message['precision']) != 0)
+                                             or np.any(np.asarray(backward_message['mean_precision']) != 0)):
+            raise NotImplementedError("kind='marginal' is built for the zero backward message")
+        precision = float(np.reshape(forward_message['precision'], -1)[0])
+        mean_precision = float(np.reshape(forward_message['mean_precision'], -1)[0])
+        if not (0.0 < precision < np.inf):
+            raise ValueError("the forward message needs a finite precision > 0, got {0}".format(precision))
+        y = np.ascontiguousarray(observations, dtype=float)
+        if y.ndim == 2:
+            if y.shape[1] != 1:
+                raise ValueError("the exact LGSSM gradient supports m = 1 observations only")
+            y = y[:, 0]
+        T = y.shape[0]
+        return dict(model="lgssm", kernel=self.default_kernel, smoother="kalman", stat="score", dtype="f64",
+                    rng="device", N=1, t1=int(subsequence_start), tL=T if subsequence_end is None else int(subsequence_end),
+                    lambduh=1.0, prior_mean=mean_precision / precision, prior_var=1.0 / precision,
+                    y=y, weights=weights, theta=parameters.theta(), flags=0)
+
+    def gradient_marginal_loglikelihood(self, observations, parameters, forward_message=None,
+                                        backward_message=None, weights=None, include_init=True, tqdm=None):
+        """Exact gradient of the (weighted) marginal log-likelihood of `observations`
+        (models/lgssm/helper.py:312-420) -> dict(A, LQinv_vec, C, LRinv_vec)."""
+        if not include_init:
+            raise NotImplementedError("include_init=False is not built (the transition term from x_{-1} is always in)")
+        q = self.kalman_problem(observations, parameters, weights=weights, forward_message=forward_message,
+                                backward_message=backward_message)
+        g = dict(zip(self.score_names, _pf.run_windows([q])[0]["mean_statistic"]))
+        return {var: np.reshape(g[var], np.shape(value)) for var, value in parameters.as_dict().items()}
+
+    def marginal_loglikelihood(self, observations, parameters, forward_message=None, backward_message=None,
+                               weights=None, tqdm=None, **kwargs):
+        """log Pr(y | theta) of `observations` given the forward message, whose log_constant is included
+        (models/lgssm/helper.py:195-233; with the zero backward message the combination term is 0)."""
+        if forward_message is None:
+            forward_message = self.default_forward_message
+        q = self.kalman_problem(observations, parameters, weights=weights, forward_message=forward_message,
+                                backward_message=backward_message)
+        return forward_message['log_constant'] + _pf.run_windows([q])[0]["loglikelihood_estimate"]
 
 
 class LGSSMSampler(SGMCMCSampler):

@@ -1,6 +1,7 @@
 """SG-MCMC samplers whose noisy gradient comes from the HIP particle filter.
 
-Host-side orchestration of the reference's `sgmcmc_ssm/sgmcmc_sampler.py` for `kind='pf'`:
+Host-side orchestration of the reference's `sgmcmc_ssm/sgmcmc_sampler.py` for `kind='pf'`, and
+for LGSSM also `kind='marginal'` (the exact Kalman gradient, one lane per window in libpfgrad.so):
 window sampling, importance weights, prior gradient, 1/T scaling, the SGD / ADAGRAD / SGLD
 parameter updates and the fit loops.  All of it costs O(#parameters) per step and stays in
 Python; everything O(N*T) runs in libpfgrad.so.
@@ -11,7 +12,7 @@ kernel launch with one workgroup per window.
 
 Behaviour kept from the reference on purpose (SURVEY.md 8b "quirks"):
   * kind='pf' always differentiates at `self.parameters`, even if `parameters=` is passed
-    (sgmcmc_sampler.py:379).
+    (sgmcmc_sampler.py:379); kind='marginal' differentiates at `parameters` (:295-296).
   * SGLD noise is drawn after the particle filter has consumed its draws, one
     np.random.normal call per variable in `parameters.as_dict()` order (:540-546).
 Consciously changed: NaN / blow-up checks look at every gradient entry, not only the last
@@ -30,6 +31,8 @@ NOISE_NUGGET = 1e-9
 
 _ONLY_PF = ("only kind='pf' is implemented by the MI355X backend; kind='{0}' (analytic / "
             "complete-data paths of the reference) is out of scope (SURVEY.md section 8)")
+_ONLY_PF_OR_MARGINAL = ("kind='{0}' is not implemented by the MI355X backend: kind='pf' for every model, "
+                        "kind='marginal' (exact Kalman gradient) for LGSSM")
 
 
 # ----------------------------------------------------------------------------------------
@@ -76,6 +79,7 @@ class PFHelper(object):
     `pf_loglikelihood_estimate` with the reference's signatures
     (models/svm/helper.py:67-185, models/garch/helper.py:59-170, models/lgssm/helper.py:1016-1143)."""
     model = None                 # 'svm' | 'garch' | 'lgssm'
+    exact = False                # kind='marginal' (an exact gradient, PFG_SMOOTHER_KALMAN) is available
     default_kernel = None
     kernels = ()
     score_names = ()             # dict keys of the gradient, in statistic-column order
@@ -270,9 +274,20 @@ class SGMCMCSampler(object):
                     left_buffer_start=max(0, start - buffer_length),
                     right_buffer_end=min(T, end + buffer_length), weights=weights)
 
-    def _window_problem(self, buffer_dict, observations, stat, **kwargs):
+    def _window_problem(self, buffer_dict, observations, stat, kind='pf', parameters=None, **kwargs):
         rel_start = buffer_dict['subsequence_start'] - buffer_dict['left_buffer_start']
         rel_end = buffer_dict['subsequence_end'] - buffer_dict['left_buffer_start']
+        if kind == 'marginal':
+            # sgmcmc_sampler.py:298-329 (gradient: left buffer, window, right buffer) and :147-174 (log-likelihood:
+            # forward only, so the right buffer is left out); the backward message of the right buffer starts from
+            # self.backward_message, the forward message of the left one from self.forward_message
+            end = buffer_dict['right_buffer_end'] if stat == "score" else buffer_dict['subsequence_end']
+            return self.message_helper.kalman_problem(
+                observations=observations[buffer_dict['left_buffer_start']:end],
+                parameters=self.parameters if parameters is None else parameters,
+                subsequence_start=rel_start, subsequence_end=rel_end, weights=buffer_dict['weights'],
+                forward_message=getattr(self, "forward_message", None),
+                backward_message=getattr(self, "backward_message", None))
         buffer_ = observations[buffer_dict['left_buffer_start']:buffer_dict['right_buffer_end']]
         return self.message_helper.pf_problem(
             observations=buffer_, parameters=self.parameters, subsequence_start=rel_start,
@@ -283,11 +298,17 @@ class SGMCMCSampler(object):
         if kind != 'pf':
             raise NotImplementedError(_ONLY_PF.format(kind))
 
+    def _require_kind(self, kind):
+        """Gradients and noisy log-likelihoods: kind='pf', or kind='marginal' where the model has an exact one."""
+        if kind == 'pf' or (kind == 'marginal' and self.message_helper.exact):
+            return
+        raise NotImplementedError(_ONLY_PF_OR_MARGINAL.format(kind))
+
     # -- log-likelihood --------------------------------------------------------------------------
     def _loglike_problems(self, kind='pf', subsequence_length=-1, minibatch_size=1, buffer_length=10,
                           num_samples=None, observations=None, parameters=None, check_shape=True,
                           **kwargs):
-        self._require_pf(kind)
+        self._require_kind(kind)
         observations = self._get_observations(observations, check_shape=check_shape)
         if kwargs.get("N", None) is None:
             kwargs['N'] = num_samples if num_samples is not None else 1000
@@ -297,7 +318,8 @@ class SGMCMCSampler(object):
             # the reference draws a window and runs its filter inside one loop body (:210-237)
             bd = self._random_subsequence_and_buffers(buffer_length=buffer_length,
                                                       subsequence_length=subsequence_length, T=T)
-            probs.append((self._window_problem(bd, observations, "suff", **kwargs), minibatch_size))
+            # (kind='marginal' evaluates at self.parameters, as the reference does: sgmcmc_sampler.py:158-172)
+            probs.append((self._window_problem(bd, observations, "suff", kind=kind, **kwargs), minibatch_size))
         return probs
 
     def predictive_loglikelihood(self, kind='pf', num_steps_ahead=10, subsequence_length=-1,
@@ -328,7 +350,8 @@ class SGMCMCSampler(object):
         return pred_loglikelihood
 
     def noisy_loglikelihood(self, **kwargs):
-        """Subsequence approximation to the log-likelihood (kind='pf')."""
+        """Subsequence approximation to the log-likelihood (kind='pf'; LGSSM also kind='marginal': the
+        forward-only sum of log Pr(y_t | y_{<t}) over each window, given its left buffer)."""
         kwargs.pop('tqdm', None)
         probs = self._loglike_problems(**kwargs)
         outs = _pf.run_windows([q for q, _ in probs])
@@ -352,8 +375,9 @@ class SGMCMCSampler(object):
                        observations=None, buffer_dicts=None, kind='pf', num_samples=None,
                        parameters=None, **kwargs):
         """All windows of one gradient for ONE series -> [(problem, minibatch_size)].  RNG order
-        as sgmcmc_sampler.py:390-418: every window is drawn first, then each filter's streams."""
-        self._require_pf(kind)
+        as sgmcmc_sampler.py:390-418: every window is drawn first, then each filter's streams.
+        kind='marginal' (LGSSM): the exact Kalman gradient of each window, at `parameters` if given."""
+        self._require_kind(kind)
         observations = self._get_observations(observations, check_shape=False)
         if kwargs.get("N", None) is None:
             kwargs['N'] = num_samples if num_samples is not None else 1000
@@ -364,7 +388,8 @@ class SGMCMCSampler(object):
                 for _ in range(minibatch_size)]
         elif len(buffer_dicts) != minibatch_size:
             raise ValueError("len(buffer_dicts != minibatch_size")
-        probs = [(self._window_problem(bd, observations, "score", **kwargs), minibatch_size)
+        at = parameters if kind == 'marginal' else None
+        probs = [(self._window_problem(bd, observations, "score", kind=kind, parameters=at, **kwargs), minibatch_size)
                  for bd in buffer_dicts]
         for q, _ in probs:
             q["_series_length"] = T          # host-side metadata (Seq rescaling); not sent to the device
@@ -435,7 +460,8 @@ class SGMCMCSampler(object):
         T_total = self._get_T(**kwargs)
         grad_loglike = self._noisy_grad_loglikelihood(**{k: v for k, v in kwargs.items() if k != 'T'})
         # a `parameters=` argument reaches the prior term and the preconditioner only: the
-        # particle filter always runs at self.parameters (sgmcmc_sampler.py:379)
+        # particle filter always runs at self.parameters (sgmcmc_sampler.py:379);
+        # the exact gradient of kind='marginal' is taken at `parameters` (:295-296, _grad_problems)
         at = kwargs.get('parameters', None)
         at = self.parameters if at is None else at
         grad_prior = self.prior.grad_logprior(parameters=at)
@@ -550,7 +576,8 @@ class SGMCMCSampler(object):
         """SGLD with control variates (sgmcmc_sampler.py:569-611): gradient = centering_gradient +
         sub_gradient(parameters) - sub_gradient(centering_parameters) on the SAME windows.  As in
         the reference, with kind='pf' both particle filters run at self.parameters (only the prior
-        term sees centering_parameters) and each consumes its own random draws."""
+        term sees centering_parameters) and each consumes its own random draws; with kind='marginal'
+        the centering gradient is the exact one at centering_parameters."""
         if "preconditioner" in kwargs:
             raise ValueError("Use SGRLD instead")
         buffer_dicts = [self._random_subsequence_and_buffers(
