@@ -85,7 +85,22 @@ enum pfg_smoother { PFG_SMOOTHER_NEMETH = 0, PFG_SMOOTHER_FILTER = 1, PFG_SMOOTH
                      * buffer (noisy_loglikelihood(kind = 'marginal'), sgmcmc_sampler.py:147-174), out[5..7] = 0.
                      * `scratch`: 16 (tL - t1 + 1) bytes rounded up to 256 (pfg_run / pfg_run_batch allocate it;
                      * resident callers supply it).  A batch is all-Kalman or Kalman-free; no trace / final outputs. */
-                    PFG_SMOOTHER_KALMAN = 6 };
+                    PFG_SMOOTHER_KALMAN = 6,
+                    /* Forward-filtering backward-sampling of the latent path, no particles: the reference's
+                     * LGSSMHelper.latent_var_sample(distr = 'joint') (models/lgssm/helper.py:650-698) and, on its paths,
+                     * the complete-data score of kind = 'complete' (sgmcmc_sampler.py:330-362; helper.py:422-491).
+                     * Model LGSSM and dtype F64 only; kernel and lambduh are ignored.  Per descriptor, one workgroup:
+                     * the forward Kalman messages of the whole buffer [0, T) from the message of x_{-1} (prior_mean,
+                     * prior_var as for PFG_SMOOTHER_KALMAN), then N = the number of paths sampled backward, one lane per
+                     * path.  REPLAY: z holds T N standard normals in the reference's draw order, z[k N + s] = path s at
+                     * time T-1-k (one np.random.standard_normal(T N)); z0 / u are not read.  DEVICE: the lane generator
+                     * keyed by (seed, stream, *step_ctr), lane = path.  stat = SCORE: out[0..3] = the complete-data score
+                     * over [t1, tL) with `weights`, averaged over the paths, in the LGSSM score column order (transition
+                     * terms only where x_{t-1} is in the buffer); stat = NONE: 0; out[4..7] = 0.  trace_x (optional):
+                     * the paths, [T][N] with t ascending; no other trace or final output.  `scratch`: 16 (T + 1) bytes
+                     * rounded up to 256, from the whole buffer (pfg_run / pfg_run_batch allocate it; resident callers
+                     * supply it).  A batch is all-FFBS or FFBS-free. */
+                    PFG_SMOOTHER_KALMAN_FFBS = 7 };
 /* additive statistic: *_complete_data_loglike_gradient (score), *_sufficient_statistics, zero */
 enum pfg_stat { PFG_STAT_SCORE = 0, PFG_STAT_SUFF = 1, PFG_STAT_NONE = 2,
                 /* k-step-ahead predictive log-likelihoods accumulated with the filter's
@@ -290,7 +305,9 @@ int pfg_last_traced(pfg_ctx *ctx);
 /* as pfg_launch_device for a batch whose descriptors all have smoother = `smoother`
  * (PFG_SMOOTHER_PARIS, _NEMETH_SYSTEMATIC and _POYIADJIS_N2 have their own kernel instantiations;
  * the plain entry point serves NEMETH / FILTER).  PFG_SMOOTHER_KALMAN: the exact-score kernel, one lane per
- * descriptor (kernel, rng and n_max are ignored; every descriptor brings its scratch) */
+ * descriptor (kernel, rng and n_max are ignored; every descriptor brings its scratch).  PFG_SMOOTHER_KALMAN_FFBS: the
+ * FFBS kernel, one workgroup per descriptor (n_max = the most paths N of a descriptor picks the workgroup size; every
+ * descriptor brings its scratch) */
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother,
                                int n_max, int B, const pfg_dev_problem *dev_probs, void *hip_stream);
 /* N above the one-workgroup kernels' maximum (16384 < N <= 4194304; the reference has no limit and its bias experiments

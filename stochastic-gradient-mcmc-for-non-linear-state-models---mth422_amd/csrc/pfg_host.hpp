@@ -97,6 +97,8 @@ enum class Family {
     Big,           // large-N kernel, device-generator fast path for np2 particle slots
     Grid,          // whole-GPU window above the one-workgroup kernels' maximum (pfg_grid_kernel.hpp), tile class (ppt, kmax)
     Kalman,        // exact Kalman score of LGSSM windows (PFG_SMOOTHER_KALMAN, pfg_kalman.hip): one lane per window
+    KalmanFfbs,    // FFBS paths and complete-data score of LGSSM windows (PFG_SMOOTHER_KALMAN_FFBS, pfg_ffbs.hip): one
+                   // workgroup of nt lanes per window, one lane per path
 };
 
 struct LaunchPlan {
@@ -112,7 +114,8 @@ struct LaunchPlan {
     int kmax = 0, tiles = 0, t_max = 0, phase = -1;   // Grid
     bool cdf_single = false;     // Grid, REPLAY: the lone-workgroup CDF kernel
     size_t lds = 0;              // dynamic LDS of the kernel (Grid: of its timestep kernel)
-    size_t scratch = 0;          // per-window HBM scratch, bytes (0: none; Kalman: from the longest window, n_max)
+    size_t scratch = 0;          // per-window HBM scratch, bytes (0: none; Kalman: from the longest window, n_max;
+                                 // KalmanFfbs: from the longest buffer, t_max)
     const char *name = nullptr;  // pfg_last_variant once the kernel is chosen
     int rc = PFG_OK;             // an error found once the kernel is chosen (name set) or before (name NULL)
     std::string err;
@@ -143,5 +146,8 @@ int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *
 
 // Launch of the Kalman window kernel (Family::Kalman), defined in pfg_kalman.hip.
 int launch_kalman(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st);
+
+// Launch of the FFBS window kernel (Family::KalmanFfbs), defined in pfg_ffbs.hip.
+int launch_ffbs(pfg_ctx *ctx, const LaunchPlan &p, int rng, int B, const pfg_dev_problem *dp, hipStream_t st);
 
 }  // namespace pfg_host

@@ -166,6 +166,7 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
     int v = -1;
     if (caller == Caller::Grid) p.family = Family::Grid;
     else if (smoother == PFG_SMOOTHER_KALMAN) p.family = Family::Kalman;
+    else if (smoother == PFG_SMOOTHER_KALMAN_FFBS) p.family = Family::KalmanFfbs;
     else if (smoother == PFG_SMOOTHER_PARIS) p.family = Family::Paris;
     else if (smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) p.family = Family::Systematic;
     else if (smoother == PFG_SMOOTHER_POYIADJIS_N2) p.family = Family::N2;
@@ -271,6 +272,14 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
             p.traced = false;
             p.scratch = (16 * ((size_t)n_max + 1) + 255) / 256 * 256;
             break;
+        case Family::KalmanFfbs:
+            // n_max = the most paths of a window (the workgroup: one lane per path, lanes loop beyond 256); t_max = the
+            // longest buffer, whose forward messages are stored per window
+            p.name = "kalman_ffbs";
+            p.traced = true;        // trace_x = the sampled paths
+            p.nt = n_max <= 64 ? 64 : n_max <= 128 ? 128 : 256;
+            p.scratch = (16 * ((size_t)t_max + 1) + 255) / 256 * 256;
+            break;
         case Family::None:
             break;
     }
@@ -281,6 +290,14 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
 int check_kalman(pfg_ctx *ctx, int model, int dtype) {
     if (model != PFG_MODEL_LGSSM) return fail(ctx, PFG_ERR_UNSUPPORTED, "the exact Kalman score (kind = 'marginal') is built for LGSSM only");
     if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, "the exact Kalman score (kind = 'marginal') is built for dtype f64 only");
+    return PFG_OK;
+}
+
+// PFG_SMOOTHER_KALMAN_FFBS ignores the proposal kernel; its normals come from REPLAY z or the DEVICE generator
+int check_ffbs(pfg_ctx *ctx, int model, int dtype, int rng) {
+    if (model != PFG_MODEL_LGSSM) return fail(ctx, PFG_ERR_UNSUPPORTED, "FFBS latent paths (kind = 'complete') are built for LGSSM only");
+    if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, "FFBS latent paths (kind = 'complete') are built for dtype f64 only");
+    if (rng != PFG_RNG_REPLAY && rng != PFG_RNG_DEVICE) return fail(ctx, PFG_ERR_INVALID, "bad rng mode");
     return PFG_OK;
 }
 
@@ -304,6 +321,7 @@ int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, in
     }
     if (p.rc) return fail(ctx, p.rc, p.err);
     if (p.family == Family::Kalman) return launch_kalman(ctx, p, B, dp, st);
+    if (p.family == Family::KalmanFfbs) return launch_ffbs(ctx, p, rng, B, dp, st);
     return with_types(model, kernel, PFG_F64, rng, [&](auto m, auto k, auto, auto g) {
         return launch_mkr<decltype(m)::value, decltype(k)::value, decltype(g)::value>(ctx, p, B, dp, st);
     });
@@ -312,7 +330,8 @@ int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, in
 int dispatch(pfg_ctx *ctx, Caller caller, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
              const pfg_dev_problem *dp, hipStream_t st, bool traced = false, int t_max = 0, int phase = -1) {
     const bool kalman = smoother == PFG_SMOOTHER_KALMAN;
-    int rc = kalman ? check_kalman(ctx, model, dtype) : check_combo(ctx, model, kernel, dtype, rng);
+    int rc = kalman ? check_kalman(ctx, model, dtype)
+             : smoother == PFG_SMOOTHER_KALMAN_FFBS ? check_ffbs(ctx, model, dtype, rng) : check_combo(ctx, model, kernel, dtype, rng);
     if (rc) return rc;
     if (B <= 0) return PFG_OK;
     if (n_max < 1 && !kalman) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
@@ -633,7 +652,7 @@ int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, i
                                int B, const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (!ctx) return PFG_ERR_INVALID;
     if (!dev_probs && B > 0) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_smoother: dev_probs is NULL");
-    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_KALMAN)
+    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_KALMAN_FFBS)
         return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     PFG_HIP(ctx, hipSetDevice(ctx->device));
     return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream);
@@ -746,7 +765,9 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     if (B == 0) return PFG_OK;
     const int model = ps[0].model, kernel = ps[0].kernel, dtype = ps[0].dtype, rng = ps[0].rng;
     const bool kalman = ps[0].smoother == PFG_SMOOTHER_KALMAN;     // the exact score: no particles, no streams
-    int rc = kalman ? check_kalman(ctx, model, dtype) : check_combo(ctx, model, kernel, dtype, rng);
+    const bool ffbs = ps[0].smoother == PFG_SMOOTHER_KALMAN_FFBS;  // FFBS paths: N paths, REPLAY normals in z only
+    int rc = kalman ? check_kalman(ctx, model, dtype)
+             : ffbs ? check_ffbs(ctx, model, dtype, rng) : check_combo(ctx, model, kernel, dtype, rng);
     if (rc) return rc;
     const int NS = state_dim(model), H = stat_dim(model), P = theta_dim(model);
 
@@ -755,7 +776,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     // windows of the batch (same pointer and length) count once in both, inputs that lie in caller-registered
     // pinned memory need device space but no staging space (same decisions as `put` / `put_shared` below)
     size_t n_in = 0, n_host = 0, n_out = 0, n_work = 0;
-    int n_max = 0;
+    int n_max = 0, t_max = 0;
     std::unordered_map<const double *, size_t> sized_shared;
     auto size_in = [&](const double *src, size_t n) {
         if (!src || n == 0) return;
@@ -777,8 +798,23 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         if (q.N < 1 && !kalman) return fail(ctx, PFG_ERR_INVALID, id + "N must be >= 1");
         if (q.T < 0) return fail(ctx, PFG_ERR_INVALID, id + "T must be >= 0");
         if (q.t1 < 0 || q.tL < q.t1) return fail(ctx, PFG_ERR_INVALID, id + "need 0 <= t1 <= tL");
-        if ((q.smoother < PFG_SMOOTHER_NEMETH || q.smoother > PFG_SMOOTHER_POYIADJIS_N2) && q.smoother != PFG_SMOOTHER_KALMAN)
+        if ((q.smoother < PFG_SMOOTHER_NEMETH || q.smoother > PFG_SMOOTHER_POYIADJIS_N2) && q.smoother != PFG_SMOOTHER_KALMAN &&
+            q.smoother != PFG_SMOOTHER_KALMAN_FFBS)
             return fail(ctx, PFG_ERR_INVALID, id + "Unrecognized pf (smoother id)");
+        if ((q.smoother == PFG_SMOOTHER_KALMAN_FFBS) != ffbs)
+            return fail(ctx, PFG_ERR_INVALID, id + "FFBS latent paths cannot share a batch with other smoothers");
+        if (ffbs) {
+            const pfg_result &r = rs[b];
+            if (q.t1 > q.T) return fail(ctx, PFG_ERR_INVALID, id + "need t1 <= T");
+            if (!(q.prior_var > 0.0) || !std::isfinite(q.prior_var) || !std::isfinite(q.prior_mean))
+                return fail(ctx, PFG_ERR_INVALID, id + "the forward message needs a finite precision > 0 (prior_var = 1 / precision)");
+            if (q.init_x || q.elementwise || q.paris_stream || (q.stat != PFG_STAT_SCORE && q.stat != PFG_STAT_NONE))
+                return fail(ctx, PFG_ERR_INVALID, id + "FFBS latent paths take no warm start or elementwise statistic; stat is score or none");
+            if (r.x_T || r.logw_T || r.stats_T || r.trace_logw || r.trace_stats || r.trace_ll || r.trace_anc ||
+                r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats)
+                return fail(ctx, PFG_ERR_INVALID, id + "FFBS latent paths have no particles: only the result record and trace_x (the paths)");
+            if (rng == PFG_RNG_REPLAY && q.T > 0 && !q.z) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY FFBS needs z (T N normals)");
+        }
         if ((q.smoother == PFG_SMOOTHER_KALMAN) != kalman)
             return fail(ctx, PFG_ERR_INVALID, id + "the exact Kalman score cannot share a batch with particle filters");
         if (kalman) {
@@ -847,7 +883,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         if (!q.theta) return fail(ctx, PFG_ERR_INVALID, id + "theta is NULL");
         if (q.T > 0 && !q.y) return fail(ctx, PFG_ERR_INVALID, id + "observations are NULL");
         const bool raw_stream = q.smoother == PFG_SMOOTHER_PARIS && (q.flags & PFG_FLAG_PARIS_RAW_STREAM) != 0;
-        const bool streams = rng == PFG_RNG_REPLAY && !raw_stream && !kalman;
+        const bool streams = rng == PFG_RNG_REPLAY && !raw_stream && !kalman && !ffbs;
         if (streams && !q.init_x && !q.z0) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs z0");
         if (streams && q.T > 0 && (!q.u || !q.z)) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs u and z");
         if (q.init_x && !q.init_logw) return fail(ctx, PFG_ERR_INVALID, id + "init_x needs init_logw");
@@ -869,12 +905,15 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         } else {
             n_max = q.N > n_max ? q.N : n_max;
         }
+        if (ffbs) t_max = q.T > t_max ? q.T : t_max;      // the plan sizes the scratch from the longest buffer
         const int nw = q.weights ? (q.tL < q.T ? q.tL : q.T) - q.t1 : 0;
         size_shared(q.y, (size_t)q.T);
         size_shared(q.weights, nw > 0 ? (size_t)nw : 0);
         n_in += PFG_MAX_THETA + (q.step ? 1 : 0);
         n_host += PFG_MAX_THETA + (q.step ? 1 : 0);
-        if (rng == PFG_RNG_REPLAY && !kalman) {
+        if (rng == PFG_RNG_REPLAY && ffbs) {
+            size_in(q.z, (size_t)q.T * q.N);
+        } else if (rng == PFG_RNG_REPLAY && !kalman) {
             size_in(q.z0, (size_t)q.N);
             size_in(q.u, (size_t)q.T * q.N);
             size_in(q.z, (size_t)q.T * q.N);
@@ -899,7 +938,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         if (r.x_T) n_out += (size_t)q.N * NS;
         if (r.logw_T) n_out += q.N;
         if (r.stats_T) n_out += (size_t)q.N * H;
-        if (r.trace_x) n_out += (size_t)(q.T + 1) * q.N * NS;
+        if (r.trace_x) n_out += (size_t)(q.T + (ffbs ? 0 : 1)) * q.N * NS;      // FFBS: the paths [T][N]
         if (r.trace_logw) n_out += (size_t)(q.T + 1) * q.N;
         if (r.trace_stats) n_out += (size_t)(q.T + 1) * q.N * H;
         if (r.trace_ll) n_out += (size_t)q.T + 1;
@@ -929,7 +968,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         }
         if (r.trace_anc && !r.trace_x) return fail(ctx, PFG_ERR_INVALID, id + "trace_anc needs trace_x");
         if ((r.logw_T || r.stats_T) && !r.x_T) return fail(ctx, PFG_ERR_INVALID, id + "logw_T/stats_T need x_T");
-        if ((r.trace_logw == nullptr) != (r.trace_x == nullptr))
+        if (!ffbs && (r.trace_logw == nullptr) != (r.trace_x == nullptr))
             return fail(ctx, PFG_ERR_INVALID, id + "trace_x and trace_logw go together");
         if (r.trace_stats && !r.trace_x) return fail(ctx, PFG_ERR_INVALID, id + "trace_stats needs trace_x");
     }
@@ -944,9 +983,10 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     const bool predictive = ps[0].stat == PFG_STAT_PREDICTIVE;   // large-N kernel only (any N)
     const bool n2 = ps[0].smoother == PFG_SMOOTHER_POYIADJIS_N2;
     LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng,
-                                kalman ? PFG_SMOOTHER_KALMAN : paris ? PFG_SMOOTHER_PARIS : sysres ? PFG_SMOOTHER_NEMETH_SYSTEMATIC : n2 ? PFG_SMOOTHER_POYIADJIS_N2
+                                ffbs ? PFG_SMOOTHER_KALMAN_FFBS : kalman ? PFG_SMOOTHER_KALMAN : paris ? PFG_SMOOTHER_PARIS
+                                : sysres ? PFG_SMOOTHER_NEMETH_SYSTEMATIC : n2 ? PFG_SMOOTHER_POYIADJIS_N2
                                 : score1 ? PFG_SMOOTHER_POYIADJIS_N : PFG_SMOOTHER_NEMETH,
-                                n_max, B, traced, predictive);
+                                n_max, B, traced, predictive, t_max);
     if (plan.rc && !plan.name) return fail(ctx, plan.rc, plan.err);
     if (plan.family == Family::Grid) {
         for (int b = 0; b < B; ++b) {
@@ -1050,7 +1090,9 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
             for (int j = 0; j < P; ++j) th[j] = q.theta[j];
             d.theta = put(th, PFG_MAX_THETA);
         }
-        if (rng == PFG_RNG_REPLAY && !kalman) {
+        if (rng == PFG_RNG_REPLAY && ffbs) {
+            d.z = put(q.z, (size_t)q.T * q.N);
+        } else if (rng == PFG_RNG_REPLAY && !kalman) {
             d.z0 = put(q.z0, q.z0 ? q.N : 0);
             d.u = put(q.u, (size_t)q.T * q.N);
             d.z = put(q.z, (size_t)q.T * q.N);
@@ -1086,7 +1128,8 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         d.final_x = take(r.x_T != nullptr, (size_t)q.N * NS);
         d.final_logw = take(r.logw_T != nullptr, q.N);
         d.final_stats = take(r.stats_T != nullptr, (size_t)q.N * H);
-        d.trace_x = take(r.trace_x != nullptr, (size_t)(q.T + 1) * q.N * NS);
+        const size_t trace_rows = (size_t)q.T + (ffbs ? 0 : 1);
+        d.trace_x = take(r.trace_x != nullptr, trace_rows * q.N * NS);
         d.trace_logw = take(r.trace_logw != nullptr, (size_t)(q.T + 1) * q.N);
         d.trace_stats = take(r.trace_stats != nullptr, (size_t)(q.T + 1) * q.N * H);
         d.trace_ll = take(r.trace_ll != nullptr, (size_t)q.T + 1);
@@ -1162,7 +1205,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
         fetch(r.x_T, d.final_x, (size_t)q.N * NS);
         fetch(r.logw_T, d.final_logw, q.N);
         fetch(r.stats_T, d.final_stats, (size_t)q.N * H);
-        fetch(r.trace_x, d.trace_x, (size_t)(q.T + 1) * q.N * NS);
+        fetch(r.trace_x, d.trace_x, ((size_t)q.T + (ffbs ? 0 : 1)) * q.N * NS);
         fetch(r.trace_logw, d.trace_logw, (size_t)(q.T + 1) * q.N);
         fetch(r.trace_stats, d.trace_stats, (size_t)(q.T + 1) * q.N * H);
         fetch(r.trace_ll, d.trace_ll, (size_t)q.T + 1);

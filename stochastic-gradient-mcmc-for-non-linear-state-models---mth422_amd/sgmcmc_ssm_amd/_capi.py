@@ -16,7 +16,8 @@ MODEL = {"svm": 0, "garch": 1, "lgssm": 2}
 KERNEL = {"prior": 0, "optimal": 1}
 SMOOTHER = {"nemeth": 0, "filter": 1, "paris": 2, "nemeth_systematic": 3, "poyiadjis_n2": 4,
             "poyiadjis_n": 5,       # launch-level id only (never in a descriptor): see include/pfgrad.h
-            "kalman": 6}            # the exact LGSSM score (kind='marginal'), no particles: see include/pfgrad.h
+            "kalman": 6,            # the exact LGSSM score (kind='marginal'), no particles: see include/pfgrad.h
+            "kalman_ffbs": 7}       # FFBS latent paths of LGSSM and their complete-data score (kind='complete')
 STAT = {"score": 0, "suff": 1, "none": 2, "predictive": 3}
 DTYPE = {"f64": 0, "f32": 1}
 RNG = {"replay": 0, "device": 1, "philox": 1}     # "philox" = alias of "device" (Philox-keyed lanes)
@@ -404,7 +405,11 @@ class Context:
                     setattr(p, name, _ptr(a))
             if arrs["weights"] is not None and arrs["weights"].shape[0] < p.tL - p.t1:
                 raise ValueError("weights shorter than tL - t1")
-            if p.rng == RNG["replay"] and not (p.flags & FLAG_PARIS_RAW_STREAM):
+            ffbs = p.smoother == SMOOTHER["kalman_ffbs"]
+            if ffbs and p.rng == RNG["replay"]:
+                if arrs["z"] is None or arrs["z"].shape[0] != T * N:
+                    raise ValueError("FFBS replay normals z must have T*N entries")
+            elif p.rng == RNG["replay"] and not (p.flags & FLAG_PARIS_RAW_STREAM):
                 if arrs["u"] is None or arrs["z"] is None or arrs["u"].shape[0] != T * N or arrs["z"].shape[0] != T * N:
                     raise ValueError("replay streams u, z must have T*N entries")
                 if arrs["init_x"] is None and (arrs["z0"] is None or arrs["z0"].shape[0] != N):
@@ -428,6 +433,15 @@ class Context:
                 if need and (arrs["pred_z"] is None or arrs["pred_z"].shape[0] != need):
                     raise ValueError("pred_z must have T*(num_steps_ahead+1)*N = {0} entries".format(need))
             is_filter = p.smoother == SMOOTHER["filter"]
+            if ffbs:
+                # FFBS: no particles; want_trace asks for the sampled paths, [T][N] with t ascending
+                if want_final or want_draws or want_elementwise:
+                    raise ValueError("FFBS latent paths have no particles: only want_trace (the paths)")
+                if want_trace:
+                    o["paths"] = np.zeros((T, N))
+                    r.trace_x = _ptr(o["paths"])
+                outs.append(o)
+                continue
             if want_final or want_trace:
                 o["x_t"] = np.zeros((N, ns))
                 o["log_weights"] = np.zeros(N)

@@ -102,6 +102,19 @@ def _tril_to_mat(vec):
     return mat
 
 
+def _pos_def_inv(mat):
+    """Inverse of a symmetric positive-definite matrix through its Cholesky factor (LAPACK dpotrf / dpotri), as
+    the reference's _utils.pos_def_mat_inv."""
+    import scipy.linalg
+    zz, info = scipy.linalg.lapack.dpotrf(mat, False, False)
+    if info != 0:
+        raise RuntimeError("Error in Cholesky Decomposition")
+    inv, info = scipy.linalg.lapack.dpotri(zz)
+    if info != 0:
+        raise RuntimeError("Error in Cholesky Inverse")
+    return np.triu(inv) + np.triu(inv, k=1).T
+
+
 class CholPrecisionVar(object):
     """Covariance X stored as the lower-triangular Cholesky factor of its precision,
     flattened: var_dict['LXinv_vec'].  Accepts X=, LXinv= or LXinv_vec= at construction.
@@ -311,10 +324,11 @@ class BaseParameters(object):
 # priors
 # ----------------------------------------------------------------------------------------
 class WishartPrecisionPrior(object):
-    """Xinv ~ Wishart(df_Xinv, scale_Xinv).  variables/covariance.py:159-317."""
+    """Xinv ~ Wishart(df_Xinv, scale_Xinv).  variables/covariance.py:159-317.  matrix_name: the matrix whose
+    rows X is the covariance of (A for Q, C for R); its hyperparameters enter the conjugate posterior (sample_posterior)."""
 
-    def __init__(self, name, dim):
-        self.name, self.dim = name, dim
+    def __init__(self, name, dim, matrix_name=None):
+        self.name, self.dim, self.matrix_name = name, dim, matrix_name
         self.scale, self.df = 'scale_{0}inv'.format(name), 'df_{0}inv'.format(name)
         self.vec, self.chol, self.prec = 'L{}inv_vec'.format(name), 'L{}inv'.format(name), '{}inv'.format(name)
 
@@ -332,6 +346,31 @@ class WishartPrecisionPrior(object):
 
     def sample(self, prior, var_dict):
         scale, df = prior.hyperparams[self.scale], prior.hyperparams[self.df]
+        draw = scipy.stats.wishart(df=df, scale=scale).rvs()
+        P = np.array([[draw]]) if np.size(scale) == 1 else draw
+        L = np.linalg.cholesky(P)
+        var_dict[self.vec] = L[_tril(L.shape[0])]
+
+    def sample_posterior(self, prior, var_dict, sufficient_stat):
+        """Gibbs draw of Xinv given the sufficient statistic sufficient_stat[name] (variables/covariance.py:207-240):
+        the matrix prior's mean and column variances enter the Schur complement, then one Wishart draw."""
+        if self.matrix_name is None:
+            raise RuntimeError("matrix_name not specified for {0}".format(self.name))
+        mean = prior.hyperparams['mean_{0}'.format(self.matrix_name)]
+        var_col = prior.hyperparams['var_col_{0}'.format(self.matrix_name)]
+        mean_prec = mean * var_col ** -1
+        prec = np.diag(var_col ** -1)
+        ss = sufficient_stat[self.name]
+        S_prevprev = prec + ss['S_prevprev']
+        S_curprev = mean_prec + ss['S_curprev']
+        if len(np.shape(prec)) == 1:
+            S_curcur = np.outer(mean, mean_prec) + ss['S_curcur']
+            S_schur = S_curcur - np.outer(S_curprev, S_curprev) / S_prevprev
+        else:
+            S_curcur = np.matmul(mean, mean_prec.T) + ss['S_curcur']
+            S_schur = S_curcur - np.matmul(S_curprev, np.linalg.solve(S_prevprev, S_curprev.T))
+        df = prior.hyperparams[self.df] + ss['S_count']
+        scale = np.linalg.inv(np.linalg.inv(prior.hyperparams[self.scale]) + S_schur)
         draw = scipy.stats.wishart(df=df, scale=scale).rvs()
         P = np.array([[draw]]) if np.size(scale) == 1 else draw
         L = np.linalg.cholesky(P)
@@ -394,6 +433,21 @@ class MatrixNormalPrior(object):
         var_dict[self.name] = scipy.stats.matrix_normal(
             mean=prior.hyperparams[self.mean], rowcov=np.linalg.inv(P),
             colcov=np.diag(prior.hyperparams[self.var_col])).rvs()
+
+    def sample_posterior(self, prior, var_dict, sufficient_stat):
+        """Gibbs draw of M given its row covariance (drawn first) and sufficient_stat[name]
+        (variables/matrices.py:556-580 square, :1022-1046 rect)."""
+        if self.row_vec not in var_dict:
+            raise ValueError("Missing {}: sample {} first".format(self.row_vec, self.row_cov))
+        mean, var_col = prior.hyperparams[self.mean], prior.hyperparams[self.var_col]
+        L = _tril_to_mat(var_dict[self.row_vec])
+        P = L.dot(L.T) + 1e-9 * np.eye(L.shape[0])
+        ss = sufficient_stat[self.name]
+        S_prevprev = np.diag(var_col ** -1) + ss['S_prevprev']
+        S_curprev = mean * var_col ** -1 + ss['S_curprev']
+        var_dict[self.name] = scipy.stats.matrix_normal(
+            mean=np.linalg.solve(S_prevprev, S_curprev.T).T, rowcov=_pos_def_inv(P),
+            colcov=_pos_def_inv(S_prevprev)).rvs()
 
     def logprior(self, prior, parameters):
         mean, var_col = prior.hyperparams[self.mean], prior.hyperparams[self.var_col]
@@ -490,6 +544,14 @@ class BasePrior(object):
         var_dict = {}
         for block in self._blocks:
             block.sample(self, var_dict)
+        return self._Parameters(**var_dict)
+
+    def sample_posterior(self, sufficient_stat, **kwargs):
+        """Conjugate (Gibbs) draw of the parameters given sufficient statistics, block by block in the order of
+        _blocks (base_parameters.py:160-167)."""
+        var_dict = {}
+        for block in self._blocks:
+            block.sample_posterior(self, var_dict, sufficient_stat)
         return self._Parameters(**var_dict)
 
     def logprior(self, parameters, **kwargs):

@@ -76,7 +76,11 @@ class ChainEnsemble(object):
                friction `friction` in (0,1]; friction = 1 is SGLD)
       kind: 'pf' (the particle-filter score) | 'marginal' (LGSSM, dtype 'f64': the exact Kalman score of
                every window, PFG_SMOOTHER_KALMAN -- the reference's kind='marginal', the KF baseline of its
-               LGSSM experiment; N, pf and resampling are ignored)
+               LGSSM experiment; N, pf and resampling are ignored) | 'complete' (LGSSM, dtype 'f64': the
+               complete-data score averaged over num_samples FFBS paths of every window's buffer,
+               PFG_SMOOTHER_KALMAN_FFBS with the device generator -- the reference's kind='complete', the
+               MC row of its LGSSM experiment; N, pf and resampling are ignored)
+      num_samples: kind='complete': the paths per window
       window_sampling: 'host' (one window start per chain and step drawn on the host, keyed by
                (seed, global chain id, step) so that a chain's windows do not depend on the rank
                partition; descriptors are re-uploaded) | 'device' (a Philox-keyed kernel rewrites the descriptors in HBM: the
@@ -88,13 +92,19 @@ class ChainEnsemble(object):
                  lambduh=None, kernel=None, epsilon=0.1, prior=None, subsequence_length=-1,
                  buffer_length=-1, dtype="f64", seed=0, chain_offset=0, device=None,
                  forward_message=None, partition_style=None, resampling="multinomial",
-                 sampler="sgld", friction=0.1, window_sampling="host", kind="pf"):
+                 sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None):
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
-        if kind not in ("pf", "marginal"):
-            raise ValueError("kind must be 'pf' or 'marginal'")
+        if kind not in ("pf", "marginal", "complete"):
+            raise ValueError("kind must be 'pf', 'marginal' or 'complete'")
         if kind == "marginal" and (model != "lgssm" or dtype != "f64"):
             raise NotImplementedError("kind='marginal' (the exact Kalman score) is built for model 'lgssm', dtype 'f64'")
+        if kind == "complete":
+            if model != "lgssm" or dtype != "f64":
+                raise NotImplementedError("kind='complete' (FFBS paths) is built for model 'lgssm', dtype 'f64'")
+            if num_samples is None or int(num_samples) < 1:
+                raise ValueError("kind='complete' needs num_samples >= 1 paths per window")
+            N = int(num_samples)        # the paths of a window take the particles' place in the descriptors
         self.kind = kind
         Parameters, Prior, Helper = _model_info(model)
         self.model, self.N, self.dtype, self.epsilon = model, int(N), dtype, float(epsilon)
@@ -102,7 +112,7 @@ class ChainEnsemble(object):
         self.ctx = _capi.default_context(self.device.index)
         self.helper = Helper(n=1, m=1, forward_message=forward_message)
         self.kernel = self.helper._get_kernel(kernel)
-        if pf == "poyiadjis_N" or kind == "marginal":
+        if pf == "poyiadjis_N" or kind in ("marginal", "complete"):
             self.lambduh = 1.0
         elif pf == "nemeth":
             self.lambduh = 0.95 if lambduh is None else float(lambduh)
@@ -190,7 +200,7 @@ class ChainEnsemble(object):
                 table[start] = self._weights_for(start)
             self._weights_table = table
             self.weights_dev = torch.from_numpy(table).to(dev)
-        if kind == "marginal":
+        if kind in ("marginal", "complete"):
             # the message of x_{-1} itself: mean mean_precision / precision, variance 1 / precision
             fm = self.helper.default_forward_message
             prec = float(np.reshape(fm['precision'], -1)[0])
@@ -213,6 +223,8 @@ class ChainEnsemble(object):
             d["flags"] = _capi.FLAG_GARCH_STATIONARY_PRIOR
         if kind == "marginal":
             d["smoother"] = _capi.SMOOTHER["kalman"]
+        elif kind == "complete":
+            d["smoother"] = _capi.SMOOTHER["kalman_ffbs"]
         elif resampling == "systematic":       # extension, see include/pfgrad.h
             if self.N > 1024:
                 raise NotImplementedError("systematic resampling is built for N <= 1024")
@@ -222,6 +234,9 @@ class ChainEnsemble(object):
         if kind == "marginal":
             # the backward messages of the longest window: S (segments: no window is longer), or the whole series
             sb = _capi.kalman_scratch_bytes(S if S > 0 else self.T)
+        elif kind == "complete":
+            # the forward messages of the longest buffer: a window and its two buffers, or the whole series
+            sb = _capi.kalman_scratch_bytes(min(self.T, S + 2 * self.B) if S > 0 else self.T)
         else:
             sb = self.ctx.scratch_bytes(model, dtype, "device", self.N)
         if sb < 0:
@@ -329,7 +344,7 @@ class ChainEnsemble(object):
     # ------------------------------------------------------------------------------------
     def launch_pf(self, stream=None, traced=False):
         """Enqueue one particle-filter launch for all chains on `stream` (default: torch's
-        current stream; kind='marginal': the exact Kalman score).  Results land in self.out_dev[C, 8]
+        current stream; kind='marginal': the exact Kalman score; kind='complete': the FFBS score).  Results land in self.out_dev[C, 8]
         (score columns, loglik).
         traced=True runs the twin instantiation that honours trace_* / rec_* buffers a caller put into
         the descriptors (tests, diagnostics); the production launch ignores them."""
@@ -339,6 +354,11 @@ class ChainEnsemble(object):
                 raise ValueError("kind='marginal' has no particles to trace")
             self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman",
                                             1, self.C, self.desc_dev.data_ptr(), st)
+        elif self.kind == "complete":
+            if traced:
+                raise ValueError("kind='complete' has no particles to trace")
+            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman_ffbs",
+                                            self.N, self.C, self.desc_dev.data_ptr(), st)
         elif traced:
             self.ctx.launch_device_traced(self.model, self.kernel, self.dtype, "device",
                                           "nemeth_systematic" if self.resampling == "systematic" else "nemeth",

@@ -522,17 +522,18 @@ def _to_reference_dict(o, q):
             out["statistics"] = o["statistics"]
     for src, dst in (("x_t", "x_t"), ("log_weights", "log_weights"), ("all_x_t", "all_x_t"),
                      ("all_log_weights", "all_log_weights"), ("all_statistics", "all_statistics"),
-                     ("all_loglikelihood_estimate", "all_loglikelihood_estimate")):
+                     ("all_loglikelihood_estimate", "all_loglikelihood_estimate"), ("paths", "paths")):
         if src in o:
             out[dst] = o[src]
     return out
 
 
-def run_windows(problems, ctx=None, want_final=False):
-    """Many independent windows (same model/kernel/dtype/rng) in ONE launch, one workgroup each."""
+def run_windows(problems, ctx=None, want_final=False, want_paths=False):
+    """Many independent windows (same model/kernel/dtype/rng) in ONE launch, one workgroup each.
+    want_paths: FFBS windows (smoother 'kalman_ffbs') also return their sampled paths, out['paths'] [T, N]."""
     ctx = ctx or _capi.default_context()
     todo = [q for q in problems if "_result" not in q]
-    outs = iter(ctx.run_batch(todo, want_final=want_final) if todo else [])
+    outs = iter(ctx.run_batch(todo, want_final=want_final, want_trace=want_paths) if todo else [])
     res = [_to_reference_dict(q["_result"] if "_result" in q else next(outs), q) for q in problems]
     _recycle_streams(problems)
     return res

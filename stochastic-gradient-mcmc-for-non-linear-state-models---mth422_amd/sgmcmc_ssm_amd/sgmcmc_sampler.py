@@ -1,7 +1,9 @@
 """SG-MCMC samplers whose noisy gradient comes from the HIP particle filter.
 
 Host-side orchestration of the reference's `sgmcmc_ssm/sgmcmc_sampler.py` for `kind='pf'`, and
-for LGSSM also `kind='marginal'` (the exact Kalman gradient, one lane per window in libpfgrad.so):
+for LGSSM also `kind='marginal'` (the exact Kalman gradient, one lane per window in libpfgrad.so)
+and `kind='complete'` (the complete-data score averaged over num_samples FFBS paths per window,
+one workgroup per window):
 window sampling, importance weights, prior gradient, 1/T scaling, the SGD / ADAGRAD / SGLD
 parameter updates and the fit loops.  All of it costs O(#parameters) per step and stays in
 Python; everything O(N*T) runs in libpfgrad.so.
@@ -12,11 +14,22 @@ kernel launch with one workgroup per window.
 
 Behaviour kept from the reference on purpose (SURVEY.md 8b "quirks"):
   * kind='pf' always differentiates at `self.parameters`, even if `parameters=` is passed
-    (sgmcmc_sampler.py:379); kind='marginal' differentiates at `parameters` (:295-296).
+    (sgmcmc_sampler.py:379); kind='marginal' and kind='complete' differentiate at `parameters`
+    (:295-296).
+  * kind='complete' draws every window first, then one np.random.standard_normal(T_buf * S) per
+    window (what its sequence of multivariate_normal calls draws, :330-362), then the update's noise.
   * SGLD noise is drawn after the particle filter has consumed its draws, one
     np.random.normal call per variable in `parameters.as_dict()` order (:540-546).
-Consciously changed: NaN / blow-up checks look at every gradient entry, not only the last
-dict key (:420-424 leaks the loop variable).
+Consciously changed:
+  * NaN / blow-up checks look at every gradient entry, not only the last dict key (:420-424 leaks
+    the loop variable).
+  * kind='complete' returns the complete-data score the reference's helper means to return: its
+    gradient_complete_data_loglikelihood (models/lgssm/helper.py:422-491) builds `grad` from
+    parameters.as_dict() (keys LQinv_vec, LRinv_vec) and then adds to grad['LQinv'] / grad['LRinv'],
+    so as shipped it always raises KeyError('LQinv'); here the matrix-shaped LQinv / LRinv
+    gradients are accumulated and returned as the _vec entries, as its last two lines intend.
+  * kind='complete' needs num_samples: the reference's num_samples=None single-path estimator is
+    num_samples=1 here (the same draws, values equal up to rounding).
 """
 import logging
 import time
@@ -33,6 +46,8 @@ _ONLY_PF = ("only kind='pf' is implemented by the MI355X backend; kind='{0}' (an
             "complete-data paths of the reference) is out of scope (SURVEY.md section 8)")
 _ONLY_PF_OR_MARGINAL = ("kind='{0}' is not implemented by the MI355X backend: kind='pf' for every model, "
                         "kind='marginal' (exact Kalman gradient) for LGSSM")
+_COMPLETE_NEEDS_SAMPLES = ("kind='complete' is built with num_samples FFBS paths per window: the reference's "
+                           "num_samples=None single-path estimator is num_samples=1 (the same draws)")
 
 
 # ----------------------------------------------------------------------------------------
@@ -277,6 +292,14 @@ class SGMCMCSampler(object):
     def _window_problem(self, buffer_dict, observations, stat, kind='pf', parameters=None, **kwargs):
         rel_start = buffer_dict['subsequence_start'] - buffer_dict['left_buffer_start']
         rel_end = buffer_dict['subsequence_end'] - buffer_dict['left_buffer_start']
+        if kind == 'complete':
+            # sgmcmc_sampler.py:330-362: S FFBS paths of the whole buffer (forward message self.forward_message), the
+            # complete-data score of the window on them; the buffer's T_buf * S normals are drawn here
+            return self.message_helper.ffbs_problem(
+                observations=observations[buffer_dict['left_buffer_start']:buffer_dict['right_buffer_end']],
+                parameters=self.parameters if parameters is None else parameters, num_samples=kwargs['N'],
+                subsequence_start=rel_start, subsequence_end=rel_end, weights=buffer_dict['weights'],
+                forward_message=getattr(self, "forward_message", None))
         if kind == 'marginal':
             # sgmcmc_sampler.py:298-329 (gradient: left buffer, window, right buffer) and :147-174 (log-likelihood:
             # forward only, so the right buffer is left out); the backward message of the right buffer starts from
@@ -298,9 +321,14 @@ class SGMCMCSampler(object):
         if kind != 'pf':
             raise NotImplementedError(_ONLY_PF.format(kind))
 
-    def _require_kind(self, kind):
-        """Gradients and noisy log-likelihoods: kind='pf', or kind='marginal' where the model has an exact one."""
+    def _require_kind(self, kind, num_samples=None, gradient=False):
+        """Gradients and noisy log-likelihoods: kind='pf', or kind='marginal' where the model has an exact one;
+        gradients also kind='complete' (FFBS paths) there, with num_samples."""
         if kind == 'pf' or (kind == 'marginal' and self.message_helper.exact):
+            return
+        if kind == 'complete' and gradient and self.message_helper.exact:
+            if num_samples is None:
+                raise NotImplementedError(_COMPLETE_NEEDS_SAMPLES)
             return
         raise NotImplementedError(_ONLY_PF_OR_MARGINAL.format(kind))
 
@@ -376,8 +404,9 @@ class SGMCMCSampler(object):
                        parameters=None, **kwargs):
         """All windows of one gradient for ONE series -> [(problem, minibatch_size)].  RNG order
         as sgmcmc_sampler.py:390-418: every window is drawn first, then each filter's streams.
-        kind='marginal' (LGSSM): the exact Kalman gradient of each window, at `parameters` if given."""
-        self._require_kind(kind)
+        kind='marginal' (LGSSM): the exact Kalman gradient of each window, at `parameters` if given;
+        kind='complete' (LGSSM): the complete-data score on num_samples FFBS paths, at `parameters` if given."""
+        self._require_kind(kind, num_samples, gradient=True)
         observations = self._get_observations(observations, check_shape=False)
         if kwargs.get("N", None) is None:
             kwargs['N'] = num_samples if num_samples is not None else 1000
@@ -388,7 +417,7 @@ class SGMCMCSampler(object):
                 for _ in range(minibatch_size)]
         elif len(buffer_dicts) != minibatch_size:
             raise ValueError("len(buffer_dicts != minibatch_size")
-        at = parameters if kind == 'marginal' else None
+        at = parameters if kind in ('marginal', 'complete') else None
         probs = [(self._window_problem(bd, observations, "score", kind=kind, parameters=at, **kwargs), minibatch_size)
                  for bd in buffer_dicts]
         for q, _ in probs:
@@ -461,7 +490,7 @@ class SGMCMCSampler(object):
         grad_loglike = self._noisy_grad_loglikelihood(**{k: v for k, v in kwargs.items() if k != 'T'})
         # a `parameters=` argument reaches the prior term and the preconditioner only: the
         # particle filter always runs at self.parameters (sgmcmc_sampler.py:379);
-        # the exact gradient of kind='marginal' is taken at `parameters` (:295-296, _grad_problems)
+        # kind='marginal' / 'complete' take theirs at `parameters` (:295-296, _grad_problems)
         at = kwargs.get('parameters', None)
         at = self.parameters if at is None else at
         grad_prior = self.prior.grad_logprior(parameters=at)
