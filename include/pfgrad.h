@@ -307,7 +307,11 @@ int pfg_last_traced(pfg_ctx *ctx);
  * the plain entry point serves NEMETH / FILTER).  PFG_SMOOTHER_KALMAN: the exact-score kernel, one lane per
  * descriptor (kernel, rng and n_max are ignored; every descriptor brings its scratch).  PFG_SMOOTHER_KALMAN_FFBS: the
  * FFBS kernel, one workgroup per descriptor (n_max = the most paths N of a descriptor picks the workgroup size; every
- * descriptor brings its scratch) */
+ * descriptor brings its scratch).  PFG_SMOOTHER_PARIS runs an LDS-resident variant for n_max <= 1024 --
+ * "paris64x2" (one wave per window, 64 threads x 2 particles: n_max <= 128, the DEVICE rng and more than 64 descriptors;
+ * PFGRAD_VARIANT=paris64x2 forces it wherever it holds n_max, REPLAY included), "paris256x1" (the rest of n_max <= 256),
+ * "paris256x4" (n_max <= 1024) -- and "paris_mem1024" above that (state in
+ * the descriptors' scratch) */
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother,
                                int n_max, int B, const pfg_dev_problem *dev_probs, void *hip_stream);
 /* N above the one-workgroup kernels' maximum (16384 < N <= 4194304; the reference has no limit and its bias experiments

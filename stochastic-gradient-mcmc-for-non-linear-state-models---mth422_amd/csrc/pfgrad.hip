@@ -86,6 +86,11 @@ constexpr int kLds4096Variant = 4, kTinyVariant = 5, kGarchVariant = 6, kTiny4Va
 constexpr int kTinySingleVariant = 8, kTiny4SingleVariant = 9;
 constexpr int kLatencyVariant = 3, kLatencyBatch = 64;
 constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
+// the LDS-resident PaRIS variants (ping-pong state, the parents' log-weights in LDS); paris64x2: one wave per window
+struct ParisVariant { int NT, PPT; const char *tag; size_t (*lds)(int, int, int, int); };
+const ParisVariant kParisVariants[] = { {64, 2, "paris64x2", reg_lds<64, 2, true, pfg::MODE_PARIS>},
+                                        {256, 1, "paris256x1", reg_lds<256, 1, true, pfg::MODE_PARIS>},
+                                        {256, 4, "paris256x4", reg_lds<256, 4, true, pfg::MODE_PARIS>} };
 
 int state_dim(int model) { return model == PFG_MODEL_GARCH ? 2 : 1; }
 int stat_dim(int model) { return model == PFG_MODEL_SVM ? 3 : 4; }
@@ -215,6 +220,23 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
         case Family::N2: {
             const bool paris = p.family == Family::Paris;
             const std::string pf = paris ? "pf = 'paris'" : "pf = 'poyiadjis_N2'";
+            if (paris) {
+                // PaRIS in one wave per window (64 threads x 2 particles, N <= 128): picked like wg64x2s for plain
+                // windows -- device generator, more than kLatencyBatch windows; REPLAY, lone windows and N > 128 keep
+                // the 256-thread variants.
+                // PFGRAD_VARIANT=<tag> forces any PaRIS LDS-resident variant that holds n_max (tests, A/B timing).
+                const ParisVariant *pv = nullptr;
+                for (const ParisVariant &e : kParisVariants)
+                    if (force && !std::strcmp(force, e.tag) && n_max <= e.NT * e.PPT) pv = &e;
+                if (!pv && n_max <= 128 && rng == PFG_RNG_DEVICE && B > kLatencyBatch) pv = &kParisVariants[0];
+                if (pv) {
+                    p.nt = pv->NT; p.ppt = pv->PPT; p.name = pv->tag;
+                    p.lds = pv->lds(model, dtype, rng, n_max);
+                    if (p.lds > kLdsLimit)
+                        return refuse(p, PFG_ERR_UNSUPPORTED, pf + ": N = " + std::to_string(n_max) + " does not fit the LDS-resident variant");
+                    break;
+                }
+            }
             if (n_max <= 1024) {
                 p.nt = 256; p.ppt = n_max <= 256 ? 1 : 4;
                 p.name = paris ? (p.ppt == 1 ? "paris256x1" : "paris256x4") : (p.ppt == 1 ? "n2_256x1" : "n2_256x4");

@@ -66,7 +66,10 @@ class ChainEnsemble(object):
              (sgmcmc_sampler.py:1249-1283)
       parameters: a Parameters object (all chains start there) or an array [C, P] of raw thetas
       num_chains: C (ignored when `parameters` is an array)
-      N, pf ('poyiadjis_N' | 'nemeth'), lambduh, kernel: particle-filter settings
+      N, pf ('poyiadjis_N' | 'nemeth' | 'paris'), lambduh, kernel: particle-filter settings
+      Ntilde, max_accept_reject, accept_reject: pf='paris' (N <= 1024): the backward draws per particle, the
+               accept-reject rounds before the exact draw (default 64; accept_reject=False: none, every draw exact),
+               as the Helper's device-generator path (particle_filters.make_problem)
       epsilon: SGLD step size;  prior: Prior (default: the model's default prior, var=100 / 1)
       subsequence_length S / buffer_length B: -1 = full sequence (no window sampling)
       dtype: 'f64' | 'f32' particle-state arithmetic;  seed: Philox key
@@ -92,7 +95,8 @@ class ChainEnsemble(object):
                  lambduh=None, kernel=None, epsilon=0.1, prior=None, subsequence_length=-1,
                  buffer_length=-1, dtype="f64", seed=0, chain_offset=0, device=None,
                  forward_message=None, partition_style=None, resampling="multinomial",
-                 sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None):
+                 sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
+                 Ntilde=2, max_accept_reject=None, accept_reject=True):
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         if kind not in ("pf", "marginal", "complete"):
@@ -112,12 +116,26 @@ class ChainEnsemble(object):
         self.ctx = _capi.default_context(self.device.index)
         self.helper = Helper(n=1, m=1, forward_message=forward_message)
         self.kernel = self.helper._get_kernel(kernel)
+        if kind in ("marginal", "complete") and pf == "paris":
+            raise ValueError("pf='paris' needs kind='pf'")
         if pf == "poyiadjis_N" or kind in ("marginal", "complete"):
             self.lambduh = 1.0
         elif pf == "nemeth":
             self.lambduh = 0.95 if lambduh is None else float(lambduh)
+        elif pf == "paris":
+            # PaRIS on the LDS-resident kernels (paris64x2 / paris256x1 / paris256x4): no per-chain scratch
+            if self.N > 1024:
+                raise NotImplementedError("ChainEnsemble(pf='paris') is built for N <= 1024, got N = {0}".format(self.N))
+            if resampling != "multinomial":
+                raise ValueError("pf='paris' resamples multinomially, got resampling = {0}".format(resampling))
+            self.lambduh = 1.0
         else:
-            raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth', got {0}".format(pf))
+            raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth' | 'paris', got {0}".format(pf))
+        self.pf = pf
+        self.Ntilde = int(Ntilde)
+        self.max_accept_reject = 0 if not accept_reject else (64 if max_accept_reject is None else max(0, int(max_accept_reject)))
+        if self.pf == "paris" and self.Ntilde < 1:
+            raise ValueError("pf='paris' needs Ntilde >= 1")
         self.P = _capi.THETA_DIM[model]
         self._Parameters = Parameters
         self.resampling = resampling
@@ -225,6 +243,9 @@ class ChainEnsemble(object):
             d["smoother"] = _capi.SMOOTHER["kalman"]
         elif kind == "complete":
             d["smoother"] = _capi.SMOOTHER["kalman_ffbs"]
+        elif self.pf == "paris":
+            d["smoother"] = _capi.SMOOTHER["paris"]
+            d["Ntilde"], d["max_accept_reject"] = self.Ntilde, self.max_accept_reject
         elif resampling == "systematic":       # extension, see include/pfgrad.h
             if self.N > 1024:
                 raise NotImplementedError("systematic resampling is built for N <= 1024")
@@ -237,6 +258,8 @@ class ChainEnsemble(object):
         elif kind == "complete":
             # the forward messages of the longest buffer: a window and its two buffers, or the whole series
             sb = _capi.kalman_scratch_bytes(min(self.T, S + 2 * self.B) if S > 0 else self.T)
+        elif self.pf == "paris":
+            sb = 0          # N <= 1024: the LDS-resident PaRIS variants keep their state in LDS
         else:
             sb = self.ctx.scratch_bytes(model, dtype, "device", self.N)
         if sb < 0:
@@ -358,6 +381,10 @@ class ChainEnsemble(object):
             if traced:
                 raise ValueError("kind='complete' has no particles to trace")
             self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman_ffbs",
+                                            self.N, self.C, self.desc_dev.data_ptr(), st)
+        elif self.pf == "paris":
+            # the PaRIS kernels always honour trace buffers: traced or not, the same launch
+            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "paris",
                                             self.N, self.C, self.desc_dev.data_ptr(), st)
         elif traced:
             self.ctx.launch_device_traced(self.model, self.kernel, self.dtype, "device",
