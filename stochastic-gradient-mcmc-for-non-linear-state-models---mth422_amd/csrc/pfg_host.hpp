@@ -52,6 +52,21 @@ struct HostArena {       // growable PINNED host buffer (hipHostMalloc): H2D / D
     void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; cap = 0; }
 };
 
+// One buffer of a pfg_run_batch window (pfgrad.hip, describe_window): the arena it lives in, its offset and length
+// there, what crosses between it and the host, and the descriptor field set to its device address once the arena
+// bases are known.
+struct Piece {
+    enum Arena : uint8_t { In, Out, Work };
+    enum Copy : uint8_t { None, Staged, Direct };   // In: packed into the staging arena, or DMA'd from registered pages
+    void *slot;              // address of the device pointer to set (a pfg_dev_problem or elementwise-pass field)
+    const double *src;       // In: the host source
+    void *dst;               // Out: where the host result goes (NULL: read back elsewhere)
+    size_t at, n;            // offset and length in the arena, doubles
+    size_t bytes;            // Out: bytes fetched into dst (an int32 payload fills fewer than n * 8)
+    Arena arena;
+    Copy copy;
+};
+
 }  // namespace pfg_host
 
 struct pfg_ctx {
@@ -62,6 +77,8 @@ struct pfg_ctx {
     pfg_host::HostArena h_in, h_out;
     std::vector<double> h_in_pageable;   // staging when the pinned arena cannot be had (hipHostMalloc refused)
     std::vector<pfg_dev_problem> h_desc;
+    std::vector<pfg_host::Piece> pieces;  // pfg_run_batch: every buffer of the batch
+    std::vector<double> h_own;           // pfg_run_batch: per window, theta padded to PFG_MAX_THETA and the step counter
     const char *last_variant = "none";   // tag of the kernel variant the latest dispatch launched
     bool last_traced = false;            // ... and whether that was a trace-honouring instantiation
     // largest dynamic-LDS size hipFuncAttributeMaxDynamicSharedMemorySize has been set to, per kernel: the

@@ -1,7 +1,9 @@
 // libpfgrad.so: host side of the C ABI declared in include/pfgrad.h + kernel dispatch.
 // The particle-filter kernels are instantiated in pfg_inst_*.hip (one unit per model x proposal
 // kernel, compiled in parallel by sgmcmc_ssm_amd/_build.py); this unit holds the dispatcher, the
-// small update / window / KSD kernels and the extern "C" entry points.
+// small update / window / KSD kernels and the extern "C" entry points.  pfg_run_batch (host buffers) checks every
+// window, plans the launch, then describes each window's buffers once (describe_window): sizing the arenas, staging the
+// inputs and fetching the outputs are loops over those descriptions.
 #include <mutex>
 #include <unordered_map>
 #include "pfg_host.hpp"
@@ -308,28 +310,23 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
     return p;
 }
 
-// PFG_SMOOTHER_KALMAN ignores the proposal kernel and the generator
-int check_kalman(pfg_ctx *ctx, int model, int dtype) {
-    if (model != PFG_MODEL_LGSSM) return fail(ctx, PFG_ERR_UNSUPPORTED, "the exact Kalman score (kind = 'marginal') is built for LGSSM only");
-    if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, "the exact Kalman score (kind = 'marginal') is built for dtype f64 only");
-    return PFG_OK;
-}
-
-// PFG_SMOOTHER_KALMAN_FFBS ignores the proposal kernel; its normals come from REPLAY z or the DEVICE generator
-int check_ffbs(pfg_ctx *ctx, int model, int dtype, int rng) {
-    if (model != PFG_MODEL_LGSSM) return fail(ctx, PFG_ERR_UNSUPPORTED, "FFBS latent paths (kind = 'complete') are built for LGSSM only");
-    if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, "FFBS latent paths (kind = 'complete') are built for dtype f64 only");
-    if (rng != PFG_RNG_REPLAY && rng != PFG_RNG_DEVICE) return fail(ctx, PFG_ERR_INVALID, "bad rng mode");
-    return PFG_OK;
-}
-
-int check_combo(pfg_ctx *ctx, int model, int kernel, int dtype, int rng) {
-    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
-    if (kernel != PFG_KERNEL_PRIOR && kernel != PFG_KERNEL_OPTIMAL)
-        return fail(ctx, PFG_ERR_INVALID, "Unrecoginized kernel id");
-    if (model == PFG_MODEL_SVM && kernel == PFG_KERNEL_OPTIMAL)
-        return fail(ctx, PFG_ERR_UNSUPPORTED, "SVM optimal kernel not analytic");   // svm/helper.py:62
-    if (dtype != PFG_F64 && dtype != PFG_F32) return fail(ctx, PFG_ERR_INVALID, "bad dtype");
+// The ids a batch of `smoother` windows is built for.  The exact Kalman score ignores the proposal kernel and the
+// generator; FFBS ignores the proposal kernel, its normals come from REPLAY z or the DEVICE generator.
+int check_ids(pfg_ctx *ctx, int smoother, int model, int kernel, int dtype, int rng) {
+    if (smoother == PFG_SMOOTHER_KALMAN || smoother == PFG_SMOOTHER_KALMAN_FFBS) {
+        const bool ffbs = smoother == PFG_SMOOTHER_KALMAN_FFBS;
+        const std::string what = ffbs ? "FFBS latent paths (kind = 'complete') are" : "the exact Kalman score (kind = 'marginal') is";
+        if (model != PFG_MODEL_LGSSM) return fail(ctx, PFG_ERR_UNSUPPORTED, what + " built for LGSSM only");
+        if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, what + " built for dtype f64 only");
+        if (!ffbs) return PFG_OK;
+    } else {
+        if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+        if (kernel != PFG_KERNEL_PRIOR && kernel != PFG_KERNEL_OPTIMAL)
+            return fail(ctx, PFG_ERR_INVALID, "Unrecoginized kernel id");
+        if (model == PFG_MODEL_SVM && kernel == PFG_KERNEL_OPTIMAL)
+            return fail(ctx, PFG_ERR_UNSUPPORTED, "SVM optimal kernel not analytic");   // svm/helper.py:62
+        if (dtype != PFG_F64 && dtype != PFG_F32) return fail(ctx, PFG_ERR_INVALID, "bad dtype");
+    }
     if (rng != PFG_RNG_REPLAY && rng != PFG_RNG_DEVICE) return fail(ctx, PFG_ERR_INVALID, "bad rng mode");
     return PFG_OK;
 }
@@ -351,12 +348,10 @@ int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, in
 
 int dispatch(pfg_ctx *ctx, Caller caller, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
              const pfg_dev_problem *dp, hipStream_t st, bool traced = false, int t_max = 0, int phase = -1) {
-    const bool kalman = smoother == PFG_SMOOTHER_KALMAN;
-    int rc = kalman ? check_kalman(ctx, model, dtype)
-             : smoother == PFG_SMOOTHER_KALMAN_FFBS ? check_ffbs(ctx, model, dtype, rng) : check_combo(ctx, model, kernel, dtype, rng);
+    const int rc = check_ids(ctx, smoother, model, kernel, dtype, rng);
     if (rc) return rc;
     if (B <= 0) return PFG_OK;
-    if (n_max < 1 && !kalman) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
+    if (n_max < 1 && smoother != PFG_SMOOTHER_KALMAN) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
     if (caller == Caller::Grid && t_max < 0) return fail(ctx, PFG_ERR_INVALID, "T_max must be >= 0");
     return launch(ctx, make_plan(caller, model, dtype, rng, smoother, n_max, B, traced, false, t_max, phase), model, kernel, rng, B, dp, st);
 }
@@ -546,6 +541,279 @@ bool host_registered(const void *p, size_t bytes) {
     for (const HostRange &r : g_host_ranges)
         if (a >= r.lo && a + bytes <= r.hi) return true;
     return false;
+}
+
+// ---- pfg_run_batch: validation, the batch summary, one description of every buffer ---------------------------------
+// One window of a batch whose first window is `first` (everything `first` decides is shared by the batch): PFG_OK, or
+// the first rule it breaks.
+int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const pfg_problem &first, int b) {
+    const std::string id = "problem " + std::to_string(b) + ": ";
+    auto bad = [&](int code, const char *msg) { return fail(ctx, code, id + msg); };
+    const int model = first.model, dtype = first.dtype, rng = first.rng;
+    const bool kalman = first.smoother == PFG_SMOOTHER_KALMAN;     // the exact score: no particles, no streams
+    const bool ffbs = first.smoother == PFG_SMOOTHER_KALMAN_FFBS;  // FFBS paths: N paths, REPLAY normals in z only
+    auto mixed = [&](int s) { return (q.smoother == s) != (first.smoother == s); };   // s is all or none of a batch
+    if (q.model != model || q.kernel != first.kernel || q.dtype != dtype || q.rng != rng)
+        return bad(PFG_ERR_INVALID, "model/kernel/dtype/rng must match across a batch");
+    if (q.N < 1 && !kalman) return bad(PFG_ERR_INVALID, "N must be >= 1");
+    if (q.T < 0) return bad(PFG_ERR_INVALID, "T must be >= 0");
+    if (q.t1 < 0 || q.tL < q.t1) return bad(PFG_ERR_INVALID, "need 0 <= t1 <= tL");
+    if ((q.smoother < PFG_SMOOTHER_NEMETH || q.smoother > PFG_SMOOTHER_POYIADJIS_N2) && q.smoother != PFG_SMOOTHER_KALMAN &&
+        q.smoother != PFG_SMOOTHER_KALMAN_FFBS)
+        return bad(PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
+    if (mixed(PFG_SMOOTHER_KALMAN_FFBS)) return bad(PFG_ERR_INVALID, "FFBS latent paths cannot share a batch with other smoothers");
+    if (mixed(PFG_SMOOTHER_KALMAN)) return bad(PFG_ERR_INVALID, "the exact Kalman score cannot share a batch with particle filters");
+    if (kalman || ffbs) {       // the exact LGSSM passes: a forward message from the prior, no particles
+        if (q.t1 > q.T) return bad(PFG_ERR_INVALID, "need t1 <= T");
+        if (!(q.prior_var > 0.0) || !std::isfinite(q.prior_var) || !std::isfinite(q.prior_mean))
+            return bad(PFG_ERR_INVALID, "the forward message needs a finite precision > 0 (prior_var = 1 / precision)");
+        if (q.init_x || q.elementwise || q.paris_stream || (ffbs ? q.stat != PFG_STAT_SCORE && q.stat != PFG_STAT_NONE : q.stat == PFG_STAT_PREDICTIVE))
+            return bad(PFG_ERR_INVALID, ffbs ? "FFBS latent paths take no warm start or elementwise statistic; stat is score or none"
+                                             : "the exact Kalman score takes no warm start, elementwise or predictive statistic");
+        if (r.x_T || r.logw_T || r.stats_T || (kalman && r.trace_x) || r.trace_logw || r.trace_stats || r.trace_ll || r.trace_anc ||
+            r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats)
+            return bad(PFG_ERR_INVALID, ffbs ? "FFBS latent paths have no particles: only the result record and trace_x (the paths)"
+                                             : "the exact Kalman score has no particles: only the result record");
+        if (ffbs && rng == PFG_RNG_REPLAY && q.T > 0 && !q.z) return bad(PFG_ERR_INVALID, "REPLAY FFBS needs z (T N normals)");
+    }
+    if (mixed(PFG_SMOOTHER_POYIADJIS_N2)) return bad(PFG_ERR_INVALID, "pf = 'poyiadjis_N2' cannot share a batch with other smoothers");
+    if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.N > pfg::MEM_MAX_N)
+        return bad(PFG_ERR_UNSUPPORTED, "pf = 'poyiadjis_N2' is implemented for N <= 16384");
+    if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.elementwise && q.N > 4096)
+        return bad(PFG_ERR_UNSUPPORTED, "elementwise statistics with pf = 'poyiadjis_N2' are implemented for N <= 4096");
+    if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.stat == PFG_STAT_PREDICTIVE)
+        return bad(PFG_ERR_INVALID, "Only can use pf = 'filter' since we are filtering");
+    if (mixed(PFG_SMOOTHER_PARIS)) return bad(PFG_ERR_INVALID, "pf = 'paris' cannot share a batch with other smoothers");
+    if (q.smoother == PFG_SMOOTHER_PARIS) {
+        if (q.Ntilde < 1 || q.Ntilde > 64) return bad(PFG_ERR_INVALID, "Ntilde must be in [1, 64]");
+        if (q.max_accept_reject < 0) return bad(PFG_ERR_INVALID, "max_accept_reject must be >= 0");
+        if (q.paris_stream) {
+            if (rng != PFG_RNG_REPLAY) return bad(PFG_ERR_INVALID, "paris_stream is a REPLAY input");
+            if (q.paris_idx_u || q.paris_acc_u || q.paris_man_u)
+                return bad(PFG_ERR_INVALID, "paris_stream replaces the addressed pools paris_idx_u / acc_u / man_u");
+            if (q.paris_stream_len < 0 || q.paris_manual_threshold < 0)
+                return bad(PFG_ERR_INVALID, "paris_stream_len and paris_manual_threshold must be >= 0");
+            if (q.N > pfg::MEM_MAX_N) return bad(PFG_ERR_UNSUPPORTED, "pf = 'paris' is implemented for N <= 16384");
+            if ((q.flags & PFG_FLAG_PARIS_RAW_STREAM) && dtype != PFG_F64)
+                return bad(PFG_ERR_UNSUPPORTED, "PFG_FLAG_PARIS_RAW_STREAM is built for dtype f64 (it reproduces np.random's doubles)");
+            if ((q.flags & PFG_FLAG_PARIS_RAW_STREAM) && (q.z0 || q.u || q.z))
+                return bad(PFG_ERR_INVALID, "PFG_FLAG_PARIS_RAW_STREAM draws z0 / u / z from paris_stream: they must be NULL");
+            if ((q.flags & PFG_FLAG_PARIS_RAW_CARRY) && (!(q.flags & PFG_FLAG_PARIS_RAW_STREAM) || q.paris_stream_len < 1))
+                return bad(PFG_ERR_INVALID, "PFG_FLAG_PARIS_RAW_CARRY needs PFG_FLAG_PARIS_RAW_STREAM and the cached Gaussian in paris_stream[0]");
+            if ((q.flags & PFG_FLAG_PARIS_RAW_CARRY) && q.init_x && q.T == 0)
+                return bad(PFG_ERR_INVALID, "PFG_FLAG_PARIS_RAW_CARRY with a warm start and T = 0 draws no normal: nothing to carry the cached Gaussian through");
+        } else if (rng == PFG_RNG_REPLAY && (!q.paris_man_u || (q.max_accept_reject > 0 && (!q.paris_idx_u || !q.paris_acc_u)))) {
+            return bad(PFG_ERR_INVALID, "REPLAY paris needs the paris_* uniform pools or paris_stream");
+        }
+        if ((q.flags & (PFG_FLAG_PARIS_RAW_STREAM | PFG_FLAG_PARIS_RAW_CARRY)) && !q.paris_stream)
+            return bad(PFG_ERR_INVALID, "PFG_FLAG_PARIS_RAW_STREAM needs paris_stream");
+        if ((q.flags & PFG_FLAG_PARIS_NO_ACCEPT_REJECT) && !q.paris_stream)
+            return bad(PFG_ERR_UNSUPPORTED, "PaRIS with accept_reject = False is built for the REPLAY stream order (paris_stream)");
+    } else if (q.paris_stream) {
+        return bad(PFG_ERR_INVALID, "paris_stream needs pf = 'paris'");
+    }
+    if (q.stat < PFG_STAT_SCORE || q.stat > PFG_STAT_PREDICTIVE) return bad(PFG_ERR_INVALID, "bad stat id");
+    if ((q.stat == PFG_STAT_PREDICTIVE) != (first.stat == PFG_STAT_PREDICTIVE))
+        return bad(PFG_ERR_INVALID, "the predictive statistic cannot share a batch with others");
+    if (q.stat == PFG_STAT_PREDICTIVE) {
+        if (q.smoother != PFG_SMOOTHER_FILTER)                                  // svm/helper.py:209-210
+            return bad(PFG_ERR_INVALID, "Only can use pf = 'filter' since we are filtering");
+        if (q.num_steps_ahead < 0 || q.num_steps_ahead >= PFG_MAX_PRED) return bad(PFG_ERR_INVALID, "num_steps_ahead must be in [0, 15]");
+        if (q.N > pfg::MEM_MAX_N) return bad(PFG_ERR_UNSUPPORTED, "N exceeds the supported maximum of 16384");
+        if (rng == PFG_RNG_REPLAY && model != PFG_MODEL_LGSSM && q.T > 0 && !q.pred_z)
+            return bad(PFG_ERR_INVALID, "REPLAY predictive needs the pred_z pool");
+    }
+    if (!q.theta) return bad(PFG_ERR_INVALID, "theta is NULL");
+    if (q.T > 0 && !q.y) return bad(PFG_ERR_INVALID, "observations are NULL");
+    const bool raw_stream = q.smoother == PFG_SMOOTHER_PARIS && (q.flags & PFG_FLAG_PARIS_RAW_STREAM) != 0;
+    const bool streams = rng == PFG_RNG_REPLAY && !raw_stream && !kalman && !ffbs;
+    if (streams && !q.init_x && !q.z0) return bad(PFG_ERR_INVALID, "REPLAY needs z0");
+    if (streams && q.T > 0 && (!q.u || !q.z)) return bad(PFG_ERR_INVALID, "REPLAY needs u and z");
+    if (q.init_x && !q.init_logw) return bad(PFG_ERR_INVALID, "init_x needs init_logw");
+    if (mixed(PFG_SMOOTHER_NEMETH_SYSTEMATIC))
+        return bad(PFG_ERR_INVALID, "systematic resampling cannot share a batch with other smoothers");
+    if (q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC && (rng != PFG_RNG_DEVICE || q.N > 1024))
+        return bad(PFG_ERR_UNSUPPORTED, "systematic resampling needs the DEVICE rng and N <= 1024");
+    if (!(q.prior_var >= 0.0) && !(q.flags & PFG_FLAG_GARCH_STATIONARY_PRIOR) && !q.init_x)
+        return bad(PFG_ERR_INVALID, "prior_var must be >= 0");
+    if (model == PFG_MODEL_SVM && std::fabs(q.theta[0]) > 1.0) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "Current AR parameter is |A| = %.17g > 1\nTry calling project_parameters?", std::fabs(q.theta[0]));
+        return fail(ctx, PFG_ERR_NUMERIC, buf);                                   // svm/kernels.py:6-11
+    }
+    if (q.elementwise) {
+        if (q.smoother != PFG_SMOOTHER_NEMETH && q.smoother != PFG_SMOOTHER_PARIS && q.smoother != PFG_SMOOTHER_POYIADJIS_N2)
+            return bad(PFG_ERR_UNSUPPORTED, "elementwise statistics are built for pf = 'poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2'");
+        if (q.stat == PFG_STAT_PREDICTIVE) return bad(PFG_ERR_INVALID, "elementwise statistics do not combine with the predictive statistic");
+        if (!r.ew_mean) return bad(PFG_ERR_INVALID, "elementwise needs ew_mean");
+        if (r.trace_x || r.trace_logw || r.trace_stats || r.trace_anc || r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud)
+            return bad(PFG_ERR_INVALID, "elementwise statistics cannot be combined with trace outputs");
+        if ((q.tL < q.T ? q.tL : q.T) - q.t1 < 1) return bad(PFG_ERR_INVALID, "elementwise needs a non-empty window [t1, tL)");
+    } else if (r.ew_mean || r.ew_stats) {
+        return bad(PFG_ERR_INVALID, "ew_mean / ew_stats need pfg_problem.elementwise");
+    }
+    if ((r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud) && (rng != PFG_RNG_DEVICE || !r.trace_x))
+        return bad(PFG_ERR_INVALID, "rec_u / rec_z / rec_z0 record the DEVICE generator's draws and need trace_x");
+    if (r.trace_anc && !r.trace_x) return bad(PFG_ERR_INVALID, "trace_anc needs trace_x");
+    if ((r.logw_T || r.stats_T) && !r.x_T) return bad(PFG_ERR_INVALID, "logw_T/stats_T need x_T");
+    if (!ffbs && (r.trace_logw == nullptr) != (r.trace_x == nullptr)) return bad(PFG_ERR_INVALID, "trace_x and trace_logw go together");
+    if (r.trace_stats && !r.trace_x) return bad(PFG_ERR_INVALID, "trace_stats needs trace_x");
+    return PFG_OK;
+}
+
+// What the plan needs of a valid batch: the longest window (Kalman: of steps [t1, tL), else of particles), the longest
+// FFBS buffer, whether any window records a trajectory, and the smoother to plan for.
+struct BatchSummary { int n_max = 0, t_max = 0; bool traced = false; int smoother = PFG_SMOOTHER_NEMETH; };
+BatchSummary summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
+    BatchSummary s;
+    bool score1 = true;         // every window the Poyiadjis O(N) score: units with a twin specialised to it run that
+    for (int b = 0; b < B; ++b) {
+        const pfg_problem &q = ps[b];
+        const pfg_result &r = rs[b];
+        s.traced = s.traced || r.trace_x || r.trace_ll || r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || q.elementwise;
+        score1 = score1 && q.smoother == PFG_SMOOTHER_NEMETH && q.lambduh == 1.0 && q.stat == PFG_STAT_SCORE;
+        const int n = q.smoother == PFG_SMOOTHER_KALMAN ? (q.tL < q.T ? q.tL : q.T) - q.t1 : q.N;
+        s.n_max = n > s.n_max ? n : s.n_max;
+        if (q.smoother == PFG_SMOOTHER_KALMAN_FFBS) s.t_max = q.T > s.t_max ? q.T : s.t_max;
+    }
+    // the smoothers with kernels of their own fill whole batches; the rest run the plain kernels
+    const int s0 = ps[0].smoother;
+    if (s0 == PFG_SMOOTHER_PARIS || s0 == PFG_SMOOTHER_NEMETH_SYSTEMATIC || s0 == PFG_SMOOTHER_POYIADJIS_N2 ||
+        s0 == PFG_SMOOTHER_KALMAN || s0 == PFG_SMOOTHER_KALMAN_FFBS)
+        s.smoother = s0;
+    else if (score1 && !s.traced)
+        s.smoother = PFG_SMOOTHER_POYIADJIS_N;
+    return s;
+}
+
+// The buffers of a batch, laid out window after window in the device arenas (offsets in doubles).  Each is described
+// once, here, by describe_window; sizing, staging and fetching are loops over the pieces.
+struct Layout {
+    std::vector<Piece> &pieces;
+    size_t n[3] = {0, 0, 0};        // doubles of the In, Out and Work arenas
+    size_t n_host = 0;              // doubles of the pinned staging arena
+    // observations / window weights that many windows share (same host pointer and length) are staged once: 12288
+    // chains on one series would otherwise carry 98 MB of copies of the same 8 KB
+    std::unordered_map<const double *, std::pair<size_t, size_t>> shared;     // source -> (length, offset)
+
+    template <typename T>
+    void add(T *&slot, Piece::Arena a, size_t at, size_t len, const double *src = nullptr, void *dst = nullptr,
+             size_t bytes = 0, Piece::Copy copy = Piece::None) {
+        pieces.push_back({&slot, src, dst, at, len, bytes, a, copy});
+    }
+    // an input of len doubles at src (none if either is 0); big inputs in caller-registered pinned memory
+    // (pfg_host_register) go to the device straight from there, everything else through the staging arena
+    template <typename T> void in(T *&slot, const double *src, size_t len) {
+        if (!src || len == 0) return;
+        const bool direct = len >= kDirectMinDoubles && host_registered(src, len * 8);
+        if (!direct) n_host += len;
+        add(slot, Piece::In, n[Piece::In], len, src, nullptr, 0, direct ? Piece::Direct : Piece::Staged);
+        n[Piece::In] += len;
+    }
+    template <typename T> void in_shared(T *&slot, const double *src, size_t len) {
+        if (!src || len == 0) return;
+        auto it = shared.find(src);
+        if (it != shared.end() && it->second.first == len) return add(slot, Piece::In, it->second.second, len);
+        shared[src] = {len, n[Piece::In]};
+        in(slot, src, len);
+    }
+    template <typename T> void out(T *&slot, size_t len, void *dst = nullptr, size_t bytes = 0) {
+        add(slot, Piece::Out, n[Piece::Out], len, nullptr, dst, bytes);
+        n[Piece::Out] += len;
+    }
+    // an output the caller asked for (dst non-NULL): len doubles of the arena, `bytes` of them fetched
+    template <typename D, typename T> void want(D *dst, T *&slot, size_t len, size_t bytes) { if (dst) out(slot, len, dst, bytes); }
+    template <typename T> void want(double *dst, T *&slot, size_t len) { want(dst, slot, len, len * 8); }
+    template <typename T> void work(T *&slot, size_t len) {
+        add(slot, Piece::Work, n[Piece::Work], len);
+        n[Piece::Work] += len;
+    }
+};
+
+// the elementwise pass's device-only statistic matrices (its traces are the descriptor's trace_x / trace_logw and
+// trace_anc or trace_paris_J, redirected into the work arena)
+struct EwPlan { double *S0, *S1, *Sbar, *w, *mean, *stats; size_t Wd; int Nt; };
+constexpr int kOwnDoubles = PFG_MAX_THETA + 1;      // h_own per window: theta padded, the step counter
+
+// Window q's buffers in arena order -- inputs: the series and weights (shared across the batch), theta, the REPLAY
+// streams, the warm start, the PaRIS pools or stream, the predictive draws, the step counter; outputs: the PaRIS stream
+// counts, the predictive statistic, the result record, then what r asks for -- and its descriptor's scalars.
+void describe_window(Layout &L, const pfg_problem &q, pfg_result &r, pfg_dev_problem &d, EwPlan &e, double *own) {
+    const int NS = state_dim(q.model), H = stat_dim(q.model), P = theta_dim(q.model);
+    const size_t N = q.N, T = q.T, TN = T * N;
+    const int tL = q.tL < q.T ? q.tL : q.T;
+    const bool replay = q.rng == PFG_RNG_REPLAY, paris = q.smoother == PFG_SMOOTHER_PARIS;
+    L.in_shared(d.y, q.y, T);
+    L.in_shared(d.weights, q.weights, tL > q.t1 ? (size_t)(tL - q.t1) : 0);
+    for (int j = 0; j < PFG_MAX_THETA; ++j) own[j] = j < P ? q.theta[j] : 0.0;
+    L.in(d.theta, own, PFG_MAX_THETA);
+    if (replay && q.smoother == PFG_SMOOTHER_KALMAN_FFBS) {
+        L.in(d.z, q.z, TN);
+    } else if (replay && q.smoother != PFG_SMOOTHER_KALMAN) {
+        L.in(d.z0, q.z0, N);
+        L.in(d.u, q.u, TN);
+        L.in(d.z, q.z, TN);
+    }
+    if (q.init_x) {
+        L.in(d.init_x, q.init_x, N * NS);
+        L.in(d.init_logw, q.init_logw, N);
+        L.in(d.init_stats, q.init_stats, N * H);
+    }
+    if (paris) {
+        d.Ntilde = q.Ntilde; d.max_accept_reject = q.max_accept_reject;
+        if (replay) {
+            L.in(d.paris_idx_u, q.paris_idx_u, TN * q.Ntilde * q.max_accept_reject);
+            L.in(d.paris_acc_u, q.paris_acc_u, TN * q.Ntilde * q.max_accept_reject);
+            L.in(d.paris_man_u, q.paris_man_u, TN * q.Ntilde);
+            if (q.paris_stream) {
+                if (q.paris_stream_len > 0) L.in(d.paris_stream, q.paris_stream, q.paris_stream_len);
+                else L.add(d.paris_stream, Piece::In, 0, 0);        // an empty stream is still "stream order" (non-NULL)
+                d.paris_stream_len = q.paris_stream_len;
+                d.paris_manual_threshold = q.paris_manual_threshold;
+                L.out(d.paris_consumed, 2);                         // the consumed count, the carry-back distance
+            }
+        }
+    }
+    if (q.stat == PFG_STAT_PREDICTIVE) {
+        d.num_steps_ahead = q.num_steps_ahead;
+        if (replay && q.model != PFG_MODEL_LGSSM) L.in(d.pred_z, q.pred_z, TN * (q.num_steps_ahead + 1));
+        L.want(r.pred, d.pred_out, PFG_MAX_PRED);
+    }
+    static_assert(offsetof(pfg_result, loglik) == offsetof(pfg_result, mean_stat) + PFG_MAX_STAT * 8, "record = mean_stat, loglik");
+    L.want(r.mean_stat, d.out, PFG_OUT_DOUBLES, (PFG_MAX_STAT + 1) * 8);
+    L.want(r.x_T, d.final_x, N * NS);
+    L.want(r.logw_T, d.final_logw, N);
+    L.want(r.stats_T, d.final_stats, N * H);
+    L.want(r.trace_x, d.trace_x, (T + (q.smoother == PFG_SMOOTHER_KALMAN_FFBS ? 0 : 1)) * N * NS);   // FFBS: the paths [T][N]
+    L.want(r.trace_logw, d.trace_logw, (T + 1) * N);
+    L.want(r.trace_stats, d.trace_stats, (T + 1) * N * H);
+    L.want(r.trace_ll, d.trace_ll, T + 1);
+    L.want(r.trace_anc, d.trace_anc, (TN + 1) / 2, TN * 4);         // int32 pairs in f64 slots
+    if (q.elementwise) {
+        e.Wd = 3 * (size_t)(tL - q.t1);
+        e.Nt = paris ? q.Ntilde : 1;
+        L.work(d.trace_x, (T + 1) * N * NS);
+        L.work(d.trace_logw, (T + 1) * N);
+        L.work(paris ? d.trace_paris_J : d.trace_anc, (TN * e.Nt + 1) / 2);
+        L.work(e.S0, N * e.Wd);
+        L.work(e.S1, N * e.Wd);
+        L.work(e.Sbar, e.Wd);
+        L.work(e.w, N);
+        L.want(r.ew_mean, e.mean, e.Wd);
+        L.want(r.ew_stats, e.stats, N * e.Wd);
+    }
+    L.want(r.rec_u, d.rec_u, (TN + 1) / 2, TN * 4);
+    L.want(r.rec_z, d.rec_z, TN);
+    L.want(r.rec_z0, d.rec_z0, N);
+    L.want(r.rec_ud, d.rec_ud, TN);
+    if (q.step) {       // the step counter of this window, as a resident chain would read it from HBM
+        std::memcpy(own + PFG_MAX_THETA, &q.step, 8);
+        L.in(d.step_ctr, own + PFG_MAX_THETA, 1);
+    }
+    d.prior_mean = q.prior_mean; d.prior_var = q.prior_var; d.lambduh = q.lambduh;
+    d.seed = q.seed; d.stream = q.stream;
+    d.T = q.T; d.t1 = q.t1; d.tL = tL; d.N = q.N;
+    d.smoother = q.smoother; d.stat = q.stat; d.flags = q.flags;
 }
 }  // namespace
 
@@ -786,229 +1054,14 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     if (B < 0 || (B > 0 && (!ps || !rs))) return fail(ctx, PFG_ERR_INVALID, "pfg_run_batch: NULL problems/results");
     if (B == 0) return PFG_OK;
     const int model = ps[0].model, kernel = ps[0].kernel, dtype = ps[0].dtype, rng = ps[0].rng;
-    const bool kalman = ps[0].smoother == PFG_SMOOTHER_KALMAN;     // the exact score: no particles, no streams
-    const bool ffbs = ps[0].smoother == PFG_SMOOTHER_KALMAN_FFBS;  // FFBS paths: N paths, REPLAY normals in z only
-    int rc = kalman ? check_kalman(ctx, model, dtype)
-             : ffbs ? check_ffbs(ctx, model, dtype, rng) : check_combo(ctx, model, kernel, dtype, rng);
+    int rc = check_ids(ctx, ps[0].smoother, model, kernel, dtype, rng);
+    for (int b = 0; b < B && !rc; ++b) rc = check_window(ctx, ps[b], rs[b], ps[0], b);
     if (rc) return rc;
-    const int NS = state_dim(model), H = stat_dim(model), P = theta_dim(model);
 
-    // ---- validate + size ------------------------------------------------------------
-    // n_in: doubles of the device input arena; n_host: doubles of the pinned staging arena -- inputs shared by many
-    // windows of the batch (same pointer and length) count once in both, inputs that lie in caller-registered
-    // pinned memory need device space but no staging space (same decisions as `put` / `put_shared` below)
-    size_t n_in = 0, n_host = 0, n_out = 0, n_work = 0;
-    int n_max = 0, t_max = 0;
-    std::unordered_map<const double *, size_t> sized_shared;
-    auto size_in = [&](const double *src, size_t n) {
-        if (!src || n == 0) return;
-        n_in += n;
-        if (!(n >= kDirectMinDoubles && host_registered(src, n * 8))) n_host += n;
-    };
-    auto size_shared = [&](const double *src, size_t n) {
-        if (!src || n == 0) return;
-        auto it = sized_shared.find(src);
-        if (it != sized_shared.end() && it->second == n) return;
-        sized_shared[src] = n;
-        size_in(src, n);
-    };
-    for (int b = 0; b < B; ++b) {
-        const pfg_problem &q = ps[b];
-        std::string id = "problem " + std::to_string(b) + ": ";
-        if (q.model != model || q.kernel != kernel || q.dtype != dtype || q.rng != rng)
-            return fail(ctx, PFG_ERR_INVALID, id + "model/kernel/dtype/rng must match across a batch");
-        if (q.N < 1 && !kalman) return fail(ctx, PFG_ERR_INVALID, id + "N must be >= 1");
-        if (q.T < 0) return fail(ctx, PFG_ERR_INVALID, id + "T must be >= 0");
-        if (q.t1 < 0 || q.tL < q.t1) return fail(ctx, PFG_ERR_INVALID, id + "need 0 <= t1 <= tL");
-        if ((q.smoother < PFG_SMOOTHER_NEMETH || q.smoother > PFG_SMOOTHER_POYIADJIS_N2) && q.smoother != PFG_SMOOTHER_KALMAN &&
-            q.smoother != PFG_SMOOTHER_KALMAN_FFBS)
-            return fail(ctx, PFG_ERR_INVALID, id + "Unrecognized pf (smoother id)");
-        if ((q.smoother == PFG_SMOOTHER_KALMAN_FFBS) != ffbs)
-            return fail(ctx, PFG_ERR_INVALID, id + "FFBS latent paths cannot share a batch with other smoothers");
-        if (ffbs) {
-            const pfg_result &r = rs[b];
-            if (q.t1 > q.T) return fail(ctx, PFG_ERR_INVALID, id + "need t1 <= T");
-            if (!(q.prior_var > 0.0) || !std::isfinite(q.prior_var) || !std::isfinite(q.prior_mean))
-                return fail(ctx, PFG_ERR_INVALID, id + "the forward message needs a finite precision > 0 (prior_var = 1 / precision)");
-            if (q.init_x || q.elementwise || q.paris_stream || (q.stat != PFG_STAT_SCORE && q.stat != PFG_STAT_NONE))
-                return fail(ctx, PFG_ERR_INVALID, id + "FFBS latent paths take no warm start or elementwise statistic; stat is score or none");
-            if (r.x_T || r.logw_T || r.stats_T || r.trace_logw || r.trace_stats || r.trace_ll || r.trace_anc ||
-                r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats)
-                return fail(ctx, PFG_ERR_INVALID, id + "FFBS latent paths have no particles: only the result record and trace_x (the paths)");
-            if (rng == PFG_RNG_REPLAY && q.T > 0 && !q.z) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY FFBS needs z (T N normals)");
-        }
-        if ((q.smoother == PFG_SMOOTHER_KALMAN) != kalman)
-            return fail(ctx, PFG_ERR_INVALID, id + "the exact Kalman score cannot share a batch with particle filters");
-        if (kalman) {
-            const pfg_result &r = rs[b];
-            if (q.t1 > q.T) return fail(ctx, PFG_ERR_INVALID, id + "need t1 <= T");
-            if (!(q.prior_var > 0.0) || !std::isfinite(q.prior_var) || !std::isfinite(q.prior_mean))
-                return fail(ctx, PFG_ERR_INVALID, id + "the forward message needs a finite precision > 0 (prior_var = 1 / precision)");
-            if (q.init_x || q.elementwise || q.stat == PFG_STAT_PREDICTIVE || q.paris_stream)
-                return fail(ctx, PFG_ERR_INVALID, id + "the exact Kalman score takes no warm start, elementwise or predictive statistic");
-            if (r.x_T || r.logw_T || r.stats_T || r.trace_x || r.trace_logw || r.trace_stats || r.trace_ll || r.trace_anc ||
-                r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats)
-                return fail(ctx, PFG_ERR_INVALID, id + "the exact Kalman score has no particles: only the result record");
-        }
-        if ((q.smoother == PFG_SMOOTHER_POYIADJIS_N2) != (ps[0].smoother == PFG_SMOOTHER_POYIADJIS_N2))
-            return fail(ctx, PFG_ERR_INVALID, id + "pf = 'poyiadjis_N2' cannot share a batch with other smoothers");
-        if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.N > pfg::MEM_MAX_N)
-            return fail(ctx, PFG_ERR_UNSUPPORTED, id + "pf = 'poyiadjis_N2' is implemented for N <= 16384");
-        if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.elementwise && q.N > 4096)
-            return fail(ctx, PFG_ERR_UNSUPPORTED, id + "elementwise statistics with pf = 'poyiadjis_N2' are implemented for N <= 4096");
-        if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.stat == PFG_STAT_PREDICTIVE)
-            return fail(ctx, PFG_ERR_INVALID, id + "Only can use pf = 'filter' since we are filtering");
-        if ((q.smoother == PFG_SMOOTHER_PARIS) != (ps[0].smoother == PFG_SMOOTHER_PARIS))
-            return fail(ctx, PFG_ERR_INVALID, id + "pf = 'paris' cannot share a batch with other smoothers");
-        if (q.smoother == PFG_SMOOTHER_PARIS) {
-            if (q.Ntilde < 1 || q.Ntilde > 64) return fail(ctx, PFG_ERR_INVALID, id + "Ntilde must be in [1, 64]");
-            if (q.max_accept_reject < 0) return fail(ctx, PFG_ERR_INVALID, id + "max_accept_reject must be >= 0");
-            if (q.paris_stream) {
-                if (rng != PFG_RNG_REPLAY) return fail(ctx, PFG_ERR_INVALID, id + "paris_stream is a REPLAY input");
-                if (q.paris_idx_u || q.paris_acc_u || q.paris_man_u)
-                    return fail(ctx, PFG_ERR_INVALID, id + "paris_stream replaces the addressed pools paris_idx_u / acc_u / man_u");
-                if (q.paris_stream_len < 0 || q.paris_manual_threshold < 0)
-                    return fail(ctx, PFG_ERR_INVALID, id + "paris_stream_len and paris_manual_threshold must be >= 0");
-                if (q.N > pfg::MEM_MAX_N)
-                    return fail(ctx, PFG_ERR_UNSUPPORTED, id + "pf = 'paris' is implemented for N <= 16384");
-                if ((q.flags & PFG_FLAG_PARIS_RAW_STREAM) && dtype != PFG_F64)
-                    return fail(ctx, PFG_ERR_UNSUPPORTED, id + "PFG_FLAG_PARIS_RAW_STREAM is built for dtype f64 (it reproduces np.random's doubles)");
-                if ((q.flags & PFG_FLAG_PARIS_RAW_STREAM) && (q.z0 || q.u || q.z))
-                    return fail(ctx, PFG_ERR_INVALID, id + "PFG_FLAG_PARIS_RAW_STREAM draws z0 / u / z from paris_stream: they must be NULL");
-                if ((q.flags & PFG_FLAG_PARIS_RAW_CARRY) && (!(q.flags & PFG_FLAG_PARIS_RAW_STREAM) || q.paris_stream_len < 1))
-                    return fail(ctx, PFG_ERR_INVALID, id + "PFG_FLAG_PARIS_RAW_CARRY needs PFG_FLAG_PARIS_RAW_STREAM and the cached Gaussian in paris_stream[0]");
-                if ((q.flags & PFG_FLAG_PARIS_RAW_CARRY) && q.init_x && q.T == 0)
-                    return fail(ctx, PFG_ERR_INVALID, id + "PFG_FLAG_PARIS_RAW_CARRY with a warm start and T = 0 draws no normal: nothing to carry the cached Gaussian through");
-            } else if (rng == PFG_RNG_REPLAY && (!q.paris_man_u || (q.max_accept_reject > 0 && (!q.paris_idx_u || !q.paris_acc_u)))) {
-                return fail(ctx, PFG_ERR_INVALID, id + "REPLAY paris needs the paris_* uniform pools or paris_stream");
-            }
-            if ((q.flags & (PFG_FLAG_PARIS_RAW_STREAM | PFG_FLAG_PARIS_RAW_CARRY)) && !q.paris_stream)
-                return fail(ctx, PFG_ERR_INVALID, id + "PFG_FLAG_PARIS_RAW_STREAM needs paris_stream");
-            if ((q.flags & PFG_FLAG_PARIS_NO_ACCEPT_REJECT) && !q.paris_stream)
-                return fail(ctx, PFG_ERR_UNSUPPORTED, id + "PaRIS with accept_reject = False is built for the REPLAY stream order (paris_stream)");
-        } else if (q.paris_stream) {
-            return fail(ctx, PFG_ERR_INVALID, id + "paris_stream needs pf = 'paris'");
-        }
-        if (q.stat < PFG_STAT_SCORE || q.stat > PFG_STAT_PREDICTIVE) return fail(ctx, PFG_ERR_INVALID, id + "bad stat id");
-        if ((q.stat == PFG_STAT_PREDICTIVE) != (ps[0].stat == PFG_STAT_PREDICTIVE))
-            return fail(ctx, PFG_ERR_INVALID, id + "the predictive statistic cannot share a batch with others");
-        if (q.stat == PFG_STAT_PREDICTIVE) {
-            if (q.smoother != PFG_SMOOTHER_FILTER)                                  // svm/helper.py:209-210
-                return fail(ctx, PFG_ERR_INVALID, id + "Only can use pf = 'filter' since we are filtering");
-            if (q.num_steps_ahead < 0 || q.num_steps_ahead >= PFG_MAX_PRED)
-                return fail(ctx, PFG_ERR_INVALID, id + "num_steps_ahead must be in [0, 15]");
-            if (q.N > pfg::MEM_MAX_N)
-                return fail(ctx, PFG_ERR_UNSUPPORTED, id + "N exceeds the supported maximum of 16384");
-            if (rng == PFG_RNG_REPLAY && model != PFG_MODEL_LGSSM && q.T > 0 && !q.pred_z)
-                return fail(ctx, PFG_ERR_INVALID, id + "REPLAY predictive needs the pred_z pool");
-        }
-        if (!q.theta) return fail(ctx, PFG_ERR_INVALID, id + "theta is NULL");
-        if (q.T > 0 && !q.y) return fail(ctx, PFG_ERR_INVALID, id + "observations are NULL");
-        const bool raw_stream = q.smoother == PFG_SMOOTHER_PARIS && (q.flags & PFG_FLAG_PARIS_RAW_STREAM) != 0;
-        const bool streams = rng == PFG_RNG_REPLAY && !raw_stream && !kalman && !ffbs;
-        if (streams && !q.init_x && !q.z0) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs z0");
-        if (streams && q.T > 0 && (!q.u || !q.z)) return fail(ctx, PFG_ERR_INVALID, id + "REPLAY needs u and z");
-        if (q.init_x && !q.init_logw) return fail(ctx, PFG_ERR_INVALID, id + "init_x needs init_logw");
-        if ((q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) != (ps[0].smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC))
-            return fail(ctx, PFG_ERR_INVALID, id + "systematic resampling cannot share a batch with other smoothers");
-        if (q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC && (rng != PFG_RNG_DEVICE || q.N > 1024))
-            return fail(ctx, PFG_ERR_UNSUPPORTED, id + "systematic resampling needs the DEVICE rng and N <= 1024");
-        if (!(q.prior_var >= 0.0) && !(q.flags & PFG_FLAG_GARCH_STATIONARY_PRIOR) && !q.init_x)
-            return fail(ctx, PFG_ERR_INVALID, id + "prior_var must be >= 0");
-        if (model == PFG_MODEL_SVM && std::fabs(q.theta[0]) > 1.0) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "Current AR parameter is |A| = %.17g > 1\nTry calling project_parameters?",
-                     std::fabs(q.theta[0]));
-            return fail(ctx, PFG_ERR_NUMERIC, buf);                                   // svm/kernels.py:6-11
-        }
-        if (kalman) {           // the plan sizes the scratch from the longest window
-            const int L = (q.tL < q.T ? q.tL : q.T) - q.t1;
-            n_max = L > n_max ? L : n_max;
-        } else {
-            n_max = q.N > n_max ? q.N : n_max;
-        }
-        if (ffbs) t_max = q.T > t_max ? q.T : t_max;      // the plan sizes the scratch from the longest buffer
-        const int nw = q.weights ? (q.tL < q.T ? q.tL : q.T) - q.t1 : 0;
-        size_shared(q.y, (size_t)q.T);
-        size_shared(q.weights, nw > 0 ? (size_t)nw : 0);
-        n_in += PFG_MAX_THETA + (q.step ? 1 : 0);
-        n_host += PFG_MAX_THETA + (q.step ? 1 : 0);
-        if (rng == PFG_RNG_REPLAY && ffbs) {
-            size_in(q.z, (size_t)q.T * q.N);
-        } else if (rng == PFG_RNG_REPLAY && !kalman) {
-            size_in(q.z0, (size_t)q.N);
-            size_in(q.u, (size_t)q.T * q.N);
-            size_in(q.z, (size_t)q.T * q.N);
-        }
-        if (q.init_x) {
-            size_in(q.init_x, (size_t)q.N * NS);
-            size_in(q.init_logw, (size_t)q.N);
-            size_in(q.init_stats, (size_t)q.N * H);
-        }
-        if (q.smoother == PFG_SMOOTHER_PARIS && rng == PFG_RNG_REPLAY) {
-            const size_t pool = (size_t)q.T * q.Ntilde * q.max_accept_reject * q.N;
-            size_in(q.paris_idx_u, pool);
-            size_in(q.paris_acc_u, pool);
-            size_in(q.paris_man_u, (size_t)q.T * q.Ntilde * q.N);
-            size_in(q.paris_stream, (size_t)q.paris_stream_len);
-            if (q.paris_stream) n_out += 2;                                   // the consumed count, the carry-back distance
-        }
-        if (q.stat == PFG_STAT_PREDICTIVE && rng == PFG_RNG_REPLAY && model != PFG_MODEL_LGSSM)
-            size_in(q.pred_z, (size_t)q.T * (q.num_steps_ahead + 1) * q.N);
-        const pfg_result &r = rs[b];
-        n_out += PFG_OUT_DOUBLES + (q.stat == PFG_STAT_PREDICTIVE ? PFG_MAX_PRED : 0);
-        if (r.x_T) n_out += (size_t)q.N * NS;
-        if (r.logw_T) n_out += q.N;
-        if (r.stats_T) n_out += (size_t)q.N * H;
-        if (r.trace_x) n_out += (size_t)(q.T + (ffbs ? 0 : 1)) * q.N * NS;      // FFBS: the paths [T][N]
-        if (r.trace_logw) n_out += (size_t)(q.T + 1) * q.N;
-        if (r.trace_stats) n_out += (size_t)(q.T + 1) * q.N * H;
-        if (r.trace_ll) n_out += (size_t)q.T + 1;
-        if (r.trace_anc) n_out += ((size_t)q.T * q.N + 1) / 2;       /* int32 pairs in f64 slots */
-        if (q.elementwise) {
-            if (q.smoother != PFG_SMOOTHER_NEMETH && q.smoother != PFG_SMOOTHER_PARIS && q.smoother != PFG_SMOOTHER_POYIADJIS_N2)
-                return fail(ctx, PFG_ERR_UNSUPPORTED, id + "elementwise statistics are built for pf = 'poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2'");
-            if (q.stat == PFG_STAT_PREDICTIVE) return fail(ctx, PFG_ERR_INVALID, id + "elementwise statistics do not combine with the predictive statistic");
-            if (!r.ew_mean) return fail(ctx, PFG_ERR_INVALID, id + "elementwise needs ew_mean");
-            if (r.trace_x || r.trace_logw || r.trace_stats || r.trace_anc || r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud)
-                return fail(ctx, PFG_ERR_INVALID, id + "elementwise statistics cannot be combined with trace outputs");
-            const int tLc = q.tL < q.T ? q.tL : q.T;
-            if (tLc - q.t1 < 1) return fail(ctx, PFG_ERR_INVALID, id + "elementwise needs a non-empty window [t1, tL)");
-            const size_t Wd = 3 * (size_t)(tLc - q.t1), Nt = q.smoother == PFG_SMOOTHER_PARIS ? (size_t)q.Ntilde : 1;
-            n_out += Wd + (r.ew_stats ? (size_t)q.N * Wd : 0);
-            n_work += (size_t)(q.T + 1) * q.N * (NS + 1) + ((size_t)q.T * q.N * Nt + 1) / 2 + 2 * (size_t)q.N * Wd + Wd + q.N + 8;
-        } else if (r.ew_mean || r.ew_stats) {
-            return fail(ctx, PFG_ERR_INVALID, id + "ew_mean / ew_stats need pfg_problem.elementwise");
-        }
-        if (r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud) {
-            if (rng != PFG_RNG_DEVICE || !r.trace_x)
-                return fail(ctx, PFG_ERR_INVALID, id + "rec_u / rec_z / rec_z0 record the DEVICE generator's draws and need trace_x");
-            if (r.rec_u) n_out += ((size_t)q.T * q.N + 1) / 2;
-            if (r.rec_z) n_out += (size_t)q.T * q.N;
-            if (r.rec_z0) n_out += q.N;
-            if (r.rec_ud) n_out += (size_t)q.T * q.N;
-        }
-        if (r.trace_anc && !r.trace_x) return fail(ctx, PFG_ERR_INVALID, id + "trace_anc needs trace_x");
-        if ((r.logw_T || r.stats_T) && !r.x_T) return fail(ctx, PFG_ERR_INVALID, id + "logw_T/stats_T need x_T");
-        if (!ffbs && (r.trace_logw == nullptr) != (r.trace_x == nullptr))
-            return fail(ctx, PFG_ERR_INVALID, id + "trace_x and trace_logw go together");
-        if (r.trace_stats && !r.trace_x) return fail(ctx, PFG_ERR_INVALID, id + "trace_stats needs trace_x");
-    }
-    bool traced = false;
-    for (int b = 0; b < B; ++b)
-        traced = traced || rs[b].trace_x || rs[b].trace_ll || rs[b].rec_u || rs[b].rec_z || rs[b].rec_z0 || rs[b].rec_ud || ps[b].elementwise;
-    bool score1 = !traced;          // every window the Poyiadjis O(N) score: units with a twin specialised to it run that
-    for (int b = 0; b < B; ++b)
-        score1 = score1 && ps[b].smoother == PFG_SMOOTHER_NEMETH && ps[b].lambduh == 1.0 && ps[b].stat == PFG_STAT_SCORE;
-    const bool paris = ps[0].smoother == PFG_SMOOTHER_PARIS;
-    const bool sysres = ps[0].smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC;
+    // ---- plan ---------------------------------------------------------------------------
+    const BatchSummary sum = summarize(B, ps, rs);
     const bool predictive = ps[0].stat == PFG_STAT_PREDICTIVE;   // large-N kernel only (any N)
-    const bool n2 = ps[0].smoother == PFG_SMOOTHER_POYIADJIS_N2;
-    LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng,
-                                ffbs ? PFG_SMOOTHER_KALMAN_FFBS : kalman ? PFG_SMOOTHER_KALMAN : paris ? PFG_SMOOTHER_PARIS
-                                : sysres ? PFG_SMOOTHER_NEMETH_SYSTEMATIC : n2 ? PFG_SMOOTHER_POYIADJIS_N2
-                                : score1 ? PFG_SMOOTHER_POYIADJIS_N : PFG_SMOOTHER_NEMETH,
-                                n_max, B, traced, predictive, t_max);
+    LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng, sum.smoother, sum.n_max, B, sum.traced, predictive, sum.t_max);
     if (plan.rc && !plan.name) return fail(ctx, plan.rc, plan.err);
     if (plan.family == Family::Grid) {
         for (int b = 0; b < B; ++b) {
@@ -1017,15 +1070,28 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
             if (q.smoother != PFG_SMOOTHER_NEMETH && q.smoother != PFG_SMOOTHER_FILTER)
                 return fail(ctx, PFG_ERR_UNSUPPORTED, id + "N > " + std::to_string(pfg::MEM_MAX_N) + " is built for pf = 'poyiadjis_N' | 'nemeth' | 'filter'");
             if (q.elementwise) return fail(ctx, PFG_ERR_UNSUPPORTED, id + "elementwise statistics are built for N <= " + std::to_string(pfg::MEM_MAX_N));
-            if (pfg::grid_ppt(q.N) != pfg::grid_ppt(n_max))
+            if (pfg::grid_ppt(q.N) != pfg::grid_ppt(sum.n_max))
                 return fail(ctx, PFG_ERR_INVALID, id + "whole-GPU windows of one batch must all have N <= 524288 or all N > 524288");
             plan.t_max = q.T > plan.t_max ? q.T : plan.t_max;
         }
     }
     // every window of the batch gets n_max-sized state (the predictive statistic's buffers after it)
-    const size_t pred_each = predictive ? ((size_t)n_max * PFG_MAX_PRED * (dtype == PFG_F64 ? 8 : 4) + 255) / 256 * 256 : 0;
+    const size_t pred_each = predictive ? ((size_t)sum.n_max * PFG_MAX_PRED * (dtype == PFG_F64 ? 8 : 4) + 255) / 256 * 256 : 0;
     const size_t scratch_each = plan.scratch + pred_each, n_scratch = scratch_each * (size_t)B;
 
+    // ---- describe, allocate -------------------------------------------------------------
+    Layout L{ctx->pieces};
+    std::vector<EwPlan> ew;
+    try {
+        ctx->h_desc.assign(B, pfg_dev_problem{});
+        ctx->h_own.resize((size_t)B * kOwnDoubles);
+        ctx->pieces.clear();
+        ew.resize(B);
+        for (int b = 0; b < B; ++b) describe_window(L, ps[b], rs[b], ctx->h_desc[b], ew[b], &ctx->h_own[(size_t)b * kOwnDoubles]);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, PFG_ERR_NOMEM, "pfg_run_batch: out of host memory");
+    }
+    const size_t n_in = L.n[Piece::In], n_out = L.n[Piece::Out], n_work = L.n[Piece::Work];
     PFG_HIP(ctx, hipSetDevice(ctx->device));
     PFG_HIP(ctx, ctx->in.ensure(n_in * 8));
     PFG_HIP(ctx, ctx->out.ensure(n_out * 8));
@@ -1034,223 +1100,73 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     if (n_work) PFG_HIP(ctx, ctx->work.ensure(n_work * 8));
     double *hin = nullptr;
     try {
-        if (ctx->h_in.ensure(n_host) == hipSuccess) {
+        if (ctx->h_in.ensure(L.n_host) == hipSuccess) {
             hin = ctx->h_in.data();
         } else {
             // the runtime refuses to page-lock that much: stage from pageable memory (slower copies, same result)
             (void)hipGetLastError();
-            ctx->h_in_pageable.resize(n_host);
+            ctx->h_in_pageable.resize(L.n_host);
             hin = ctx->h_in_pageable.data();
         }
         if (ctx->h_out.ensure(n_out) != hipSuccess) throw std::bad_alloc();
-        ctx->h_desc.assign(B, pfg_dev_problem{});
     } catch (const std::bad_alloc &) {
         return fail(ctx, PFG_ERR_NOMEM, "pfg_run_batch: out of host memory");
     }
 
-    // ---- pack ---------------------------------------------------------------------------
-    const double *din = static_cast<const double *>(ctx->in.ptr);
-    double *dout = static_cast<double *>(ctx->out.ptr);
-    size_t oi = 0, oh = 0, oo = 0;       // offsets into the device input arena, the host staging arena, the output arena
-    // big inputs that lie in caller-registered pinned memory (pfg_host_register) go to the device straight
-    // from there; everything else is packed into the library's staging arena.  `copies` = the H2D transfers:
-    // runs of packed pieces (contiguous on both sides) and the direct pieces.
+    // ---- stage: point every descriptor at its buffers, pack the staged inputs --------------------------------------
+    // `copies` = the H2D transfers: runs of packed pieces (contiguous on both sides) and the direct pieces
+    char *const base[3] = {static_cast<char *>(ctx->in.ptr), static_cast<char *>(ctx->out.ptr), static_cast<char *>(ctx->work.ptr)};
     struct Copy { size_t at; const double *src; size_t n; bool packed; };
     std::vector<Copy> copies;
-    bool overflow = false;               // a piece that would not fit what the sizing pass reserved (it never copies)
-    auto put = [&](const double *src, size_t n) -> const double * {
-        if (!src || n == 0) return nullptr;
-        const bool direct = n >= kDirectMinDoubles && host_registered(src, n * 8);
-        if (oi + n > n_in || (!direct && oh + n > n_host)) { overflow = true; return nullptr; }
-        if (direct) {
-            copies.push_back({oi, src, n, false});
-        } else {
-            std::memcpy(hin + oh, src, n * 8);
-            if (!copies.empty() && copies.back().packed && copies.back().src + copies.back().n == hin + oh && copies.back().at + copies.back().n == oi)
-                copies.back().n += n;                     // extends the current packed run
+    size_t oh = 0;                      // offset into the host staging arena
+    for (const Piece &p : ctx->pieces) {
+        void *dev = base[p.arena] + p.at * 8;
+        std::memcpy(p.slot, &dev, sizeof dev);
+        if (p.copy == Piece::Direct) {
+            copies.push_back({p.at, p.src, p.n, false});
+        } else if (p.copy == Piece::Staged) {
+            std::memcpy(hin + oh, p.src, p.n * 8);
+            if (!copies.empty() && copies.back().packed && copies.back().src + copies.back().n == hin + oh && copies.back().at + copies.back().n == p.at)
+                copies.back().n += p.n;                   // extends the current packed run
             else
-                copies.push_back({oi, hin + oh, n, true});
-            oh += n;
+                copies.push_back({p.at, hin + oh, p.n, true});
+            oh += p.n;
         }
-        const double *d = din + oi;
-        oi += n;
-        return d;
-    };
-    // observations / window weights that many windows of the batch share (same host pointer and length) are
-    // staged once: 12288 chains on one series would otherwise carry 98 MB of copies of the same 8 KB
-    std::unordered_map<const double *, std::pair<size_t, const double *>> shared;
-    auto put_shared = [&](const double *src, size_t n) -> const double * {
-        if (!src || n == 0) return nullptr;
-        auto it = shared.find(src);
-        if (it != shared.end() && it->second.first == n) return it->second.second;
-        const double *d = put(src, n);
-        shared[src] = std::make_pair(n, d);
-        return d;
-    };
-    auto take = [&](bool want, size_t n) -> double * {
-        if (!want) return nullptr;
-        double *d = dout + oo;
-        oo += n;
-        return d;
-    };
-    // elementwise pass: device-only buffers (traces the filter records, the statistic matrices)
-    struct EwPlan { double *tx, *tlw, *S0, *S1, *Sbar, *w, *mean, *stats; int32_t *par; size_t Wd; int Nt; const double *theta; };
-    std::vector<EwPlan> ew(B, EwPlan{});
-    double *dwork = static_cast<double *>(ctx->work.ptr);
-    size_t ow = 0;
-    auto work = [&](size_t n) -> double * { double *d = dwork + ow; ow += n; return d; };
+    }
     for (int b = 0; b < B; ++b) {
-        const pfg_problem &q = ps[b];
-        const pfg_result &r = rs[b];
         pfg_dev_problem &d = ctx->h_desc[b];
-        const int tL = q.tL < q.T ? q.tL : q.T;
-        const int nw = q.weights ? tL - q.t1 : 0;
-        d.y = put_shared(q.y, q.T);
-        d.weights = put_shared(q.weights, nw > 0 ? nw : 0);
-        {
-            double th[PFG_MAX_THETA] = {0, 0, 0, 0};
-            for (int j = 0; j < P; ++j) th[j] = q.theta[j];
-            d.theta = put(th, PFG_MAX_THETA);
-        }
-        if (rng == PFG_RNG_REPLAY && ffbs) {
-            d.z = put(q.z, (size_t)q.T * q.N);
-        } else if (rng == PFG_RNG_REPLAY && !kalman) {
-            d.z0 = put(q.z0, q.z0 ? q.N : 0);
-            d.u = put(q.u, (size_t)q.T * q.N);
-            d.z = put(q.z, (size_t)q.T * q.N);
-        }
-        if (q.init_x) {
-            d.init_x = put(q.init_x, (size_t)q.N * NS);
-            d.init_logw = put(q.init_logw, q.N);
-            d.init_stats = put(q.init_stats, q.init_stats ? (size_t)q.N * H : 0);
-        }
-        if (paris) {
-            d.Ntilde = q.Ntilde; d.max_accept_reject = q.max_accept_reject;
-            if (rng == PFG_RNG_REPLAY) {
-                const size_t pool = (size_t)q.T * q.Ntilde * q.max_accept_reject * q.N;
-                d.paris_idx_u = put(q.paris_idx_u, pool);
-                d.paris_acc_u = put(q.paris_acc_u, pool);
-                d.paris_man_u = put(q.paris_man_u, (size_t)q.T * q.Ntilde * q.N);
-                if (q.paris_stream) {
-                    d.paris_stream = put(q.paris_stream, (size_t)q.paris_stream_len);
-                    if (!d.paris_stream) d.paris_stream = din;        // an empty stream is still "stream order" (non-NULL)
-                    d.paris_stream_len = q.paris_stream_len;
-                    d.paris_manual_threshold = q.paris_manual_threshold;
-                    d.paris_consumed = reinterpret_cast<int64_t *>(take(true, 2));
-                }
-            }
-        }
-        if (predictive) {
-            d.num_steps_ahead = q.num_steps_ahead;
-            if (rng == PFG_RNG_REPLAY && model != PFG_MODEL_LGSSM)
-                d.pred_z = put(q.pred_z, (size_t)q.T * (q.num_steps_ahead + 1) * q.N);
-            d.pred_out = take(true, PFG_MAX_PRED);
-        }
-        d.out = take(true, PFG_OUT_DOUBLES);
-        d.final_x = take(r.x_T != nullptr, (size_t)q.N * NS);
-        d.final_logw = take(r.logw_T != nullptr, q.N);
-        d.final_stats = take(r.stats_T != nullptr, (size_t)q.N * H);
-        const size_t trace_rows = (size_t)q.T + (ffbs ? 0 : 1);
-        d.trace_x = take(r.trace_x != nullptr, trace_rows * q.N * NS);
-        d.trace_logw = take(r.trace_logw != nullptr, (size_t)(q.T + 1) * q.N);
-        d.trace_stats = take(r.trace_stats != nullptr, (size_t)(q.T + 1) * q.N * H);
-        d.trace_ll = take(r.trace_ll != nullptr, (size_t)q.T + 1);
-        d.trace_anc = reinterpret_cast<int32_t *>(take(r.trace_anc != nullptr, ((size_t)q.T * q.N + 1) / 2));
-        if (q.elementwise) {
-            EwPlan &e = ew[b];
-            e.Wd = 3 * (size_t)(tL - q.t1);
-            e.Nt = q.smoother == PFG_SMOOTHER_PARIS ? q.Ntilde : 1;
-            e.tx = work((size_t)(q.T + 1) * q.N * NS);
-            e.tlw = work((size_t)(q.T + 1) * q.N);
-            e.par = reinterpret_cast<int32_t *>(work(((size_t)q.T * q.N * e.Nt + 1) / 2));
-            e.S0 = work((size_t)q.N * e.Wd); e.S1 = work((size_t)q.N * e.Wd);
-            e.Sbar = work(e.Wd); e.w = work(q.N);
-            e.mean = take(true, e.Wd);
-            e.stats = take(r.ew_stats != nullptr, (size_t)q.N * e.Wd);
-            d.trace_x = e.tx; d.trace_logw = e.tlw;
-            e.theta = d.theta;
-            if (q.smoother == PFG_SMOOTHER_PARIS) d.trace_paris_J = e.par; else d.trace_anc = e.par;
-        }
-        d.rec_u = reinterpret_cast<uint32_t *>(take(r.rec_u != nullptr, ((size_t)q.T * q.N + 1) / 2));
-        d.rec_z = take(r.rec_z != nullptr, (size_t)q.T * q.N);
-        d.rec_z0 = take(r.rec_z0 != nullptr, q.N);
-        d.rec_ud = take(r.rec_ud != nullptr, (size_t)q.T * q.N);
-        d.step_ctr = nullptr;
-        if (q.step) {       // the step counter of this window, as a resident chain would read it from HBM
-            double slot;
-            std::memcpy(&slot, &q.step, sizeof slot);
-            d.step_ctr = reinterpret_cast<const uint64_t *>(put(&slot, 1));
-        }
         d.scratch = n_scratch ? static_cast<void *>(static_cast<char *>(ctx->scratch.ptr) + scratch_each * (size_t)b) : nullptr;
         if (predictive) d.pred_scratch = static_cast<char *>(d.scratch) + plan.scratch;
-        d.prior_mean = q.prior_mean; d.prior_var = q.prior_var; d.lambduh = q.lambduh;
-        d.seed = q.seed; d.stream = q.stream;
-        d.T = q.T; d.t1 = q.t1; d.tL = tL; d.N = q.N;
-        d.smoother = q.smoother; d.stat = q.stat; d.flags = q.flags;
     }
 
-    // ---- stage, launch, fetch -----------------------------------------------------------
-    if (overflow || oi > n_in || oh > n_host)
-        return fail(ctx, PFG_ERR_INVALID, "pfg_run_batch: internal sizing error (an input changed its registration state during the call?)");
+    // ---- launch, elementwise pass, fetch ------------------------------------------------
     for (const Copy &cp : copies)
         PFG_HIP(ctx, hipMemcpyAsync(static_cast<double *>(ctx->in.ptr) + cp.at, cp.src, cp.n * 8, hipMemcpyHostToDevice, ctx->stream));
     PFG_HIP(ctx, hipMemcpyAsync(ctx->desc.ptr, ctx->h_desc.data(), (size_t)B * sizeof(pfg_dev_problem),
                                 hipMemcpyHostToDevice, ctx->stream));
-    PFG_HIP(ctx, hipMemsetAsync(ctx->out.ptr, 0, oo * 8, ctx->stream));
+    PFG_HIP(ctx, hipMemsetAsync(ctx->out.ptr, 0, n_out * 8, ctx->stream));
     rc = launch(ctx, plan, model, kernel, rng, B, static_cast<const pfg_dev_problem *>(ctx->desc.ptr), ctx->stream);
     if (rc) return rc;
     for (int b = 0; b < B; ++b) {
         if (!ps[b].elementwise) continue;
-        rc = elementwise_pass(ctx, ps[b], ew[b].theta, ew[b].tx, ew[b].tlw, ew[b].par, ew[b].Nt, ew[b].Wd, ew[b].S0, ew[b].S1,
-                              ew[b].Sbar, ew[b].w, ew[b].mean, ew[b].stats);
+        const pfg_dev_problem &d = ctx->h_desc[b];
+        const EwPlan &e = ew[b];
+        rc = elementwise_pass(ctx, ps[b], d.theta, d.trace_x, d.trace_logw, ps[b].smoother == PFG_SMOOTHER_PARIS ? d.trace_paris_J : d.trace_anc, e.Nt,
+                              e.Wd, e.S0, e.S1, e.Sbar, e.w, e.mean, e.stats);
         if (rc) return rc;
     }
-    PFG_HIP(ctx, hipMemcpyAsync(ctx->h_out.data(), ctx->out.ptr, oo * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PFG_HIP(ctx, hipMemcpyAsync(ctx->h_out.data(), ctx->out.ptr, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
     PFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-
     const double *hout = ctx->h_out.data();
-    for (int b = 0; b < B; ++b) {
-        const pfg_problem &q = ps[b];
-        pfg_result &r = rs[b];
-        const pfg_dev_problem &d = ctx->h_desc[b];
-        auto host_of = [&](const double *dev) { return hout + (dev - dout); };
-        const double *o = host_of(d.out);
-        for (int h = 0; h < PFG_MAX_STAT; ++h) r.mean_stat[h] = o[h];
-        r.loglik = o[4];
-        if (predictive) {
-            const double *pp = host_of(d.pred_out);
-            for (int k = 0; k < PFG_MAX_PRED; ++k) r.pred[k] = pp[k];
-        }
-        auto fetch = [&](double *dst, const double *dev, size_t n) {
-            if (dst && dev) std::memcpy(dst, host_of(dev), n * 8);
-        };
-        fetch(r.x_T, d.final_x, (size_t)q.N * NS);
-        fetch(r.logw_T, d.final_logw, q.N);
-        fetch(r.stats_T, d.final_stats, (size_t)q.N * H);
-        fetch(r.trace_x, d.trace_x, ((size_t)q.T + (ffbs ? 0 : 1)) * q.N * NS);
-        fetch(r.trace_logw, d.trace_logw, (size_t)(q.T + 1) * q.N);
-        fetch(r.trace_stats, d.trace_stats, (size_t)(q.T + 1) * q.N * H);
-        fetch(r.trace_ll, d.trace_ll, (size_t)q.T + 1);
-        if (r.trace_anc && d.trace_anc)
-            std::memcpy(r.trace_anc, host_of(reinterpret_cast<const double *>(d.trace_anc)), (size_t)q.T * q.N * 4);
-        if (r.rec_u && d.rec_u)
-            std::memcpy(r.rec_u, host_of(reinterpret_cast<const double *>(d.rec_u)), (size_t)q.T * q.N * 4);
-        fetch(r.rec_z, d.rec_z, (size_t)q.T * q.N);
-        fetch(r.rec_z0, d.rec_z0, q.N);
-        fetch(r.rec_ud, d.rec_ud, (size_t)q.T * q.N);
-        r.paris_consumed = 0;
-        r.paris_carry_back = 0;
-        if (d.paris_consumed) {
-            int64_t two[2];
-            std::memcpy(two, host_of(reinterpret_cast<const double *>(d.paris_consumed)), 16);
-            r.paris_consumed = two[0];
-            r.paris_carry_back = (int32_t)two[1];
-        }
-        if (q.elementwise) {
-            fetch(r.ew_mean, ew[b].mean, ew[b].Wd);
-            fetch(r.ew_stats, ew[b].stats, (size_t)q.N * ew[b].Wd);
-        }
-        r.status = PFG_OK;
+    for (const Piece &p : ctx->pieces)
+        if (p.dst) std::memcpy(p.dst, hout + p.at, p.bytes);
+    for (int b = 0; b < B; ++b) {       // the PaRIS stream counts: an int64 pair into two fields of the record
+        const int64_t *pc = ctx->h_desc[b].paris_consumed;
+        int64_t two[2] = {0, 0};
+        if (pc) std::memcpy(two, hout + (reinterpret_cast<const double *>(pc) - static_cast<const double *>(ctx->out.ptr)), 16);
+        rs[b].paris_consumed = two[0];
+        rs[b].paris_carry_back = (int32_t)two[1];
+        rs[b].status = PFG_OK;
     }
     return PFG_OK;
 }

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import pf_oracle as po
+from sgmcmc_ssm_amd import _capi
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,6 @@ RTOL, ATOL = 1e-9, 1e-9
 
 @pytest.fixture(scope="module")
 def ctx():
-    from sgmcmc_ssm_amd import _capi
     return _capi.default_context(0)
 
 
@@ -219,6 +219,151 @@ def test_error_paths(ctx):
     with pytest.raises(ValueError):
         ctx.run_batch([q])
     assert ctx.run_batch([]) == []
+    # every refusal of pfg_run_batch itself, on ctypes arrays (Context.run_batch refuses some of these in Python first)
+    lib, h = ctx.lib, ctx.handle
+    assert lib.pfg_run_batch(h, -1, None, None) == _capi.PFG_ERR_INVALID
+    assert "NULL problems/results" in lib.pfg_last_error(h).decode()
+    for row in _REFUSALS:
+        base, which, fault, code, text = row
+        keep = []
+        ps, rs = _refusal_batch(keep, base, which, fault)
+        rc = lib.pfg_run_batch(h, len(ps), ps, rs)
+        msg = lib.pfg_last_error(h).decode()
+        assert (rc, text in msg) == (code, True), (row, rc, msg)
+
+
+_INV, _UNS, _NUM = _capi.PFG_ERR_INVALID, _capi.PFG_ERR_UNSUPPORTED, _capi.PFG_ERR_NUMERIC
+_RAW, _CARRY = _capi.FLAG_PARIS_RAW_STREAM, _capi.FLAG_PARIS_RAW_CARRY
+_NO_STREAMS = dict(z0=None, u=None, z=None)
+# valid two-window batches (SVM, REPLAY, N = 8, T = 2 unless stated); a row changes one of them
+_BASES = {
+    "svm": {},
+    "device": dict(rng=1, **_NO_STREAMS),
+    "kalman": dict(model=2, smoother=6, theta=[0.5, 1.0, 1.0, 1.0], **_NO_STREAMS),
+    "ffbs": dict(model=2, smoother=7, theta=[0.5, 1.0, 1.0, 1.0], z0=None, u=None),
+    "n2": dict(smoother=4),
+    "n2_ew": dict(smoother=4, elementwise=1, ew_mean=6),
+    "paris": dict(smoother=2, Ntilde=2, paris_man_u=32),
+    "paris_device": dict(smoother=2, Ntilde=2, rng=1, **_NO_STREAMS),
+    "paris_stream": dict(smoother=2, Ntilde=2, paris_stream=64, paris_stream_len=64),
+    "predictive": dict(smoother=1, stat=3, num_steps_ahead=1, pred_z=32),
+    "systematic": dict(smoother=3, rng=1, **_NO_STREAMS),
+    "elementwise": dict(elementwise=1, ew_mean=6),
+}
+# (base, window the fault goes into (None: both), fault, code, message substring).  Not here, because no input reaches
+# them: elementwise with the predictive statistic (elementwise needs a smoother the predictive statistic refuses), and
+# the whole-GPU smoother refusal (only NEMETH / FILTER batches are planned as whole-GPU windows).
+_REFUSALS = [
+    ("svm", None, dict(model=3), _INV, "Unrecognized model id"),
+    ("svm", None, dict(kernel=2), _INV, "Unrecoginized kernel id"),
+    ("svm", None, dict(kernel=1), _UNS, "SVM optimal kernel not analytic"),
+    ("svm", None, dict(dtype=2), _INV, "bad dtype"),
+    ("svm", None, dict(rng=2), _INV, "bad rng mode"),
+    ("kalman", None, dict(model=1), _UNS, "the exact Kalman score (kind = 'marginal') is built for LGSSM only"),
+    ("kalman", None, dict(dtype=1), _UNS, "the exact Kalman score (kind = 'marginal') is built for dtype f64 only"),
+    ("ffbs", None, dict(model=0), _UNS, "FFBS latent paths (kind = 'complete') are built for LGSSM only"),
+    ("ffbs", None, dict(dtype=1), _UNS, "FFBS latent paths (kind = 'complete') are built for dtype f64 only"),
+    ("ffbs", None, dict(rng=2), _INV, "bad rng mode"),
+    ("svm", 1, dict(model=1), _INV, "problem 1: model/kernel/dtype/rng must match across a batch"),
+    ("svm", 1, dict(rng=1), _INV, "problem 1: model/kernel/dtype/rng must match across a batch"),
+    ("svm", 1, dict(N=0), _INV, "problem 1: N must be >= 1"),
+    ("svm", 1, dict(T=-1), _INV, "problem 1: T must be >= 0"),
+    ("svm", 1, dict(t1=2, tL=1), _INV, "problem 1: need 0 <= t1 <= tL"),
+    ("svm", 1, dict(smoother=5), _INV, "problem 1: Unrecognized pf (smoother id)"),
+    ("ffbs", 1, dict(smoother=6), _INV, "problem 1: FFBS latent paths cannot share a batch with other smoothers"),
+    ("ffbs", 1, dict(t1=3, tL=3), _INV, "problem 1: need t1 <= T"),
+    ("ffbs", 1, dict(prior_var=0.0), _INV, "problem 1: the forward message needs a finite precision > 0"),
+    ("ffbs", 1, dict(prior_mean=np.inf), _INV, "problem 1: the forward message needs a finite precision > 0"),
+    ("ffbs", 1, dict(stat=1), _INV, "problem 1: FFBS latent paths take no warm start or elementwise statistic"),
+    ("ffbs", 1, dict(init_x=8), _INV, "problem 1: FFBS latent paths take no warm start or elementwise statistic"),
+    ("ffbs", 1, dict(x_T=8), _INV, "problem 1: FFBS latent paths have no particles"),
+    ("ffbs", 1, dict(z=None), _INV, "problem 1: REPLAY FFBS needs z"),
+    ("kalman", 1, dict(smoother=0), _INV, "problem 1: the exact Kalman score cannot share a batch with particle filters"),
+    ("svm", 1, dict(smoother=6), _INV, "problem 1: the exact Kalman score cannot share a batch with particle filters"),
+    ("kalman", 1, dict(t1=3, tL=3), _INV, "problem 1: need t1 <= T"),
+    ("kalman", 1, dict(prior_var=np.nan), _INV, "problem 1: the forward message needs a finite precision > 0"),
+    ("kalman", 1, dict(stat=3), _INV, "problem 1: the exact Kalman score takes no warm start, elementwise or predictive"),
+    ("kalman", 1, dict(trace_x=16), _INV, "problem 1: the exact Kalman score has no particles"),
+    ("n2", 1, dict(smoother=0), _INV, "problem 1: pf = 'poyiadjis_N2' cannot share a batch with other smoothers"),
+    ("n2", 1, dict(N=16385), _UNS, "problem 1: pf = 'poyiadjis_N2' is implemented for N <= 16384"),
+    ("n2_ew", 1, dict(N=5000), _UNS, "problem 1: elementwise statistics with pf = 'poyiadjis_N2' are implemented for N <= 4096"),
+    ("n2", 1, dict(stat=3), _INV, "problem 1: Only can use pf = 'filter' since we are filtering"),
+    ("paris", 1, dict(smoother=0), _INV, "problem 1: pf = 'paris' cannot share a batch with other smoothers"),
+    ("paris", 1, dict(Ntilde=0), _INV, "problem 1: Ntilde must be in [1, 64]"),
+    ("paris", 1, dict(max_accept_reject=-1), _INV, "problem 1: max_accept_reject must be >= 0"),
+    ("paris_stream", None, dict(rng=1), _INV, "problem 0: paris_stream is a REPLAY input"),
+    ("paris_stream", 1, dict(paris_man_u=32), _INV, "problem 1: paris_stream replaces the addressed pools"),
+    ("paris_stream", 1, dict(paris_stream_len=-1), _INV, "problem 1: paris_stream_len and paris_manual_threshold must be >= 0"),
+    ("paris_stream", 1, dict(paris_manual_threshold=-1), _INV, "problem 1: paris_stream_len and paris_manual_threshold must be >= 0"),
+    ("paris_stream", 1, dict(N=16385), _UNS, "problem 1: pf = 'paris' is implemented for N <= 16384"),
+    ("paris_stream", None, dict(dtype=1, flags=_RAW, **_NO_STREAMS), _UNS, "problem 0: PFG_FLAG_PARIS_RAW_STREAM is built for dtype f64"),
+    ("paris_stream", 1, dict(flags=_RAW), _INV, "problem 1: PFG_FLAG_PARIS_RAW_STREAM draws z0 / u / z from paris_stream"),
+    ("paris_stream", 1, dict(flags=_CARRY), _INV, "problem 1: PFG_FLAG_PARIS_RAW_CARRY needs PFG_FLAG_PARIS_RAW_STREAM"),
+    ("paris_stream", 1, dict(flags=_RAW | _CARRY, paris_stream_len=0, **_NO_STREAMS), _INV,
+     "problem 1: PFG_FLAG_PARIS_RAW_CARRY needs PFG_FLAG_PARIS_RAW_STREAM"),
+    ("paris_stream", 1, dict(flags=_RAW | _CARRY, init_x=8, init_logw=8, T=0, tL=0, **_NO_STREAMS), _INV,
+     "problem 1: PFG_FLAG_PARIS_RAW_CARRY with a warm start and T = 0"),
+    ("paris", 1, dict(paris_man_u=None), _INV, "problem 1: REPLAY paris needs the paris_* uniform pools or paris_stream"),
+    ("paris", 1, dict(max_accept_reject=1), _INV, "problem 1: REPLAY paris needs the paris_* uniform pools or paris_stream"),
+    ("paris_device", 1, dict(flags=_RAW), _INV, "problem 1: PFG_FLAG_PARIS_RAW_STREAM needs paris_stream"),
+    ("paris_device", 1, dict(flags=_CARRY), _INV, "problem 1: PFG_FLAG_PARIS_RAW_STREAM needs paris_stream"),
+    ("paris_device", 1, dict(flags=_capi.FLAG_PARIS_NO_ACCEPT_REJECT), _UNS,
+     "problem 1: PaRIS with accept_reject = False is built for the REPLAY stream order"),
+    ("svm", 1, dict(paris_stream=8, paris_stream_len=8), _INV, "problem 1: paris_stream needs pf = 'paris'"),
+    ("svm", 1, dict(stat=4), _INV, "problem 1: bad stat id"),
+    ("predictive", 1, dict(stat=0), _INV, "problem 1: the predictive statistic cannot share a batch with others"),
+    ("predictive", 1, dict(smoother=0), _INV, "problem 1: Only can use pf = 'filter' since we are filtering"),
+    ("predictive", 1, dict(num_steps_ahead=16), _INV, "problem 1: num_steps_ahead must be in [0, 15]"),
+    ("predictive", 1, dict(N=16385), _UNS, "problem 1: N exceeds the supported maximum of 16384"),
+    ("predictive", 1, dict(pred_z=None), _INV, "problem 1: REPLAY predictive needs the pred_z pool"),
+    ("svm", 1, dict(theta=None), _INV, "problem 1: theta is NULL"),
+    ("svm", 1, dict(y=None), _INV, "problem 1: observations are NULL"),
+    ("svm", 1, dict(z0=None), _INV, "problem 1: REPLAY needs z0"),
+    ("svm", 1, dict(u=None), _INV, "problem 1: REPLAY needs u and z"),
+    ("svm", 1, dict(init_x=8), _INV, "problem 1: init_x needs init_logw"),
+    ("systematic", 1, dict(smoother=0), _INV, "problem 1: systematic resampling cannot share a batch with other smoothers"),
+    ("systematic", 1, dict(N=1025), _UNS, "problem 1: systematic resampling needs the DEVICE rng and N <= 1024"),
+    ("svm", 1, dict(prior_var=-1.0), _INV, "problem 1: prior_var must be >= 0"),
+    ("svm", 1, dict(theta=[1.5, 1.0, 1.0]), _NUM, "Current AR parameter is |A| = 1.5 > 1\nTry calling project_parameters?"),
+    ("elementwise", 1, dict(smoother=1), _UNS, "problem 1: elementwise statistics are built for pf = 'poyiadjis_N'"),
+    ("elementwise", 1, dict(ew_mean=None), _INV, "problem 1: elementwise needs ew_mean"),
+    ("elementwise", 1, dict(rec_z=16), _INV, "problem 1: elementwise statistics cannot be combined with trace outputs"),
+    ("elementwise", 1, dict(t1=2), _INV, "problem 1: elementwise needs a non-empty window [t1, tL)"),
+    ("svm", 1, dict(ew_stats=48), _INV, "problem 1: ew_mean / ew_stats need pfg_problem.elementwise"),
+    ("svm", 1, dict(rec_u=16), _INV, "problem 1: rec_u / rec_z / rec_z0 record the DEVICE generator's draws and need trace_x"),
+    ("device", 1, dict(rec_z0=8), _INV, "problem 1: rec_u / rec_z / rec_z0 record the DEVICE generator's draws and need trace_x"),
+    ("svm", 1, dict(trace_anc=16), _INV, "problem 1: trace_anc needs trace_x"),
+    ("svm", 1, dict(stats_T=24), _INV, "problem 1: logw_T/stats_T need x_T"),
+    ("svm", 1, dict(trace_x=24), _INV, "problem 1: trace_x and trace_logw go together"),
+    ("svm", 1, dict(trace_stats=72), _INV, "problem 1: trace_stats needs trace_x"),
+    ("device", None, dict(N=20000, elementwise=1, ew_mean=6), _UNS, "problem 0: elementwise statistics are built for N <= 16384"),
+    ("device", None, [dict(N=20000), dict(N=600000)], _INV, "problem 0: whole-GPU windows of one batch must all have N <= 524288 or all N > 524288"),
+]
+
+
+def _refusal_batch(keep, base, which, fault):
+    """Two windows of _BASES[base] as ctypes arrays, `fault` applied to window `which` (None: both; a list: one fault per
+    window).  Pointer fields take
+    an entry count (a zero buffer of the field's type), a list (those doubles) or None (NULL)."""
+    ps, rs = (_capi.Problem * 2)(), (_capi.Result * 2)()
+    for b in range(2):
+        fields = dict(model=0, kernel=0, smoother=0, stat=0, dtype=0, rng=0, N=8, T=2, t1=0, tL=2, lambduh=1.0,
+                      prior_var=1.0, y=2, theta=[0.5, 1.0, 1.0], z0=8, u=16, z=16)
+        fields.update(_BASES[base])
+        if isinstance(fault, list):
+            fields.update(fault[b])
+        elif which is None or which == b:
+            fields.update(fault)
+        for name, v in fields.items():
+            rec = ps[b] if hasattr(_capi.Problem, name) else rs[b]
+            ftype = dict(type(rec)._fields_)[name]
+            if hasattr(ftype, "contents"):
+                if v is not None:
+                    a = np.asarray(v, dtype=np.float64) if isinstance(v, list) else np.zeros(v, dtype=ftype._type_)
+                    keep.append(a)
+                    v = a.ctypes.data_as(ftype)
+            setattr(rec, name, v)
+    return ps, rs
 
 
 @pytest.mark.parametrize("model,kernel", [("svm", "prior"), ("garch", "optimal"), ("lgssm", "optimal")])
