@@ -289,7 +289,10 @@ void *pfg_ctx_stream(pfg_ctx *ctx);
 /* Resident entry point: `dev_probs` is a DEVICE array of B descriptors; launches on
  * `hip_stream` (a hipStream_t used as is: NULL is HIP's default stream; pass
  * pfg_ctx_stream(ctx) for the context's own) and returns without synchronising.
- * n_max = the largest N in the batch (selects the kernel variant). */
+ * n_max = the largest N in the batch (selects the kernel variant).  The variant is chosen without
+ * reading the descriptors: where it is the large-N kernel's N <= 4096 instantiation (REPLAY,
+ * 1024 < n_max <= 4096), a PFG_STAT_PREDICTIVE descriptor gets NaNs in out[] -- that statistic is
+ * served by pfg_run_batch, which plans predictive batches onto the general kernel. */
 int pfg_launch_device(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max,
                       int B, const pfg_dev_problem *dev_probs, void *hip_stream);
 /* pfg_launch_device / pfg_launch_device_smoother are the PRODUCTION launches: for the plain (NEMETH / FILTER)
@@ -321,7 +324,7 @@ int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, i
  * the reference's CDF -- NumPy's sequential cumsum, bit for bit -- with the particle axis spread over the GPU).  T_max = the largest T of
  * the batch (the host issues the launches, so it has to know; shorter windows leave theirs at once).  NEMETH / FILTER
  * with the score, sufficient or no statistic.  Every descriptor needs `scratch` of pfg_scratch_bytes(model, dtype, rng, N)
- * bytes (256-byte aligned); windows of one batch must all have N <= 524288 or all N > 524288 (the tile size differs).
+ * bytes (256-byte aligned; non-decreasing in N within a tile class, so the size for n_max serves every window); windows of one batch must all have N <= 524288 or all N > 524288 (the tile size differs).
  * DEVICE rng: the resampling uniforms are SORTED uniforms (exponential spacings, rec_ud), generator lane = particle
  * index mod tile; out[7] = 1.  REPLAY: u / z as for every kernel, out[7] = the smallest |u - cdf| margin of the run.
  * pfg_run / pfg_run_batch route N > 16384 here by themselves (PFGRAD_VARIANT=grid forces it for smaller N). */

@@ -18,7 +18,9 @@
 //                         (G <= 2048 values): the step needs no separate reduction pass and no grid-wide synchronisation
 //     rng[G*NT]           jsf32 lane-generator states between launches (device generator)
 //     head[32]            log-likelihood, filter accumulators, tie margin
-//     REPLAY only: cdf[N] (the reference's CDF, bit for bit: pfg_grid_cdf.hpp), coarse[C], walk list
+//     REPLAY only: cdf[N] (the reference's CDF, bit for bit: pfg_grid_cdf.hpp), coarse[C] (room for CR >= C), walk list
+// Every size in the layout is non-decreasing in N within a tile class: a batch's scratch stride and the step kernel's LDS
+// are sized once from its largest window (tests/test_launch_sizes.py).
 //
 // DEVICE generator (the throughput path, pfg_grid_step_dev_kernel in pfg_grid_dev_kernel.hpp): the resampling uniforms of a
 // timestep are the order statistics of N i.i.d. uniforms (exponential spacings, as pf_big_kernel; multinomial resampling
@@ -66,8 +68,16 @@ __host__ __device__ inline int grid_ppt(int N) { return N <= GRID_SMALL_N ? 4 : 
 // to this bound, so the N <= 2^20 launches (<= 512 tiles) run an instantiation with 2, larger ones with 8
 __host__ __device__ inline int grid_kmax(int N) { return N <= (1 << 20) ? 2 : 8; }
 
+// REPLAY: the coarse entries a window of N particles reserves, in its scratch and (N = the batch's n_max) in the step
+// kernel's LDS.  C = ceil(N / S) itself is not monotone in N -- S doubles at 2^20 + 1 and 2^21 + 1, so C drops from 16384
+// to 8193 --, but every batch is sized from its largest window: min(GRID_COARSE_MAX, ceil(N / 64)) is >= C for every
+// stride, non-decreasing in N, and equal to C for N <= 2^20.
+__host__ __device__ constexpr int grid_coarse_reserve(int N) {
+    return (N + 63) / 64 < GRID_COARSE_MAX ? (N + 63) / 64 : GRID_COARSE_MAX;
+}
+
 struct GridLayout {
-    int N, NT, PPT, TILE, G, C, S, PSTRIDE;          // C coarse entries of stride S (REPLAY); PSTRIDE doubles per partial parity
+    int N, NT, PPT, TILE, G, C, S, CR, PSTRIDE;      // C coarse entries of stride S, CR reserved (REPLAY); PSTRIDE doubles per partial parity
     size_t lw[2], rec[2], part[2], rng, head, cdf, coarse, walk_i, walk_p, walk_q, walk_s, cdfx, cs[2], tab, consts, bytes;
 };
 
@@ -90,6 +100,7 @@ __host__ __device__ inline GridLayout grid_layout(int N, bool replay) {
     while ((N + S - 1) / S > GRID_COARSE_MAX) S <<= 1;
     L.S = S;
     L.C = (N + S - 1) / S;
+    L.CR = grid_coarse_reserve(N);
     L.PSTRIDE = 7 * L.G + 8;
     constexpr int REC = mem_rec_len<MODEL, REAL>();
     size_t o = 0;
@@ -108,7 +119,7 @@ __host__ __device__ inline GridLayout grid_layout(int N, bool replay) {
     }
     if (replay) {
         L.cdf = o; o = grid_align(o + (size_t)N * 8);
-        L.coarse = o; o = grid_align(o + (size_t)L.C * 8);
+        L.coarse = o; o = grid_align(o + (size_t)L.CR * 8);
         L.walk_i = o; o = grid_align(o + (size_t)N * 4);
         L.walk_p = o; o = grid_align(o + (size_t)N * 8);
         L.walk_q = o; o = grid_align(o + (size_t)N * 8);
@@ -520,7 +531,7 @@ __global__ __launch_bounds__(NT) void pfg_grid_step_kernel(const pfg_dev_problem
     double *head = reinterpret_cast<double *>(base + L.head);
 
     double *pw = reinterpret_cast<double *>(smem);                       // [G + 1]
-    double *tab2 = pw + (GRID_MAX_TILES + 1);                            // DEVICE: tile CDF [TILE] + bitmap; REPLAY: coarse [C]
+    double *tab2 = pw + (GRID_MAX_TILES + 1);                            // DEVICE: tile CDF [TILE] + bitmap; REPLAY: coarse [C] (the launch holds CR(n_max) >= C)
     double *red = tab2 + (DEV ? TILE + GRID_MAX_TILES / 64 : L.C);
     double *tabmem = red + (4 * PPT * NW + 16 + PFG_MAX_STAT * NW);
     GridMath<MODEL, REAL, RNG> mth;

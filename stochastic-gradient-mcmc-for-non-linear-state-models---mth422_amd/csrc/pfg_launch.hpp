@@ -41,6 +41,9 @@ int launch_grid_ppt(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_prob
     const int t_lo = phase >= 0 ? phase : 0, t_hi = phase >= 0 ? phase + 1 : (phase == PFG_GRID_ALL ? p.t_max : 0);
     if (phase == PFG_GRID_ALL || phase == PFG_GRID_INIT) hipLaunchKernelGGL(k_init, grid, blk, lds_init, st, dp);
     if constexpr (RNG == PFG_RNG_REPLAY) {
+        // the plan sizes the step kernel's LDS from grid_coarse_reserve(n_max) <= GRID_COARSE_MAX coarse entries
+        static_assert(pfg::grid_step_lds_bytes<NT, PPT, REAL, RNG>(pfg::GRID_COARSE_MAX) <= kLdsLimit,
+                      "a full coarse table must fit the REPLAY step kernel's LDS");
         auto k_step = pfg::pfg_grid_step_kernel<MODEL, KERNEL, REAL, RNG, NT, PPT>;
         PFG_ENSURE_LDS(ctx, k_step, p.lds);
         // the reference's CDF: four launches that spread the particle axis over the GPU (cdf_single: the lone-workgroup

@@ -82,7 +82,8 @@ __host__ __device__ inline size_t mem_kernel_lds_bytes(int N) {
 // SCORE1 (PFG_SMOOTHER_POYIADJIS_N launches of the N <= 4096 variant): the Poyiadjis O(N) score only -- the filter, the
 // lambda != 1 shrinkage and the other statistics compiled out.  BASELINE config 4 through the seed-compatible path:
 // 37.9 -> 32.1 ms per 402 windows (-15 %; the N = 10^4 kernel gains nothing: profiles/r04_ab_score1_twin.txt).  REPLAY
-// units are built without contraction: bitwise the general kernel's numbers.  A window that is not that estimator gets NaNs.
+// units are built without contraction: bitwise the general kernel's numbers.  A window that is not that estimator gets NaNs,
+// and so does a PFG_STAT_PREDICTIVE window in the LW4 kernel.
 template <int MODEL, int KERNEL, typename REAL, int RNG, bool PARIS = false, bool LW4 = false, bool SCORE1 = false>
 __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *__restrict__ probs) {
     static_assert(!(PARIS && LW4), "LW4 is a variant of the plain kernel");
@@ -106,8 +107,10 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
     const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
     const int nchunk = (N + NT - 1) / NT;
     const int np2 = mem_np2(N);
-    if constexpr (SCORE1) {
-        if (P.smoother != PFG_SMOOTHER_NEMETH || P.lambduh != 1.0 || P.stat != PFG_STAT_SCORE) {
+    if constexpr (LW4) {
+        // SCORE1: a window that is not the Poyiadjis O(N) score; LW4 (no predictive branch): a predictive window, which
+        // only pfg_launch_device* can hand it (pfg_run_batch plans predictive batches onto the general kernel)
+        if (SCORE1 ? (P.smoother != PFG_SMOOTHER_NEMETH || P.lambduh != 1.0 || P.stat != PFG_STAT_SCORE) : P.stat == PFG_STAT_PREDICTIVE) {
             if (threadIdx.x < PFG_OUT_DOUBLES && P.out) P.out[threadIdx.x] = __builtin_nan("");
             return;
         }

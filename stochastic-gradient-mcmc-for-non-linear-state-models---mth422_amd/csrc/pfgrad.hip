@@ -281,9 +281,9 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
                 const pfg::GridLayout L = pfg::grid_layout<decltype(m)::value, REAL>(n_max, rng == PFG_RNG_REPLAY);
                 p.tiles = L.G;
                 p.scratch = L.bytes;
-                if (rng == PFG_RNG_REPLAY)      // the timestep kernel's LDS
-                    p.lds = p.ppt == 4 ? pfg::grid_step_lds_bytes<pfg::GRID_NT, 4, REAL, decltype(g)::value>(L.C)
-                                       : pfg::grid_step_lds_bytes<pfg::GRID_NT, 8, REAL, decltype(g)::value>(L.C);
+                if (rng == PFG_RNG_REPLAY)      // the timestep kernel's LDS: the coarse table of any window N <= n_max fits CR(n_max)
+                    p.lds = p.ppt == 4 ? pfg::grid_step_lds_bytes<pfg::GRID_NT, 4, REAL, decltype(g)::value>(L.CR)
+                                       : pfg::grid_step_lds_bytes<pfg::GRID_NT, 8, REAL, decltype(g)::value>(L.CR);
                 else
                     p.lds = 8 * (p.ppt == 4 ? pfg::grid_dev_lds_doubles<pfg::GRID_NT, 4>(L.G) : pfg::grid_dev_lds_doubles<pfg::GRID_NT, 8>(L.G));
                 return 0;
@@ -1072,6 +1072,15 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
             if (q.elementwise) return fail(ctx, PFG_ERR_UNSUPPORTED, id + "elementwise statistics are built for N <= " + std::to_string(pfg::MEM_MAX_N));
             if (pfg::grid_ppt(q.N) != pfg::grid_ppt(sum.n_max))
                 return fail(ctx, PFG_ERR_INVALID, id + "whole-GPU windows of one batch must all have N <= 524288 or all N > 524288");
+            // every window lays out its own scratch from its own N inside a stride sized from n_max: never launch one
+            // that would not fit (the layout is monotone in N, so this only fails if that invariant is broken)
+            const size_t need = with_types(model, dtype, rng, [&](auto m, auto, auto real, auto) {
+                return pfg::grid_layout<decltype(m)::value, decltype(real)>(q.N, rng == PFG_RNG_REPLAY).bytes;
+            });
+            if (need > plan.scratch)
+                return fail(ctx, PFG_ERR_INVALID, id + "whole-GPU layout of N = " + std::to_string(q.N) + " needs " + std::to_string(need) +
+                                                      " scratch bytes, more than the " + std::to_string(plan.scratch) + " planned for n_max = " +
+                                                      std::to_string(sum.n_max));
             plan.t_max = q.T > plan.t_max ? q.T : plan.t_max;
         }
     }

@@ -8,6 +8,12 @@ def _al(x):
     return (x + 255) & ~255
 
 
+def grid_step_lds_coarse(N):
+    """Coarse entries the REPLAY layout reserves for a window of N particles (and the step kernel's LDS holds when N is
+    the batch's n_max): min(16384, ceil(N / 64)), non-decreasing in N and >= C = ceil(N / S) for every S."""
+    return min(16384, (N + 63) // 64)
+
+
 def grid_layout(model, dtype, N, replay):
     rs = 8 if dtype == "f64" else 4
     L = {"N": N}
@@ -18,6 +24,7 @@ def grid_layout(model, dtype, N, replay):
     while (N + S - 1) // S > 16384:
         S <<= 1
     L["S"], L["C"] = S, (N + S - 1) // S
+    L["CR"] = grid_step_lds_coarse(N)
     o = 0
     L["lw"] = []
     for _ in range(2):
@@ -38,7 +45,7 @@ def grid_layout(model, dtype, N, replay):
         L["consts"] = o; o = _al(o + 23 * 8)
     if replay:
         L["cdf"] = o; o = _al(o + N * 8)
-        L["coarse"] = o; o = _al(o + L["C"] * 8)
+        L["coarse"] = o; o = _al(o + L["CR"] * 8)
         L["walk_i"] = o; o = _al(o + N * 4)
         L["walk_p"] = o; o = _al(o + N * 8)
         L["walk_q"] = o; o = _al(o + N * 8)

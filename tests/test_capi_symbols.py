@@ -31,7 +31,10 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
 
 
-def test_binding_struct_sizes_and_version():
+def test_binding_struct_sizes_version_and_grid_scratch():
+    """ABI struct sizes, the version, the variant names of the plan, and pfg_scratch_bytes of the whole-GPU window equal
+    to the Python mirror of its layout on both sides of every tile-class and coarse-stride boundary.  (The REPLAY layout
+    reserves min(16384, ceil(N / 64)) coarse entries, so the sizes above 2^20 are those of a layout monotone in N.)"""
     lib = _capi.load_library()          # asserts the struct sizes against pfg_struct_size()
     assert lib.pfg_version() == 125
     assert lib.pfg_struct_size(2) == _capi.DEV_PROBLEM_DTYPE.itemsize == 376
@@ -60,7 +63,8 @@ def test_binding_struct_sizes_and_version():
     for model, mname in enumerate(("svm", "garch", "lgssm")):
         for dtype, dname in enumerate(("f64", "f32")):
             for rng in (0, 1):
-                for N in (16385, 100000, 1 << 19, (1 << 19) + 1, 1000000, (1 << 20) + 1, 1 << 22):
+                for N in (16385, 100000, 1 << 19, (1 << 19) + 1, 1000000, 1 << 20, (1 << 20) + 1, 1 << 21, (1 << 21) + 1,
+                          (1 << 22) - 1, 1 << 22):
                     assert lib.pfg_scratch_bytes(model, dtype, rng, N) == grid_layout(mname, dname, N, rng == 0)["bytes"]
     assert lib.pfg_scratch_bytes(0, 0, 1, 10000) == (10000 * 9 * 8 + 16 + 255) // 256 * 256
 

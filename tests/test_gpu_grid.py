@@ -103,6 +103,59 @@ def test_giant_replay_ancestors_are_the_references(ctx, case):
     np.testing.assert_allclose(o["log_weights"], r["log_weights"], rtol=RTOL, atol=ATOL)
 
 
+STRADDLE = [
+    # model, dtype, theta, Ns (window order), T: each batch's windows sit on both sides of a doubling of the coarse-table
+    # stride S (2^20 -> 2^20 + 1, 2^21 -> 2^21 + 1), inside the 2048-particle tile class
+    ("svm", "f64", [0.9, 1.2, 1.1], (1000000, 1100003), 3),
+    ("svm", "f64", [0.95, 1.3, 1.0], ((1 << 20) + 1, 1 << 20), 3),           # the smaller window last
+    ("svm", "f64", [0.8, 1.1, 1.2], ((1 << 21) + 1, 1 << 21), 2),
+    ("garch", "f64", [0.0, 2.0, 2.0, 1.8], ((1 << 20) + 1, 1000000), 2),      # the longest particle record
+    ("svm", "f32", [0.9, 1.2, 1.1], (1100003, (1 << 20) - 1), 3),
+]
+
+
+@pytest.mark.parametrize("case", STRADDLE, ids=lambda c: "{0}-{1}-{2}".format(c[0], c[1], "-".join(map(str, c[3]))))
+def test_giant_replay_batch_across_the_coarse_stride_doublings(ctx, case):
+    """REPLAY batches whose windows straddle a doubling of the coarse-table stride: the batch is sized from its largest
+    window, so the coarse table, LDS and scratch stride must also cover a smaller window with MORE coarse entries.
+    Every window equals itself run alone, bit for bit (same kernels: only the allotted LDS differs), and, in fp64, the
+    oracle with the tolerances of test_giant_replay_ancestors_are_the_references (zero ancestor flips)."""
+    model, dtype, theta, Ns, T = case
+    qs = []
+    for i, N in enumerate(Ns):
+        rs = np.random.RandomState(N % 9973 + i)
+        y = rs.normal(size=T)
+        z0, u, z = po.draw_streams(rs, N, T)
+        q = dict(model=model, kernel="prior", smoother="nemeth", stat="score", dtype=dtype, rng="replay", N=N, t1=0, tL=T,
+                 lambduh=1.0 if i == 0 else 0.95, prior_mean=0.0, prior_var=1.5, y=y, theta=theta, z0=z0, u=u, z=z)
+        if i % 2:
+            q["weights"] = rs.uniform(1.0, 40.0, size=T)
+        qs.append(q)
+    outs = ctx.run_batch(qs, want_final=True, want_trace=True)
+    assert ctx.last_variant() == "grid2048"
+    for i, (q, o) in enumerate(zip(qs, outs)):
+        alone = ctx.run_batch([q], want_final=True, want_trace=True)[0]
+        assert ctx.last_variant() == "grid2048"
+        for k in ("mean_stat", "loglik", "x_t", "log_weights", "statistics", "all_x_t", "all_log_weights", "all_statistics",
+                  "all_loglikelihood_estimate", "all_ancestors"):
+            a, b = np.asarray(o[k]), np.asarray(alone[k])
+            assert a.tobytes() == b.tobytes(), (case, i, k)
+        if dtype != "f64":
+            continue
+        r = po.pf_window(model, theta, q["y"], q["N"], q["z0"], q["u"], q["z"], kernel="prior", pf="nemeth",
+                         lambduh=q["lambduh"], t1=0, tL=T, weights=q.get("weights"), prior_mean=0.0, prior_var=1.5,
+                         save_all=True)
+        flips = int(np.sum(o["all_ancestors"] != r["all_ancestors"]))
+        assert flips == 0, (case, i, flips)
+        np.testing.assert_allclose(o["all_x_t"], r["all_x_t"], rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(o["all_log_weights"], r["all_log_weights"], rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(o["x_t"], r["x_t"], rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(o["log_weights"], r["log_weights"], rtol=RTOL, atol=ATOL)
+        ref = r["mean_statistic"]
+        assert np.linalg.norm(o["mean_stat"] - ref) <= 1e-9 * max(1.0, np.linalg.norm(ref)), (case, i, o["mean_stat"], ref)
+        assert abs(o["loglik"] - r["loglikelihood_estimate"]) <= ATOL + RTOL * abs(r["loglikelihood_estimate"])
+
+
 def test_giant_replay_batch_of_windows(ctx):
     """Several whole-GPU windows in one call (blockIdx.y = window), different N, T and parameters."""
     rs = np.random.RandomState(5)
