@@ -106,7 +106,13 @@ enum pfg_stat { PFG_STAT_SCORE = 0, PFG_STAT_SUFF = 1, PFG_STAT_NONE = 2,
                 /* k-step-ahead predictive log-likelihoods accumulated with the filter's
                  * logsumexp update (pf.py:72-76; statistic functions svm/helper.py:352-395,
                  * lgssm/helper.py:1281-1336, garch/helper.py:374-412).  FILTER smoother only. */
-                PFG_STAT_PREDICTIVE = 3 };
+                PFG_STAT_PREDICTIVE = 3,
+                /* the sufficient statistics of the blocked Gibbs sampler (lgssm/helper.py:502-555) of the one path of
+                 * a PFG_SMOOTHER_KALMAN_FFBS window (N = 1 only), over the whole buffer: t1, tL and the weights are
+                 * ignored.  out[0..7] = [sum_{t>=1} x_{t-1}^2, sum_{t>=1} x_t x_{t-1}, sum_{t>=1} x_t^2, sum_t x_t^2,
+                 * sum_t y_t x_t, sum_t y_t^2, T, 0]; pfg_run / pfg_run_batch return the record in pfg_result.pred[0..7]
+                 * (mean_stat and loglik are not written).  FFBS only: another smoother refuses it as a bad stat id. */
+                PFG_STAT_GIBBS = 4 };
 /* particle-state arithmetic type.  Weight normalisation, CDF and search are always f64. */
 enum pfg_dtype { PFG_F64 = 0, PFG_F32 = 1 };
 /* REPLAY: caller supplies the NumPy legacy stream (z0[N], u[T*N], z[T*N]) -> results
@@ -398,6 +404,28 @@ int pfg_sghmc_update_device(pfg_ctx *ctx, int model, int B, double *theta, doubl
                             const double *outs, const pfg_prior_hyper *hyper, double epsilon, double alpha,
                             double Tscale, uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr,
                             void *hip_stream);
+
+/* SGRLD parameter update for B resident LGSSM chains: sample_sgrld with the LGSSM preconditioner
+ * (sgmcmc_sampler.py:613-640, lgssm/parameters.py:58-67), then project_parameters.  With theta = (A, C, LQinv,
+ * LRinv), Qinv = LQinv^2 + 1e-16, Q = 1 / Qinv and g_v = grad_logprior_v + ghat_v, all at the pre-step theta:
+ *   A     += eps Q g_A / Tscale                           + sqrt(2 eps / Tscale) z_A / LQinv
+ *   LQinv += eps (0.5 Qinv g_LQinv + LQinv) / Tscale      + sqrt(2 eps / Tscale) sqrt(0.5) LQinv z_Q
+ * (C and LRinv likewise with R); the projection then sets C = 1.  The four normals of chain b are those of
+ * pfg_sgld_update_device: keyed by (seed, chain_offset + b, *step_ctr).  *step_ctr is incremented afterwards.
+ * LGSSM only: SVM and GARCH return PFG_ERR_UNSUPPORTED (the reference defines no preconditioner for them). */
+int pfg_sgrld_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                            const pfg_prior_hyper *hyper, double epsilon, double Tscale,
+                            uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream);
+
+/* Gibbs parameter draw for B resident LGSSM chains: LGSSMPrior.sample_posterior (base_parameters.py:354-377,
+ * 437-450) from the PFG_STAT_GIBBS statistics an FFBS launch with one path per chain left in `outs`
+ * [B][PFG_OUT_DOUBLES] -- Qinv, Rinv from their 1 x 1 Wishart (scale * chi2(df)) posteriors, A given Q from its
+ * normal posterior -- then project_parameters (C = 1, so C is not drawn).  The chi2 variates come from a bounded
+ * rejection sampler, every attempt keyed by (seed, chain_offset + b, *step_ctr, attempt); a chain whose 64 attempts
+ * are all rejected gets NaN.  *step_ctr is incremented afterwards.  LGSSM only (PFG_ERR_UNSUPPORTED otherwise). */
+int pfg_gibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                            const pfg_prior_hyper *hyper, uint64_t seed, uint64_t chain_offset,
+                            uint64_t *step_ctr, void *hip_stream);
 
 /* Inverse-multiquadric kernel Stein discrepancy of K points x[K][d] with score estimates
  * g[K][d] (HOST pointers, d <= 8): sqrt(sum_{i,j} k0(x_i,x_j)) / K for

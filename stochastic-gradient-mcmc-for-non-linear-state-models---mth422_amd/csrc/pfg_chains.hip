@@ -1,0 +1,173 @@
+// Update rules of resident LGSSM chains beyond SGLD / SGHMC (those stay in pfgrad.hip): one lane per chain, f64.
+//   sgrld  SGMCMCSampler.sample_sgrld with LGSSMPreconditioner (sgmcmc_sampler.py:631-641, base_parameters.py:588-661,
+//          models/lgssm.py:51-54), then project_parameters.  With theta = (A, C, LQinv, LRinv), Qinv = LQinv^2 + 1e-16,
+//          Q = 1 / Qinv, g_v = grad_logprior_v(theta) + ghat_v and every preconditioner term at the pre-step theta:
+//            A     += eps (Q g_A / T)                          + sqrt(2 eps) (z_A / LQinv) sqrt(1 / T)
+//            C     += eps (R g_C / T)                          + sqrt(2 eps) (z_C / LRinv) sqrt(1 / T)   (not taken: C = 1 after)
+//            LQinv += eps ((0.5 Qinv g_LQinv) / T + LQinv / T) + sqrt(2 eps) (sqrt(0.5) LQinv z_Q) sqrt(1 / T)
+//            LRinv += eps ((0.5 Rinv g_LRinv) / T + LRinv / T) + sqrt(2 eps) (sqrt(0.5) LRinv z_R) sqrt(1 / T)
+//          (the LQinv / T, LRinv / T terms: correction_term, (n + 1) / 2 L with n = 1).  The four normals of chain b are
+//          those of sgld_update_kernel: Philox4x32-10 keyed by (seed, chain_offset + b, *step_ctr), drawn A, C, Q, R.
+//   gibbs  LGSSMPrior.sample_posterior (base_parameters.py:354-377, 437-450) from the statistics an FFBS window with
+//          PFG_STAT_GIBBS left in out[0..7] (pfg_ffbs.hip), block by block: Qinv, Rinv (1 x 1 Wishart = scale chi2(df)),
+//          A given Q, then project_parameters.  The C draw is skipped: the projection pins C to 1 whatever it drew.
+//          chi2(df) = 2 Gamma(df / 2), Gamma by Marsaglia-Tsang (shape >= 1) or Gamma(a + 1) U^(1/a) (shape < 1); every
+//          attempt is keyed by (seed, chain, *step_ctr, variable, attempt), so a draw is a pure function of its key.
+//          A variable still rejected after kMaxRounds attempts is NaN.
+// Built with -ffp-contract=off; IEEE division and ::sqrt / ::log throughout.
+#include "pfg_host.hpp"
+#include "pfg_math.hpp"
+
+namespace {
+
+constexpr int kMaxRounds = 64;
+
+__device__ __forceinline__ double reflect_chol(double L) { return L < 0.0 ? sqrt(L * L + 1e-16) : L; }
+
+// project_parameters of LGSSM: |A| <= 0.9999 (_utils.py:165-170), C = 1 (lgssm/parameters.py:39-42), the Cholesky
+// factors reflected (covariance.py:68-80)
+__device__ __forceinline__ void lgssm_project_store(double *th, double A, double LQ, double LR) {
+    const double aa = fabs(A);
+    if (aa > 0.9999) A *= 0.9999 / aa;
+    th[0] = A; th[1] = 1.0; th[2] = reflect_chol(LQ); th[3] = reflect_chol(LR);
+}
+
+__global__ void sgrld_update_kernel(int B, double *__restrict__ theta, const double *__restrict__ outs, pfg_prior_hyper hy,
+                                    double eps, double Tscale, uint64_t seed, uint64_t chain_offset,
+                                    const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    const double *g = outs + (size_t)b * PFG_OUT_DOUBLES;
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const uint32_t c1 = (uint32_t)step, c2 = (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32);
+    const pfg::u32x4 r0 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x5A11u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const pfg::u32x4 r1 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x5A12u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    double zA, zC, zQ, zR;
+    const pfg::Math<double, false> mth = {};
+    mth.normal_pair(r0.x, r0.y, zA, zC);
+    mth.normal_pair(r1.x, r1.y, zQ, zR);
+
+    (void)zC;       // C's step is not taken: the projection pins C to 1 whatever it would be
+    const double A = th[0], LQ = th[2], LR = th[3];
+    const double Qinv = LQ * LQ + 1e-16, Rinv = LR * LR + 1e-16;
+    const double Q = 1.0 / Qinv;
+    // score columns [LRinv, LQinv, C, A]; grad_logprior as sgld_update_kernel (covariance.py:272-284, matrices.py:597-607)
+    const double pLQ = (hy.df_Qinv - 2.0) / LQ - LQ / hy.scale_Qinv;
+    const double pLR = (hy.df_Rinv - 2.0) / LR - LR / hy.scale_Rinv;
+    const double pA = -1.0 * (Qinv * (A - hy.mean_A)) / hy.var_col_A;
+    const double gA = pA + g[3], gLQ = pLQ + g[1], gLR = pLR + g[0];
+    const double scale = 1.0 / Tscale, nsd = sqrt(2.0 * eps), rs = sqrt(scale), half = sqrt(0.5);
+    const double nA = (zA / LQ) * rs;
+    const double nQ = ((half * LQ) * zQ) * rs, nR = ((half * LR) * zR) * rs;
+    const double A1 = A + (eps * ((Q * gA) * scale + 0.0) + nsd * nA);
+    const double LQ1 = LQ + (eps * (((0.5 * Qinv) * gLQ) * scale + LQ * scale) + nsd * nQ);
+    const double LR1 = LR + (eps * (((0.5 * Rinv) * gLR) * scale + LR * scale) + nsd * nR);
+    lgssm_project_store(th, A1, LQ1, LR1);
+}
+
+// The keyed draws of one chain and step: attempt k of variable v is Philox4x32-10 of (chain, step, tag(v, k)).
+struct ChainKey {
+    uint32_t gid, c1, c2, k0, k1;
+    __device__ __forceinline__ pfg::u32x4 draw(uint32_t var, uint32_t attempt) const {
+        return pfg::philox4x32_10({gid, c1, c2, 0x61B50000u | (var << 8) | attempt}, k0, k1);
+    }
+};
+
+__device__ __forceinline__ double uniform53(uint32_t a, uint32_t b) {      // (0, 1)
+    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6) + 0.5) * (1.0 / 9007199254740992.0);
+}
+
+// Gamma(shape, 1): Marsaglia & Tsang (2000) on (shape + 1 when shape < 1, then times U^(1 / shape)); NaN when every
+// round is rejected or shape is not a positive number
+__device__ double gamma_draw(const ChainKey &key, uint32_t var, double shape) {
+    if (!(shape > 0.0) || !(shape < INFINITY)) return NAN;
+    const bool boost = shape < 1.0;
+    const double a = boost ? shape + 1.0 : shape;
+    const double d = a - 1.0 / 3.0, c = 1.0 / ::sqrt(9.0 * d);
+    const pfg::Math<double, false> mth = {};
+    for (uint32_t k = 0; k < (uint32_t)kMaxRounds; ++k) {
+        const pfg::u32x4 r = key.draw(var, k);
+        double z, unused;
+        mth.normal_pair(r.x, r.y, z, unused);
+        const double t = 1.0 + c * z;
+        if (t <= 0.0) continue;
+        const double v = t * t * t;
+        const double u = uniform53(r.z, r.w);
+        if (::log(u) < 0.5 * z * z + d - d * v + d * ::log(v)) {
+            double x = d * v;
+            if (boost) {
+                const pfg::u32x4 s = key.draw(var | 0x80u, 0);
+                x *= ::exp(::log(uniform53(s.x, s.y)) / shape);
+            }
+            return x;
+        }
+    }
+    return NAN;
+}
+
+// Qinv | x, y of one Wishart block (covariance.py:207-240, 1 x 1): its posterior df and scale, from the paired matrix's
+// prior (mean, var_col) and the statistics (S_prevprev, S_curprev, S_curcur)
+struct Conj { double df, scale, Spp, Scp; };
+__device__ __forceinline__ Conj conjugate(double df0, double scale0, double mean, double var_col, double spp, double scp,
+                                          double scc, double count) {
+    const double mean_prec = mean * (1.0 / var_col), prec = 1.0 / var_col;
+    Conj o;
+    o.Spp = prec + spp;
+    o.Scp = mean_prec + scp;
+    const double Scc = mean * mean_prec + scc;
+    const double schur = Scc - (o.Scp * o.Scp) / o.Spp;
+    o.df = df0 + count;
+    o.scale = 1.0 / (1.0 / scale0 + schur);
+    return o;
+}
+
+__global__ void gibbs_update_kernel(int B, double *__restrict__ theta, const double *__restrict__ outs, pfg_prior_hyper hy,
+                                    uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    const double *s = outs + (size_t)b * PFG_OUT_DOUBLES;
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const ChainKey key{(uint32_t)gid, (uint32_t)step, (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32), (uint32_t)seed,
+                       (uint32_t)(seed >> 32)};
+    const double T = s[6];
+    // transitions (t >= 1): T - 1 of them; emissions: T
+    const Conj q = conjugate(hy.df_Qinv, hy.scale_Qinv, hy.mean_A, hy.var_col_A, s[0], s[1], s[2], T - 1.0);
+    const Conj r = conjugate(hy.df_Rinv, hy.scale_Rinv, hy.mean_C, hy.var_col_C, s[3], s[4], s[5], T);
+    const double Qinv = q.scale * (2.0 * gamma_draw(key, 0, 0.5 * q.df));
+    const double Rinv = r.scale * (2.0 * gamma_draw(key, 1, 0.5 * r.df));
+    const double LQ = ::sqrt(Qinv), LR = ::sqrt(Rinv);
+    // A | Q ~ N(Scp / Spp, 1 / ((LQinv^2 + 1e-9) Spp)) (matrices.py:556-580)
+    const pfg::u32x4 ra = key.draw(2, 0);
+    double zA, unused;
+    const pfg::Math<double, false> mth = {};
+    mth.normal_pair(ra.x, ra.y, zA, unused);
+    const double P = LQ * LQ + 1e-9;
+    const double A = q.Scp / q.Spp + ::sqrt((1.0 / P) * (1.0 / q.Spp)) * zA;
+    lgssm_project_store(th, A, LQ, LR);
+}
+
+}  // namespace
+
+namespace pfg_host {
+
+int launch_sgrld_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, double eps,
+                        double Tscale, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st) {
+    hipLaunchKernelGGL(sgrld_update_kernel, dim3((B + 127) / 128), dim3(128), 0, st, B, theta, outs, hy, eps, Tscale, seed,
+                       chain_offset, step_ctr);
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
+}
+
+int launch_gibbs_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, uint64_t seed,
+                        uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st) {
+    hipLaunchKernelGGL(gibbs_update_kernel, dim3((B + 127) / 128), dim3(128), 0, st, B, theta, outs, hy, seed, chain_offset,
+                       step_ctr);
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
+}
+
+}  // namespace pfg_host

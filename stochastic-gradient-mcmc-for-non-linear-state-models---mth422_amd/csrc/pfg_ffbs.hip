@@ -18,6 +18,11 @@
 //               C      w Rinv <(y_t - C x_t) x_t>             LRinv  w (1/LRinv - <(y_t - C x_t)^2> LRinv)
 //             the two transition terms only where x_{t-1} is inside the buffer (t >= 1).  Each lane sums its paths'
 //             terms, one workgroup reduction ends the window.  stat = NONE samples only (out[0..7] = 0).
+//   gibbs     stat = GIBBS (N = 1 path): the sufficient statistics of LGSSMHelper.calc_gibbs_sufficient_statistic
+//             (lgssm/helper.py:502-555) of the whole buffer's path, summed by its lane while it samples backward;
+//             t1, tL and the weights are ignored.  out = [sum_{t>=1} x_{t-1}^2, sum_{t>=1} x_t x_{t-1},
+//             sum_{t>=1} x_t^2, sum_t x_t^2, sum_t y_t x_t, sum_t y_t^2, T, 0]: what gibbs_update_kernel
+//             (pfg_chains.hip) draws the parameters from.
 //   paths     trace_x, when non-NULL: the sampled paths [T][N], t ascending.  Without it a SCORE window stops
 //             sampling at t = t1 - 1.
 // An invalid descriptor gets out[0..7] = NaN.  Built with -ffp-contract=off; IEEE division and ::sqrt throughout.
@@ -26,6 +31,53 @@
 #include "pfg_math.hpp"
 
 namespace {
+
+// PFG_STAT_GIBBS: the one path of the buffer, sampled backward with the normals and arithmetic of the score loop below
+// (same path), and the sufficient statistics of lgssm/helper.py:502-555 summed on the way
+template <bool DEVICE>
+__device__ __forceinline__ void ffbs_gibbs_path(const pfg_dev_problem &d, const KalmanTheta &k, const double2 *__restrict__ fm,
+                                             double *__restrict__ trace, double *__restrict__ out) {
+    const int T = d.T;
+    const double *__restrict__ y = d.y;
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (T > 0) {
+        const pfg::Math<double, true> mth{};
+        pfg::LaneRng g{};
+        if (DEVICE) g = pfg::lane_rng_init(d.seed, d.stream, d.step_ctr ? *d.step_ctr : 0, 0u);
+        double z_next = 0.0;
+        bool have = false;
+        auto normal = [&](int t) -> double {        // REPLAY: z[T-1-t]; DEVICE: Box-Muller pairs, as the score loop
+            if (!DEVICE) return d.z[T - 1 - t];
+            if (have) { have = false; return z_next; }
+            const uint32_t a = g.next();
+            const uint32_t b = g.next();
+            double z0, z1;
+            mth.normal_pair(a, b, z0, z1);
+            z_next = z1; have = true;
+            return z0;
+        };
+        const double2 mT = fm[T - 1];
+        double x = normal(T - 1) * ::sqrt(mT.y) + mT.y * mT.x;
+        if (trace) trace[T - 1] = x;
+        s[3] += x * x;
+        s[4] += y[T - 1] * x;
+        for (int t = T - 2; t >= 0; --t) {
+            const double2 m = fm[t];
+            const double xp = m.y * (m.x + k.AtQinv * x) + (normal(t) * ::sqrt(m.y) + 0.0);
+            if (trace) trace[t] = xp;
+            s[0] += xp * xp;            // the transition of time t + 1
+            s[1] += x * xp;
+            s[2] += x * x;
+            s[3] += xp * xp;            // the emission of time t
+            s[4] += y[t] * xp;
+            x = xp;
+        }
+        for (int t = T - 1; t >= 0; --t) s[5] += y[t] * y[t];
+    }
+    for (int i = 0; i < 6; ++i) out[i] = s[i];
+    out[6] = (double)T;
+    out[7] = 0.0;
+}
 
 template <int NT, bool DEVICE>
 __global__ __launch_bounds__(NT) void ffbs_window_kernel(const pfg_dev_problem *__restrict__ dp) {
@@ -36,8 +88,10 @@ __global__ __launch_bounds__(NT) void ffbs_window_kernel(const pfg_dev_problem *
     const int tL = d.tL < T ? d.tL : T;
     const double prior_var = d.prior_var;
     const bool score = d.stat == PFG_STAT_SCORE;
+    const bool gibbs = d.stat == PFG_STAT_GIBBS;
     const bool ok = out && d.theta && T >= 0 && N >= 1 && t1 >= 0 && t1 <= tL &&
-                    (T == 0 || (d.y && d.scratch && (DEVICE || d.z))) && (score || d.stat == PFG_STAT_NONE) &&
+                    (T == 0 || (d.y && d.scratch && (DEVICE || d.z))) &&
+                    (score || d.stat == PFG_STAT_NONE || (gibbs && N == 1)) &&
                     prior_var > 0.0 && prior_var < INFINITY && isfinite(d.prior_mean);
     if (!ok) {
         if (out && tid == 0)
@@ -64,6 +118,10 @@ __global__ __launch_bounds__(NT) void ffbs_window_kernel(const pfg_dev_problem *
 
     // 2. backward sampling, one lane per path
     double *__restrict__ trace = d.trace_x;
+    if (gibbs) {        // one path, lane 0's; its own loop keeps the score loop's registers as they are
+        if (tid == 0) ffbs_gibbs_path<DEVICE>(d, k, fm, trace, out);
+        return;
+    }
     const int t_stop = (trace || !score || t1 == 0) ? 0 : t1 - 1;
     const uint64_t step = d.step_ctr ? *d.step_ctr : 0;
     const pfg::Math<double, true> mth{};

@@ -167,4 +167,10 @@ int launch_kalman(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_proble
 // Launch of the FFBS window kernel (Family::KalmanFfbs), defined in pfg_ffbs.hip.
 int launch_ffbs(pfg_ctx *ctx, const LaunchPlan &p, int rng, int B, const pfg_dev_problem *dp, hipStream_t st);
 
+// Launches of the SGRLD and Gibbs updates of resident LGSSM chains, defined in pfg_chains.hip.
+int launch_sgrld_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, double eps,
+                        double Tscale, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st);
+int launch_gibbs_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, uint64_t seed,
+                        uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st);
+
 }  // namespace pfg_host

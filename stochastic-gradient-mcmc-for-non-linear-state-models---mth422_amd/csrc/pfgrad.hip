@@ -567,14 +567,17 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
         if (q.t1 > q.T) return bad(PFG_ERR_INVALID, "need t1 <= T");
         if (!(q.prior_var > 0.0) || !std::isfinite(q.prior_var) || !std::isfinite(q.prior_mean))
             return bad(PFG_ERR_INVALID, "the forward message needs a finite precision > 0 (prior_var = 1 / precision)");
-        if (q.init_x || q.elementwise || q.paris_stream || (ffbs ? q.stat != PFG_STAT_SCORE && q.stat != PFG_STAT_NONE : q.stat == PFG_STAT_PREDICTIVE))
-            return bad(PFG_ERR_INVALID, ffbs ? "FFBS latent paths take no warm start or elementwise statistic; stat is score or none"
+        if (q.init_x || q.elementwise || q.paris_stream ||
+            (ffbs ? q.stat != PFG_STAT_SCORE && q.stat != PFG_STAT_NONE && q.stat != PFG_STAT_GIBBS : q.stat == PFG_STAT_PREDICTIVE))
+            return bad(PFG_ERR_INVALID, ffbs ? "FFBS latent paths take no warm start or elementwise statistic; stat is score, none or gibbs"
                                              : "the exact Kalman score takes no warm start, elementwise or predictive statistic");
         if (r.x_T || r.logw_T || r.stats_T || (kalman && r.trace_x) || r.trace_logw || r.trace_stats || r.trace_ll || r.trace_anc ||
             r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats)
             return bad(PFG_ERR_INVALID, ffbs ? "FFBS latent paths have no particles: only the result record and trace_x (the paths)"
                                              : "the exact Kalman score has no particles: only the result record");
         if (ffbs && rng == PFG_RNG_REPLAY && q.T > 0 && !q.z) return bad(PFG_ERR_INVALID, "REPLAY FFBS needs z (T N normals)");
+        if (ffbs && q.stat == PFG_STAT_GIBBS && q.N != 1)
+            return bad(PFG_ERR_INVALID, "the Gibbs statistic (PFG_STAT_GIBBS) is of one path: N must be 1");
     }
     if (mixed(PFG_SMOOTHER_POYIADJIS_N2)) return bad(PFG_ERR_INVALID, "pf = 'poyiadjis_N2' cannot share a batch with other smoothers");
     if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.N > pfg::MEM_MAX_N)
@@ -612,7 +615,8 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
     } else if (q.paris_stream) {
         return bad(PFG_ERR_INVALID, "paris_stream needs pf = 'paris'");
     }
-    if (q.stat < PFG_STAT_SCORE || q.stat > PFG_STAT_PREDICTIVE) return bad(PFG_ERR_INVALID, "bad stat id");
+    if ((q.stat < PFG_STAT_SCORE || q.stat > PFG_STAT_PREDICTIVE) && !(ffbs && q.stat == PFG_STAT_GIBBS))
+        return bad(PFG_ERR_INVALID, "bad stat id");
     if ((q.stat == PFG_STAT_PREDICTIVE) != (first.stat == PFG_STAT_PREDICTIVE))
         return bad(PFG_ERR_INVALID, "the predictive statistic cannot share a batch with others");
     if (q.stat == PFG_STAT_PREDICTIVE) {
@@ -780,7 +784,8 @@ void describe_window(Layout &L, const pfg_problem &q, pfg_result &r, pfg_dev_pro
         L.want(r.pred, d.pred_out, PFG_MAX_PRED);
     }
     static_assert(offsetof(pfg_result, loglik) == offsetof(pfg_result, mean_stat) + PFG_MAX_STAT * 8, "record = mean_stat, loglik");
-    L.want(r.mean_stat, d.out, PFG_OUT_DOUBLES, (PFG_MAX_STAT + 1) * 8);
+    if (q.stat == PFG_STAT_GIBBS) L.want(r.pred, d.out, PFG_OUT_DOUBLES);      // the whole record: 7 statistics
+    else L.want(r.mean_stat, d.out, PFG_OUT_DOUBLES, (PFG_MAX_STAT + 1) * 8);
     L.want(r.x_T, d.final_x, N * NS);
     L.want(r.logw_T, d.final_logw, N);
     L.want(r.stats_T, d.final_stats, N * H);
@@ -1002,6 +1007,52 @@ int pfg_sghmc_update_device(pfg_ctx *ctx, int model, int B, double *theta, doubl
     hipStream_t st = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(sgld_update_kernel, dim3((B + 127) / 128), dim3(128), 0, st, model, B, theta, outs,
                        *hyper, epsilon, Tscale, seed, chain_offset, (const uint64_t *)step_ctr, momentum, alpha);
+    if (step_ctr) hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, st, step_ctr);
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
+}
+
+// the checks the SGRLD and Gibbs updates share: LGSSM chains only (the reference's one preconditioner and conjugate prior)
+static int check_lgssm_update(pfg_ctx *ctx, const char *what, bool sgrld, int model, const double *theta,
+                              const double *outs, const pfg_prior_hyper *hyper) {
+    if (!theta || !outs || !hyper) return fail(ctx, PFG_ERR_INVALID, std::string(what) + ": NULL argument");
+    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+    const char *sampler = model == PFG_MODEL_SVM ? "SVMSampler" : "GARCHSampler";
+    if (model != PFG_MODEL_LGSSM && sgrld)          // sgmcmc_sampler.py:643-646
+        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(what) + ": No Default Preconditioner for " + sampler);
+    if (model != PFG_MODEL_LGSSM)
+        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(what) + ": no conjugate Gibbs draw for " + sampler);
+    return PFG_OK;
+}
+
+int pfg_sgrld_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                            const pfg_prior_hyper *hyper, double epsilon, double Tscale,
+                            uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    const int rc = check_lgssm_update(ctx, "pfg_sgrld_update_device", true, model, theta, outs, hyper);
+    if (rc) return rc;
+    if (!(epsilon > 0.0) || !(Tscale > 0.0)) return fail(ctx, PFG_ERR_INVALID, "epsilon and Tscale must be > 0");
+    if (B <= 0) return PFG_OK;
+    PFG_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int lrc = launch_sgrld_update(ctx, B, theta, outs, *hyper, epsilon, Tscale, seed, chain_offset, step_ctr, st);
+    if (lrc) return lrc;
+    if (step_ctr) hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, st, step_ctr);
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
+}
+
+int pfg_gibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                            const pfg_prior_hyper *hyper, uint64_t seed, uint64_t chain_offset,
+                            uint64_t *step_ctr, void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    const int rc = check_lgssm_update(ctx, "pfg_gibbs_update_device", false, model, theta, outs, hyper);
+    if (rc) return rc;
+    if (B <= 0) return PFG_OK;
+    PFG_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int lrc = launch_gibbs_update(ctx, B, theta, outs, *hyper, seed, chain_offset, step_ctr, st);
+    if (lrc) return lrc;
     if (step_ctr) hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, st, step_ctr);
     PFG_HIP(ctx, hipGetLastError());
     return PFG_OK;

@@ -18,7 +18,8 @@ SMOOTHER = {"nemeth": 0, "filter": 1, "paris": 2, "nemeth_systematic": 3, "poyia
             "poyiadjis_n": 5,       # launch-level id only (never in a descriptor): see include/pfgrad.h
             "kalman": 6,            # the exact LGSSM score (kind='marginal'), no particles: see include/pfgrad.h
             "kalman_ffbs": 7}       # FFBS latent paths of LGSSM and their complete-data score (kind='complete')
-STAT = {"score": 0, "suff": 1, "none": 2, "predictive": 3}
+STAT = {"score": 0, "suff": 1, "none": 2, "predictive": 3,
+        "gibbs": 4}         # FFBS, one path: the Gibbs sufficient statistics of the buffer (include/pfgrad.h)
 DTYPE = {"f64": 0, "f32": 1}
 RNG = {"replay": 0, "device": 1, "philox": 1}     # "philox" = alias of "device" (Philox-keyed lanes)
 FLAG_GARCH_STATIONARY_PRIOR = 1
@@ -141,7 +142,7 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_sgld_update_device", "pfg_sghmc_update_device", "pfg_imq_ksd", "pfg_sample_windows_device",
            "pfg_last_variant", "pfg_legacy_streams", "pfg_host_register", "pfg_host_unregister",
            "pfg_launch_device_traced", "pfg_last_traced", "pfg_launch_device_grid", "pfg_launch_device_grid_phase",
-           "pfg_launch_device_grid_smoother")
+           "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device")
 
 _lib = None
 
@@ -236,6 +237,13 @@ def load_library():
                                             C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_double,
                                             C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.pfg_sghmc_update_device.restype = C.c_int
+    lib.pfg_sgrld_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_uint64,
+                                            C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pfg_sgrld_update_device.restype = C.c_int
+    lib.pfg_gibbs_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.POINTER(PriorHyper), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pfg_gibbs_update_device.restype = C.c_int
     lib.pfg_imq_ksd.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp]
     lib.pfg_imq_ksd.restype = C.c_int
     lib.pfg_sample_windows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -332,7 +340,8 @@ class Context:
              model, kernel, smoother, stat, dtype, rng (strings), N, T (implied by y), t1, tL,
              lambduh, prior_mean, prior_var, flags, y, weights, theta, z0,u,z | seed,stream,
              init_x, init_logw, init_stats
-           returns list of dicts(mean_stat, loglik[, x_t, log_weights, statistics, all_*])."""
+           returns list of dicts(mean_stat, loglik[, x_t, log_weights, statistics, all_*]).  stat='gibbs' (FFBS
+           windows, N = 1): mean_stat = the 8-double record of the Gibbs statistics, loglik = nan."""
         B = len(problems)
         if B == 0:
             return []
@@ -355,6 +364,11 @@ class Context:
         self.last_call_seconds = time.perf_counter() - t_call      # the C call alone (pack, H2D, launch, D2H), without this marshalling
         self._check(rc)
         for b, o in enumerate(outs):
+            if problems[b].get("stat", "score") == "gibbs":
+                # the Gibbs statistics of an FFBS path: the whole record, returned in pfg_result.pred; no log-likelihood
+                o["mean_stat"] = np.array(rs[b].pred[:OUT_DOUBLES])
+                o["loglik"] = float("nan")
+                continue
             # the device record is STAT_DIM[model] wide; sufficient statistics use 3 columns
             h = 3 if problems[b].get("stat", "score") != "score" else STAT_DIM[problems[b]["model"]]
             o["mean_stat"] = np.array(rs[b].mean_stat[:h])
@@ -488,7 +502,7 @@ class Context:
         B = len(problems)
         blocked = ("z0", "u", "z", "init_x", "init_logw", "init_stats", "paris_idx_u", "paris_acc_u", "paris_man_u", "pred_z", "paris_stream")
         for q in problems:
-            if RNG[q.get("rng", "replay")] != RNG["device"] or q.get("stat", "score") == "predictive":
+            if RNG[q.get("rng", "replay")] != RNG["device"] or q.get("stat", "score") in ("predictive", "gibbs"):
                 return None
             for name in blocked:
                 if q.get(name, None) is not None:
@@ -609,6 +623,21 @@ class Context:
             float(epsilon), float(Tscale), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
             C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
             C.c_void_p(int(stream_ptr))))
+
+    def sgrld_update_device(self, model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, seed,
+                            chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
+        self._check(self.lib.pfg_sgrld_update_device(
+            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper),
+            float(epsilon), float(Tscale), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
+            C.c_void_p(int(stream_ptr))))
+
+    def gibbs_update_device(self, model, B, theta_ptr, outs_ptr, hyper, seed, chain_offset=0, step_ctr_ptr=None,
+                            stream_ptr=0):
+        self._check(self.lib.pfg_gibbs_update_device(
+            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
 
     def scratch_bytes(self, model, dtype, rng, N):
         return int(self.lib.pfg_scratch_bytes(MODEL[model], DTYPE[dtype], RNG[rng], int(N)))

@@ -1,4 +1,4 @@
-"""ChainEnsemble: many independent SGLD chains resident on one MI355X.
+"""ChainEnsemble: many independent SGLD / SGHMC / SGRLD / Gibbs chains resident on one MI355X.
 
 The reference runs one chain in one Python thread; its experiment grid fans chains / settings
 out over processes (driver_utils.py:69-111).  On an MI355X one chain keeps one workgroup (one
@@ -76,7 +76,12 @@ class ChainEnsemble(object):
       chain_offset: global index of this rank's first chain (keeps streams distinct across GPUs)
       resampling: 'multinomial' (the reference's) | 'systematic' (extension, parity-unpinned)
       sampler: 'sgld' (sample_sgld + project_parameters) | 'sghmc' (extension: momentum with
-               friction `friction` in (0,1]; friction = 1 is SGLD)
+               friction `friction` in (0,1]; friction = 1 is SGLD) | 'sgrld' (model 'lgssm': sample_sgrld with the
+               LGSSM preconditioner + project_parameters, pfg_sgrld_update_device; every kind, pf and dtype) |
+               'gibbs' (model 'lgssm', dtype 'f64', subsequence_length = buffer_length = -1: the blocked Gibbs sampler
+               of sample_gibbs -- one FFBS path of the whole series with the PFG_STAT_GIBBS statistics, then the
+               conjugate draw of pfg_gibbs_update_device; kind, N, pf, num_samples and epsilon are ignored, sequence
+               lists are refused, and last_gradient_statistics() returns the sufficient statistics)
       kind: 'pf' (the particle-filter score) | 'marginal' (LGSSM, dtype 'f64': the exact Kalman score of
                every window, PFG_SMOOTHER_KALMAN -- the reference's kind='marginal', the KF baseline of its
                LGSSM experiment; N, pf and resampling are ignored) | 'complete' (LGSSM, dtype 'f64': the
@@ -97,6 +102,20 @@ class ChainEnsemble(object):
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
                  Ntilde=2, max_accept_reject=None, accept_reject=True):
+        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs"):
+            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld' or 'gibbs'")
+        if sampler == "sgrld" and model != "lgssm":           # sgmcmc_sampler.py:643-646: LGSSM alone has one
+            raise NotImplementedError("No Default Preconditioner for {0}: sampler='sgrld' is built for model 'lgssm'".format(
+                dict(svm="SVMSampler", garch="GARCHSampler").get(model, model)))
+        if sampler == "gibbs":
+            if model != "lgssm" or dtype != "f64":
+                raise NotImplementedError("sampler='gibbs' (FFBS paths, conjugate draws) is built for model 'lgssm', dtype 'f64'")
+            if isinstance(observations, (list, tuple)):
+                raise NotImplementedError("Gibbs over lists of sequences is not built")
+            if int(subsequence_length) != -1 or int(buffer_length) != -1:
+                raise NotImplementedError("sampler='gibbs' samples the path of the whole series: "
+                                          "subsequence_length = buffer_length = -1")
+            kind, num_samples, pf = "complete", 1, "poyiadjis_N"      # one FFBS path per chain and step
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         if kind not in ("pf", "marginal", "complete"):
@@ -139,8 +158,6 @@ class ChainEnsemble(object):
         self.P = _capi.THETA_DIM[model]
         self._Parameters = Parameters
         self.resampling = resampling
-        if sampler not in ("sgld", "sghmc"):
-            raise ValueError("sampler must be 'sgld' or 'sghmc'")
         self.sampler, self.friction = sampler, float(friction)
         if window_sampling not in ("host", "device"):
             raise ValueError("window_sampling must be 'host' or 'device'")
@@ -243,6 +260,8 @@ class ChainEnsemble(object):
             d["smoother"] = _capi.SMOOTHER["kalman"]
         elif kind == "complete":
             d["smoother"] = _capi.SMOOTHER["kalman_ffbs"]
+            if sampler == "gibbs":
+                d["stat"] = _capi.STAT["gibbs"]
         elif self.pf == "paris":
             d["smoother"] = _capi.SMOOTHER["paris"]
             d["Ntilde"], d["max_accept_reject"] = self.Ntilde, self.max_accept_reject
@@ -403,7 +422,15 @@ class ChainEnsemble(object):
 
     def launch_update(self, stream=None):
         st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
-        if self.sampler == "sghmc":
+        if self.sampler == "sgrld":
+            self.ctx.sgrld_update_device(self.model, self.C, self.theta_dev.data_ptr(), self.out_dev.data_ptr(),
+                                         self.hyper, self.epsilon, float(self.T), self.seed ^ 0x5DEECE66D,
+                                         self.chain_offset, self.step_ctr.data_ptr(), st)
+        elif self.sampler == "gibbs":
+            self.ctx.gibbs_update_device(self.model, self.C, self.theta_dev.data_ptr(), self.out_dev.data_ptr(),
+                                         self.hyper, self.seed ^ 0x5DEECE66D, self.chain_offset,
+                                         self.step_ctr.data_ptr(), st)
+        elif self.sampler == "sghmc":
             self.ctx.sghmc_update_device(self.model, self.C, self.theta_dev.data_ptr(), self.momentum_dev.data_ptr(),
                                          self.out_dev.data_ptr(), self.hyper, self.epsilon, self.friction,
                                          float(self.T), self.seed ^ 0x5DEECE66D, self.chain_offset,
@@ -435,7 +462,7 @@ class ChainEnsemble(object):
         self.launch_update()
 
     def step(self, num_steps=1):
-        """num_steps x (sample_sgld + project_parameters) for every chain.  Asynchronous."""
+        """num_steps x (the sampler's step + project_parameters) for every chain.  Asynchronous."""
         for _ in range(num_steps):
             self._enqueue_step()
             self.steps_done += 1
@@ -550,8 +577,12 @@ class ChainEnsemble(object):
 
     def last_gradient_statistics(self):
         """[C, h] score estimates and [C] log-likelihood estimates of the latest PF launch (kind='marginal':
-        the exact window scores and forward log-likelihoods)."""
+        the exact window scores and forward log-likelihoods).  sampler='gibbs': the [C, 7] sufficient statistics of
+        the latest FFBS paths (PFG_STAT_GIBBS: sum_{t>=1} x_{t-1}^2, x_t x_{t-1}, x_t^2; sum_t x_t^2, y_t x_t, y_t^2;
+        T) and None: a sampled path has no log-likelihood estimate."""
         out = self.out_dev.cpu().numpy()
+        if self.sampler == "gibbs":
+            return out[:, :7], None
         return out[:, :_capi.STAT_DIM[self.model]], out[:, 4]
 
     def parameters_list(self):

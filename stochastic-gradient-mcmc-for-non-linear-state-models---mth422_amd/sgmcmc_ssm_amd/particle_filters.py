@@ -530,7 +530,9 @@ def _to_reference_dict(o, q):
 
 def run_windows(problems, ctx=None, want_final=False, want_paths=False):
     """Many independent windows (same model/kernel/dtype/rng) in ONE launch, one workgroup each.
-    want_paths: FFBS windows (smoother 'kalman_ffbs') also return their sampled paths, out['paths'] [T, N]."""
+    want_paths: FFBS windows (smoother 'kalman_ffbs') also return their sampled paths, out['paths'] [T, N].
+    An FFBS window with stat='gibbs' (N = 1) returns the 8-double record of its path's Gibbs sufficient statistics as
+    out['mean_statistic'] (include/pfgrad.h, PFG_STAT_GIBBS)."""
     ctx = ctx or _capi.default_context()
     todo = [q for q in problems if "_result" not in q]
     outs = iter(ctx.run_batch(todo, want_final=want_final, want_trace=want_paths) if todo else [])
