@@ -366,10 +366,50 @@ int pfg_sample_windows_device(pfg_ctx *ctx, int B, pfg_dev_problem *dev_probs, c
                               uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr,
                               void *hip_stream);
 
+/* Several windows per chain and step (the reference's minibatch_size and num_sequences, sgmcmc_sampler.py:390-425,
+ * 1249-1283), for C resident chains over n_seq sequences laid end to end in y_dev: sequence k is
+ * y_dev[seq_bounds_dev[k], seq_bounds_dev[k+1]) (DEVICE int64 [n_seq + 1], increasing; a single series is n_seq = 1).
+ * Per chain, K_eff sequences: num_sequences = -1 takes all n_seq in index order (no draw); 1 <= num_sequences = K <=
+ * min(n_seq, PFG_MAX_DRAWN_SEQUENCES) draws K distinct sequences, uniformly and in random order (the law of
+ * np.random.choice(n_seq, K, replace=False)).  In each, M windows: start as pfg_sample_windows_device ('uniform':
+ * U{0..T_k-S}; strict != 0: S U{0..T_k/S-1}), the window [start, start + S) with `buffer` points each side clipped to
+ * the SEQUENCE; a sequence with T_k <= S (or S < 1) is taken whole, weights NULL.  Writes y / T / t1 / tL / weights of
+ * dev_probs[c W + w], W = K_eff M, chain-major, window w = k M + m the m-th window in the k-th chosen sequence, and
+ * seq_len_dev[c W + w] = T_k (DEVICE int32 [C W]); every other descriptor field is left as it is.  weights_dev: the
+ * per-sequence random_subsequence_and_weights tables, UNSCALED, sequence k's [T_k - S + 1][S] rows (one per start)
+ * from weights_dev + weight_offsets_dev[k] (DEVICE int64 [n_seq]; entries of sequences with T_k <= S are not read);
+ * NULL: weights NULL.  Draws: Philox4x32-10 keyed by `seed`, counter (global chain id = chain_offset + c, *step_ctr,
+ * draw index): sequence draw j and the start of window w are distinct draws, so a chain's windows depend on its global
+ * id and the step only.  Asynchronous on `hip_stream`.  Refuses num_sequences outside -1 / 1..n_seq (INVALID), above
+ * PFG_MAX_DRAWN_SEQUENCES or W >= 2^24 (UNSUPPORTED), M < 1, buffer < 0, strict with S < 1. */
+#define PFG_MAX_DRAWN_SEQUENCES 1024
+int pfg_sample_windows_multi_device(pfg_ctx *ctx, int C, int n_seq, const int64_t *seq_bounds_dev,
+                                    const int64_t *weight_offsets_dev, int num_sequences, int M,
+                                    pfg_dev_problem *dev_probs, int32_t *seq_len_dev, const double *y_dev,
+                                    const double *weights_dev, int S, int buffer, int strict, uint64_t seed,
+                                    uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream);
+/* The C W window records win_outs [C W][PFG_OUT_DOUBLES] (layout of pfg_sample_windows_multi_device, W = K M with
+ * K = num_seq_windows, the sequences of a chain) -> one record per chain, outs [C][PFG_OUT_DOUBLES], in the reference's
+ * order of operations (sgmcmc_sampler.py:411-418, 1264-1282), for out[0..3] (score columns) and out[4] (log-likelihood):
+ *   part_k = 0.0; for m in 0..M-1: part_k = part_k + (g[k M + m] * 1.0) / M
+ *   acc = part_0; for k in 1..K-1: acc = acc + part_k
+ *   rescale != 0:  S = 0.0; S = S + T_k in the same order (seq_len_dev of window k M);  acc = (acc * T_total) / S
+ * out[5..7] of the reduced record are 0 (the windows' weight sums, maximum log-weights and tie margins do not combine).
+ * No atomics: the order above is the contract, a host restatement is bitwise equal.  seq_len_dev may be NULL without
+ * rescale.  With Tscale = T_total, pfg_sgld / sghmc / sgrld_update_device on `outs` is noisy_gradient's step
+ * (sgmcmc_sampler.py:427-464).  Asynchronous on `hip_stream`. */
+int pfg_reduce_windows_device(pfg_ctx *ctx, int C, int num_seq_windows, int M, const double *win_outs,
+                              const int32_t *seq_len_dev, int rescale, double T_total, double *outs, void *hip_stream);
+
 /* bytes of per-problem HBM scratch (pfg_dev_problem.scratch, 256-byte aligned) the large-N
  * kernel (N <= 16384) or the whole-GPU window (N <= 4194304) needs for (model, dtype, rng, N); 0 when an LDS-resident
  * variant serves this size, -1 when N is above the supported maximum */
 int64_t pfg_scratch_bytes(int model, int dtype, int rng, int N);
+/* the same for a resident batch of `smoother` windows (PFG_SMOOTHER_NEMETH .. PFG_SMOOTHER_POYIADJIS_N) launched
+ * through pfg_launch_device_smoother: what that launch's plan sizes per descriptor -- PFG_SMOOTHER_PARIS: the
+ * paris_mem1024 state for 1024 < N <= 16384, 0 where an LDS-resident variant serves -- and -1 above the one-workgroup
+ * kernels' maximum (16384), for another smoother id, or for a combination that launch refuses */
+int64_t pfg_scratch_bytes_smoother(int model, int dtype, int rng, int smoother, int N);
 /* name of the kernel variant pfg_launch_device would pick (for profiles / logs) */
 const char *pfg_variant_name(int model, int kernel, int dtype, int rng, int n_max);
 /* tag of the kernel variant the latest launch through this context ran ("wg256x4s", "wg1024x1",

@@ -919,6 +919,12 @@ int64_t pfg_scratch_bytes(int model, int dtype, int rng, int N) {
     return p.name ? (int64_t)p.scratch : -1;
 }
 
+int64_t pfg_scratch_bytes_smoother(int model, int dtype, int rng, int smoother, int N) {
+    if (model < 0 || model > 2 || N < 1 || smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_POYIADJIS_N) return -1;
+    const LaunchPlan p = make_plan(Caller::Device, model, dtype, rng, smoother, N, 1 << 30, false);
+    return p.rc || !p.name ? -1 : (int64_t)p.scratch;
+}
+
 const char *pfg_variant_name(int model, int kernel, int dtype, int rng, int n_max) {
     (void)kernel;
     const LaunchPlan p = make_plan(Caller::Query, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, 1 << 30, false);

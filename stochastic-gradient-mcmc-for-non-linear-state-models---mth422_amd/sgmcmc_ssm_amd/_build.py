@@ -3,7 +3,8 @@
 The particle-filter kernels are instantiated in ten translation units (one per model x proposal
 kernel x generator, csrc/pfg_inst_*.hip) plus the dispatcher / C ABI unit (csrc/pfgrad.hip) and the
 exact Kalman score of LGSSM windows (csrc/pfg_kalman.hip) and their FFBS latent paths
-(csrc/pfg_ffbs.hip), and the SGRLD / Gibbs updates of resident LGSSM chains (csrc/pfg_chains.hip); the units are compiled to objects in parallel and linked into one shared library."""
+(csrc/pfg_ffbs.hip), and the SGRLD / Gibbs updates of resident LGSSM chains (csrc/pfg_chains.hip), and the
+multi-window sampler and window reduction of resident chains (csrc/pfg_windows.hip); the units are compiled to objects in parallel and linked into one shared library."""
 import os
 import shutil
 import subprocess
@@ -17,7 +18,7 @@ INCLUDE = os.path.join(REPO, "include")
 LIB_PATH = os.path.join(CSRC, "libpfgrad.so")
 _UNITS = ["svm_prior", "garch_prior", "garch_optimal", "lgssm_prior", "lgssm_optimal"]
 SOURCES = ["pfgrad.hip", "pfg_legacy_rng.hip"] + ["pfg_inst_{0}_{1}.hip".format(u, r) for u in _UNITS for r in ("device", "replay")] + \
-          ["pfg_kalman.hip", "pfg_ffbs.hip", "pfg_chains.hip"]
+          ["pfg_kalman.hip", "pfg_ffbs.hip", "pfg_chains.hip", "pfg_windows.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("pfg_device.hpp", "pfg_math.hpp", "pfg_models.hpp", "pfg_reg_kernel.hpp",
                                            "pfg_mem_kernel.hpp", "pfg_big_kernel.hpp", "pfg_grid_kernel.hpp", "pfg_grid_dev_kernel.hpp", "pfg_grid_cdf.hpp", "pfg_elementwise.hpp", "pfg_host.hpp",
                                            "pfg_launch.hpp", "pfg_kalman.hpp")] + \

@@ -27,6 +27,7 @@ FLAG_PARIS_NO_ACCEPT_REJECT = 2
 FLAG_PARIS_RAW_STREAM = 4        # paris_stream = the window's whole np.random stream of doubles (pfgrad.h)
 FLAG_PARIS_RAW_CARRY = 8         # ... whose first entry is the generator's pending cached Gaussian
 MAX_STAT, MAX_THETA, OUT_DOUBLES, MAX_PRED, STAMP_WORDS = 4, 4, 8, 16, 16
+MAX_DRAWN_SEQUENCES = 1024       # PFG_MAX_DRAWN_SEQUENCES: sequences a chain draws per step (num_sequences != -1)
 STATE_DIM = {"svm": 1, "garch": 2, "lgssm": 1}
 STAT_DIM = {"svm": 3, "garch": 4, "lgssm": 4}
 
@@ -142,7 +143,8 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_sgld_update_device", "pfg_sghmc_update_device", "pfg_imq_ksd", "pfg_sample_windows_device",
            "pfg_last_variant", "pfg_legacy_streams", "pfg_host_register", "pfg_host_unregister",
            "pfg_launch_device_traced", "pfg_last_traced", "pfg_launch_device_grid", "pfg_launch_device_grid_phase",
-           "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device")
+           "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device",
+           "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother")
 
 _lib = None
 
@@ -250,6 +252,15 @@ def load_library():
                                               C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p,
                                               C.c_void_p]
     lib.pfg_sample_windows_device.restype = C.c_int
+    lib.pfg_sample_windows_multi_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pfg_sample_windows_multi_device.restype = C.c_int
+    lib.pfg_reduce_windows_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_double, C.c_void_p, C.c_void_p]
+    lib.pfg_reduce_windows_device.restype = C.c_int
+    lib.pfg_scratch_bytes_smoother.argtypes = [C.c_int] * 5
+    lib.pfg_scratch_bytes_smoother.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -616,6 +627,23 @@ class Context:
             int(T), int(S), int(buffer), int(bool(strict)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
             C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr or 0), C.c_void_p(int(stream_ptr))))
 
+    def sample_windows_multi_device(self, num_chains, n_seq, bounds_ptr, weight_offsets_ptr, num_sequences, M, dev_probs_ptr,
+                                    seq_len_ptr, y_ptr, weights_ptr, S, buffer, strict, seed, chain_offset=0,
+                                    step_ctr_ptr=None, stream_ptr=0):
+        """pfg_sample_windows_multi_device: W = K_eff * M window descriptors per chain, chain-major (include/pfgrad.h)."""
+        self._check(self.lib.pfg_sample_windows_multi_device(
+            self.handle, int(num_chains), int(n_seq), C.c_void_p(bounds_ptr), C.c_void_p(weight_offsets_ptr or 0),
+            int(num_sequences), int(M), C.c_void_p(dev_probs_ptr), C.c_void_p(seq_len_ptr), C.c_void_p(y_ptr),
+            C.c_void_p(weights_ptr or 0), int(S), int(buffer), int(bool(strict)),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr or 0),
+            C.c_void_p(int(stream_ptr))))
+
+    def reduce_windows_device(self, num_chains, K, M, win_outs_ptr, seq_len_ptr, rescale, T_total, outs_ptr, stream_ptr=0):
+        """pfg_reduce_windows_device: [C*K*M][8] window records -> [C][8], in the reference's order (include/pfgrad.h)."""
+        self._check(self.lib.pfg_reduce_windows_device(
+            self.handle, int(num_chains), int(K), int(M), C.c_void_p(win_outs_ptr), C.c_void_p(seq_len_ptr or 0),
+            int(bool(rescale)), float(T_total), C.c_void_p(outs_ptr), C.c_void_p(int(stream_ptr))))
+
     def sgld_update_device(self, model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, seed,
                            chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
         self._check(self.lib.pfg_sgld_update_device(
@@ -641,6 +669,10 @@ class Context:
 
     def scratch_bytes(self, model, dtype, rng, N):
         return int(self.lib.pfg_scratch_bytes(MODEL[model], DTYPE[dtype], RNG[rng], int(N)))
+
+    def scratch_bytes_smoother(self, model, dtype, rng, smoother, N):
+        """Per-descriptor scratch of a pfg_launch_device_smoother batch of `smoother` windows (-1: above its maximum)."""
+        return int(self.lib.pfg_scratch_bytes_smoother(MODEL[model], DTYPE[dtype], RNG[rng], SMOOTHER[smoother], int(N)))
 
     def imq_ksd(self, x, gradlogp, c=1.0, beta=0.5):
         x, g = _as_f64(x), _as_f64(gradlogp)

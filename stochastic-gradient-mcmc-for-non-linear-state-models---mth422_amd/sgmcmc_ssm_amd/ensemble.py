@@ -94,6 +94,19 @@ class ChainEnsemble(object):
                partition; descriptors are re-uploaded) | 'device' (a Philox-keyed kernel rewrites the descriptors in HBM: the
                step is three launches with no host work, and `run(..., graph_steps=K)` replays K
                steps per hipGraph launch)
+      minibatch_size, num_sequences: SEVERAL windows per chain and step, the reference's _noisy_grad_loglikelihood
+               (sgmcmc_sampler.py:390-425, 1249-1283): minibatch_size = M windows in each of K_eff sequences -- a single
+               series: K_eff = 1 (num_sequences = 1 only); a list: num_sequences = K in 1..len(list) distinct
+               sequences drawn per chain and step, or -1 = every sequence in order (the reference's default; here the
+               default stays 1, one sequence per step, as above).  W = K_eff * M windows per chain run in ONE
+               particle-filter launch of C * W descriptors (window w of global chain g: stream g * W + w), then a
+               reduction in the reference's order of operations (within a sequence, across sequences, times
+               T_total / sum of the chosen T_k when num_sequences != -1: pfg_reduce_windows_device) and the update.
+               Passing either argument (1 included) selects this multi-window path; it samples windows on the device
+               (window_sampling='device', needed whenever there is anything to draw), so it replays in hipGraphs for
+               sequence lists too, and it runs pf='paris' up to N = 16384 (paris_mem1024 above N = 1024).  Leaving
+               both out keeps the single-window launches described above.  Refused: sampler='gibbs' or kind != 'pf'
+               with W > 1, window_sampling='host' when windows are drawn, N > 16384.
     """
 
     def __init__(self, model, observations, parameters, num_chains=None, N=1000, pf="poyiadjis_N",
@@ -101,9 +114,19 @@ class ChainEnsemble(object):
                  buffer_length=-1, dtype="f64", seed=0, chain_offset=0, device=None,
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
-                 Ntilde=2, max_accept_reject=None, accept_reject=True):
+                 Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None):
         if sampler not in ("sgld", "sghmc", "sgrld", "gibbs"):
             raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld' or 'gibbs'")
+        M, K, W = self._window_counts(observations, minibatch_size, num_sequences)
+        if W > 1 and sampler == "gibbs":
+            raise NotImplementedError("sampler='gibbs' draws one FFBS path per chain and step: W = 1 window "
+                                      "(minibatch_size = num_sequences = 1), got W = {0}".format(W))
+        if W > 1 and kind != "pf":
+            raise NotImplementedError("kind='{0}' with W = {1} windows per chain and step is not built: "
+                                      "the multi-window path is kind='pf' only".format(kind, W))
+        explicit = minibatch_size is not None or num_sequences is not None
+        self._multi = W > 1 or (explicit and kind == "pf" and sampler != "gibbs")
+        self.W = W
         if sampler == "sgrld" and model != "lgssm":           # sgmcmc_sampler.py:643-646: LGSSM alone has one
             raise NotImplementedError("No Default Preconditioner for {0}: sampler='sgrld' is built for model 'lgssm'".format(
                 dict(svm="SVMSampler", garch="GARCHSampler").get(model, model)))
@@ -142,9 +165,12 @@ class ChainEnsemble(object):
         elif pf == "nemeth":
             self.lambduh = 0.95 if lambduh is None else float(lambduh)
         elif pf == "paris":
-            # PaRIS on the LDS-resident kernels (paris64x2 / paris256x1 / paris256x4): no per-chain scratch
-            if self.N > 1024:
-                raise NotImplementedError("ChainEnsemble(pf='paris') is built for N <= 1024, got N = {0}".format(self.N))
+            # PaRIS on the LDS-resident kernels (paris64x2 / paris256x1 / paris256x4): no per-chain scratch; the
+            # multi-window path also runs paris_mem1024 (1024 < N <= 16384, its state in the descriptors' scratch)
+            if self.N > 1024 and not self._multi:
+                raise NotImplementedError("ChainEnsemble(pf='paris') is built for N <= 1024 on the single-window path, "
+                                          "got N = {0}: pass minibatch_size / num_sequences for the multi-window path "
+                                          "(paris_mem1024, N <= 16384)".format(self.N))
             if resampling != "multinomial":
                 raise ValueError("pf='paris' resamples multinomially, got resampling = {0}".format(resampling))
             self.lambduh = 1.0
@@ -191,9 +217,10 @@ class ChainEnsemble(object):
         self.seed, self.chain_offset = int(seed), int(chain_offset)
 
         S, B = int(subsequence_length), int(buffer_length)
-        if self.segments is not None:
+        if self.segments is not None and not self._multi:
             if window_sampling != "host":
-                raise NotImplementedError("sequence lists use host-side window sampling")
+                raise NotImplementedError("sequence lists use host-side window sampling (device-side: pass num_sequences, "
+                                          "the multi-window path)")
             if S == -1:
                 S = int(np.max(np.diff(self.segments)))      # whole sequences
         elif S == -1 or self.T - S <= 0:
@@ -209,6 +236,10 @@ class ChainEnsemble(object):
         self.out_dev = torch.zeros((self.C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         self.momentum_dev = torch.zeros((self.C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
+        if self._multi:
+            self._init_multi(M, K, theta0, proto)
+            return
+        self._nd = self.C
         self.weights_dev = None
         self._weights_table = None
         if self.segments is not None:
@@ -292,6 +323,99 @@ class ChainEnsemble(object):
             raise ValueError("S {0} does not evenly divide T {1}".format(S, self.T))     # sgmcmc_sampler.py:1991-1993
         self._set_windows(first=True)
         self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self.C, -1)).to(dev)
+
+    @staticmethod
+    def _window_counts(observations, minibatch_size, num_sequences):
+        """(M, K, W): windows per sequence, sequences per step (-1 = all), windows per chain and step."""
+        M = 1 if minibatch_size is None else int(minibatch_size)
+        K = 1 if num_sequences is None else int(num_sequences)
+        if M < 1:
+            raise ValueError("minibatch_size must be >= 1, got {0}".format(M))
+        if not isinstance(observations, (list, tuple)):
+            if K != 1:
+                raise ValueError("a single series takes num_sequences = 1, got {0}".format(K))
+            return M, K, M
+        n_seq = len(observations)
+        if K != -1 and not 1 <= K <= n_seq:
+            raise ValueError("num_sequences must be -1 or in 1..{0} (the number of sequences), got {1}".format(n_seq, K))
+        if K > _capi.MAX_DRAWN_SEQUENCES:
+            raise NotImplementedError("num_sequences = {0}: at most {1} sequences are drawn per chain and step "
+                                      "(num_sequences = -1 takes them all)".format(K, _capi.MAX_DRAWN_SEQUENCES))
+        return M, K, M * (n_seq if K == -1 else K)
+
+    def _init_multi(self, M, K, theta0, proto):
+        """The multi-window path: W = K_eff * M descriptors per chain (chain-major, window w = k * M + m), their records
+        win_out_dev [C * W, 8], each window's sequence length seq_len_dev [C * W]; out_dev [C, 8] holds the reduced
+        records the update reads.  The descriptors' windows are written by pfg_sample_windows_multi_device: every step
+        when there is something to draw, once here when not (num_sequences = -1 and no sequence longer than S)."""
+        dev, C, W = self.device, self.C, self.W
+        bounds = self.segments if self.segments is not None else np.array([0, self.T], dtype=np.int64)
+        n_seq = len(bounds) - 1
+        Tk = np.diff(bounds)
+        self.M, self.num_sequences = M, K
+        self.K_eff = W // M
+        self._nd = C * W
+        self._rescale = self.segments is not None and K != -1      # T_total / S (sgmcmc_sampler.py:1278-1282)
+        S = self.S
+        longer = (Tk > S) if S > 0 else np.zeros(n_seq, dtype=bool)
+        if (self.partition_style or 'uniform') == 'strict' and np.any(Tk[longer] % S != 0):
+            k = int(np.flatnonzero(longer & (Tk % max(S, 1) != 0))[0])
+            raise ValueError("S {0} does not evenly divide T {1}".format(S, int(Tk[k])))   # sgmcmc_sampler.py:1991-1993
+        self._draws = (self.segments is not None and K != -1) or bool(np.any(longer))
+        if self._draws and self.window_sampling != "device":
+            raise NotImplementedError("the W = {0} windows per chain and step are drawn on the device: "
+                                      "window_sampling='device'".format(W))
+        if self.N > 16384:
+            raise NotImplementedError("the multi-window path is built for N <= 16384 (one workgroup per window), "
+                                      "got N = {0}".format(self.N))
+        # random_subsequence_and_weights per sequence longer than S, one row per start, UNSCALED: the T_total / S
+        # rescaling is the reduction's
+        blocks, offs, off = [], np.zeros(n_seq, dtype=np.int64), 0
+        for k in np.flatnonzero(longer):
+            blk = np.stack([self._weights_for(st, T=int(Tk[k])) for st in range(int(Tk[k]) - S + 1)])
+            offs[k], off = off, off + blk.size
+            blocks.append(blk.reshape(-1))
+        self.weights_dev = torch.from_numpy(np.concatenate(blocks)).to(dev) if blocks else None
+        self.bounds_dev = torch.from_numpy(np.ascontiguousarray(bounds, dtype=np.int64)).to(dev)
+        self.woffs_dev = torch.from_numpy(offs).to(dev)
+        self.seq_len_dev = torch.zeros(self._nd, dtype=torch.int32, device=dev)
+        self.win_out_dev = torch.zeros((self._nd, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
+        pm, pv, _ = self._prior_x(proto, theta0[0])
+        d = self._desc = np.zeros(self._nd, dtype=_capi.DEV_PROBLEM_DTYPE)
+        chain = np.repeat(np.arange(C, dtype=np.uint64), W)
+        d["theta"] = self.theta_dev.data_ptr() + chain * np.uint64(8 * _capi.MAX_THETA)
+        d["out"] = self.win_out_dev.data_ptr() + np.arange(self._nd, dtype=np.uint64) * np.uint64(8 * _capi.OUT_DOUBLES)
+        d["step_ctr"] = self.step_ctr.data_ptr()
+        d["prior_mean"], d["prior_var"], d["lambduh"] = pm, pv, self.lambduh
+        d["seed"] = np.uint64(self.seed & 0xFFFFFFFFFFFFFFFF)
+        d["stream"] = (chain + np.uint64(self.chain_offset)) * np.uint64(W) + np.tile(np.arange(W, dtype=np.uint64), C)
+        d["N"] = self.N
+        d["stat"] = _capi.STAT["score"]
+        if self.model == "garch" and self.helper.default_forward_message is None:
+            d["flags"] = _capi.FLAG_GARCH_STATIONARY_PRIOR
+        smoother = "nemeth"
+        if self.pf == "paris":
+            smoother = "paris"
+            d["Ntilde"], d["max_accept_reject"] = self.Ntilde, self.max_accept_reject
+        elif self.resampling == "systematic":
+            if self.N > 1024:
+                raise NotImplementedError("systematic resampling is built for N <= 1024")
+            smoother = "nemeth_systematic"
+        elif self.resampling != "multinomial":
+            raise ValueError("Unrecognized resampling = {0}".format(self.resampling))
+        d["smoother"] = _capi.SMOOTHER[smoother]
+        sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", smoother, self.N)
+        if sb < 0:
+            raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(self.N))
+        self.scratch_bytes_per_window = sb
+        self.scratch_dev = None
+        if sb > 0:       # paris_mem1024 / the large-N kernel: one slab per window
+            self.scratch_dev = torch.empty(self._nd * sb, dtype=torch.uint8, device=dev)
+            d["scratch"] = self.scratch_dev.data_ptr() + np.arange(self._nd, dtype=np.uint64) * np.uint64(sb)
+        self.steps_done = 0
+        self.desc_dev = torch.from_numpy(d.view(np.uint8).reshape(self._nd, -1)).to(dev)
+        if not self._draws:
+            self.launch_windows()           # static windows: written once, no draw
 
     # ------------------------------------------------------------------------------------
     def _weights_for(self, start, T=None):
@@ -395,29 +519,29 @@ class ChainEnsemble(object):
             if traced:
                 raise ValueError("kind='marginal' has no particles to trace")
             self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman",
-                                            1, self.C, self.desc_dev.data_ptr(), st)
+                                            1, self._nd, self.desc_dev.data_ptr(), st)
         elif self.kind == "complete":
             if traced:
                 raise ValueError("kind='complete' has no particles to trace")
             self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman_ffbs",
-                                            self.N, self.C, self.desc_dev.data_ptr(), st)
+                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
         elif self.pf == "paris":
             # the PaRIS kernels always honour trace buffers: traced or not, the same launch
             self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "paris",
-                                            self.N, self.C, self.desc_dev.data_ptr(), st)
+                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
         elif traced:
             self.ctx.launch_device_traced(self.model, self.kernel, self.dtype, "device",
                                           "nemeth_systematic" if self.resampling == "systematic" else "nemeth",
-                                          self.N, self.C, self.desc_dev.data_ptr(), st)
+                                          self.N, self._nd, self.desc_dev.data_ptr(), st)
         elif self.resampling == "systematic":
             self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "nemeth_systematic",
-                                            self.N, self.C, self.desc_dev.data_ptr(), st)
+                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
         elif self.lambduh == 1.0:
             # every chain the Poyiadjis O(N) score (NEMETH, lambduh = 1, score): units with a twin specialised to it run that
             self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "poyiadjis_n",
-                                            self.N, self.C, self.desc_dev.data_ptr(), st)
+                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
         else:
-            self.ctx.launch_device(self.model, self.kernel, self.dtype, "device", self.N, self.C,
+            self.ctx.launch_device(self.model, self.kernel, self.dtype, "device", self.N, self._nd,
                                    self.desc_dev.data_ptr(), st)
 
     def launch_update(self, stream=None):
@@ -442,17 +566,40 @@ class ChainEnsemble(object):
 
     def launch_windows(self, stream=None):
         """Device-side window sampling (window_sampling='device'): rewrite y / T / t1 / tL / weights of
-        every descriptor for the step *step_ctr is at.  No-op for full-sequence chains."""
+        every descriptor for the step *step_ctr is at.  No-op for full-sequence chains.  Multi-window path: all
+        C * W descriptors and their sequence lengths (pfg_sample_windows_multi_device)."""
+        st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if self._multi:
+            self.ctx.sample_windows_multi_device(
+                self.C, self.bounds_dev.numel() - 1, self.bounds_dev.data_ptr(), self.woffs_dev.data_ptr(),
+                self.num_sequences if self.segments is not None else -1, self.M, self.desc_dev.data_ptr(),
+                self.seq_len_dev.data_ptr(), self.y_dev.data_ptr(),
+                self.weights_dev.data_ptr() if self.weights_dev is not None else 0, self.S, self.B,
+                (self.partition_style or 'uniform') == 'strict', self.seed ^ 0x4D554C5449574E44, self.chain_offset,
+                self.step_ctr.data_ptr(), st)
+            return
         if self.S == -1:
             return
-        st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
         self.ctx.sample_windows_device(
             self.C, self.desc_dev.data_ptr(), self.y_dev.data_ptr(),
             self.weights_dev.data_ptr() if self.weights_dev is not None else 0, self.T, self.S, self.B,
             (self.partition_style or 'uniform') == 'strict', self.seed ^ 0x2545F4914F6CDD1D, self.chain_offset,
             self.step_ctr.data_ptr(), st)
 
+    def launch_reduce(self, stream=None):
+        """Multi-window path: the C * W window records -> the C records the update reads (pfg_reduce_windows_device)."""
+        st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        self.ctx.reduce_windows_device(self.C, self.K_eff, self.M, self.win_out_dev.data_ptr(), self.seq_len_dev.data_ptr(),
+                                       self._rescale, float(self.T), self.out_dev.data_ptr(), st)
+
     def _enqueue_step(self):
+        if self._multi:
+            if self._draws:
+                self.launch_windows()
+            self.launch_pf()
+            self.launch_reduce()
+            self.launch_update()
+            return
         if self.window_sampling == "device":
             self.launch_windows()
         elif self.steps_done > 0 and self._set_windows():
@@ -472,7 +619,7 @@ class ChainEnsemble(object):
         Every input that changes between steps (parameters, descriptors, RNG step counter) lives
         in HBM and is advanced by the kernels themselves, so replaying the graph IS running K
         more steps; it is bitwise the same computation as K eager steps."""
-        if self.S != -1 and self.window_sampling != "device":
+        if not self._multi and self.S != -1 and self.window_sampling != "device":
             raise ValueError("graph capture needs window_sampling='device' (or full-sequence chains): "
                              "host-side window sampling cannot be replayed")
         g = self._graphs.get(K)
@@ -552,10 +699,12 @@ class ChainEnsemble(object):
     def enable_stamps(self):
         """Point every descriptor at a [C, 16] uint64 stamp record (pfg_dev_problem.stamps): the PF
         kernel's wave 0 then writes s_memtime / s_memrealtime at its start and end (two scalar
-        instructions outside the T-loop)."""
-        self.stamps_dev = torch.zeros((self.C, _capi.STAMP_WORDS), dtype=torch.int64, device=self.device)
-        self._desc["stamps"] = self.stamps_dev.data_ptr() + np.arange(self.C, dtype=np.uint64) * np.uint64(8 * _capi.STAMP_WORDS)
-        self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self.C, -1)))
+        instructions outside the T-loop).  Multi-window path: one record per window, [C * W, 16]."""
+        if self._multi:         # the device wrote the windows: start from its copy
+            self._desc = self.desc_dev.cpu().numpy().reshape(-1).view(_capi.DEV_PROBLEM_DTYPE).copy()
+        self.stamps_dev = torch.zeros((self._nd, _capi.STAMP_WORDS), dtype=torch.int64, device=self.device)
+        self._desc["stamps"] = self.stamps_dev.data_ptr() + np.arange(self._nd, dtype=np.uint64) * np.uint64(8 * _capi.STAMP_WORDS)
+        self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)))
         self.synchronize()
 
     def kernel_clock(self):
@@ -579,11 +728,17 @@ class ChainEnsemble(object):
         """[C, h] score estimates and [C] log-likelihood estimates of the latest PF launch (kind='marginal':
         the exact window scores and forward log-likelihoods).  sampler='gibbs': the [C, 7] sufficient statistics of
         the latest FFBS paths (PFG_STAT_GIBBS: sum_{t>=1} x_{t-1}^2, x_t x_{t-1}, x_t^2; sum_t x_t^2, y_t x_t, y_t^2;
-        T) and None: a sampled path has no log-likelihood estimate."""
+        T) and None: a sampled path has no log-likelihood estimate.  Multi-window path: the REDUCED records
+        (pfg_reduce_windows_device); window_statistics() has the windows'."""
         out = self.out_dev.cpu().numpy()
         if self.sampler == "gibbs":
             return out[:, :7], None
         return out[:, :_capi.STAT_DIM[self.model]], out[:, 4]
+
+    def window_statistics(self):
+        """Multi-window path: the latest launch's [C, W, 8] window records and [C, W] sequence lengths."""
+        return (self.win_out_dev.cpu().numpy().reshape(self.C, self.W, _capi.OUT_DOUBLES),
+                self.seq_len_dev.cpu().numpy().reshape(self.C, self.W))
 
     def parameters_list(self):
         return [self._params_from_theta(th) for th in self.theta()]
