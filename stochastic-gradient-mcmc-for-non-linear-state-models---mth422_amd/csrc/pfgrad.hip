@@ -444,13 +444,14 @@ __global__ void sample_windows_kernel(int B, pfg_dev_problem *__restrict__ probs
     const uint64_t bits = ((uint64_t)r.x << 32) | r.y;
     const int idx = (int)__umul64hi(bits, (uint64_t)range);
     const int start = strict ? idx * S : idx;
-    const int left = start - buffer > 0 ? start - buffer : 0;
-    const int right = start + S + buffer < T ? start + S + buffer : T;
+    // in 64 bits: start + S + buffer overflows int for any buffer the entry point accepts (as sample_windows_multi_kernel)
+    const int64_t left = start - buffer > 0 ? (int64_t)start - buffer : 0;
+    const int64_t right = (int64_t)start + S + buffer < T ? (int64_t)start + S + buffer : T;
     pfg_dev_problem &P = probs[b];
     P.y = y + left;
-    P.T = right - left;
-    P.t1 = start - left;
-    P.tL = start + S - left;
+    P.T = (int)(right - left);
+    P.t1 = (int)(start - left);
+    P.tL = (int)(start + S - left);
     P.weights = wtab ? wtab + (size_t)start * S : nullptr;
 }
 

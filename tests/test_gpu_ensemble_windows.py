@@ -14,6 +14,7 @@ import scipy.stats
 from test_host_logic import default_params, GEN, eurus_segments, vec
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "helpers"))
+import device_windows  # noqa: E402
 import window_reduce  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -30,16 +31,7 @@ def _segments(model, lengths, seed=6):
     return [y[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
 
 
-def _device_windows(ens):
-    """The device-written descriptors of the latest step as host windows: [C*W] dicts (y offset, T, t1, tL, weights
-    offset or None) and the sequence lengths."""
-    from sgmcmc_ssm_amd import _capi
-    d = ens.desc_dev.cpu().numpy().reshape(-1).view(_capi.DEV_PROBLEM_DTYPE)
-    yoff = (d["y"].astype(np.int64) - ens.y_dev.data_ptr()) // 8
-    wbase = ens.weights_dev.data_ptr() if ens.weights_dev is not None else 0
-    woff = np.where(d["weights"] == 0, -1, (d["weights"].astype(np.int64) - wbase) // 8)
-    _, seq_len = ens.window_statistics()
-    return d, yoff, woff, seq_len.reshape(-1)
+_device_windows = device_windows.ensemble_windows       # (records, y offset, weights offset or -1, sequence lengths)
 
 
 def _restate_step(ens, y_host, theta, pf, dtype):
