@@ -80,6 +80,22 @@ __device__ __forceinline__ Consts<REAL> make_consts(const double *__restrict__ t
     return c;
 }
 
+// SVM log-weight of a child x1 (svm/kernels.py:56-62) from e = exp(-x1) and y2 = y^2: a function of the child's own
+// state and the observation only.  particle_step and the stale-shift retry of pf_reg_kernel (which recomputes the
+// log-weights from the published states) both call it, so the two values are bitwise equal.
+template <typename REAL>
+__device__ __forceinline__ REAL svm_logw(const Consts<REAL> &c, REAL x1, REAL e, REAL y2) {
+    const REAL half = (REAL)0.5;
+#ifdef PFG_FAST_ALGEBRA
+    // device-generator units (no operation-order parity to keep): the same expressions with
+    // the wave-uniform factors of the step collected (they are computed once per step)
+    const REAL k0 = c.c0 + c.logLRinv, ke = (-half * y2) * c.Rinv;
+    return fma(ke, e, fma(-half, x1, k0));
+#else
+    return ((c.c0 + ((-half * y2) * e) * c.Rinv) + c.logLRinv) + (-half * x1);
+#endif
+}
+
 // One particle: parent state xp -> proposal x' (Kernel.rv), log weight (Kernel.reweight) and
 // additive statistic (STAT = PFG_STAT_SCORE: complete-data score; otherwise the sufficient
 // statistics), all from the same registers, straight-line.  add[] is NOT yet scaled by weight_t.
@@ -96,14 +112,7 @@ __device__ __forceinline__ void particle_step(const Consts<REAL> &c, const MATH 
         REAL x1 = c.iLQinv * z + xpA;
         REAL e = mth.exp_finite(-x1);          // x1 is finite
         REAL y2 = y * y;
-#ifdef PFG_FAST_ALGEBRA
-        // device-generator units (no operation-order parity to keep): the same expressions with
-        // the wave-uniform factors of the step collected (they are computed once per step)
-        const REAL k0 = c.c0 + c.logLRinv, ke = (-half * y2) * c.Rinv;
-        lw = fma(ke, e, fma(-half, x1, k0));
-#else
-        lw = ((c.c0 + ((-half * y2) * e) * c.Rinv) + c.logLRinv) + (-half * x1);
-#endif
+        lw = svm_logw(c, x1, e, y2);
         xn[0] = x1;
         if (STAT == PFG_STAT_SCORE) {
             REAL dx = x1 - c.A * xp[0];

@@ -120,6 +120,36 @@ __host__ __device__ constexpr int occ_min(int NT, int PPT, size_t real, bool PP,
 // level cost more than the round trips they save; the children of a step kept in registers and written behind
 // barrier 1 of the NEXT step (every wave is past its gathers by then: three barriers per timestep on one buffer, the
 // gathers' latency overlapped with the generator calls): SVM +5.5 % (32 spilled registers), GARCH +1 %, N = 4000 +2 %.
+//  PFG_OPT_STALESHIFT  (SVM prior kernel, 256 x 4 on one buffer, fp64: STALE in pf_reg_kernel) the shift s of
+//                  exp(lw - s) is the exact maximum of the PREVIOUS step instead of this step's: the max reduction
+//                  needs no barrier of its own (three s_barrier per timestep instead of four).  Any shift gives the
+//                  same normalised weights and the same s + log(W/N) up to rounding; it only has to keep exp in range.
+//                  Unlike the two tries above nothing is rescaled and nothing extra stays live: this step's wave maxima
+//                  ride to LDS before barrier 2 and are read behind it next to the scan totals.
+//                  Range guard, wave-uniform (every wave reads the same maxima): the hot path holds while
+//                  |m_t - s| <= 512 -- fp64 exp is normal down to -708 and particles within e^-100 of the maximum must
+//                  stay normal (m_t - s > -608); 1024 terms must not overflow (m_t - s < 702).  Otherwise (a gross
+//                  outlier, NaN, +-inf) a cold path recomputes the log-weights from the published states
+//                  (svm_logw: a function of the child's own state and y only), takes s = m_t and redoes exp, sums and
+//                  scan: today's arithmetic.  The shift of t = 0 is the exact maximum (prologue: init_logw may be
+//                  anything).
+//                  Hazards: the maxima of step t are written to red_maxf before barrier 2 of step t and read between
+//                  its barriers 2 and 3; those of step t + 1 are written behind barriers 3 and 4 of step t, when every
+//                  wave is done with that read.  The retry's own two barriers order its rewrite of red_scan / red_S
+//                  behind every wave's first read of them.  The state, red_scan and the CDF keep the barriers they have.
+//  PFG_OPT_GATHERADDR  (the same kernel) the search's final byte offset becomes the gather's byte address in eight
+//                  instructions per particle instead of ten: see GADDR.  (Six with the CDF's base folded into the
+//                  ds_read immediates of a search on relative offsets -- the compiler does not fold the base of the
+//                  dynamic LDS block, it adds it per probe: 36 more VALU per lane-timestep, not built.)
+//  Measured, bench config c2 (12288 chains, kernel ms, median of five interleaved runs per library, the parent's own
+//  max - min 0.13 ms; profiles/r05_ab_stale_shift.txt): both off 42.75, STALESHIFT alone 42.25, GATHERADDR alone 42.35,
+//  both 41.84 (-2.1 %).
+#ifndef PFG_OPT_STALESHIFT
+#define PFG_OPT_STALESHIFT 1
+#endif
+#ifndef PFG_OPT_GATHERADDR
+#define PFG_OPT_GATHERADDR 1
+#endif
 // TRACE (template parameter of pf_reg_kernel): the instantiation honours the trace_* / rec_* buffers of its
 // descriptors (save_all trajectories, recorded generator draws: tests, elementwise statistics).  TRACE = false is
 // the production twin of the plain device-generator kernels: the same code with every trace / record test compiled
@@ -266,6 +296,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
 #define PFG_OPT_PAIRSTATE 1
 #endif
     constexpr bool PAIRED = PFG_OPT_PAIRSTATE && BLK && sizeof(REAL) == 8 && ((NS + H) % 2 == 0);
+    // STALE: the previous step's maximum as this step's shift, see PFG_OPT_STALESHIFT
+    constexpr bool STALE = PFG_OPT_STALESHIFT && BLK && MODEL == PFG_MODEL_SVM && KERNEL == PFG_KERNEL_PRIOR && NT == 256 && PPT == 4 &&
+                           !PP && sizeof(REAL) == 8;
+    // GADDR (256 x 4): search offset -> gather byte address.  rel = 4 x physical CDF position (one pad slot per 32
+    // entries), p4 = rel - 4 (rel * 993 >> 17) = 4 x CDF position p (exact: rel * 993 < 2^23), and
+    // (p4 * 1025) & 0x3ff0 = 16 x the particle index ((p & 3) << 8) | (p >> 2): p4 < 2^12, so the copies p4 << 10 and p4
+    // do not overlap -- bits 4..11 of p4 are p >> 2 and bits 12, 13 of p4 << 10 are p & 3.  Clamped to 16 x last it is
+    // the byte offset of the parent's first 16-byte pair.  Ancestors are those of the general form, bit for bit
+    // (tests/test_gather_address_host.py).
+#ifdef PFG_EXP_OWNGATHER
+    constexpr bool GADDR = false;
+#else
+    // (the arithmetic holds for every BLK && PAIRED 256 x 4 kernel; it is switched on where it was timed: the SVM kernel
+    // on one buffer, bench config c2, and its TRACE twin)
+    constexpr bool GADDR = PFG_OPT_GATHERADDR && BLK && PAIRED && NT == 256 && PPT == 4 && MODEL == PFG_MODEL_SVM && !PP;
+#endif
+    static_assert(!GADDR || 4 * (NT * PPT + NT * PPT / 32) * 993 < (1 << 23), "GADDR: rel * 993 must fit the 24-bit multiply");
     // element index of component d of particle i
     auto sidx = [&](int d, int i) -> size_t {
         return PAIRED ? (size_t)(d >> 1) * (2 * (size_t)NLS) + 2 * (size_t)i + (size_t)(d & 1) : (size_t)d * NLS + (size_t)i;
@@ -473,6 +520,22 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         if (!valid[k]) lw[k] = -INFINITY;
     }
     const int last = N - 1;
+    [[maybe_unused]] float m_next = 0.0f;
+    if constexpr (STALE) {
+        // the shift of t = 0 is the exact maximum; the second barrier keeps the loop's first write of red_maxf behind
+        // every wave's read
+        float ml = (float)lw[0];
+#pragma unroll
+        for (int k = 1; k < PPT; ++k) ml = fmaxf(ml, (float)lw[k]);
+        ml = wave_max(ml);
+        if (lane == 0) red_maxf[wave] = ml;
+        block_sync<NW>();
+        float mm = red_maxf[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
+        m = uniform_f64((double)mm);
+        block_sync<NW>();
+    }
 
     for (int t = 0; t <= T; ++t) {
         [[maybe_unused]] double uu_raw[PPT];
@@ -498,9 +561,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         ml = wave_max(ml);
         if (NW > 1 && lane == 0) red_maxf[wave] = ml;
         PFG_PH(0)
-        block_sync<NW>();                                                       // barrier 1
+        if constexpr (!STALE) block_sync<NW>();                                 // barrier 1
         PFG_PH(1)
-        {
+        if constexpr (!STALE) {
             float mm = NW > 1 ? red_maxf[0] : ml;     // one wave: its maximum IS the block maximum, no LDS round trip
 #pragma unroll
             for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
@@ -601,6 +664,54 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             for (int k = 0; k < PPT; ++k) cs[k] += off;
             W = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(inc), NW - 1),
                                  __builtin_amdgcn_readlane(__double2loint(inc), NW - 1));
+            if constexpr (STALE) {
+                // this step's exact maximum: the next step's shift, and the range guard of this one (NaN, +-inf fail it)
+                float mm = red_maxf[0];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
+                m_next = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mm)));
+                if (t > 0 && !(fabsf(m_next - (float)m) <= 512.0f)) {
+                    PFG_MARK("cold stale-shift-retry")
+                    block_sync<NW>();
+                    m = uniform_f64((double)m_next);
+                    const REAL y_p = (REAL)yv[t - 1], y2_p = y_p * y_p;
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k) {
+                        const REAL x1 = cur[sidx(0, own[k])];
+                        const REAL lwk = valid[k] ? svm_logw(c, x1, mth.exp_finite(-x1), y2_p) : (REAL)(-INFINITY);
+                        cs[k] = (double)mth.exp((REAL)(lwk - (REAL)m));
+                    }
+                    if (needS) {
+#pragma unroll
+                        for (int h = 0; h < H; ++h) {
+                            double part = 0.0;
+#pragma unroll
+                            for (int k = 0; k < PPT; ++k) part += (double)cur[sidx((NS + h), own[k])] * cs[k];
+                            part = wave_sum(part);
+                            if (lane == 0) red_S[h * NW + wave] = part;
+                        }
+                    }
+#pragma unroll
+                    for (int k = 1; k < PPT; ++k) cs[k] += cs[k - 1];
+                    const double inc2 = wave_incl_scan(cs[PPT - 1]);
+                    const double exc2 = inc2 - cs[PPT - 1];
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k) cs[k] += exc2;
+                    if (lane == WAVE - 1) red_scan[wave] = inc2;
+                    block_sync<NW>();
+                    const double tot2 = (lane < NW) ? red_scan[lane] : 0.0;
+                    double incw = tot2;
+                    incw += dpp_shr0_f64<0x111>(incw);
+                    incw += dpp_shr0_f64<0x112>(incw);
+                    const double excw = incw - tot2;
+                    const double off2 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(excw), wave),
+                                                         __builtin_amdgcn_readlane(__double2loint(excw), wave));
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k) cs[k] += off2;
+                    W = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(incw), NW - 1),
+                                         __builtin_amdgcn_readlane(__double2loint(incw), NW - 1));
+                }
+            }
             if (SORTED && t < T) {
                 const double totE = (lane < NW) ? red_scan[NW + lane] : 0.0;
                 double incE = totE;
@@ -698,6 +809,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             for (int h = 0; h < H; ++h) filt[h] = uniform_f64(filt[h] + S[h]);
         }
         if (t == T) break;
+        if constexpr (STALE) m = uniform_f64((double)m_next);      // the log-likelihood above used the shift W was formed with
 
         // ---- (D) normalised CDF to LDS (RandomState.choice: cumsum, /= last) -------------
         const double y_t = yv[t];
@@ -741,8 +853,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             }
         }
         int anc[PPT];
+        [[maybe_unused]] uint32_t gaddr[PPT];       // GADDR: byte offset of the parent's record in a state array
 #pragma unroll
-        for (int k = 0; k < PPT; ++k) anc[k] = 0;
+        for (int k = 0; k < PPT; ++k) { anc[k] = 0; gaddr[k] = 0u; }
         if (BLK) {
             uint32_t ua[PPT];
 #pragma unroll
@@ -809,6 +922,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                 for (int k = 0; k < PPT; ++k) off[k] += (cv[k] <= ua[k]) ? 4u * adv : 0u;
                 }
             }
+            if constexpr (GADDR) {
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) {
+                    const uint32_t rel = off[k] - cdf_base;
+                    // p4 = rel - 4 q in ONE multiply-add (the compiler's own form is shift, mask, subtract)
+                    const uint32_t q = __umul24(rel, 993u) >> 17;
+                    uint32_t p4;
+                    asm("v_mad_i32_i24 %0, %1, -4, %2" : "=v"(p4) : "v"(q), "v"(rel));
+                    const uint32_t a = __umul24(p4, 1025u) & 0x3ff0u;
+                    gaddr[k] = min(a, 16u * (uint32_t)last);
+                    if constexpr (TRACE) anc[k] = (int)(gaddr[k] >> 4);
+                }
+            } else
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
                 uint32_t p = (off[k] - cdf_base) >> 2;
@@ -881,7 +1007,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                     REAL rec[NS + H];
 #pragma unroll
                     for (int p = 0; p < (NS + H) / 2; ++p) {
-                        const dv2 v = *reinterpret_cast<const dv2 *>(&cur[sidx(2 * p, anc[k])]);
+                        dv2 v;
+                        if constexpr (GADDR) {
+                            using lds_byte = const __attribute__((address_space(3))) unsigned char;
+                            v = *(const __attribute__((address_space(3))) dv2 *)((lds_byte *)cur + gaddr[k] + (uint32_t)(p * 16 * NLS));
+                        } else {
+                            v = *reinterpret_cast<const dv2 *>(&cur[sidx(2 * p, anc[k])]);
+                        }
                         rec[2 * p] = (REAL)v.x; rec[2 * p + 1] = (REAL)v.y;
                     }
 #pragma unroll

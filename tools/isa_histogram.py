@@ -144,6 +144,15 @@ def weights(blocks):
                     lo, hi = j + 1, min(tgt)
                     break
             if lo is None:
+                # the skipping branch jumps BACK (the region is the tail of the loop body, its join block sits at the
+                # loop's top): the region runs from the marker's block to the end of the loop
+                pos = [n for n, (k, t) in enumerate(b["items"]) if k == "marker" and t == text][0]
+                own = [t for k, t in b["items"][:pos] if k == "inst" and t.startswith("s_cbranch")]
+                prev = [t for k, t in blocks[i - 1]["items"] if k == "inst"][-1:] if i > 0 and not own else []
+                back = [t for t in own + prev if t.startswith("s_cbranch") and index.get(t.split()[-1], i) < i]
+                if back:
+                    lo, hi = (i + 1 if own else i), len(blocks)
+            if lo is None:
                 continue
             for j in range(max(lo, i if lo <= i else lo), hi):
                 if weight < w[j] or w[j] == 1.0:
