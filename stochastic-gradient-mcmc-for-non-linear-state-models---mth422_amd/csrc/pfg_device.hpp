@@ -16,7 +16,8 @@
 #pragma once
 #include "pfg_math.hpp"          // wave primitives, generators, table math
 #include "pfg_models.hpp"        // model constants and the per-particle step
-#include "pfg_reg_kernel.hpp"    // N <= 1024: LDS-resident kernel (+ PaRIS / systematic / O(N^2))
+#include "pfg_reg_traits.hpp"    // ... its compile-time switches and its one LDS layout (host sizing and kernel pointers)
+#include "pfg_reg_kernel.hpp"    // N <= 4096: LDS-resident kernel (+ PaRIS / systematic / O(N^2))
 #include "pfg_mem_kernel.hpp"    // N <= 16384: general large-N kernel
 #include "pfg_big_kernel.hpp"    // N <= 16384: device-generator fast path
 #include "pfg_grid_kernel.hpp"   // N <= 2^22: one window over the whole GPU, one launch per timestep

@@ -1,41 +1,20 @@
-// libpfgrad device code: pf_reg_kernel, the LDS-resident particle filter (N <= 1024) incl. its
-// PaRIS, systematic-resampling and O(N^2) instantiations.
+// libpfgrad device code: pf_reg_kernel, the LDS-resident particle filter (N <= 4096) incl. its PaRIS, systematic-resampling
+// and O(N^2) instantiations.  Its build switches, derived compile-time switches and its one LDS layout: pfg_reg_traits.hpp.
 #pragma once
-#include "pfg_models.hpp"
+#include "pfg_reg_traits.hpp"
 
 namespace pfg {
 
-// ------------------------------------------------------------------------------------
 // LDS-resident kernel: N <= NT*PPT particles; particle i = k*NT + tid belongs to thread tid,
 // slot k.  Only the log-weights live in registers across timesteps; particles and statistics
 // live in LDS as struct-of-arrays over the particle axis (lane i <-> particle i: conflict-free).
-//   LDS: cdf[NL] f64 | buf0 {x[NS][NL], stats[H][NL]} | buf1 (PP only) | reduction scratch
+//   LDS: cdf | buf0 {x[NS][NLS], stats[H][NLS]} | buf1 (PP only) | reduction scratch | math tables | PaRIS / O(N^2) tail:
+//   RegTraits::layout says where each starts and what aliases what
 // PP = ping-pong state buffers: children are written to the other buffer, so no barrier is
 // needed between gathering parents and publishing children (3 barriers per timestep, and a
 // slot's parent state dies as soon as its child is computed).  PP = false keeps ONE buffer
 // (larger N fits in 160 KiB) at the price of a 4th barrier and of holding all gathered
 // parents in registers across it.
-// ------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ constexpr int cdf_phys(int i) { return i + (i >> 5); }
-// FAST layout = LDS math tables + sentinel-padded, bank-conflict-free cdf with an unrolled search.
-// Everything except the 1024-thread single-buffer variant (which spends all LDS on particles).
-__host__ __device__ constexpr bool fast_layout(int NT, bool PP) { return PP || NT <= 512 || NT == 1024; }
-
-// State arrays x[NS][.], stats[H][.] of a FAST layout are NL + pad elements apart (pad = 8 bytes).  With a stride of
-// exactly NL = NT * PPT elements (a multiple of 512 bytes) the compiler fuses the gathers / stores of one particle's
-// entries in two arrays into ds_read2st64_b64 / ds_write2st64_b64, which the LDS serves at HALF the rate of two
-// ds_read_b64 (MI355X_MICROARCH.md, LDS table: 8 cycles per wave-instruction against 2 + 2; with the random
-// addresses of a gather about 24 against 14).  A stride that is no multiple of 512 bytes keeps them apart.
-// Device-generator kernels only: they are bound by LDS-array cycles (c2: 51.4 -> 47.0 ms with the pad).  The REPLAY
-// kernels wait on their HBM streams instead and run 17 % SLOWER with twice the LDS instructions (768 windows of
-// T = N = 1000: 6.8 ms fused, 8.0 ms padded), so they keep the fused form.  -DPFG_OPT_PADSTATE=0 restores it everywhere (A/B).
-#ifndef PFG_OPT_PADSTATE
-#define PFG_OPT_PADSTATE 1
-#endif
-template <typename REAL, int RNG> __host__ __device__ constexpr int state_pad() {
-    return (PFG_OPT_PADSTATE && RNG == PFG_RNG_DEVICE) ? (int)(8 / sizeof(REAL)) : 0;
-}
-
 // workgroup barrier; a one-wave workgroup only needs its own LDS accesses kept in program order (the LDS
 // executes a wave's instructions in order): no s_barrier, no drain of the LDS queue
 template <int NW> __device__ __forceinline__ void block_sync() {
@@ -47,175 +26,24 @@ template <int NW> __device__ __forceinline__ void block_sync() {
         __syncthreads();
     }
 }
-template <int NT, int PPT> struct RegLayout {
-    static constexpr int NW = NT / WAVE;
-    static constexpr int RED = PPT * NW + NW + PFG_MAX_STAT * NW + 8;  // doubles of scratch
-};
-
-// PP variants: cdf has NT*PPT entries (tail = sentinel 2.0 -> unrolled, clamp-free search) and
-// the fp64 math runs on LDS tables; the single-buffer variant spends its LDS on particles.
-template <int MODEL, typename REAL, int NT, int PPT, int RNG, bool PP, int MODE = 0>
-__host__ __device__ inline size_t reg_kernel_lds_bytes(int N) {
-    constexpr bool PARIS = (MODE == MODE_PARIS || MODE == MODE_N2);   // parents' log-weights in LDS
-    constexpr bool FAST = fast_layout(NT, PP);
-    // FAST layouts hold NT*PPT particle slots whatever N is: the array stride is a compile-time
-    // constant and folds into the ds_read / ds_write immediates
-    size_t NL = FAST ? (size_t)NT * PPT : (size_t)(N + WAVE - 1) / WAVE * WAVE;
-    size_t NC = FAST ? (size_t)NT * PPT + (size_t)NT * PPT / 32 : NL;   // padded 33/32 (see cdf_phys)
-    // device generator (plain smoothers): 32-bit fixed-point CDF, see pf_reg_kernel
-    constexpr bool BLK = FAST && RNG == PFG_RNG_DEVICE && MODE == MODE_PLAIN && (PPT & (PPT - 1)) == 0;
-    const size_t NLS = NL + (FAST ? state_pad<REAL, RNG>() : 0);
-    return (NC * (BLK ? 4 : 8) + 15) / 16 * 16 + (PP ? 2 : 1) * NLS * (ModelDims<MODEL>::NS + ModelDims<MODEL>::H) * sizeof(REAL) +
-           (size_t)RegLayout<NT, PPT>::RED * 8 + tab_bytes<REAL, RNG, FAST>() +
-           (PARIS ? NL * 8 + NL * 4 + 3 * NL * 4 : 0);   // PaRIS: parents' log-weights, fallback queue,
-                                                         // two wave-queue arrays, accepted parents
-}
-
-// waves per SIMD the register allocator should aim for: what LDS lets a CU hold anyway.
-// 256x4 fp64: ping-pong state is 80 KB/workgroup -> 2 workgroups (2 waves/SIMD); the single
-// buffer is 50 KB -> 3, which is worth a few spilled registers (measured +15 %).
-// One-wave workgroups (NT = 64): LDS admits many windows per CU, the register budget decides how many waves a SIMD
-// holds (-DPFG_OCC64=n for A/B builds)
-#ifndef PFG_OCC64
-#define PFG_OCC64 4
-#endif
-// 4096 particle slots in fewer than 1024 threads (N <= 4096 state fills the LDS of a CU: ONE workgroup per CU
-// whatever its thread count): 512 threads = 2 waves per SIMD and 256 VGPRs, 256 threads = 1 wave per SIMD and 512.
-// (A/B instantiations of round 3, slower than 1024 x 4 and no longer built: see the variant table in pfgrad.hip.)
-__host__ __device__ constexpr bool occ_lds4096(int NT, int PPT) { return NT * PPT == 4096 && NT < 1024; }
-__host__ __device__ constexpr int occ_max(int NT, int PPT, size_t real, bool PP, bool dev4 = false) {
-    if (occ_lds4096(NT, PPT)) return NT == 512 ? 2 : 1;
-    if (NT == 64) return PFG_OCC64;
-    return (NT >= 512 || PPT == 1 || dev4) ? 4 : ((PP && real == 8) ? 2 : 3);
-}
-__host__ __device__ constexpr int occ_min(int NT, int PPT, size_t real, bool PP, bool dev4 = false) {
-    if (occ_lds4096(NT, PPT)) return NT == 512 ? 2 : 1;
-    if (NT == 512) return 4;        // two 8-wave workgroups per CU
-    return dev4 ? 4 : ((NT == 256 && PPT == 4 && !PP) ? 3 : 1);
-}
-// Device-generator units only (-DPFG_FAST_ALGEBRA; the REPLAY units keep the reference's operation
-// order and phase structure).  Each can be switched off for A/B timing (-DPFG_OPT_x=0):
-//  PFG_OPT_LAZYLL  the log-likelihood increment  w (m + log(W/N))  used to cost wave 0 an fp64 log and
-//                  a division per timestep while the other waves waited at the next barrier; now wave 0
-//                  parks (W, m, w) of step t in lane t % 64 and evaluates 64 steps at once (one table log
-//                  per lane + one wave sum);
-//  PFG_OPT_RCPW    1/W by v_rcp_f64 + two Newton steps instead of the IEEE division sequence.
-// Measured and NOT kept (profiles/r02b_knockouts.txt): a wave-local maximum with the rescaling
-// exp(m_w - m) folded into the prefix-sum exchange (drops the max barrier, lengthens the chain behind
-// barrier 2: +4 %); the step's generator calls and Box-Muller issued between the search probes (E grows by
-// what G shrinks: +4 %); a per-workgroup start-up stagger (0 %); jsf32 instead of xoshiro128++ (0 %); the
-// model's closed-form upper bound of the log-weights as the shift (no max reduction, no max barrier, exact
-// maximum only on underflow: SVM +10 %, GARCH 0 % -- the retry path costs 9 more spilled registers); the
-// step's words / normals drawn behind barrier 2, next to the serial offsets chain (+10 %: 4-8 more live
-// registers); search levels 1-3 compared in registers against 7 broadcast pivots (7 instead of 10 dependent
-// LDS round trips: 0 % -- the search is issue-bound, not LDS-latency-bound); fewer, wider threads for the same
-// four LDS-bound workgroups per CU (128 threads x 8 particles at 2 waves per SIMD and 227 VGPRs, no spills:
-// +18 %; 64 x 16 at one wave per SIMD, no barriers left: +51 %) -- thread-level parallelism hides the LDS and
-// fp64 latencies better than the same independent work inside one wave; the particle arrays on a 512-byte
-// boundary so that their base folds into the ds_read2st64 / ds_write2st64 offsets (0 %); descriptor-field tests
-// hoisted out of the loop and the observations held 64 steps at a time in the lanes of a register instead of a
-// scalar load per step (+0.5 % / +2 %: 15 more spilled registers); the CDF as an implicit 4-ary search tree (a node
-// = three pivots read with ds_read2_b32 + ds_read_b32, five dependent LDS round trips instead of ten, no padding to
-// undo; bit-identical ancestors): SVM +6 %, GARCH +3 %, N = 100 0 %, N = 4000 -2 % -- three compares and two selects per
-// level cost more than the round trips they save; the children of a step kept in registers and written behind
-// barrier 1 of the NEXT step (every wave is past its gathers by then: three barriers per timestep on one buffer, the
-// gathers' latency overlapped with the generator calls): SVM +5.5 % (32 spilled registers), GARCH +1 %, N = 4000 +2 %.
-//  PFG_OPT_STALESHIFT  (SVM prior kernel, 256 x 4 on one buffer, fp64: STALE in pf_reg_kernel) the shift s of
-//                  exp(lw - s) is the exact maximum of the PREVIOUS step instead of this step's: the max reduction
-//                  needs no barrier of its own (three s_barrier per timestep instead of four).  Any shift gives the
-//                  same normalised weights and the same s + log(W/N) up to rounding; it only has to keep exp in range.
-//                  Unlike the two tries above nothing is rescaled and nothing extra stays live: this step's wave maxima
-//                  ride to LDS before barrier 2 and are read behind it next to the scan totals.
-//                  Range guard, wave-uniform (every wave reads the same maxima): the hot path holds while
-//                  |m_t - s| <= 512 -- fp64 exp is normal down to -708 and particles within e^-100 of the maximum must
-//                  stay normal (m_t - s > -608); 1024 terms must not overflow (m_t - s < 702).  Otherwise (a gross
-//                  outlier, NaN, +-inf) a cold path recomputes the log-weights from the published states
-//                  (svm_logw: a function of the child's own state and y only), takes s = m_t and redoes exp, sums and
-//                  scan: today's arithmetic.  The shift of t = 0 is the exact maximum (prologue: init_logw may be
-//                  anything).
-//                  Hazards: the maxima of step t are written to red_maxf before barrier 2 of step t and read between
-//                  its barriers 2 and 3; those of step t + 1 are written behind barriers 3 and 4 of step t, when every
-//                  wave is done with that read.  The retry's own two barriers order its rewrite of red_scan / red_S
-//                  behind every wave's first read of them.  The state, red_scan and the CDF keep the barriers they have.
-//  PFG_OPT_GATHERADDR  (the same kernel) the search's final byte offset becomes the gather's byte address in eight
-//                  instructions per particle instead of ten: see GADDR.  (Six with the CDF's base folded into the
-//                  ds_read immediates of a search on relative offsets -- the compiler does not fold the base of the
-//                  dynamic LDS block, it adds it per probe: 36 more VALU per lane-timestep, not built.)
-//  Measured, bench config c2 (12288 chains, kernel ms, median of five interleaved runs per library, the parent's own
-//  max - min 0.13 ms; profiles/r05_ab_stale_shift.txt): both off 42.75, STALESHIFT alone 42.25, GATHERADDR alone 42.35,
-//  both 41.84 (-2.1 %).
-#ifndef PFG_OPT_STALESHIFT
-#define PFG_OPT_STALESHIFT 1
-#endif
-#ifndef PFG_OPT_GATHERADDR
-#define PFG_OPT_GATHERADDR 1
-#endif
-// TRACE (template parameter of pf_reg_kernel): the instantiation honours the trace_* / rec_* buffers of its
-// descriptors (save_all trajectories, recorded generator draws: tests, elementwise statistics).  TRACE = false is
-// the production twin of the plain device-generator kernels: the same code with every trace / record test compiled
-// out of the T-loop -- each was a scalar load of a descriptor field plus a wait on the critical path of every
-// timestep, and their address registers cost spills (measured: -5 % kernel time on BASELINE configs[1], -12 % on
-// config 3, -6 % on config 1, -2 % on config 4).  tests/test_gpu_device_replay.py replays the TRACE = true twin from its
-// recorded draws and asserts that the TRACE = false twin returns bitwise the same statistics for the same key.
-// A/B experiment switch (diagnostic builds only; default = production):
-//  PFG_EXP_PLAIN    compile the filter / lambda != 1 / no-statistic cases out (Poyiadjis O(N) score only)
-#ifndef PFG_EXP_PLAIN
-#define PFG_EXP_PLAIN 0
-#endif
-#define PFG_TR(p) (TRACE && (p))
-#ifdef PFG_FAST_ALGEBRA
-#ifndef PFG_OPT_LAZYLL
-#define PFG_OPT_LAZYLL 1
-#endif
-#ifndef PFG_OPT_RCPW
-#define PFG_OPT_RCPW 1
-#endif
-#ifndef PFG_OPT_SEL32
-#define PFG_OPT_SEL32 1
-#endif
-#ifndef PFG_OPT_PIVOTS
-#define PFG_OPT_PIVOTS 0
-#endif
-#else
-#undef PFG_OPT_LAZYLL
-#undef PFG_OPT_RCPW
-#define PFG_OPT_LAZYLL 0
-#define PFG_OPT_RCPW 0
-#undef PFG_OPT_SEL32
-#define PFG_OPT_SEL32 0
-#undef PFG_OPT_PIVOTS
-#define PFG_OPT_PIVOTS 0
-#endif
-// The device-generator SVM single-buffer workgroup needs 39.5 KB of LDS with the 32-bit CDF:
-// FOUR workgroups fit a CU if the kernel stays within 128 VGPRs (34 spilled registers; measured
-// +3.6 % workgroups per ms over occupancy 3).  -DPFG_OCC4=0 restores occupancy 3.
-#ifndef PFG_OCC4
-#define PFG_OCC4 1
-#endif
-// GARCH fp64 single buffer: six state arrays = 56.8 KB of LDS -> two workgroups per CU whatever
-// the registers; give the allocator the 256 VGPRs that occupancy leaves (168 -> 32 spills)
-__host__ __device__ constexpr bool occ_two(int MODEL, int NT, int PPT, size_t real, bool PP) {
-    return MODEL == PFG_MODEL_GARCH && real == 8 && NT == 256 && PPT == 4 && !PP;
-}
-__host__ __device__ constexpr bool occ_dev4(int MODEL, int NT, int PPT, int RNG, bool PP, int MODE) {
-    return PFG_OCC4 && MODEL == PFG_MODEL_SVM && NT == 256 && PPT == 4 && !PP && RNG == PFG_RNG_DEVICE && MODE == MODE_PLAIN;
+// 1 / x by v_rcp_f64 + two Newton steps instead of the IEEE division sequence
+__device__ __forceinline__ double rcp_newton2(double x) {
+    double r = __builtin_amdgcn_rcp(x);
+    r = fma(fma(-x, r, 1.0), r, r);
+    r = fma(fma(-x, r, 1.0), r, r);
+    return r;
 }
 
 template <int MODEL, int KERNEL, typename REAL, int NT, int PPT, int RNG, bool PP, int MODE = 0, bool TRACE = true, bool SCORE1 = false>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODEL, NT, PPT, sizeof(REAL), PP) ? 2 : occ_min(NT, PPT, sizeof(REAL), PP, occ_dev4(MODEL, NT, PPT, RNG, PP, MODE)), occ_two(MODEL, NT, PPT, sizeof(REAL), PP) ? 2 : occ_max(NT, PPT, sizeof(REAL), PP, occ_dev4(MODEL, NT, PPT, RNG, PP, MODE))))) void pf_reg_kernel(const pfg_dev_problem *__restrict__ probs) {
-    constexpr bool PARIS = (MODE == MODE_PARIS);
-    constexpr bool systematic = (MODE == MODE_SYSTEMATIC);
-    constexpr bool N2 = (MODE == MODE_N2);
-    static_assert(!(PARIS || N2) || PP, "PaRIS / O(N^2) need the parents intact while children are built: ping-pong buffers");
-    static_assert(!systematic || RNG == PFG_RNG_DEVICE, "systematic resampling draws its offset on the device");
-    constexpr int NS = ModelDims<MODEL>::NS;
-    constexpr int H = ModelDims<MODEL>::H;
-    constexpr int NW = NT / WAVE;
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MODEL, KERNEL, REAL, NT, PPT, RNG, PP, MODE>::OCC_MIN, RegTraits<MODEL, KERNEL, REAL, NT, PPT, RNG, PP, MODE>::OCC_MAX))) void pf_reg_kernel(const pfg_dev_problem *__restrict__ probs) {
+    using TR = RegTraits<MODEL, KERNEL, REAL, NT, PPT, RNG, PP, MODE>;
+    constexpr int NS = TR::NS, H = TR::H, NW = TR::NW;
+    static_assert(!TR::LWL || PP, "PaRIS / O(N^2) need the parents intact while children are built: ping-pong buffers");
+    static_assert(!TR::SYSTEMATIC || RNG == PFG_RNG_DEVICE, "systematic resampling draws its offset on the device");
     extern __shared__ __align__(16) unsigned char smem[];
 
     const pfg_dev_problem &P = probs[blockIdx.x];
     const int N = P.N, T = P.T, t1 = P.t1, tL = P.tL;
-    const int NL = fast_layout(NT, PP) ? NT * PPT : (N + WAVE - 1) / WAVE * WAVE;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
     // SCORE1 (PFG_SMOOTHER_POYIADJIS_N launches of the 1024 x 4 unit): the Poyiadjis O(N) score only -- the filter, the
@@ -231,7 +59,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
     }
     const bool is_filter = !ONLY_SCORE1 && (P.smoother == PFG_SMOOTHER_FILTER);
     const int stat = ONLY_SCORE1 ? (int)PFG_STAT_SCORE : P.stat;
-    const double lam_d = ONLY_SCORE1 ? 1.0 : is_filter ? 0.0 : ((P.smoother == PFG_SMOOTHER_PARIS || N2) ? 1.0 : P.lambduh);
+    const double lam_d = ONLY_SCORE1 ? 1.0 : is_filter ? 0.0 : ((P.smoother == PFG_SMOOTHER_PARIS || TR::N2) ? 1.0 : P.lambduh);
     const REAL lam = (REAL)lam_d, oml = (REAL)(1.0 - lam_d);
     const bool needS_every = is_filter || (lam_d != 1.0);
     const gptr<const double> yv = global_ptr(P.y);
@@ -239,101 +67,31 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
     const gptr<const double> uv = global_ptr(P.u);
     const gptr<const double> zv = global_ptr(P.z);
 
-    constexpr bool FAST = fast_layout(NT, PP);
-    constexpr bool TAB = FAST;
-    // Device RNG only: the CDF is built in THREAD-major order (position tid*PPT + k <-> particle
-    // k*NT + tid).  Multinomial resampling does not care how particles are labelled, and in this
-    // order a thread's PPT weights are contiguous: one in-register prefix + ONE wave scan per
-    // thread instead of PPT wave scans.  REPLAY keeps the reference's index order (parity).
-    constexpr bool BLK = FAST && RNG == PFG_RNG_DEVICE && MODE == MODE_PLAIN && (PPT & (PPT - 1)) == 0;
-    // SORTED (the 1024-thread device-generator variant, N <= 4096): the N resampling uniforms of a timestep are drawn
-    // as the ORDER STATISTICS of N i.i.d. uniforms -- exponential spacings e_r = -log u_r, U_(r) = sum_{q<=r} e_q /
-    // sum_{q<=N+1} e_q, by a second prefix scan that rides on the weight scan's barriers -- and child r takes U_(r)
-    // (multinomial resampling does not care which child gets which uniform; children are exchangeable).  CDF and
-    // ranks both run in thread-major order, so neighbouring lanes search neighbouring keys (coherent probes: LDS
-    // broadcasts instead of bank conflicts) and gather neighbouring parents.  One such workgroup fills a CU's LDS, so
-    // nothing else hides its LDS stalls: the knock-out with evenly spaced words was worth 15 % there (4 % on the
-    // 256-thread SVM kernel, where the second scan costs more than that).  -DPFG_OPT_SORTED1024=0 restores i.i.d. words.
-#ifndef PFG_OPT_SORTED1024
-#define PFG_OPT_SORTED1024 1
-#endif
-    constexpr bool SORTED = PFG_OPT_SORTED1024 && BLK && NT == 1024 && PPT == 4 && !systematic && NW > 1;
-    // PRIO: wave issue priority (s_setprio) by phase.  A timestep alternates between phases that are mostly LDS round
-    // trips (E search, F gather) and phases that are mostly VALU work (A-D, G, H); the arbiter of a SIMD otherwise picks
-    // by age.  256 x 4, four workgroups per CU in different phases: the VALU phases at priority 2 and E, F at 0 -- a wave
-    // that is about to wait for the LDS anyway gives way -- 45.6 -> 44.8 ms per bench launch (-1.9 %; the same with 3
-    // instead of 2; nothing if only G, H are raised).  1024 x 4, ONE workgroup per CU whose 16 waves are in the same
-    // phase: the other way round (E, F at 2: the waves that reach the search first get their probes out) 11.26 ->
-    // 11.03 ms (-2.0 %), and +0.4 % with the 256 x 4 setting.  512 x 2 (GARCH) and the one-wave kernels: 0 ... +4 % with
-    // either, so none (profiles/r03_ab_wave_priority.txt).  The REPLAY instantiation of 256 x 4 (768 windows, three per CU):
-    // 5.85 -> 5.26 ms with the 256 x 4 setting (5.52 with the opposite one).  -DPFG_OPT_PRIO=0 builds without.
-#ifndef PFG_OPT_PRIO
-#define PFG_OPT_PRIO 1
-#endif
-    constexpr int PRIO = !(PFG_OPT_PRIO && (BLK || (RNG == PFG_RNG_REPLAY && MODE == MODE_PLAIN)) && !PP && PPT == 4) ? 0 : (NT == 1024 ? 1 : (NT == 256 ? 2 : 0));
-    constexpr int LOG_PPT = PPT == 1 ? 0 : (PPT == 2 ? 1 : (PPT == 4 ? 2 : (PPT == 8 ? 3 : 4)));
-    static_assert(PPT <= 16, "LOG_PPT covers 1, 2, 4, 8, 16 particles per thread");
-    // PP: the cdf is stored at physical index i + (i >> 5) (one pad slot per 32 entries): the
-    // binary search probes at power-of-two strides, which would otherwise all hit one LDS bank
-    // (measured: 720 conflict cycles per wave-timestep, i.e. all of SQ_LDS_BANK_CONFLICT).
-    const int NC = FAST ? NT * PPT + NT * PPT / 32 : NL;
-    double *cdf = reinterpret_cast<double *>(smem);
-    // BLK: the uniforms carry 32 random bits, so the CDF is kept as 32-bit fixed point
-    // (floor(cdf * 2^32)) and searched with the raw generator word: integer compares, half the
-    // LDS bytes per probe, no u32 -> f64 conversion of the uniform.
-    uint32_t *cdfu = reinterpret_cast<uint32_t *>(smem);
-    REAL *buf0 = reinterpret_cast<REAL *>(smem + ((size_t)NC * (BLK ? 4 : 8) + 15) / 16 * 16);
-    // stride of the state arrays: NL + one 8-byte pad (FAST layouts) -- see state_pad()
-    const int NLS = NL + (FAST ? state_pad<REAL, RNG>() : 0);
-    const size_t bufsz = (size_t)(NS + H) * NLS;
-    REAL *cur = buf0, *nxt = PP ? buf0 + bufsz : buf0;
-    // PAIRED (round 4; the device-generator production kernels in fp64 with an even record length: SVM, GARCH): the state
-    // is stored as (NS + H) / 2 arrays of 16-byte PAIRS {component 2p, component 2p + 1} instead of NS + H arrays of
-    // doubles.  The parent gathers -- 16 random ds_read_b64 per lane-timestep of the SVM kernel, 56 % of its LDS
-    // bank-conflict cycles (profiles/r04_lds_conflict_split.txt) -- become 8 ds_read_b128, which use the full width of
-    // the LDS; the children's stores stay lane-contiguous (ds_write_b128).  -DPFG_OPT_PAIRSTATE=0 restores the arrays.
-#ifndef PFG_OPT_PAIRSTATE
-#define PFG_OPT_PAIRSTATE 1
-#endif
-    constexpr bool PAIRED = PFG_OPT_PAIRSTATE && BLK && sizeof(REAL) == 8 && ((NS + H) % 2 == 0);
-    // STALE: the previous step's maximum as this step's shift, see PFG_OPT_STALESHIFT
-    constexpr bool STALE = PFG_OPT_STALESHIFT && BLK && MODEL == PFG_MODEL_SVM && KERNEL == PFG_KERNEL_PRIOR && NT == 256 && PPT == 4 &&
-                           !PP && sizeof(REAL) == 8;
-    // GADDR (256 x 4): search offset -> gather byte address.  rel = 4 x physical CDF position (one pad slot per 32
-    // entries), p4 = rel - 4 (rel * 993 >> 17) = 4 x CDF position p (exact: rel * 993 < 2^23), and
-    // (p4 * 1025) & 0x3ff0 = 16 x the particle index ((p & 3) << 8) | (p >> 2): p4 < 2^12, so the copies p4 << 10 and p4
-    // do not overlap -- bits 4..11 of p4 are p >> 2 and bits 12, 13 of p4 << 10 are p & 3.  Clamped to 16 x last it is
-    // the byte offset of the parent's first 16-byte pair.  Ancestors are those of the general form, bit for bit
-    // (tests/test_gather_address_host.py).
-#ifdef PFG_EXP_OWNGATHER
-    constexpr bool GADDR = false;
-#else
-    // (the arithmetic holds for every BLK && PAIRED 256 x 4 kernel; it is switched on where it was timed: the SVM kernel
-    // on one buffer, bench config c2, and its TRACE twin)
-    constexpr bool GADDR = PFG_OPT_GATHERADDR && BLK && PAIRED && NT == 256 && PPT == 4 && MODEL == PFG_MODEL_SVM && !PP;
-#endif
-    static_assert(!GADDR || 4 * (NT * PPT + NT * PPT / 32) * 993 < (1 << 23), "GADDR: rel * 993 must fit the 24-bit multiply");
+    // every pointer into the LDS block comes from the one layout the host sized it with (RegTraits::layout)
+    const int NLS = TR::FAST ? TR::layout(0).NLS : TR::layout(N).NLS;
+    double *cdf = reg_lds_ptr<double, TR, &RegLdsLayout::cdf>(smem, N);
+    uint32_t *cdfu = reg_lds_ptr<uint32_t, TR, &RegLdsLayout::cdf>(smem, N);         // BLK: 32-bit fixed point
+    REAL *cur = reg_lds_ptr<REAL, TR, &RegLdsLayout::buf0>(smem, N), *nxt = reg_lds_ptr<REAL, TR, &RegLdsLayout::buf1>(smem, N);
     // element index of component d of particle i
-    auto sidx = [&](int d, int i) -> size_t {
-        return PAIRED ? (size_t)(d >> 1) * (2 * (size_t)NLS) + 2 * (size_t)i + (size_t)(d & 1) : (size_t)d * NLS + (size_t)i;
-    };
-    double *red = reinterpret_cast<double *>(buf0 + (PP ? 2 : 1) * bufsz);
-    double *red_scan = red;                 // [PPT*NW]
-    double *red_max = red + PPT * NW;       // [NW]
+    auto sidx = [&](int d, int i) -> size_t { return TR::sidx(NLS, d, i); };
+    double *red_scan = reg_lds_ptr<double, TR, &RegLdsLayout::red_scan>(smem, N);
+    double *red_max = reg_lds_ptr<double, TR, &RegLdsLayout::red_max>(smem, N);
     float *red_maxf = reinterpret_cast<float *>(red_max);
-    double *red_S = red_max + NW;           // [H*NW]
-    double *red_W0 = red_S + PFG_MAX_STAT * NW;      // [8] spare doubles (systematic-resampling offset)
+    double *red_S = reg_lds_ptr<double, TR, &RegLdsLayout::red_S>(smem, N);
+    double *red_W0 = reg_lds_ptr<double, TR, &RegLdsLayout::red_W0>(smem, N);
     const double invN = 1.0 / (double)N;
-    double *tabmem = red + RegLayout<NT, PPT>::RED;
-    REAL *lwL = reinterpret_cast<REAL *>(tabmem + tab_bytes<REAL, RNG, TAB>() / 8);    // [NL], PARIS only
-    int *paris_queue = reinterpret_cast<int *>(tabmem + tab_bytes<REAL, RNG, TAB>() / 8 + NL);   // [NL], PARIS only
+    double *tabmem = reg_lds_ptr<double, TR, &RegLdsLayout::tab>(smem, N);
+    REAL *lwL = reg_lds_ptr<REAL, TR, &RegLdsLayout::lwL>(smem, N);                   // PaRIS / O(N^2) only, like the next four
+    int *paris_queue = reg_lds_ptr<int, TR, &RegLdsLayout::queue>(smem, N);
+    int *paris_wq0 = reg_lds_ptr<int, TR, &RegLdsLayout::wq0>(smem, N), *paris_wq1 = reg_lds_ptr<int, TR, &RegLdsLayout::wq1>(smem, N);
+    int *paris_Jres = reg_lds_ptr<int, TR, &RegLdsLayout::Jres>(smem, N);
 
-    Math<REAL, TAB> mth;
+    Math<REAL, TR::TAB> mth;
     mth.t.e2 = tabmem;
     mth.t.lg = reinterpret_cast<const double2 *>(tabmem + TAB_E2);
     mth.t.sc = reinterpret_cast<const double2 *>(tabmem + TAB_E2 + 2 * TAB_LG);
-    if (tab_bytes<REAL, RNG, TAB>() > 0) tab_fill(tabmem, RNG == PFG_RNG_DEVICE, tid, NT);
-    if (FAST && !BLK) {
+    if (tab_bytes<REAL, RNG, TR::TAB>() > 0) tab_fill(tabmem, RNG == PFG_RNG_DEVICE, tid, NT);
+    if (TR::FAST && !TR::BLK) {
 #pragma unroll
         for (int k = 0; k < PPT; ++k)
             if (k * NT + tid >= N) cdf[cdf_phys(k * NT + tid)] = 2.0;      // sentinel: never <= u
@@ -384,8 +142,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
     // variate of a pair cached for the next call): accept / reject is exact fp64 arithmetic (no contraction in the REPLAY
     // units), so the CONSUMPTION is the reference's to the double; the values go through this device's log (<= 1 ulp from
     // the host libm's), within the REPLAY tolerance.
-    constexpr bool RAWCAP = MODE == MODE_PARIS && RNG == PFG_RNG_REPLAY;
-    const bool raw = RAWCAP && (P.flags & PFG_FLAG_PARIS_RAW_STREAM) != 0 && P.paris_stream != nullptr;
+    const bool raw = TR::RAWCAP && (P.flags & PFG_FLAG_PARIS_RAW_STREAM) != 0 && P.paris_stream != nullptr;
     bool carry_has = false;                // a cached second variate is pending (workgroup-uniform); its value sits in red_W0[1]
     double *const zbuf = reinterpret_cast<double *>(paris_queue);          // [N] normals of the current call (queue scratch is free then)
     long long *const raw_slots = reinterpret_cast<long long *>(red_W0 + 2);  // [0] cut-off attempt of a call, [1] stream position of the cached pair
@@ -447,7 +204,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         if (need > 0 && !paris_overflow) paris_cursor = base + 2 * (raw_slots[0] + 1);
         carry_has = ((N - produced0) & 1) != 0;
     };
-    if (RAWCAP && raw && (P.flags & PFG_FLAG_PARIS_RAW_CARRY)) {          // the generator came with a cached Gaussian: stream[0]
+    if (TR::RAWCAP && raw && (P.flags & PFG_FLAG_PARIS_RAW_CARRY)) {          // the generator came with a cached Gaussian: stream[0]
         carry_has = true;
         if (tid == 0) red_W0[1] = P.paris_stream[0];
         paris_cursor = 1;
@@ -460,7 +217,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         const double sd = sqrt(pv);
         REAL z0[PPT];
         if (RNG == PFG_RNG_DEVICE) draw_normals(z0);
-        if constexpr (RAWCAP) { if (raw && !P.init_x) legacy_normals(); }
+        if constexpr (TR::RAWCAP) { if (raw && !P.init_x) legacy_normals(); }
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const int i = k * NT + tid;
@@ -480,7 +237,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                         for (int h = 0; h < H; ++h) s[h] = (REAL)P.init_stats[(size_t)i * H + h];
                     }
                 } else {
-                    const double z = (RNG == PFG_RNG_REPLAY) ? ((RAWCAP && raw) ? zbuf[i] : P.z0[i]) : (double)z0[k];
+                    const double z = (RNG == PFG_RNG_REPLAY) ? ((TR::RAWCAP && raw) ? zbuf[i] : P.z0[i]) : (double)z0[k];
                     x[0] = (REAL)(P.prior_mean + sd * z);
                     if (RNG == PFG_RNG_DEVICE && PFG_TR(P.trace_x) && P.rec_z0) P.rec_z0[i] = z;
                 }
@@ -502,7 +259,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
     }
 
     double ll = 0.0, wt_prev = 1.0, tie = 1.0;
-    constexpr bool LAZYLL = PFG_OPT_LAZYLL && TAB && sizeof(REAL) == 8;
     double ll_W = 1.0, ll_w = 0.0;          // LAZYLL: lane t % 64 of wave 0 holds step t's (W, w, m)
     float ll_m = 0.0f;
     double filt[H], S[H];
@@ -521,7 +277,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
     }
     const int last = N - 1;
     [[maybe_unused]] float m_next = 0.0f;
-    if constexpr (STALE) {
+    if constexpr (TR::STALE) {
         // the shift of t = 0 is the exact maximum; the second barrier keeps the loop's first write of red_maxf behind
         // every wave's read
         float ml = (float)lw[0];
@@ -540,7 +296,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
     for (int t = 0; t <= T; ++t) {
         [[maybe_unused]] double uu_raw[PPT];
         [[maybe_unused]] REAL zz_raw[PPT];
-        if constexpr (RAWCAP) {
+        if constexpr (TR::RAWCAP) {
             if (raw && t < T) {
                 // np.random's order within a timestep: N uniforms (np.random.choice), N normals (Kernel.rv), then the
                 // backward sampling's draws (at the end of this iteration)
@@ -561,9 +317,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         ml = wave_max(ml);
         if (NW > 1 && lane == 0) red_maxf[wave] = ml;
         PFG_PH(0)
-        if constexpr (!STALE) block_sync<NW>();                                 // barrier 1
+        if constexpr (!TR::STALE) block_sync<NW>();                                 // barrier 1
         PFG_PH(1)
-        if constexpr (!STALE) {
+        if constexpr (!TR::STALE) {
             float mm = NW > 1 ? red_maxf[0] : ml;     // one wave: its maximum IS the block maximum, no LDS round trip
 #pragma unroll
             for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
@@ -590,7 +346,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                                         // sums < 2^9 in f32: good to 1e-5 of a spacing, half the registers across barrier 2 and a
                                         // 6-instruction wave scan; the cross-wave offsets and the normalisation are f64)
         uint32_t us[PPT];               // SORTED: the sorted uniforms as 32-bit fixed point
-        if (BLK) {
+        if (TR::BLK) {
 #pragma unroll
             for (int k = 1; k < PPT; ++k) cs[k] += cs[k - 1];
             const double inc = wave_incl_scan(cs[PPT - 1]);
@@ -599,7 +355,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             for (int k = 0; k < PPT; ++k) cs[k] += exc;
             if (NW > 1 && lane == WAVE - 1) red_scan[wave] = inc;
             wave_inc = inc;
-            if (SORTED && t < T) {
+            if (TR::SORTED && t < T) {
                 // exponential spacings of this thread's (valid) children, thread-local prefix + one wave scan; the
                 // (N+1)-th spacing rides in the last wave's total
 #pragma unroll
@@ -624,7 +380,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                 if (lane == WAVE - 1) red_scan[k * NW + wave] = cs[k];
             }
         }
-        if (RNG != PFG_RNG_REPLAY && systematic && tid == 0) red_W0[0] = u01_32(rng.next());
+        if (RNG != PFG_RNG_REPLAY && TR::SYSTEMATIC && tid == 0) red_W0[0] = u01_32(rng.next());
         // this step's randomness: REPLAY loads are issued here so that their latency overlaps the
         // barrier; device draws happen right before their use (keeps register pressure down).  (Loading a timestep
         // ahead was measured, round 3: a lone window 2.90 -> 2.85 ms, 768 windows 6.85 -> 7.60 ms -- the registers
@@ -632,7 +388,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         double uu[PPT];
         REAL zz[PPT];
         if (t < T && RNG == PFG_RNG_REPLAY) {
-            if (RAWCAP && raw) {
+            if (TR::RAWCAP && raw) {
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) { uu[k] = uu_raw[k]; zz[k] = zz_raw[k]; }
             } else {
@@ -646,11 +402,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         PFG_PH(2)
         block_sync<NW>();                                                       // barrier 2
         PFG_PH(3)
-        if (BLK && NW == 1) {
+        if (TR::BLK && NW == 1) {
             // one wave: no other totals to add, W is the scan's last lane
             W = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wave_inc), WAVE - 1),
                                  __builtin_amdgcn_readlane(__double2loint(wave_inc), WAVE - 1));
-        } else if (BLK) {
+        } else if (TR::BLK) {
             // NW wave totals: exclusive prefix by a DPP scan over the first lanes
             const double tot = (lane < NW) ? red_scan[lane] : 0.0;
             double inc = tot;
@@ -664,7 +420,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             for (int k = 0; k < PPT; ++k) cs[k] += off;
             W = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(inc), NW - 1),
                                  __builtin_amdgcn_readlane(__double2loint(inc), NW - 1));
-            if constexpr (STALE) {
+            if constexpr (TR::STALE) {
                 // this step's exact maximum: the next step's shift, and the range guard of this one (NaN, +-inf fail it)
                 float mm = red_maxf[0];
 #pragma unroll
@@ -712,7 +468,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                                          __builtin_amdgcn_readlane(__double2loint(incw), NW - 1));
                 }
             }
-            if (SORTED && t < T) {
+            if (TR::SORTED && t < T) {
                 const double totE = (lane < NW) ? red_scan[NW + lane] : 0.0;
                 double incE = totE;
                 incE += dpp_shr0_f64<0x111>(incE);
@@ -724,10 +480,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                                                      __builtin_amdgcn_readlane(__double2loint(excE), wave));
                 const double Etot = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(incE), NW - 1),
                                                      __builtin_amdgcn_readlane(__double2loint(incE), NW - 1));
-                double r = __builtin_amdgcn_rcp(Etot);
-                r = fma(fma(-Etot, r, 1.0), r, r);
-                r = fma(fma(-Etot, r, 1.0), r, r);
-                const double fe = uniform_f64(r * 4294967296.0);
+                const double fe = uniform_f64(rcp_newton2(Etot) * 4294967296.0);
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) us[k] = cvt_u32_sat(((double)es[k] + offE) * fe);
             }
@@ -763,15 +516,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             }
             W = uniform_f64(run);
         }
-        double invW;
-        if (PFG_OPT_RCPW) {
-            double r = __builtin_amdgcn_rcp(W);
-            r = fma(fma(-W, r, 1.0), r, r);
-            r = fma(fma(-W, r, 1.0), r, r);
-            invW = uniform_f64(r);
-        } else {
-            invW = uniform_f64(1.0 / W);
-        }
+        const double invW = uniform_f64(PFG_OPT_RCPW ? rcp_newton2(W) : 1.0 / W);
         if (needS) {
             PFG_MARK("cold needS")
 #pragma unroll
@@ -787,7 +532,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         if (wave == 0) {
             PFG_MARK("w0.25 wave0-loglik")
             const bool counts = t > 0 && (t - 1) >= t1 && (t - 1) < tL;
-            if (LAZYLL) {
+            if (TR::LAZYLL) {
                 const bool mine = lane == (t & (WAVE - 1));
                 ll_W = mine ? W : ll_W;
                 ll_w = mine ? (counts ? wt_prev : 0.0) : ll_w;
@@ -809,7 +554,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             for (int h = 0; h < H; ++h) filt[h] = uniform_f64(filt[h] + S[h]);
         }
         if (t == T) break;
-        if constexpr (STALE) m = uniform_f64((double)m_next);      // the log-likelihood above used the shift W was formed with
+        if constexpr (TR::STALE) m = uniform_f64((double)m_next);      // the log-likelihood above used the shift W was formed with
 
         // ---- (D) normalised CDF to LDS (RandomState.choice: cumsum, /= last) -------------
         const double y_t = yv[t];
@@ -817,7 +562,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         const double wt = (inside && wv) ? wv[t - t1] : 1.0;
         const bool use_stat = inside && (stat != PFG_STAT_NONE);
         const bool plain = !needS_every;                 // not filter and lambda == 1
-        if (BLK) {
+        if (TR::BLK) {
             // all PPT positions: slots beyond N carry weight 0 (flat CDF, never selected)
             {
                 const double fixs = invW * 4294967296.0;
@@ -829,25 +574,25 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
 #pragma unroll
             for (int k = 0; k < PPT; ++k)
                 if (valid[k]) {
-                    cdf[FAST ? cdf_phys(k * NT + tid) : k * NT + tid] = cs[k] * invW;
-                    if (PARIS || N2) lwL[k * NT + tid] = lw[k];
+                    cdf[TR::FAST ? cdf_phys(k * NT + tid) : k * NT + tid] = cs[k] * invW;
+                    if (TR::PARIS || TR::N2) lwL[k * NT + tid] = lw[k];
                 }
         }
         PFG_PH(4)
         block_sync<NW>();                                                       // barrier 3
         PFG_PH(5)
-        if (PRIO == 1) __builtin_amdgcn_s_setprio(2);                           // the LDS-heavy phases E, F: see PRIO
-        if (PRIO == 2) __builtin_amdgcn_s_setprio(0);
+        if (TR::PRIO == 1) __builtin_amdgcn_s_setprio(2);                           // the LDS-heavy phases E, F: see PRIO
+        if (TR::PRIO == 2) __builtin_amdgcn_s_setprio(0);
 
         // ---- (E) ancestors: smallest j with cdf[j] > u (searchsorted 'right').  Branch-free:
         // probes past the end read cdf[N-1] (= 1 > u), the final clamp covers rounding.
         if (RNG != PFG_RNG_REPLAY) {
-            if (systematic) {
+            if (TR::SYSTEMATIC) {
                 // extension: one uniform per timestep (drawn by thread 0 before barrier 2)
                 const double u0 = red_W0[0];
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) uu[k] = ((double)(k * NT + tid) + u0) * invN;
-            } else if (!BLK) {
+            } else if (!TR::BLK) {
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) uu[k] = u01_32(rng.next());
             }
@@ -856,10 +601,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
         [[maybe_unused]] uint32_t gaddr[PPT];       // GADDR: byte offset of the parent's record in a state array
 #pragma unroll
         for (int k = 0; k < PPT; ++k) { anc[k] = 0; gaddr[k] = 0u; }
-        if (BLK) {
+        if (TR::BLK) {
             uint32_t ua[PPT];
 #pragma unroll
-            for (int k = 0; k < PPT; ++k) ua[k] = SORTED ? us[k] : rng.next();
+            for (int k = 0; k < PPT; ++k) ua[k] = TR::SORTED ? us[k] : rng.next();
 #ifdef PFG_EXP_EVENWORDS
             // knock-out (timing only, NOT a valid resampler): evenly spaced words in CDF order -- what sorted uniforms
             // would do to the LDS bank conflicts of the search and the gathers, without their cost
@@ -878,12 +623,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             uint32_t off[PPT];
 #pragma unroll
             for (int k = 0; k < PPT; ++k) off[k] = cdf_base;
-            // PIVOTS (A/B, -DPFG_OPT_PIVOTS=1; 1024 slots): the three entries the first two levels of every search
-            // compare with (positions 511, 255, 767) are read ONCE per wave and timestep (broadcast reads) and held in
-            // scalar registers: two dependent LDS round trips and eight ds_read per lane-timestep less
-            constexpr bool PIVOTS = PFG_OPT_PIVOTS && NT * PPT == 1024;
-            constexpr int FIRST_STEP = PIVOTS ? 128 : (NT * PPT) >> 1;
-            if constexpr (PIVOTS) {
+            constexpr int FIRST_STEP = TR::PIVOTS ? 128 : (NT * PPT) >> 1;
+            if constexpr (TR::PIVOTS) {
                 const uint32_t p511 = __builtin_amdgcn_readfirstlane(cdfu[cdf_phys(511)]);
                 const uint32_t p255 = __builtin_amdgcn_readfirstlane(cdfu[cdf_phys(255)]);
                 const uint32_t p767 = __builtin_amdgcn_readfirstlane(cdfu[cdf_phys(767)]);
@@ -922,7 +663,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                 for (int k = 0; k < PPT; ++k) off[k] += (cv[k] <= ua[k]) ? 4u * adv : 0u;
                 }
             }
-            if constexpr (GADDR) {
+            if constexpr (TR::GADDR) {
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) {
                     const uint32_t rel = off[k] - cdf_base;
@@ -939,9 +680,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             for (int k = 0; k < PPT; ++k) {
                 uint32_t p = (off[k] - cdf_base) >> 2;
                 p -= __umul24(p, 993u) >> 15;                                   // physical -> CDF position (p < 2^15)
-                anc[k] = (int)(((p << (NT == 256 ? 8 : (NT == 512 ? 9 : (NT == 1024 ? 10 : 6)))) & (uint32_t)((PPT - 1) * NT)) | (p >> LOG_PPT));   // -> particle index
+                anc[k] = (int)(((p << (NT == 256 ? 8 : (NT == 512 ? 9 : (NT == 1024 ? 10 : 6)))) & (uint32_t)((PPT - 1) * NT)) | (p >> TR::LOG_PPT));   // -> particle index
             }
-        } else if (FAST) {
+        } else if (TR::FAST) {
             // sentinel-padded cdf, physical positions: log2(NT*PPT) fixed probes whose offsets
             // fold into the ds_read immediates; logical index recovered once at the end
             // on byte offsets, like the 32-bit search above (the LDS address is the search variable)
@@ -988,8 +729,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             // near-tie margin: how close u came to flipping an ancestor index
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
-                const double hi = cdf[FAST ? cdf_phys(anc[k]) : anc[k]] - uu[k];
-                const double lo = anc[k] > 0 ? uu[k] - cdf[FAST ? cdf_phys(anc[k] - 1) : anc[k] - 1] : 1.0;
+                const double hi = cdf[TR::FAST ? cdf_phys(anc[k]) : anc[k]] - uu[k];
+                const double lo = anc[k] > 0 ? uu[k] - cdf[TR::FAST ? cdf_phys(anc[k] - 1) : anc[k] - 1] : 1.0;
                 const double mg = hi < lo ? hi : lo;
                 tie = (valid[k] && mg < tie) ? mg : tie;
             }
@@ -1002,13 +743,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             REAL xp[PPT][NS], sp[PPT][H];
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
-                if constexpr (PAIRED) {
+                if constexpr (TR::PAIRED) {
                     typedef double dv2 __attribute__((ext_vector_type(2)));
                     REAL rec[NS + H];
 #pragma unroll
                     for (int p = 0; p < (NS + H) / 2; ++p) {
                         dv2 v;
-                        if constexpr (GADDR) {
+                        if constexpr (TR::GADDR) {
                             using lds_byte = const __attribute__((address_space(3))) unsigned char;
                             v = *(const __attribute__((address_space(3))) dv2 *)((lds_byte *)cur + gaddr[k] + (uint32_t)(p * 16 * NLS));
                         } else {
@@ -1028,8 +769,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                 }
             }
             PFG_PH(7)
-            if (PRIO == 1) __builtin_amdgcn_s_setprio(0);
-            if (PRIO == 2) __builtin_amdgcn_s_setprio(2);
+            if (TR::PRIO == 1) __builtin_amdgcn_s_setprio(0);
+            if (TR::PRIO == 2) __builtin_amdgcn_s_setprio(2);
             if (!PP) block_sync<NW>();                                          // barrier 4 (single buffer)
             PFG_PH(8)
             if (RNG != PFG_RNG_REPLAY) {
@@ -1067,9 +808,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                     }
                     // (1024 threads: the guarded store keeps the particles in separate blocks -- 19 instead of 27
                     // spilled registers at the 128-VGPR cap, 13.1 instead of 14.5 ms per config-4 launch)
-                    if ((FAST && NT < 1024) || valid[k]) {
+                    if ((TR::FAST && NT < 1024) || valid[k]) {
                         const int i = k * NT + tid;
-                        if constexpr (PAIRED) {
+                        if constexpr (TR::PAIRED) {
                             typedef double dv2 __attribute__((ext_vector_type(2)));
                             REAL rec[NS + H];
 #pragma unroll
@@ -1126,9 +867,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             }
             // wave-local work queues of pending children (this wave's NT*PPT/NW slots of two [NL]
             // arrays) and the accepted parent of every child of the current backward draw
-            int *const wq0 = paris_queue + NL + wave * (PPT * WAVE);
-            int *const wq1 = paris_queue + 2 * NL + wave * (PPT * WAVE);
-            int *const Jres = paris_queue + 3 * NL;
+            int *const wq0 = paris_wq0 + wave * (PPT * WAVE);
+            int *const wq1 = paris_wq1 + wave * (PPT * WAVE);
+            int *const Jres = paris_Jres;
             const unsigned long long ltmask = (1ull << lane) - 1ull;
             const bool ordered = RNG == PFG_RNG_REPLAY && P.paris_stream != nullptr;
             for (int j = 0; j < Nt; ++j) {
@@ -1228,7 +969,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
                     const long long cap = P.paris_stream_len;
                     const bool noar = (P.flags & PFG_FLAG_PARIS_NO_ACCEPT_REJECT) != 0;
                     const int mthr = P.paris_manual_threshold;
-                    int *const wcnt = paris_queue + NL;                 // [PPT][NW] pending children per (slot, wave)
+                    int *const wcnt = paris_wq0;                       // [PPT][NW] pending children per (slot, wave)
                     bool pend[PPT];
 #pragma unroll
                     for (int k = 0; k < PPT; ++k) pend[k] = valid[k];
@@ -1518,12 +1259,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
             }
         };
         bool did_paris = false;
-        if constexpr (N2) {
+        if constexpr (TR::N2) {
             if (stat == PFG_STAT_SCORE) n2_slots(std::integral_constant<int, PFG_STAT_SCORE>{});
             else n2_slots(std::integral_constant<int, PFG_STAT_SUFF>{});
             did_paris = true;
         }
-        if constexpr (MODE == MODE_PARIS) {
+        if constexpr (TR::PARIS) {
             if (P.smoother == PFG_SMOOTHER_PARIS) {
                 if (stat == PFG_STAT_SCORE) paris_slots(std::integral_constant<int, PFG_STAT_SCORE>{});
                 else paris_slots(std::integral_constant<int, PFG_STAT_SUFF>{});
@@ -1576,10 +1317,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(occ_two(MODE
 #pragma unroll
         for (int w = 1; w < NW; ++w) tie = red_max[w] < tie ? red_max[w] : tie;
     }
-    if (PARIS && tid == 0 && P.paris_consumed) {
+    if (TR::PARIS && tid == 0 && P.paris_consumed) {
         P.paris_consumed[0] = paris_overflow ? -1ll : paris_cursor;
         // RAW: a cached Gaussian is pending -> how far back from the end of the consumption its pair of doubles starts
-        P.paris_consumed[1] = (RAWCAP && raw && carry_has && !paris_overflow) ? paris_cursor - raw_slots[1] : 0ll;
+        P.paris_consumed[1] = (TR::RAWCAP && raw && carry_has && !paris_overflow) ? paris_cursor - raw_slots[1] : 0ll;
     }
     if (tid == 0 && P.out) {
 #pragma unroll
