@@ -138,6 +138,27 @@ DEV_PROBLEM_DTYPE = np.dtype([
     ("stamps", "u8"),
 ], align=True)
 
+
+def device_descriptors(n, *, theta, row, out, step_ctr, scratch, scratch_bytes, stream, prior_mean, prior_var, lambduh, seed,
+                       N, smoother, stat="score", flags=0, Ntilde=0, max_accept_reject=0):
+    """The static fields of n pfg_dev_problem records (the windows -- y, T, t1, tL, weights -- are the caller's):
+    descriptor i reads row `row[i]` of the tensor theta [*, MAX_THETA], writes record i of out [n, OUT_DOUBLES], owns bytes
+    [i * scratch_bytes, (i + 1) * scratch_bytes) of `scratch` (None: no scratch) and draws from the stream id `stream[i]`."""
+    d = np.zeros(n, dtype=DEV_PROBLEM_DTYPE)
+    idx = np.arange(n, dtype=np.uint64)
+    d["theta"] = theta.data_ptr() + np.asarray(row, dtype=np.uint64) * np.uint64(8 * MAX_THETA)
+    d["out"] = out.data_ptr() + idx * np.uint64(8 * OUT_DOUBLES)
+    if scratch is not None:
+        d["scratch"] = scratch.data_ptr() + idx * np.uint64(scratch_bytes)
+    d["step_ctr"] = step_ctr.data_ptr()
+    d["prior_mean"], d["prior_var"], d["lambduh"] = prior_mean, prior_var, lambduh
+    d["seed"] = np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+    d["stream"] = stream
+    d["N"], d["smoother"], d["stat"], d["flags"] = N, SMOOTHER[smoother], STAT[stat], int(flags)
+    d["Ntilde"], d["max_accept_reject"] = Ntilde, max_accept_reject
+    return d
+
+
 EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_last_error", "pfg_run", "pfg_run_batch",
            "pfg_ctx_stream", "pfg_launch_device", "pfg_launch_device_smoother", "pfg_scratch_bytes", "pfg_variant_name", "pfg_synchronize",
            "pfg_sgld_update_device", "pfg_sghmc_update_device", "pfg_imq_ksd", "pfg_sample_windows_device",

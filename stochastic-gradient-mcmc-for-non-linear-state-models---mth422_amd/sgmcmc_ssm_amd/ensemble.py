@@ -18,6 +18,7 @@ the device Philox generator, so trajectories are statistically, not bitwise, equ
 the reference (bitwise parity is what the REPLAY mode of the Sampler classes is for).
 """
 import ctypes
+import types
 
 import numpy as np
 import torch
@@ -107,6 +108,23 @@ class ChainEnsemble(object):
                sequence lists too, and it runs pf='paris' up to N = 16384 (paris_mem1024 above N = 1024).  Leaving
                both out keeps the single-window launches described above.  Refused: sampler='gibbs' or kind != 'pf'
                with W > 1, window_sampling='host' when windows are drawn, N > 16384.
+
+    How it is put together (each decision is made in one place):
+      _resolve_settings: the arguments above -> kind, pf, N, lambduh, the descriptor smoother `_smoother` and the launch
+               smoother `_launch_smoother`, the stat, the PaRIS fields, M / K / W, the path (`_multi`: W descriptors per
+               chain, records in win_out_dev, a reduction before the update), S, B, `strict`, the sequence bounds, and
+               every refusal that needs no device.  Nothing is allocated before it returns.
+      _capi.device_descriptors: the static fields of the `_nd` = C (single-window) or C * W (multi-window, chain-major)
+               records of `_desc`; stream ids chain_offset + c, or (chain_offset + c) * W + w.
+      _weights_blocks: weights_dev, one row per window start of every sequence longer than S, with the offsets of the
+               sequences' blocks (_seg_weight_offsets; woffs_dev on the multi-window path); _weights_table is the 2-D
+               view of a single series' block.
+      _set_windows: the host draw of (sequence, start) per chain and the one derivation of
+               y, T, t1, tL, weights from it -- a single series is a list of one sequence; a full single series has a
+               null weights pointer, a whole short sequence of a list points at its row of T_total / T_k.
+      _scratch_bytes: the scratch per descriptor of the resolved smoother.
+      launch_windows / launch_pf / launch_reduce / launch_update: the launches of a step on one stream (_stream);
+               _enqueue_step orders them, step / run / _graph drive them.
     """
 
     def __init__(self, model, observations, parameters, num_chains=None, N=1000, pf="poyiadjis_N",
@@ -115,9 +133,110 @@ class ChainEnsemble(object):
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
                  Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None):
+        s = self._resolve_settings(
+            model, observations, parameters, num_chains=num_chains, N=N, pf=pf, lambduh=lambduh,
+            subsequence_length=subsequence_length, buffer_length=buffer_length, dtype=dtype, partition_style=partition_style,
+            resampling=resampling, sampler=sampler, window_sampling=window_sampling, kind=kind, num_samples=num_samples,
+            Ntilde=Ntilde, max_accept_reject=max_accept_reject, accept_reject=accept_reject, minibatch_size=minibatch_size,
+            num_sequences=num_sequences)
+        if not torch.cuda.is_available():
+            raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
+        Parameters, Prior, Helper = _model_info(model)
+        self.model, self.dtype, self.epsilon, self._Parameters = model, dtype, float(epsilon), Parameters
+        self.kind, self.pf, self.N, self.lambduh = s.kind, s.pf, s.N, s.lambduh
+        self._smoother, self._launch_smoother = s.smoother, s.launch_smoother
+        self.Ntilde, self.max_accept_reject = s.Ntilde, s.max_accept_reject
+        self.resampling, self.sampler, self.friction = resampling, sampler, float(friction)
+        self.window_sampling, self.partition_style, self.strict = window_sampling, partition_style, s.strict
+        self._multi, self.W, self.segments, self.T, self.S, self.B = s.multi, s.W, s.segments, s.T, s.S, s.B
+        self.P, self.C = s.theta0.shape[1], s.theta0.shape[0]
+        self.seed, self.chain_offset = int(seed), int(chain_offset)
+        self._graphs = {}
+        self.steps_done = 0
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.ctx = _capi.default_context(self.device.index)
+        self.helper = Helper(n=1, m=1, forward_message=forward_message)
+        self.kernel = self.helper._get_kernel(kernel)
+        if prior is None:
+            prior = Prior.generate_default_prior(var=1.0 if model == "garch" else 100.0, n=1, m=1)
+        self.prior = prior
+        self.hyper = prior_hyper(model, prior)
+        if s.kind in ("marginal", "complete"):
+            # (a refusal that needs no device either, but it reads the Helper's message, so it is stated here, before
+            # anything is allocated, and not in _resolve_settings)
+            # the message of x_{-1} itself: mean mean_precision / precision, variance 1 / precision
+            fm = self.helper.default_forward_message
+            prec = float(np.reshape(fm['precision'], -1)[0])
+            if not (0.0 < prec < np.inf):
+                raise ValueError("the forward message needs a finite precision > 0, got {0}".format(prec))
+            pm, pv = float(np.reshape(fm['mean_precision'], -1)[0]) / prec, 1.0 / prec
+        else:
+            pm, pv, _ = self._prior_x(s.proto, s.theta0[0])
+
+        dev, C, W = self.device, self.C, self.W
+        th = np.zeros((C, _capi.MAX_THETA))
+        th[:, :self.P] = s.theta0
+        self.y_dev = torch.from_numpy(s.y).to(dev)
+        self.theta_dev = torch.from_numpy(th).to(dev)
+        self.out_dev = torch.zeros((C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
+        self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.momentum_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
+        # one weights row per window start of every sequence longer than S.  Single-window lists: every row times
+        # T_total / T_sequence, the Seq sampler's rescaling of a one-sequence gradient, whole short sequences a row of it;
+        # the multi-window path leaves that rescaling to the reduction
+        bounds = self._bounds = s.bounds
+        scale = self.T / np.diff(bounds).astype(np.float64) if self.segments is not None and not self._multi else None
+        flat, self._seg_weight_offsets = self._weights_blocks(bounds, self.S, scale)
+        self._weights_table = None
+        if flat is not None and self.segments is None and not self._multi:
+            flat = self._weights_table = flat.reshape(-1, self.S)       # a single series: resident as the [starts, S] table
+        self.weights_dev = torch.from_numpy(flat).to(dev) if flat is not None else None
+        self._nd = C * W if self._multi else C
+        records = self.out_dev
+        chain = np.repeat(np.arange(C, dtype=np.uint64), W if self._multi else 1)
+        stream = chain + np.uint64(self.chain_offset)
+        if self._multi:
+            # W = K_eff * M descriptors per chain (chain-major, window w = k * M + m), their records win_out_dev [C * W, 8],
+            # each window's sequence length seq_len_dev [C * W]; out_dev [C, 8] holds the reduced records the update reads
+            self.M, self.num_sequences, self.K_eff = s.M, s.K, W // s.M
+            self._draws, self._rescale = s.draws, s.rescale       # rescale: T_total / S (sgmcmc_sampler.py:1278-1282)
+            self.bounds_dev = torch.from_numpy(np.ascontiguousarray(bounds, dtype=np.int64)).to(dev)
+            self.woffs_dev = torch.from_numpy(self._seg_weight_offsets).to(dev)
+            self.seq_len_dev = torch.zeros(self._nd, dtype=torch.int32, device=dev)
+            records = self.win_out_dev = torch.zeros((self._nd, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
+            stream = stream * np.uint64(W) + np.tile(np.arange(W, dtype=np.uint64), C)
+        sb = self._scratch_bytes()
+        if self._multi:
+            self.scratch_bytes_per_window = sb
+        self.scratch_dev = None
+        if sb > 0:       # state in HBM (L2-resident), one slab per descriptor: the large-N kernel, paris_mem1024, Kalman messages
+            self.scratch_dev = torch.empty(self._nd * sb, dtype=torch.uint8, device=dev)
+        garch_stationary = model == "garch" and self.helper.default_forward_message is None
+        self._desc = _capi.device_descriptors(
+            self._nd, theta=self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
+            scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv, lambduh=self.lambduh, seed=self.seed, N=self.N,
+            smoother=s.smoother, stat=s.stat, flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0, **s.paris)
+        if not self._multi:
+            self._set_windows(first=True)
+        self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)).to(dev)
+        if self._multi and not self._draws:
+            self.launch_windows()           # static windows: written once, no draw
+
+    @staticmethod
+    def _resolve_settings(model, observations, parameters=None, num_chains=None, N=1000, pf="poyiadjis_N", lambduh=None,
+                          subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
+                          resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
+                          Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None):
+        """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
+        device is made here and nowhere else, so it runs (and is tested) without a GPU.
+
+        kind, pf, N (kind='complete': num_samples), lambduh; smoother (what the descriptors say) and launch_smoother (what the
+        launch states: 'poyiadjis_n' for 'nemeth' with lambduh = 1); stat; paris (the descriptors' PaRIS fields, {} otherwise),
+        Ntilde, max_accept_reject; M, K, W, multi; S, B, strict; y (the concatenated series), T, segments ([K+1] offsets
+        into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto."""
         if sampler not in ("sgld", "sghmc", "sgrld", "gibbs"):
             raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld' or 'gibbs'")
-        M, K, W = self._window_counts(observations, minibatch_size, num_sequences)
+        M, K, W = ChainEnsemble._window_counts(observations, minibatch_size, num_sequences)
         if W > 1 and sampler == "gibbs":
             raise NotImplementedError("sampler='gibbs' draws one FFBS path per chain and step: W = 1 window "
                                       "(minibatch_size = num_sequences = 1), got W = {0}".format(W))
@@ -125,11 +244,11 @@ class ChainEnsemble(object):
             raise NotImplementedError("kind='{0}' with W = {1} windows per chain and step is not built: "
                                       "the multi-window path is kind='pf' only".format(kind, W))
         explicit = minibatch_size is not None or num_sequences is not None
-        self._multi = W > 1 or (explicit and kind == "pf" and sampler != "gibbs")
-        self.W = W
+        multi = W > 1 or (explicit and kind == "pf" and sampler != "gibbs")
         if sampler == "sgrld" and model != "lgssm":           # sgmcmc_sampler.py:643-646: LGSSM alone has one
             raise NotImplementedError("No Default Preconditioner for {0}: sampler='sgrld' is built for model 'lgssm'".format(
                 dict(svm="SVMSampler", garch="GARCHSampler").get(model, model)))
+        stat = "score"
         if sampler == "gibbs":
             if model != "lgssm" or dtype != "f64":
                 raise NotImplementedError("sampler='gibbs' (FFBS paths, conjugate draws) is built for model 'lgssm', dtype 'f64'")
@@ -138,9 +257,7 @@ class ChainEnsemble(object):
             if int(subsequence_length) != -1 or int(buffer_length) != -1:
                 raise NotImplementedError("sampler='gibbs' samples the path of the whole series: "
                                           "subsequence_length = buffer_length = -1")
-            kind, num_samples, pf = "complete", 1, "poyiadjis_N"      # one FFBS path per chain and step
-        if not torch.cuda.is_available():
-            raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
+            kind, num_samples, pf, stat = "complete", 1, "poyiadjis_N", "gibbs"      # one FFBS path per chain and step
         if kind not in ("pf", "marginal", "complete"):
             raise ValueError("kind must be 'pf', 'marginal' or 'complete'")
         if kind == "marginal" and (model != "lgssm" or dtype != "f64"):
@@ -151,178 +268,93 @@ class ChainEnsemble(object):
             if num_samples is None or int(num_samples) < 1:
                 raise ValueError("kind='complete' needs num_samples >= 1 paths per window")
             N = int(num_samples)        # the paths of a window take the particles' place in the descriptors
-        self.kind = kind
-        Parameters, Prior, Helper = _model_info(model)
-        self.model, self.N, self.dtype, self.epsilon = model, int(N), dtype, float(epsilon)
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self.ctx = _capi.default_context(self.device.index)
-        self.helper = Helper(n=1, m=1, forward_message=forward_message)
-        self.kernel = self.helper._get_kernel(kernel)
-        if kind in ("marginal", "complete") and pf == "paris":
-            raise ValueError("pf='paris' needs kind='pf'")
-        if pf == "poyiadjis_N" or kind in ("marginal", "complete"):
-            self.lambduh = 1.0
-        elif pf == "nemeth":
-            self.lambduh = 0.95 if lambduh is None else float(lambduh)
+        N, Ntilde = int(N), int(Ntilde)
+        max_accept_reject = 0 if not accept_reject else (64 if max_accept_reject is None else max(0, int(max_accept_reject)))
+        # which smoother runs: the one decision the descriptors, the launch and the scratch sizing follow
+        lam, paris = 1.0, {}
+        if kind != "pf":
+            if pf == "paris":
+                raise ValueError("pf='paris' needs kind='pf'")
+            smoother = {"marginal": "kalman", "complete": "kalman_ffbs"}[kind]
         elif pf == "paris":
             # PaRIS on the LDS-resident kernels (paris64x2 / paris256x1 / paris256x4): no per-chain scratch; the
             # multi-window path also runs paris_mem1024 (1024 < N <= 16384, its state in the descriptors' scratch)
-            if self.N > 1024 and not self._multi:
+            if N > 1024 and not multi:
                 raise NotImplementedError("ChainEnsemble(pf='paris') is built for N <= 1024 on the single-window path, "
                                           "got N = {0}: pass minibatch_size / num_sequences for the multi-window path "
-                                          "(paris_mem1024, N <= 16384)".format(self.N))
+                                          "(paris_mem1024, N <= 16384)".format(N))
             if resampling != "multinomial":
                 raise ValueError("pf='paris' resamples multinomially, got resampling = {0}".format(resampling))
-            self.lambduh = 1.0
+            if Ntilde < 1:
+                raise ValueError("pf='paris' needs Ntilde >= 1")
+            smoother, paris = "paris", dict(Ntilde=Ntilde, max_accept_reject=max_accept_reject)
+        elif pf in ("poyiadjis_N", "nemeth"):
+            if pf == "nemeth":
+                lam = 0.95 if lambduh is None else float(lambduh)
+            smoother = "nemeth"
+            if resampling == "systematic":       # extension, see include/pfgrad.h
+                if N > 1024:
+                    raise NotImplementedError("systematic resampling is built for N <= 1024")
+                smoother = "nemeth_systematic"
+            elif resampling != "multinomial":
+                raise ValueError("Unrecognized resampling = {0}".format(resampling))
         else:
             raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth' | 'paris', got {0}".format(pf))
-        self.pf = pf
-        self.Ntilde = int(Ntilde)
-        self.max_accept_reject = 0 if not accept_reject else (64 if max_accept_reject is None else max(0, int(max_accept_reject)))
-        if self.pf == "paris" and self.Ntilde < 1:
-            raise ValueError("pf='paris' needs Ntilde >= 1")
-        self.P = _capi.THETA_DIM[model]
-        self._Parameters = Parameters
-        self.resampling = resampling
-        self.sampler, self.friction = sampler, float(friction)
+        # every chain the Poyiadjis O(N) score (NEMETH, lambduh = 1, score): units with a twin specialised to it run that
+        launch_smoother = "poyiadjis_n" if smoother == "nemeth" and lam == 1.0 else smoother
         if window_sampling not in ("host", "device"):
             raise ValueError("window_sampling must be 'host' or 'device'")
-        self.window_sampling = window_sampling
-        self._graphs = {}
 
-        self.segments = None
+        segments = None
         if isinstance(observations, (list, tuple)):
             segs = [np.ascontiguousarray(o, dtype=np.float64).reshape(-1) for o in observations]
             if len(segs) == 0 or min(len(o) for o in segs) == 0:
                 raise ValueError("every sequence needs at least one observation")
-            bounds = np.concatenate([[0], np.cumsum([len(o) for o in segs])]).astype(np.int64)
-            self.segments = bounds                    # [K+1] offsets into the concatenated series
+            segments = np.concatenate([[0], np.cumsum([len(o) for o in segs])]).astype(np.int64)
             y = np.concatenate(segs)
         else:
             y = np.ascontiguousarray(observations, dtype=np.float64).reshape(-1)
-        self.T = y.shape[0]
+        T = y.shape[0]
+        bounds = segments if segments is not None else np.array([0, T], dtype=np.int64)
+        proto = None
         if isinstance(parameters, np.ndarray):
-            theta0 = np.ascontiguousarray(parameters, dtype=np.float64).reshape(-1, self.P)
-            proto = None
+            theta0 = np.ascontiguousarray(parameters, dtype=np.float64).reshape(-1, _capi.THETA_DIM[model])
         else:
             if num_chains is None:
                 raise ValueError("num_chains is required when `parameters` is a Parameters object")
-            theta0 = np.tile(parameters.theta(), (int(num_chains), 1))
-            proto = parameters
-        self.C = theta0.shape[0]
-        if prior is None:
-            prior = Prior.generate_default_prior(var=1.0 if model == "garch" else 100.0, n=1, m=1)
-        self.prior = prior
-        self.hyper = prior_hyper(model, prior)
-        self.seed, self.chain_offset = int(seed), int(chain_offset)
+            theta0, proto = np.tile(parameters.theta(), (int(num_chains), 1)), parameters
 
         S, B = int(subsequence_length), int(buffer_length)
-        if self.segments is not None and not self._multi:
+        if segments is not None and not multi:
             if window_sampling != "host":
                 raise NotImplementedError("sequence lists use host-side window sampling (device-side: pass num_sequences, "
                                           "the multi-window path)")
             if S == -1:
-                S = int(np.max(np.diff(self.segments)))      # whole sequences
-        elif S == -1 or self.T - S <= 0:
+                S = int(np.max(np.diff(segments)))      # whole sequences
+        elif S == -1 or T - S <= 0:
             S = -1
-        self.S, self.B = S, (self.T if B == -1 else B)
-        self.partition_style = partition_style
-
-        dev = self.device
-        th = np.zeros((self.C, _capi.MAX_THETA))
-        th[:, :self.P] = theta0
-        self.y_dev = torch.from_numpy(y).to(dev)
-        self.theta_dev = torch.from_numpy(th).to(dev)
-        self.out_dev = torch.zeros((self.C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
-        self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.momentum_dev = torch.zeros((self.C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
-        if self._multi:
-            self._init_multi(M, K, theta0, proto)
-            return
-        self._nd = self.C
-        self.weights_dev = None
-        self._weights_table = None
-        if self.segments is not None:
-            # one weights block per sequence: rows = window starts (or the single whole-sequence
-            # row when the sequence is no longer than S), every row pre-multiplied by
-            # T_total / T_sequence -- the Seq sampler's rescaling of a one-sequence gradient
-            blocks, offs, off = [], [], 0
-            for k in range(len(self.segments) - 1):
-                Tk = int(self.segments[k + 1] - self.segments[k])
-                scale = self.T / float(Tk)
-                if Tk - S <= 0:
-                    blk = np.ones((1, Tk)) * scale
-                else:
-                    blk = np.stack([self._weights_for(st, T=Tk) for st in range(Tk - S + 1)]) * scale
-                offs.append(off)
-                off += blk.size
-                blocks.append(blk.reshape(-1))
-            self._seg_weight_offsets = np.array(offs, dtype=np.int64)
-            self.weights_dev = torch.from_numpy(np.concatenate(blocks)).to(dev)
-        elif S > 0:
-            # importance weights depend on the window start only: one resident row per start
-            table = np.zeros((self.T - S + 1, S))
-            for start in range(self.T - S + 1):
-                table[start] = self._weights_for(start)
-            self._weights_table = table
-            self.weights_dev = torch.from_numpy(table).to(dev)
-        if kind in ("marginal", "complete"):
-            # the message of x_{-1} itself: mean mean_precision / precision, variance 1 / precision
-            fm = self.helper.default_forward_message
-            prec = float(np.reshape(fm['precision'], -1)[0])
-            if not (0.0 < prec < np.inf):
-                raise ValueError("the forward message needs a finite precision > 0, got {0}".format(prec))
-            pm, pv = float(np.reshape(fm['mean_precision'], -1)[0]) / prec, 1.0 / prec
-        else:
-            pm, pv, _ = self._prior_x(proto, theta0[0])
-        self._desc = np.zeros(self.C, dtype=_capi.DEV_PROBLEM_DTYPE)
-        d = self._desc
-        d["theta"] = self.theta_dev.data_ptr() + np.arange(self.C, dtype=np.uint64) * (8 * _capi.MAX_THETA)
-        d["out"] = self.out_dev.data_ptr() + np.arange(self.C, dtype=np.uint64) * (8 * _capi.OUT_DOUBLES)
-        d["step_ctr"] = self.step_ctr.data_ptr()
-        d["prior_mean"], d["prior_var"], d["lambduh"] = pm, pv, self.lambduh
-        d["seed"] = np.uint64(self.seed & 0xFFFFFFFFFFFFFFFF)
-        d["stream"] = np.arange(self.C, dtype=np.uint64) + np.uint64(self.chain_offset)
-        d["N"] = self.N
-        d["smoother"], d["stat"] = _capi.SMOOTHER["nemeth"], _capi.STAT["score"]
-        if model == "garch" and self.helper.default_forward_message is None:
-            d["flags"] = _capi.FLAG_GARCH_STATIONARY_PRIOR
-        if kind == "marginal":
-            d["smoother"] = _capi.SMOOTHER["kalman"]
-        elif kind == "complete":
-            d["smoother"] = _capi.SMOOTHER["kalman_ffbs"]
-            if sampler == "gibbs":
-                d["stat"] = _capi.STAT["gibbs"]
-        elif self.pf == "paris":
-            d["smoother"] = _capi.SMOOTHER["paris"]
-            d["Ntilde"], d["max_accept_reject"] = self.Ntilde, self.max_accept_reject
-        elif resampling == "systematic":       # extension, see include/pfgrad.h
-            if self.N > 1024:
-                raise NotImplementedError("systematic resampling is built for N <= 1024")
-            d["smoother"] = _capi.SMOOTHER["nemeth_systematic"]
-        elif resampling != "multinomial":
-            raise ValueError("Unrecognized resampling = {0}".format(resampling))
-        if kind == "marginal":
-            # the backward messages of the longest window: S (segments: no window is longer), or the whole series
-            sb = _capi.kalman_scratch_bytes(S if S > 0 else self.T)
-        elif kind == "complete":
-            # the forward messages of the longest buffer: a window and its two buffers, or the whole series
-            sb = _capi.kalman_scratch_bytes(min(self.T, S + 2 * self.B) if S > 0 else self.T)
-        elif self.pf == "paris":
-            sb = 0          # N <= 1024: the LDS-resident PaRIS variants keep their state in LDS
-        else:
-            sb = self.ctx.scratch_bytes(model, dtype, "device", self.N)
-        if sb < 0:
-            raise ValueError("N = {0} is above the supported maximum".format(self.N))
-        self.scratch_dev = None
-        if sb > 0:       # large-N kernel: particle state lives in HBM (L2-resident), one slab per chain (Kalman: messages)
-            self.scratch_dev = torch.empty(self.C * sb, dtype=torch.uint8, device=dev)
-            d["scratch"] = self.scratch_dev.data_ptr() + np.arange(self.C, dtype=np.uint64) * np.uint64(sb)
-        self.steps_done = 0
-        if (partition_style or 'uniform') == 'strict' and S > 0 and self.segments is None and self.T % S != 0:
-            raise ValueError("S {0} does not evenly divide T {1}".format(S, self.T))     # sgmcmc_sampler.py:1991-1993
-        self._set_windows(first=True)
-        self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self.C, -1)).to(dev)
+        B = T if B == -1 else B
+        Tk = np.diff(bounds)
+        longer = (Tk > S) if S > 0 else np.zeros(len(Tk), dtype=bool)
+        strict = (partition_style or 'uniform') == 'strict'
+        # (single-window lists draw their strict starts from Tk // S blocks without asking for divisibility)
+        if strict and (multi or segments is None) and np.any(Tk[longer] % S != 0):
+            k = int(np.flatnonzero(longer & (Tk % max(S, 1) != 0))[0])
+            raise ValueError("S {0} does not evenly divide T {1}".format(S, int(Tk[k])))   # sgmcmc_sampler.py:1991-1993
+        draws = rescale = None
+        if multi:
+            rescale = segments is not None and K != -1
+            draws = rescale or bool(np.any(longer))
+            if draws and window_sampling != "device":
+                raise NotImplementedError("the W = {0} windows per chain and step are drawn on the device: "
+                                          "window_sampling='device'".format(W))
+            if N > 16384:
+                raise NotImplementedError("the multi-window path is built for N <= 16384 (one workgroup per window), "
+                                          "got N = {0}".format(N))
+        return types.SimpleNamespace(
+            kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
+            Ntilde=Ntilde, max_accept_reject=max_accept_reject, M=M, K=K, W=W, multi=multi, S=S, B=B, strict=strict, y=y, T=T,
+            segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto)
 
     @staticmethod
     def _window_counts(observations, minibatch_size, num_sequences):
@@ -343,79 +375,45 @@ class ChainEnsemble(object):
                                       "(num_sequences = -1 takes them all)".format(K, _capi.MAX_DRAWN_SEQUENCES))
         return M, K, M * (n_seq if K == -1 else K)
 
-    def _init_multi(self, M, K, theta0, proto):
-        """The multi-window path: W = K_eff * M descriptors per chain (chain-major, window w = k * M + m), their records
-        win_out_dev [C * W, 8], each window's sequence length seq_len_dev [C * W]; out_dev [C, 8] holds the reduced
-        records the update reads.  The descriptors' windows are written by pfg_sample_windows_multi_device: every step
-        when there is something to draw, once here when not (num_sequences = -1 and no sequence longer than S)."""
-        dev, C, W = self.device, self.C, self.W
-        bounds = self.segments if self.segments is not None else np.array([0, self.T], dtype=np.int64)
-        n_seq = len(bounds) - 1
-        Tk = np.diff(bounds)
-        self.M, self.num_sequences = M, K
-        self.K_eff = W // M
-        self._nd = C * W
-        self._rescale = self.segments is not None and K != -1      # T_total / S (sgmcmc_sampler.py:1278-1282)
-        S = self.S
-        longer = (Tk > S) if S > 0 else np.zeros(n_seq, dtype=bool)
-        if (self.partition_style or 'uniform') == 'strict' and np.any(Tk[longer] % S != 0):
-            k = int(np.flatnonzero(longer & (Tk % max(S, 1) != 0))[0])
-            raise ValueError("S {0} does not evenly divide T {1}".format(S, int(Tk[k])))   # sgmcmc_sampler.py:1991-1993
-        self._draws = (self.segments is not None and K != -1) or bool(np.any(longer))
-        if self._draws and self.window_sampling != "device":
-            raise NotImplementedError("the W = {0} windows per chain and step are drawn on the device: "
-                                      "window_sampling='device'".format(W))
-        if self.N > 16384:
-            raise NotImplementedError("the multi-window path is built for N <= 16384 (one workgroup per window), "
-                                      "got N = {0}".format(self.N))
-        # random_subsequence_and_weights per sequence longer than S, one row per start, UNSCALED: the T_total / S
-        # rescaling is the reduction's
-        blocks, offs, off = [], np.zeros(n_seq, dtype=np.int64), 0
-        for k in np.flatnonzero(longer):
-            blk = np.stack([self._weights_for(st, T=int(Tk[k])) for st in range(int(Tk[k]) - S + 1)])
+    def _scratch_bytes(self):
+        """pfg_dev_problem.scratch bytes per descriptor of the resolved smoother; refuses what the library refuses."""
+        if self._smoother == "kalman":
+            # the backward messages of the longest window: S (segments: no window is longer), or the whole series
+            return _capi.kalman_scratch_bytes(self.S if self.S > 0 else self.T)
+        if self._smoother == "kalman_ffbs":
+            # the forward messages of the longest buffer: a window and its two buffers, or the whole series
+            return _capi.kalman_scratch_bytes(min(self.T, self.S + 2 * self.B) if self.S > 0 else self.T)
+        if self._multi or self._smoother == "paris":
+            # PaRIS, N <= 1024: 0, the LDS-resident variants keep their state in LDS; above: paris_mem1024's slab.  The
+            # single-window PaRIS path (N <= 1024 only) relies on that answer of 0 where it once wrote the literal
+            sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", self._smoother, self.N)
+            if sb < 0:
+                raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(self.N))
+            return sb
+        # pfg_scratch_bytes answers above N = 16384 too (the whole-GPU plan's slab) where pfg_scratch_bytes_smoother says -1,
+        # and 'nemeth_systematic' says -1 above N = 1024; the single-window path keeps the query it has always made
+        sb = self.ctx.scratch_bytes(self.model, self.dtype, "device", self.N)
+        if sb < 0:
+            raise ValueError("N = {0} is above the supported maximum".format(self.N))
+        return sb
+
+    def _weights_blocks(self, bounds, S, scale=None):
+        """(flat array or None, [n_seq] offsets into it): for every sequence longer than S one row of
+        random_subsequence_and_weights per window start; scale [n_seq]: every row times scale[k], and a sequence no longer
+        than S gets the one row of its whole window (without a scale it needs none: its weights are 1)."""
+        blocks, offs, off = [], np.zeros(len(bounds) - 1, dtype=np.int64), 0
+        for k, Tk in enumerate(np.diff(bounds).tolist()):
+            if S > 0 and Tk > S:
+                blk = np.stack([self._weights_for(st, T=Tk) for st in range(Tk - S + 1)])
+            elif scale is not None:
+                blk = np.ones((1, Tk))
+            else:
+                continue
+            if scale is not None:
+                blk = blk * scale[k]
             offs[k], off = off, off + blk.size
             blocks.append(blk.reshape(-1))
-        self.weights_dev = torch.from_numpy(np.concatenate(blocks)).to(dev) if blocks else None
-        self.bounds_dev = torch.from_numpy(np.ascontiguousarray(bounds, dtype=np.int64)).to(dev)
-        self.woffs_dev = torch.from_numpy(offs).to(dev)
-        self.seq_len_dev = torch.zeros(self._nd, dtype=torch.int32, device=dev)
-        self.win_out_dev = torch.zeros((self._nd, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
-        pm, pv, _ = self._prior_x(proto, theta0[0])
-        d = self._desc = np.zeros(self._nd, dtype=_capi.DEV_PROBLEM_DTYPE)
-        chain = np.repeat(np.arange(C, dtype=np.uint64), W)
-        d["theta"] = self.theta_dev.data_ptr() + chain * np.uint64(8 * _capi.MAX_THETA)
-        d["out"] = self.win_out_dev.data_ptr() + np.arange(self._nd, dtype=np.uint64) * np.uint64(8 * _capi.OUT_DOUBLES)
-        d["step_ctr"] = self.step_ctr.data_ptr()
-        d["prior_mean"], d["prior_var"], d["lambduh"] = pm, pv, self.lambduh
-        d["seed"] = np.uint64(self.seed & 0xFFFFFFFFFFFFFFFF)
-        d["stream"] = (chain + np.uint64(self.chain_offset)) * np.uint64(W) + np.tile(np.arange(W, dtype=np.uint64), C)
-        d["N"] = self.N
-        d["stat"] = _capi.STAT["score"]
-        if self.model == "garch" and self.helper.default_forward_message is None:
-            d["flags"] = _capi.FLAG_GARCH_STATIONARY_PRIOR
-        smoother = "nemeth"
-        if self.pf == "paris":
-            smoother = "paris"
-            d["Ntilde"], d["max_accept_reject"] = self.Ntilde, self.max_accept_reject
-        elif self.resampling == "systematic":
-            if self.N > 1024:
-                raise NotImplementedError("systematic resampling is built for N <= 1024")
-            smoother = "nemeth_systematic"
-        elif self.resampling != "multinomial":
-            raise ValueError("Unrecognized resampling = {0}".format(self.resampling))
-        d["smoother"] = _capi.SMOOTHER[smoother]
-        sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", smoother, self.N)
-        if sb < 0:
-            raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(self.N))
-        self.scratch_bytes_per_window = sb
-        self.scratch_dev = None
-        if sb > 0:       # paris_mem1024 / the large-N kernel: one slab per window
-            self.scratch_dev = torch.empty(self._nd * sb, dtype=torch.uint8, device=dev)
-            d["scratch"] = self.scratch_dev.data_ptr() + np.arange(self._nd, dtype=np.uint64) * np.uint64(sb)
-        self.steps_done = 0
-        self.desc_dev = torch.from_numpy(d.view(np.uint8).reshape(self._nd, -1)).to(dev)
-        if not self._draws:
-            self.launch_windows()           # static windows: written once, no draw
+        return (np.concatenate(blocks) if blocks else None), offs
 
     # ------------------------------------------------------------------------------------
     def _weights_for(self, start, T=None):
@@ -463,134 +461,92 @@ class ChainEnsemble(object):
         return (x >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
 
     def _set_windows(self, first=False):
-        """Full sequence: static descriptors.  Buffered windows: draw one start per chain on the
-        host (sgmcmc_sampler.py:259-288) and point y / weights / t1 / tL at it."""
-        d = self._desc
-        if self.segments is not None:
-            # one sequence per chain (np.random.choice(K, 1)), then a window inside it
-            K = len(self.segments) - 1
-            seg = np.minimum((self._host_uniforms(1) * K).astype(np.int64), K - 1)
-            base, Tk = self.segments[seg], self.segments[seg + 1] - self.segments[seg]
-            S, B = self.S, self.B
-            whole = Tk - S <= 0
-            span = np.where(whole, 1, Tk - S + 1)
-            if (self.partition_style or 'uniform') == 'strict':
-                start = np.where(whole, 0, (self._host_uniforms(2) * np.maximum(Tk // S, 1)).astype(np.int64) * S)
-            else:
-                start = np.where(whole, 0, (self._host_uniforms(2) * span).astype(np.int64))
-            length = np.where(whole, Tk, S)
-            left = np.maximum(0, start - B)
-            right = np.minimum(Tk, start + length + B)
-            d["y"] = self.y_dev.data_ptr() + (base + left).astype(np.uint64) * 8
-            d["T"] = right - left
-            d["t1"] = start - left
-            d["tL"] = start + length - left
-            d["weights"] = self.weights_dev.data_ptr() + (self._seg_weight_offsets[seg] + start * length).astype(np.uint64) * 8
-            return True
-        if self.S == -1:
-            if first:
-                d["y"] = self.y_dev.data_ptr()
-                d["T"], d["t1"], d["tL"] = self.T, 0, self.T
-                d["weights"] = 0
+        """Full series: static descriptors (placed once, `first`).  Otherwise draw, per chain, the sequence (lists:
+        np.random.choice(K, 1)) and a window start inside it on the host (sgmcmc_sampler.py:259-288).  Either way
+        y / T / t1 / tL / weights follow from (sequence, start) below, a single series being a list of one sequence: the
+        window is S long, or the whole sequence when that is no longer than S; weights is the start's row of the sequence's
+        block, null without a table (a full single series).  Returns whether the descriptors changed."""
+        d, S, B, C, bounds = self._desc, self.S, self.B, self.C, self._bounds
+        static = self.segments is None and S == -1
+        if static and not first:
             return False
-        S, B, T = self.S, self.B, self.T
-        if (self.partition_style or 'uniform') == 'strict':
-            start = np.minimum((self._host_uniforms(2) * (T // S)).astype(np.int64), T // S - 1) * S
+        K = len(bounds) - 1
+        seg = np.zeros(C, dtype=np.int64) if K == 1 else np.minimum((self._host_uniforms(1) * K).astype(np.int64), K - 1)
+        base, Tk = bounds[seg], bounds[seg + 1] - bounds[seg]
+        whole = Tk - S <= 0 if S > 0 else np.ones(C, dtype=bool)
+        if static:
+            start = np.zeros(C, dtype=np.int64)
         else:
-            start = np.minimum((self._host_uniforms(2) * (T - S + 1)).astype(np.int64), T - S)
+            # starts to choose from: one in a whole sequence, else the S-blocks ('strict') or every offset
+            span = np.where(whole, 1, Tk // S if self.strict else Tk - S + 1)
+            start = np.minimum((self._host_uniforms(2) * span).astype(np.int64), span - 1)
+            if self.strict:
+                start = start * S
+        length = np.where(whole, Tk, S)
         left = np.maximum(0, start - B)
-        right = np.minimum(T, start + S + B)
-        d["y"] = self.y_dev.data_ptr() + left.astype(np.uint64) * 8
+        right = np.minimum(Tk, start + length + B)
+        d["y"] = self.y_dev.data_ptr() + (base + left).astype(np.uint64) * 8
         d["T"] = right - left
         d["t1"] = start - left
-        d["tL"] = start + S - left
-        d["weights"] = self.weights_dev.data_ptr() + start.astype(np.uint64) * (8 * S)
-        return True
+        d["tL"] = start + length - left
+        if self.weights_dev is not None:
+            d["weights"] = self.weights_dev.data_ptr() + (self._seg_weight_offsets[seg] + start * length).astype(np.uint64) * 8
+        return not static
 
     # ------------------------------------------------------------------------------------
+    def _stream(self, stream):
+        """The hipStream_t handle of `stream` (default: torch's current stream on the ensemble's device)."""
+        return (stream or torch.cuda.current_stream(self.device)).cuda_stream
+
     def launch_pf(self, stream=None, traced=False):
         """Enqueue one particle-filter launch for all chains on `stream` (default: torch's
         current stream; kind='marginal': the exact Kalman score; kind='complete': the FFBS score).  Results land in self.out_dev[C, 8]
         (score columns, loglik).
         traced=True runs the twin instantiation that honours trace_* / rec_* buffers a caller put into
-        the descriptors (tests, diagnostics); the production launch ignores them."""
-        st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
-        if self.kind == "marginal":
-            if traced:
-                raise ValueError("kind='marginal' has no particles to trace")
-            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman",
-                                            1, self._nd, self.desc_dev.data_ptr(), st)
-        elif self.kind == "complete":
-            if traced:
-                raise ValueError("kind='complete' has no particles to trace")
-            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "kalman_ffbs",
-                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
-        elif self.pf == "paris":
-            # the PaRIS kernels always honour trace buffers: traced or not, the same launch
-            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "paris",
-                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
-        elif traced:
-            self.ctx.launch_device_traced(self.model, self.kernel, self.dtype, "device",
-                                          "nemeth_systematic" if self.resampling == "systematic" else "nemeth",
-                                          self.N, self._nd, self.desc_dev.data_ptr(), st)
-        elif self.resampling == "systematic":
-            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "nemeth_systematic",
-                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
-        elif self.lambduh == 1.0:
-            # every chain the Poyiadjis O(N) score (NEMETH, lambduh = 1, score): units with a twin specialised to it run that
-            self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", "poyiadjis_n",
-                                            self.N, self._nd, self.desc_dev.data_ptr(), st)
-        else:
-            self.ctx.launch_device(self.model, self.kernel, self.dtype, "device", self.N, self._nd,
-                                   self.desc_dev.data_ptr(), st)
+        the descriptors (tests, diagnostics); the production launch ignores them.
+        The launch is the resolved one: the launch smoother (_resolve_settings), at most N particles (the Kalman score has
+        none: 1) in each of _nd descriptors."""
+        if traced and self.kind != "pf":
+            raise ValueError("kind='{0}' has no particles to trace".format(self.kind))
+        launch, smoother = self.ctx.launch_device_smoother, self._launch_smoother
+        if traced and self.pf != "paris":       # the PaRIS kernels always honour trace buffers: traced or not, the same launch
+            launch, smoother = self.ctx.launch_device_traced, self._smoother
+        launch(self.model, self.kernel, self.dtype, "device", smoother, 1 if self._smoother == "kalman" else self.N, self._nd,
+               self.desc_dev.data_ptr(), self._stream(stream))
 
     def launch_update(self, stream=None):
-        st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        theta, out = (self.model, self.C, self.theta_dev.data_ptr()), (self.out_dev.data_ptr(), self.hyper)
+        key = (self.seed ^ 0x5DEECE66D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
         if self.sampler == "sgrld":
-            self.ctx.sgrld_update_device(self.model, self.C, self.theta_dev.data_ptr(), self.out_dev.data_ptr(),
-                                         self.hyper, self.epsilon, float(self.T), self.seed ^ 0x5DEECE66D,
-                                         self.chain_offset, self.step_ctr.data_ptr(), st)
+            self.ctx.sgrld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
         elif self.sampler == "gibbs":
-            self.ctx.gibbs_update_device(self.model, self.C, self.theta_dev.data_ptr(), self.out_dev.data_ptr(),
-                                         self.hyper, self.seed ^ 0x5DEECE66D, self.chain_offset,
-                                         self.step_ctr.data_ptr(), st)
+            self.ctx.gibbs_update_device(*theta, *out, *key)
         elif self.sampler == "sghmc":
-            self.ctx.sghmc_update_device(self.model, self.C, self.theta_dev.data_ptr(), self.momentum_dev.data_ptr(),
-                                         self.out_dev.data_ptr(), self.hyper, self.epsilon, self.friction,
-                                         float(self.T), self.seed ^ 0x5DEECE66D, self.chain_offset,
-                                         self.step_ctr.data_ptr(), st)
+            self.ctx.sghmc_update_device(*theta, self.momentum_dev.data_ptr(), *out, self.epsilon, self.friction,
+                                         float(self.T), *key)
         else:
-            self.ctx.sgld_update_device(self.model, self.C, self.theta_dev.data_ptr(), self.out_dev.data_ptr(),
-                                        self.hyper, self.epsilon, float(self.T), self.seed ^ 0x5DEECE66D,
-                                        self.chain_offset, self.step_ctr.data_ptr(), st)
+            self.ctx.sgld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
 
     def launch_windows(self, stream=None):
         """Device-side window sampling (window_sampling='device'): rewrite y / T / t1 / tL / weights of
         every descriptor for the step *step_ctr is at.  No-op for full-sequence chains.  Multi-window path: all
         C * W descriptors and their sequence lengths (pfg_sample_windows_multi_device)."""
-        st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        weights = self.weights_dev.data_ptr() if self.weights_dev is not None else 0
         if self._multi:
             self.ctx.sample_windows_multi_device(
                 self.C, self.bounds_dev.numel() - 1, self.bounds_dev.data_ptr(), self.woffs_dev.data_ptr(),
                 self.num_sequences if self.segments is not None else -1, self.M, self.desc_dev.data_ptr(),
-                self.seq_len_dev.data_ptr(), self.y_dev.data_ptr(),
-                self.weights_dev.data_ptr() if self.weights_dev is not None else 0, self.S, self.B,
-                (self.partition_style or 'uniform') == 'strict', self.seed ^ 0x4D554C5449574E44, self.chain_offset,
-                self.step_ctr.data_ptr(), st)
-            return
-        if self.S == -1:
-            return
-        self.ctx.sample_windows_device(
-            self.C, self.desc_dev.data_ptr(), self.y_dev.data_ptr(),
-            self.weights_dev.data_ptr() if self.weights_dev is not None else 0, self.T, self.S, self.B,
-            (self.partition_style or 'uniform') == 'strict', self.seed ^ 0x2545F4914F6CDD1D, self.chain_offset,
-            self.step_ctr.data_ptr(), st)
+                self.seq_len_dev.data_ptr(), self.y_dev.data_ptr(), weights, self.S, self.B, self.strict,
+                self.seed ^ 0x4D554C5449574E44, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
+        elif self.S != -1:
+            self.ctx.sample_windows_device(
+                self.C, self.desc_dev.data_ptr(), self.y_dev.data_ptr(), weights, self.T, self.S, self.B, self.strict,
+                self.seed ^ 0x2545F4914F6CDD1D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
 
     def launch_reduce(self, stream=None):
         """Multi-window path: the C * W window records -> the C records the update reads (pfg_reduce_windows_device)."""
-        st = (stream or torch.cuda.current_stream(self.device)).cuda_stream
         self.ctx.reduce_windows_device(self.C, self.K_eff, self.M, self.win_out_dev.data_ptr(), self.seq_len_dev.data_ptr(),
-                                       self._rescale, float(self.T), self.out_dev.data_ptr(), st)
+                                       self._rescale, float(self.T), self.out_dev.data_ptr(), self._stream(stream))
 
     def _enqueue_step(self):
         if self._multi:
@@ -646,27 +602,19 @@ class ChainEnsemble(object):
         step is launch-bound (short buffered windows, few chains)."""
         keep = num_steps // thin
         buf = torch.empty((max(keep, 1), self.C, self.P), dtype=torch.float64, device=self.device)
-        k = 0
         K = int(graph_steps)
-        if K > 0:
-            if thin % K != 0:
-                raise ValueError("graph_steps must divide thin")
-            g = self._graph(K)
-            it = 0
-            while it < num_steps:
-                if num_steps - it >= K:
-                    g.replay()
-                    self.steps_done += K
-                    it += K
-                else:
-                    self.step(1)
-                    it += 1
-                if it % thin == 0 and k < keep:
-                    buf[k].copy_(self.theta_dev[:, :self.P])
-                    k += 1
-            return buf[:keep].cpu().numpy()
-        for it in range(1, num_steps + 1):
-            self.step(1)
+        if K > 0 and thin % K != 0:
+            raise ValueError("graph_steps must divide thin")
+        g = self._graph(K) if K > 0 else None
+        it = k = 0
+        while it < num_steps:
+            if g is not None and num_steps - it >= K:
+                g.replay()
+                self.steps_done += K
+                it += K
+            else:
+                self.step(1)
+                it += 1
             if it % thin == 0 and k < keep:
                 buf[k].copy_(self.theta_dev[:, :self.P])
                 k += 1

@@ -52,24 +52,19 @@ class ResidentWindows(object):
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         self.scratch_dev = torch.empty(self.B * sb, dtype=torch.uint8, device=dev)
         self.weights_dev = None
-        d = np.zeros(self.B, dtype=_capi.DEV_PROBLEM_DTYPE)
         idx = np.arange(self.B, dtype=np.uint64)
+        d = _capi.device_descriptors(
+            self.B, theta=self.theta_dev, row=idx, out=self.out_dev, step_ctr=self.step_ctr, scratch=self.scratch_dev,
+            scratch_bytes=sb, stream=np.uint64(int(stream0)) + idx, prior_mean=float(prior_mean), prior_var=float(prior_var),
+            lambduh=lam, seed=seed, N=self.N, smoother=smoother, stat=stat, flags=flags)
         d["y"] = self.y_dev.data_ptr()
+        d["T"], d["t1"], d["tL"] = self.T, int(t1), tL
         if weights is not None:
             w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
             if w.shape[0] < tL - int(t1):
                 raise ValueError("weights shorter than tL - t1")
             self.weights_dev = torch.from_numpy(w).to(dev)
             d["weights"] = self.weights_dev.data_ptr()
-        d["theta"] = self.theta_dev.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
-        d["out"] = self.out_dev.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
-        d["scratch"] = self.scratch_dev.data_ptr() + idx * np.uint64(sb)
-        d["step_ctr"] = self.step_ctr.data_ptr()
-        d["prior_mean"], d["prior_var"], d["lambduh"] = float(prior_mean), float(prior_var), lam
-        d["seed"] = np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
-        d["stream"] = np.uint64(int(stream0)) + idx
-        d["T"], d["t1"], d["tL"], d["N"] = self.T, int(t1), tL, self.N
-        d["smoother"], d["stat"], d["flags"] = _capi.SMOOTHER[smoother], _capi.STAT[stat], int(flags)
         self._desc = d
         self.desc_dev = torch.from_numpy(d.view(np.uint8).reshape(self.B, -1)).to(dev)
         self.launches = 0
