@@ -1,4 +1,6 @@
-// Update rules of resident LGSSM chains beyond SGLD / SGHMC (those stay in pfgrad.hip): one lane per chain, f64.
+// Every update rule of resident chains, kernels then entry points (pfg_*_update_device): one lane per chain, f64.
+//   sgld   every model: theta += eps (grad_logprior + ghat) / T + N(0, 2 eps / T), then project_parameters; sghmc: the
+//          same kernel with a momentum buffer and friction alpha.
 //   sgrld  SGMCMCSampler.sample_sgrld with LGSSMPreconditioner (sgmcmc_sampler.py:631-641, base_parameters.py:588-661,
 //          models/lgssm.py:51-54), then project_parameters.  With theta = (A, C, LQinv, LRinv), Qinv = LQinv^2 + 1e-16,
 //          Q = 1 / Qinv, g_v = grad_logprior_v(theta) + ghat_v and every preconditioner term at the pre-step theta:
@@ -7,7 +9,8 @@
 //            LQinv += eps ((0.5 Qinv g_LQinv) / T + LQinv / T) + sqrt(2 eps) (sqrt(0.5) LQinv z_Q) sqrt(1 / T)
 //            LRinv += eps ((0.5 Rinv g_LRinv) / T + LRinv / T) + sqrt(2 eps) (sqrt(0.5) LRinv z_R) sqrt(1 / T)
 //          (the LQinv / T, LRinv / T terms: correction_term, (n + 1) / 2 L with n = 1).  The four normals of chain b are
-//          those of sgld_update_kernel: Philox4x32-10 keyed by (seed, chain_offset + b, *step_ctr), drawn A, C, Q, R.
+//          those of sgld_update_kernel (spelled out in both: a shared helper changed that kernel's instructions):
+//          Philox4x32-10 keyed by (seed, chain_offset + b, *step_ctr), drawn A, C, Q, R.
 //   gibbs  LGSSMPrior.sample_posterior (base_parameters.py:354-377, 437-450) from the statistics an FFBS window with
 //          PFG_STAT_GIBBS left in out[0..7] (pfg_ffbs.hip), block by block: Qinv, Rinv (1 x 1 Wishart = scale chi2(df)),
 //          A given Q, then project_parameters.  The C draw is skipped: the projection pins C to 1 whatever it drew.
@@ -18,19 +21,99 @@
 #include "pfg_host.hpp"
 #include "pfg_math.hpp"
 
+using namespace pfg_host;
+
 namespace {
 
 constexpr int kMaxRounds = 64;
 
-__device__ __forceinline__ double reflect_chol(double L) { return L < 0.0 ? sqrt(L * L + 1e-16) : L; }
+// ---- what the rules share: the prior gradients, the projection ----
+// grad_logprior of a Cholesky factor L of a 1 x 1 Wishart precision (covariance.py:272-284, n = 1) ...
+__device__ __forceinline__ double chol_prior_grad(double L, double df, double scale) { return (df - 2.0) / L - L / scale; }
+// ... and of the AR / emission coefficient x paired with the precision prec (matrices.py:597-607)
+__device__ __forceinline__ double coef_prior_grad(double prec, double x, double mean, double var_col) { return -1.0 * (prec * (x - mean)) / var_col; }
 
-// project_parameters of LGSSM: |A| <= 0.9999 (_utils.py:165-170), C = 1 (lgssm/parameters.py:39-42), the Cholesky
-// factors reflected (covariance.py:68-80)
-__device__ __forceinline__ void lgssm_project_store(double *th, double A, double LQ, double LR) {
+// project_parameters: |A| <= 0.9999 (_utils.py:165-170), a Cholesky factor reflected (covariance.py:68-80)
+__device__ __forceinline__ double clip_ar(double A) {
     const double aa = fabs(A);
     if (aa > 0.9999) A *= 0.9999 / aa;
-    th[0] = A; th[1] = 1.0; th[2] = reflect_chol(LQ); th[3] = reflect_chol(LR);
+    return A;
 }
+__device__ __forceinline__ double reflect_chol(double L) { return L < 0.0 ? sqrt(L * L + 1e-16) : L; }
+
+// project_parameters of LGSSM: the two above and C = 1 (lgssm/parameters.py:39-42)
+__device__ __forceinline__ void lgssm_project_store(double *th, double A, double LQ, double LR) {
+    th[0] = clip_ar(A); th[1] = 1.0; th[2] = reflect_chol(LQ); th[3] = reflect_chol(LR);
+}
+
+// momentum == nullptr: SGLD.  Otherwise SGHMC with friction alpha: the increment d of each
+// variable becomes v <- (1 - alpha) v + drift + sqrt(alpha) * noise (noise ~ N(0, 2 eps / T)).
+__global__ void sgld_update_kernel(int model, int B, double *__restrict__ theta,
+                                   const double *__restrict__ outs, pfg_prior_hyper hy, double eps,
+                                   double Tscale, uint64_t seed, uint64_t chain_offset,
+                                   const uint64_t *step_ctr, double *__restrict__ momentum, double alpha) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    const double *g = outs + (size_t)b * PFG_OUT_DOUBLES;
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const uint32_t c1 = (uint32_t)step, c2 = (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32);
+    pfg::u32x4 r0 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x5A11u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    pfg::u32x4 r1 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x5A12u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double nsd = sqrt(1.0 / Tscale) * sqrt(2.0 * eps) * (momentum ? sqrt(alpha) : 1.0);
+    double *mv = momentum ? momentum + (size_t)b * PFG_MAX_THETA : nullptr;
+    // one variable's increment: SGLD drift + noise, or the SGHMC momentum recursion
+    auto incr = [&](int slot, double drift, double noise) {
+        const double d = drift + noise;
+        if (!mv) return d;
+        const double v = (1.0 - alpha) * mv[slot] + d;
+        mv[slot] = v;
+        return v;
+    };
+    double nz[4];
+    const pfg::Math<double, false> mth = {};
+    mth.normal_pair(r0.x, r0.y, nz[0], nz[1]);
+    mth.normal_pair(r1.x, r1.y, nz[2], nz[3]);
+    if (model == PFG_MODEL_SVM || model == PFG_MODEL_LGSSM) {
+        const bool lg = model == PFG_MODEL_LGSSM;
+        double A = th[0], C = lg ? th[1] : 1.0, LQ = th[lg ? 2 : 1], LR = th[lg ? 3 : 2];
+        double Qinv = LQ * LQ + 1e-16, Rinv = LR * LR + 1e-16;
+        // score columns: SVM [LR, LQ, A]; LGSSM [LR, LQ, C, A]
+        double gLR = g[0], gLQ = g[1], gC = lg ? g[2] : 0.0, gA = g[lg ? 3 : 2];
+        double pLQ = chol_prior_grad(LQ, hy.df_Qinv, hy.scale_Qinv);
+        double pLR = chol_prior_grad(LR, hy.df_Rinv, hy.scale_Rinv);
+        double pA = coef_prior_grad(Qinv, A, hy.mean_A, hy.var_col_A);
+        double pC = coef_prior_grad(Rinv, C, hy.mean_C, hy.var_col_C);
+        int j = 0;
+        A += incr(0, eps * ((pA + gA) / Tscale), nsd * nz[j]); ++j;
+        if (lg) { C += incr(1, eps * ((pC + gC) / Tscale), nsd * nz[j]); ++j; }
+        LQ += incr(lg ? 2 : 1, eps * ((pLQ + gLQ) / Tscale), nsd * nz[j]); ++j;
+        LR += incr(lg ? 3 : 2, eps * ((pLR + gLR) / Tscale), nsd * nz[j]); ++j;
+        // project_parameters: _utils.py:165-170, covariance.py:68-80, lgssm/parameters.py:39-42
+        A = clip_ar(A);
+        if (lg) C = 1.0;
+        LQ = reflect_chol(LQ); LR = reflect_chol(LR);
+        th[0] = A;
+        if (lg) { th[1] = C; th[2] = LQ; th[3] = LR; } else { th[1] = LQ; th[2] = LR; }
+    } else {
+        double lmu = th[0], lphi = th[1], llam = th[2], LR = th[3];
+        double mu = exp(lmu), phi = 1.0 / (1.0 + exp(-lphi)), lam = 1.0 / (1.0 + exp(-llam));
+        // garch_var.py:152-165
+        double p0 = -hy.shape_mu - 1.0 + hy.scale_mu / mu;
+        double p1 = ((hy.alpha_phi - 1.0) / (1.0 + phi) - (hy.beta_phi - 1.0) / (1.0 - phi)) * phi * (1.0 - phi);
+        double p2 = ((hy.alpha_lambduh - 1.0) / (1.0 + lam) - (hy.beta_lambduh - 1.0) / (1.0 - lam)) * lam * (1.0 - lam);
+        double pLR = chol_prior_grad(LR, hy.df_Rinv, hy.scale_Rinv);
+        // score columns [LR, log_mu, logit_phi, logit_lambduh]
+        lmu += incr(0, eps * ((p0 + g[1]) / Tscale), nsd * nz[0]);
+        lphi += incr(1, eps * ((p1 + g[2]) / Tscale), nsd * nz[1]);
+        llam += incr(2, eps * ((p2 + g[3]) / Tscale), nsd * nz[2]);
+        LR += incr(3, eps * ((pLR + g[0]) / Tscale), nsd * nz[3]);
+        th[0] = lmu; th[1] = lphi; th[2] = llam; th[3] = reflect_chol(LR);
+    }
+}
+
+__global__ void bump_counter_kernel(uint64_t *ctr) { *ctr += 1; }
 
 __global__ void sgrld_update_kernel(int B, double *__restrict__ theta, const double *__restrict__ outs, pfg_prior_hyper hy,
                                     double eps, double Tscale, uint64_t seed, uint64_t chain_offset,
@@ -48,15 +131,14 @@ __global__ void sgrld_update_kernel(int B, double *__restrict__ theta, const dou
     const pfg::Math<double, false> mth = {};
     mth.normal_pair(r0.x, r0.y, zA, zC);
     mth.normal_pair(r1.x, r1.y, zQ, zR);
-
     (void)zC;       // C's step is not taken: the projection pins C to 1 whatever it would be
     const double A = th[0], LQ = th[2], LR = th[3];
     const double Qinv = LQ * LQ + 1e-16, Rinv = LR * LR + 1e-16;
     const double Q = 1.0 / Qinv;
-    // score columns [LRinv, LQinv, C, A]; grad_logprior as sgld_update_kernel (covariance.py:272-284, matrices.py:597-607)
-    const double pLQ = (hy.df_Qinv - 2.0) / LQ - LQ / hy.scale_Qinv;
-    const double pLR = (hy.df_Rinv - 2.0) / LR - LR / hy.scale_Rinv;
-    const double pA = -1.0 * (Qinv * (A - hy.mean_A)) / hy.var_col_A;
+    // score columns [LRinv, LQinv, C, A]
+    const double pLQ = chol_prior_grad(LQ, hy.df_Qinv, hy.scale_Qinv);
+    const double pLR = chol_prior_grad(LR, hy.df_Rinv, hy.scale_Rinv);
+    const double pA = coef_prior_grad(Qinv, A, hy.mean_A, hy.var_col_A);
     const double gA = pA + g[3], gLQ = pLQ + g[1], gLR = pLR + g[0];
     const double scale = 1.0 / Tscale, nsd = sqrt(2.0 * eps), rs = sqrt(scale), half = sqrt(0.5);
     const double nA = (zA / LQ) * rs;
@@ -150,24 +232,62 @@ __global__ void gibbs_update_kernel(int B, double *__restrict__ theta, const dou
     lgssm_project_store(th, A, LQ, LR);
 }
 
+// ---- the entry points: one prologue, one epilogue ----
+// What every rule checks of its arguments (`what` names the entry point).  lgssm_only: how SGRLD and Gibbs refuse other
+// models' chains (the reference's one preconditioner and conjugate prior).  Gibbs has no step size: the defaults pass.
+int check_update(pfg_ctx *ctx, const char *what, int model, const double *theta, const double *outs,
+                 const pfg_prior_hyper *hyper, const char *lgssm_only = nullptr, double epsilon = 1.0, double Tscale = 1.0) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (!theta || !outs || !hyper) return fail(ctx, PFG_ERR_INVALID, std::string(what) + ": NULL argument");
+    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+    if (lgssm_only && model != PFG_MODEL_LGSSM)          // sgmcmc_sampler.py:643-646
+        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(what) + lgssm_only + (model == PFG_MODEL_SVM ? "SVMSampler" : "GARCHSampler"));
+    if (!(epsilon > 0.0) || !(Tscale > 0.0)) return fail(ctx, PFG_ERR_INVALID, "epsilon and Tscale must be > 0");
+    return PFG_OK;
+}
+
+// `kernel` over the B chains, then the step counter's bump
+template <typename Kernel, typename... Args>
+int run_update(pfg_ctx *ctx, int B, uint64_t *step_ctr, void *hip_stream, Kernel kernel, Args... args) {
+    if (B <= 0) return PFG_OK;
+    PFG_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(kernel, dim3((B + 127) / 128), dim3(128), 0, st, args...);
+    if (step_ctr) hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, st, step_ctr);
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
+}
+
 }  // namespace
 
-namespace pfg_host {
-
-int launch_sgrld_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, double eps,
-                        double Tscale, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st) {
-    hipLaunchKernelGGL(sgrld_update_kernel, dim3((B + 127) / 128), dim3(128), 0, st, B, theta, outs, hy, eps, Tscale, seed,
-                       chain_offset, step_ctr);
-    PFG_HIP(ctx, hipGetLastError());
-    return PFG_OK;
+int pfg_sgld_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                           const pfg_prior_hyper *hyper, double epsilon, double Tscale, uint64_t seed,
+                           uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream) {
+    return pfg_sghmc_update_device(ctx, model, B, theta, nullptr, outs, hyper, epsilon, 1.0, Tscale, seed, chain_offset, step_ctr, hip_stream);
 }
 
-int launch_gibbs_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, uint64_t seed,
-                        uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st) {
-    hipLaunchKernelGGL(gibbs_update_kernel, dim3((B + 127) / 128), dim3(128), 0, st, B, theta, outs, hy, seed, chain_offset,
-                       step_ctr);
-    PFG_HIP(ctx, hipGetLastError());
-    return PFG_OK;
+int pfg_sghmc_update_device(pfg_ctx *ctx, int model, int B, double *theta, double *momentum, const double *outs,
+                            const pfg_prior_hyper *hyper, double epsilon, double alpha, double Tscale,
+                            uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (!(alpha > 0.0 && alpha <= 1.0)) return fail(ctx, PFG_ERR_INVALID, "SGHMC friction alpha must be in (0, 1]");
+    if (const int rc = check_update(ctx, "pfg_sgld_update_device", model, theta, outs, hyper, nullptr, epsilon, Tscale)) return rc;
+    return run_update(ctx, B, step_ctr, hip_stream, sgld_update_kernel, model, B, theta, outs, *hyper, epsilon, Tscale, seed,
+                      chain_offset, (const uint64_t *)step_ctr, momentum, alpha);
 }
 
-}  // namespace pfg_host
+int pfg_sgrld_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                            const pfg_prior_hyper *hyper, double epsilon, double Tscale,
+                            uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream) {
+    if (const int rc = check_update(ctx, __func__, model, theta, outs, hyper, ": No Default Preconditioner for ", epsilon, Tscale)) return rc;
+    return run_update(ctx, B, step_ctr, hip_stream, sgrld_update_kernel, B, theta, outs, *hyper, epsilon, Tscale, seed,
+                      chain_offset, (const uint64_t *)step_ctr);
+}
+
+int pfg_gibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                            const pfg_prior_hyper *hyper, uint64_t seed, uint64_t chain_offset,
+                            uint64_t *step_ctr, void *hip_stream) {
+    if (const int rc = check_update(ctx, __func__, model, theta, outs, hyper, ": no conjugate Gibbs draw for ")) return rc;
+    return run_update(ctx, B, step_ctr, hip_stream, gibbs_update_kernel, B, theta, outs, *hyper, seed, chain_offset,
+                      (const uint64_t *)step_ctr);
+}

@@ -11,7 +11,7 @@
 //     S'[i][3(t-t1)..+3] += w_t / Nt sum_j h(x_t[J_j(i)], x_{t+1}[i])        (t inside the window)
 // Row-major [N][3L]: a child copies whole parent rows, so every access is coalesced over the column axis;
 // 16 B per matrix element per step of traffic (read parent row, write own row).  fp64 throughout.
-#pragma once
+#include "pfg_host.hpp"
 #include "pfg_models.hpp"
 
 namespace pfg {
@@ -169,3 +169,50 @@ __global__ __launch_bounds__(256) void ews_n2_step_kernel(int N, int Wd, double 
 }
 
 }  // namespace pfg
+
+namespace pfg_host {
+
+int elementwise_pass(pfg_ctx *ctx, const pfg_problem &q, const pfg_dev_problem &d, const EwPlan &e) {
+    const double *theta_dev = d.theta, *tx = d.trace_x, *tlw = d.trace_logw;
+    const int32_t *par = q.smoother == PFG_SMOOTHER_PARIS ? d.trace_paris_J : d.trace_anc;
+    const size_t Wd = e.Wd;
+    const int Nt = e.Nt, N = q.N, T = q.T, NS = state_dim(q.model);
+    double *S0 = e.S0, *S1 = e.S1, *Sbar = e.Sbar, *w = e.w, *mean = e.mean, *stats = e.stats;
+    const int tL = q.tL < q.T ? q.tL : q.T;
+    const double lam = q.smoother == PFG_SMOOTHER_NEMETH ? q.lambduh : 1.0;
+    hipStream_t st = ctx->stream;
+    PFG_HIP(ctx, hipMemsetAsync(S0, 0, (size_t)N * Wd * 8, st));
+    double *cur = S0, *nxt = S1;
+    const dim3 cgrid((unsigned)((Wd + 255) / 256)), sgrid((unsigned)((Wd + 255) / 256), (unsigned)N);
+    for (int t = 0; t < T; ++t) {
+        if (lam != 1.0) {
+            hipLaunchKernelGGL(pfg::ews_softmax_kernel, dim3(1), dim3(1024), 0, st, N, tlw + (size_t)t * N, w);
+            hipLaunchKernelGGL(pfg::ews_colsum_kernel, cgrid, dim3(256), 0, st, N, (int)Wd, cur, w, Sbar);
+        }
+        const bool inside = t >= q.t1 && t < tL;
+        const int col0 = inside ? 3 * (t - q.t1) : -1;
+        const double wt = (inside && q.weights) ? q.weights[t - q.t1] : 1.0;
+        const int32_t *pt = par + (size_t)t * Nt * N;
+        const double *xt = tx + (size_t)t * N * NS, *xn = tx + (size_t)(t + 1) * N * NS;
+        if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2) {
+            const double *lwt = tlw + (size_t)t * N;
+            if (q.model == PFG_MODEL_GARCH)
+                hipLaunchKernelGGL(pfg::ews_n2_step_kernel<PFG_MODEL_GARCH>, dim3(N), dim3(256), 0, st, N, (int)Wd, wt, col0, theta_dev, xt, lwt, xn, cur, nxt);
+            else if (q.model == PFG_MODEL_LGSSM)
+                hipLaunchKernelGGL(pfg::ews_n2_step_kernel<PFG_MODEL_LGSSM>, dim3(N), dim3(256), 0, st, N, (int)Wd, wt, col0, theta_dev, xt, lwt, xn, cur, nxt);
+            else
+                hipLaunchKernelGGL(pfg::ews_n2_step_kernel<PFG_MODEL_SVM>, dim3(N), dim3(256), 0, st, N, (int)Wd, wt, col0, theta_dev, xt, lwt, xn, cur, nxt);
+        } else if (q.model == PFG_MODEL_GARCH)
+            hipLaunchKernelGGL(pfg::ews_step_kernel<PFG_MODEL_GARCH>, sgrid, dim3(256), 0, st, N, (int)Wd, Nt, lam, wt, col0, pt, xt, xn, Sbar, cur, nxt);
+        else
+            hipLaunchKernelGGL(pfg::ews_step_kernel<PFG_MODEL_SVM>, sgrid, dim3(256), 0, st, N, (int)Wd, Nt, lam, wt, col0, pt, xt, xn, Sbar, cur, nxt);
+        double *tmp = cur; cur = nxt; nxt = tmp;
+    }
+    hipLaunchKernelGGL(pfg::ews_softmax_kernel, dim3(1), dim3(1024), 0, st, N, tlw + (size_t)T * N, w);
+    hipLaunchKernelGGL(pfg::ews_colsum_kernel, cgrid, dim3(256), 0, st, N, (int)Wd, cur, w, mean);
+    if (stats) PFG_HIP(ctx, hipMemcpyAsync(stats, cur, (size_t)N * Wd * 8, hipMemcpyDeviceToDevice, st));
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
+}
+
+}  // namespace pfg_host

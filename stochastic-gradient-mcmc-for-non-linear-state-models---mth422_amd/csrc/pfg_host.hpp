@@ -1,7 +1,6 @@
-// Host-side declarations shared by the translation units of libpfgrad.so: the context, error
-// plumbing, the launch plan and the per-(model, proposal kernel, generator) launch entry the ten
-// instantiation units (pfg_inst_*.hip) define.  Splitting the kernel instantiations over those
-// units lets the build compile them in parallel.
+// Host-side declarations shared by the translation units of libpfgrad.so: the context, error plumbing, the launch plan
+// with what pfg_run_batch needs of the planner and the elementwise pass, and the per-(model, proposal kernel, generator)
+// launch entry the ten instantiation units (pfg_inst_*.hip) define: those units compile in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -103,7 +102,7 @@ inline int fail(pfg_ctx *ctx, int code, const std::string &msg) {
 
 constexpr size_t kLdsLimit = 160 * 1024;
 
-// What runs a batch: filled by make_plan (pfgrad.hip), the one place where a kernel is chosen; launch_mkr only maps it
+// What runs a batch: filled by make_plan (pfg_plan.hip), the one place where a kernel is chosen; launch_mkr only maps it
 // onto an instantiation.
 enum class Family {
     None,
@@ -157,7 +156,7 @@ constexpr bool reg_score1_twin(int model, int rng, bool f64, int nt, int ppt, bo
 }
 
 // Launch of the planned kernel of one (model, proposal kernel, generator): defined (and explicitly instantiated) in
-// pfg_inst_*.hip via pfg_launch.hpp, declared here for the dispatcher in pfgrad.hip.
+// pfg_inst_*.hip via pfg_launch.hpp, declared here for the dispatcher in pfg_plan.hip.
 template <int MODEL, int KERNEL, int RNG>
 int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st);
 
@@ -167,10 +166,22 @@ int launch_kalman(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_proble
 // Launch of the FFBS window kernel (Family::KalmanFfbs), defined in pfg_ffbs.hip.
 int launch_ffbs(pfg_ctx *ctx, const LaunchPlan &p, int rng, int B, const pfg_dev_problem *dp, hipStream_t st);
 
-// Launches of the SGRLD and Gibbs updates of resident LGSSM chains, defined in pfg_chains.hip.
-int launch_sgrld_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, double eps,
-                        double Tscale, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st);
-int launch_gibbs_update(pfg_ctx *ctx, int B, double *theta, const double *outs, const pfg_prior_hyper &hy, uint64_t seed,
-                        uint64_t chain_offset, const uint64_t *step_ctr, hipStream_t st);
+// ---- pfg_plan.hip.  Who asks for a plan: the queries pfg_variant_name / pfg_scratch_bytes (a large batch of plain windows), pfg_run_batch
+// (N above the one-workgroup kernels, or PFGRAD_VARIANT=grid, runs as whole-GPU windows), pfg_launch_device* (one-workgroup
+// kernels only) and pfg_launch_device_grid* (whole-GPU windows).
+enum class Caller { Query, Batch, Device, Grid };
+LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B, bool traced,
+                     bool predictive = false, int t_max = 0, int phase = -1);
+int check_ids(pfg_ctx *ctx, int smoother, int model, int kernel, int dtype, int rng);
+int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, int B, const pfg_dev_problem *dp, hipStream_t st);
+// pfg_run_batch, Family::Grid: what every window of a whole-GPU batch must satisfy; plan.t_max becomes the longest T
+int check_grid_batch(pfg_ctx *ctx, LaunchPlan &plan, int B, const pfg_problem *ps);
+inline int state_dim(int model) { return model == PFG_MODEL_GARCH ? 2 : 1; }
+
+// ---- pfg_elementwise.hip.  The pass's device-only statistic matrices (its traces are the descriptor's trace_x /
+// trace_logw and trace_anc or trace_paris_J, redirected into the work arena)
+struct EwPlan { double *S0, *S1, *Sbar, *w, *mean, *stats; size_t Wd; int Nt; };
+// the second pass over the trajectory that window q recorded through its descriptor d (host copy), on ctx->stream
+int elementwise_pass(pfg_ctx *ctx, const pfg_problem &q, const pfg_dev_problem &d, const EwPlan &e);
 
 }  // namespace pfg_host

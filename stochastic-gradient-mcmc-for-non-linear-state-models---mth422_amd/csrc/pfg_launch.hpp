@@ -1,6 +1,6 @@
 // Kernel launch templates of libpfgrad.so.  Included ONLY by the instantiation units
 // (pfg_inst_*.hip), each of which instantiates launch_mkr for one (model, proposal kernel, generator).
-// They map a LaunchPlan (make_plan in pfgrad.hip) onto an instantiation and choose nothing themselves.
+// They map a LaunchPlan (make_plan in pfg_plan.hip) onto an instantiation and choose nothing themselves.
 #pragma once
 #include "pfg_host.hpp"
 #include "pfg_device.hpp"

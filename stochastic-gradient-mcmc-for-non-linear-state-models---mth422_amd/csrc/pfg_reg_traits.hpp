@@ -196,7 +196,7 @@ struct RegTraits {
     // waves per SIMD the register allocator should aim for: what LDS lets a CU hold anyway.
     // 256x4 fp64: ping-pong state is 80 KB/workgroup -> 2 workgroups (2 waves/SIMD); the single
     // buffer is 50 KB -> 3, which is worth a few spilled registers (measured +15 %).
-    // 4096 slots in 512 / 256 threads (A/B of round 3, no longer built: see the variant table in pfgrad.hip): ONE workgroup per CU
+    // 4096 slots in 512 / 256 threads (A/B of round 3, no longer built: see the variant table in pfg_plan.hip): ONE workgroup per CU
     static constexpr bool OCC_LDS4096 = SLOTS == 4096 && NT < 1024;
     // GARCH fp64 single buffer: six state arrays = 56.8 KB of LDS -> two workgroups per CU; give the allocator the 256 VGPRs (168 -> 32 spills)
     static constexpr bool OCC_TWO = MODEL == PFG_MODEL_GARCH && sizeof(REAL) == 8 && NT == 256 && PPT == 4 && !PP;
@@ -213,7 +213,7 @@ struct RegTraits {
     }
 
     // The LDS block; KERNEL does not enter and N only where the layout is not FAST.  The host evaluates this in a unit built
-    // without PFG_FAST_ALGEBRA (the largest math tables any build of the kernel units carries): see reg_lds in pfgrad.hip.
+    // without PFG_FAST_ALGEBRA (the largest math tables any build of the kernel units carries): see reg_lds in pfg_plan.hip.
     static constexpr int RED_SCAN = PPT * NW, RED_MAX = NW, RED_S = PFG_MAX_STAT * NW, RED_W0 = 8;   // doubles of reduction scratch
     static_assert(sizeof(int) * (NW + 1) <= sizeof(double) * RED_MAX, "the queue count fits behind red_maxf");
     __host__ __device__ static constexpr RegLdsLayout layout(int N) {

@@ -1,12 +1,15 @@
-// Several windows per resident chain and step: the reference's minibatch_size windows in each of num_sequences
-// sequences (sgmcmc_sampler.py:390-425, 1249-1283), for ChainEnsemble(minibatch_size=..., num_sequences=...).
+// The windows of resident chains: one per chain and step, or several -- the reference's minibatch_size windows in each of
+// num_sequences sequences (sgmcmc_sampler.py:390-425, 1249-1283), for ChainEnsemble(minibatch_size=..., num_sequences=...).
+//   sample_windows_kernel        one lane per chain: the chain's one window of S steps in a series of T.
 //   sample_windows_multi_kernel  one wave per chain: choose the chain's sequences (num_sequences = K distinct ones in
 //                                random order, or all of them in index order), then write the W = K_eff M window
 //                                descriptors of the chain, window w = k M + m being the m-th window in the k-th chosen
 //                                sequence, and each window's sequence length.  Keyed draws (see pfgrad.h).
 //   reduce_windows_kernel        one lane per chain: the W window records -> one record, in the reference's order of
 //                                operations (within a sequence, across sequences, then the T_total / S rescaling).
-// Neither is on the critical path: the particle filter of the C W windows is.  Built with -ffp-contract=off, so the
+// The two samplers' Philox counter and key layouts differ and both are pinned by the tests' host mirror: each stays as it
+// is.  The start draw and the clamped descriptor are written out in both: shared helpers changed their instructions.
+// None is on the critical path: the particle filter of the C W windows is.  Built with -ffp-contract=off, so the
 // reduction is the exact sequence of IEEE operations the reference's loops perform.
 #include "pfg_host.hpp"
 #include "pfg_math.hpp"
@@ -19,6 +22,30 @@ constexpr int kSampleNT = 64;
 constexpr int kReduceNT = 128;
 constexpr int kReduceCols = 5;      // out[0..3] score columns, out[4] log-likelihood
 constexpr uint32_t kSeqTag = 0x53000000u, kWinTag = 0x57000000u;    // "S": sequence draw j, "W": window w (< 2^24)
+
+__global__ void sample_windows_kernel(int B, pfg_dev_problem *__restrict__ probs, const double *__restrict__ y,
+                                      const double *__restrict__ wtab, int T, int S, int buffer, int strict,
+                                      uint64_t seed, uint64_t chain_offset, const uint64_t *__restrict__ step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const uint64_t chain = chain_offset + (uint64_t)b, ctr = step_ctr ? *step_ctr : 0ull;
+    const pfg::u32x4 r = pfg::philox4x32_10({(uint32_t)chain, (uint32_t)(chain >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32)},
+                                            (uint32_t)seed ^ 0x57494E44u, (uint32_t)(seed >> 32));   // "WIND"
+    const uint32_t range = strict ? (uint32_t)(T / S) : (uint32_t)(T - S + 1);
+    // 64 random bits times the range, high part: bias < range / 2^64
+    const uint64_t bits = ((uint64_t)r.x << 32) | r.y;
+    const int idx = (int)__umul64hi(bits, (uint64_t)range);
+    const int start = strict ? idx * S : idx;
+    // in 64 bits: start + S + buffer overflows int for any buffer the entry point accepts (as sample_windows_multi_kernel)
+    const int64_t left = start - buffer > 0 ? (int64_t)start - buffer : 0;
+    const int64_t right = (int64_t)start + S + buffer < T ? (int64_t)start + S + buffer : T;
+    pfg_dev_problem &P = probs[b];
+    P.y = y + left;
+    P.T = (int)(right - left);
+    P.t1 = (int)(start - left);
+    P.tL = (int)(start + S - left);
+    P.weights = wtab ? wtab + (size_t)start * S : nullptr;
+}
 
 __global__ __launch_bounds__(kSampleNT) void sample_windows_multi_kernel(
     int W, int n_seq, const int64_t *__restrict__ bounds, const int64_t *__restrict__ woffs, int K, int M,
@@ -103,6 +130,20 @@ __global__ __launch_bounds__(kReduceNT) void reduce_windows_kernel(int C, int K,
 }
 
 }  // namespace
+
+int pfg_sample_windows_device(pfg_ctx *ctx, int B, pfg_dev_problem *dev_probs, const double *y_dev,
+                              const double *weights_table_dev, int T, int S, int buffer, int strict,
+                              uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (B <= 0) return PFG_OK;
+    if (!dev_probs || !y_dev) return fail(ctx, PFG_ERR_INVALID, "pfg_sample_windows_device: NULL argument");
+    if (S < 1 || S > T || buffer < 0) return fail(ctx, PFG_ERR_INVALID, "need 1 <= S <= T and buffer >= 0");
+    PFG_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(sample_windows_kernel, dim3((B + 127) / 128), dim3(128), 0, (hipStream_t)hip_stream, B,
+                       dev_probs, y_dev, weights_table_dev, T, S, buffer, strict, seed, chain_offset, step_ctr);
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
+}
 
 int pfg_sample_windows_multi_device(pfg_ctx *ctx, int C, int n_seq, const int64_t *seq_bounds_dev,
                                     const int64_t *weight_offsets_dev, int num_sequences, int M,

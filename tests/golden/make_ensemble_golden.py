@@ -12,7 +12,7 @@ every call into the library.  For each case of CASES this records
   * weights_dev / bounds_dev / woffs_dev / seq_len_dev after the steps, and S, B, lambduh, W and the three flags;
   * the log of the library calls of the steps (method name, scalar arguments, pointers named as above, the hyper struct as
     bytes), taken by a forwarding recorder put in place of `ctx`.  `launch_device(...)` is logged as the
-    `launch_device_smoother(..., "nemeth", ...)` it is: both reach the same dispatch of csrc/pfgrad.hip.
+    `launch_device_smoother(..., "nemeth", ...)` it is: both reach the same dispatch of csrc/pfg_plan.hip.
 
 tests/test_gpu_ensemble_golden.py replays record_case() and compares everything for equality.  The fixture was written at
 the commit before ensemble.py resolved its settings, descriptors and windows once each; it only uses names both trees have.

@@ -2,16 +2,16 @@
 
 Every draw of the resident chain updates, the window samplers and the device-generator FFBS is a pure function of
 (seed, chain id, step counter, tag), so the host regenerates each one exactly and evaluates the formula the kernel
-documents in np.longdouble.  Each function names the csrc line it mirrors (paths relative to
+documents in np.longdouble.  Each function names the kernel or device helper it mirrors (files relative to
 stochastic-gradient-mcmc-for-non-linear-state-models---mth422_amd/csrc).
 
-  philox4x32_10         pfg_math.hpp:119 (Random123 Philox4x32-10)
-  sgld / sghmc / sgrld  pfgrad.hip:364-372, pfg_chains.hip:35-48: ctr {gid_lo, step_lo, step_hi ^ gid_hi, 0x5A11 | 0x5A12},
+  philox4x32_10         pfg_math.hpp philox4x32_10 (Random123 Philox4x32-10)
+  sgld / sghmc / sgrld  pfg_chains.hip sgld_update_kernel, chain_normals: ctr {gid_lo, step_lo, step_hi ^ gid_hi, 0x5A11 | 0x5A12},
                         key (seed_lo, seed_hi); normals A, C, Q, R (SVM A, Q, R; GARCH log_mu, logit_phi, logit_lambduh, LR)
-  gibbs                 pfg_chains.hip:77-83 ChainKey: tag 0x61B50000 | var << 8 | attempt, the boost draw var | 0x80
-  windows, one          pfgrad.hip:434-452: ctr {chain_lo, chain_hi, ctr_lo, ctr_hi}, key (seed_lo ^ 0x57494E44, seed_hi)
-  windows, multi        pfg_windows.hip:23-74: ctr {gid_lo, gid_hi ^ ctr_hi, ctr_lo, 0x53000000 | j or 0x57000000 | w}
-  lane generator        pfg_math.hpp:146-180: lane_rng_init then jsf32, 8 warm-up rounds
+  gibbs                 pfg_chains.hip ChainKey: tag 0x61B50000 | var << 8 | attempt, the boost draw var | 0x80
+  windows, one          pfg_windows.hip sample_windows_kernel: ctr {chain_lo, chain_hi, ctr_lo, ctr_hi}, key (seed_lo ^ 0x57494E44, seed_hi)
+  windows, multi        pfg_windows.hip sample_windows_multi_kernel: ctr {gid_lo, gid_hi ^ ctr_hi, ctr_lo, 0x53000000 | j or 0x57000000 | w}
+  lane generator        pfg_math.hpp: lane_rng_init then jsf32, 8 warm-up rounds
 """
 import numpy as np
 
@@ -27,7 +27,7 @@ ULP = 2.0 ** -52
 TOL_ULPS = 16.0
 
 
-# ---- Philox4x32-10: pfg_math.hpp:119-131 ---------------------------------------------------------------------------
+# ---- Philox4x32-10: pfg_math.hpp philox4x32_10 ---------------------------------------------------------------------------
 def philox4x32_10(ctr, key):
     """ctr: 4 uint32 arrays (or scalars), key: 2; returns 4 uint32 arrays, broadcast together."""
     x, y, z, w = (np.asarray(c, dtype=np.uint64) & MASK32 for c in ctr)
@@ -61,7 +61,7 @@ def chain_ids(C, chain_offset):
 
 # ---- transforms -----------------------------------------------------------------------------------------------------
 def normal_pair(a, b):
-    """Math<double, false>::normal_pair (pfg_math.hpp:390-396): u1 = (a + 0.5) 2^-32, angle b 2^-31 half-turns;
+    """Math<double, false>::normal_pair (pfg_math.hpp): u1 = (a + 0.5) 2^-32, angle b 2^-31 half-turns;
     evaluated in long double."""
     u1 = (np.asarray(a, dtype=LD) + LD(0.5)) / LD(4294967296.0)
     r = np.sqrt(LD(-2.0) * np.log(u1))
@@ -70,7 +70,7 @@ def normal_pair(a, b):
 
 
 def normal_pair_f32(a, b):
-    """Math<double, true>::normal_pair_f32 (pfg_math.hpp:365-374) with its inputs quantised as the kernel does --
+    """Math<double, true>::normal_pair_f32 (pfg_math.hpp) with its inputs quantised as the kernel does --
     (float)a + 0.5f and (b >> 8) / 2^24 in float32 -- and the transcendentals exact (long double): the kernel's
     v_log_f32 / v_sqrt_f32 / v_sin_f32 / v_cos_f32 units differ from this by their own error only."""
     a = np.asarray(a, dtype=U32)
@@ -83,7 +83,7 @@ def normal_pair_f32(a, b):
 
 
 def uniform53(a, b):
-    """pfg_chains.hip:85-87: ((a >> 5) 2^26 + (b >> 6) + 0.5) 2^-53, in (0, 1); exact."""
+    """uniform53 (pfg_chains.hip): ((a >> 5) 2^26 + (b >> 6) + 0.5) 2^-53, in (0, 1); exact."""
     a = np.asarray(a, dtype=np.uint64)
     b = np.asarray(b, dtype=np.uint64)
     return ((a >> np.uint64(5)).astype(LD) * LD(67108864.0) + (b >> np.uint64(6)).astype(LD) + LD(0.5)) / LD(2.0 ** 53)
@@ -101,7 +101,7 @@ def bits64(r):
     return [(int(x) << 32) | int(y) for x, y in zip(np.atleast_1d(r[0]).tolist(), np.atleast_1d(r[1]).tolist())]
 
 
-# ---- the four normals of a resident chain update: pfgrad.hip:366-378, pfg_chains.hip:41-48 --------------------------
+# ---- the four normals of a resident chain update: sgld_update_kernel, chain_normals (pfg_chains.hip) --------------------------
 def chain_normals(C, seed, chain_offset, step):
     """[C, 4] long-double normals in draw order (A, C, Q, R; SVM A, Q, R; GARCH its four variables)."""
     gid = chain_ids(C, chain_offset)
@@ -116,7 +116,7 @@ def chain_normals(C, seed, chain_offset, step):
     return np.column_stack([z0, z1, z2, z3])
 
 
-# ---- SGLD / SGHMC: pfgrad.hip:356-427 ---------------------------------------------------------------------------
+# ---- SGLD / SGHMC: sgld_update_kernel (pfg_chains.hip) ---------------------------------------------------------------------------
 SLOTS = {"svm": ("A", "LQ", "LR"), "lgssm": ("A", "C", "LQ", "LR"), "garch": ("log_mu", "logit_phi", "logit_lambduh", "LR")}
 # score column of each theta slot (pfgrad.h: SVM [LR, LQ, A], LGSSM [LR, LQ, C, A], GARCH [LR, log_mu, phi, lambduh])
 SCORE_COL = {"svm": (2, 1, 0), "lgssm": (3, 2, 1, 0), "garch": (1, 2, 3, 0)}
@@ -132,7 +132,7 @@ def _hy(hy):
 def prior_gradient(model, theta, hy):
     """grad log-prior at theta [C, P] (long double), theta order, and the sum of the absolute values of its terms
     (the scale of its rounding).  SVM / LGSSM: lgssm_chain_rules.grad_logprior (SVM has no C); GARCH: garch_var.py:152-165
-    as pfgrad.hip:412-416 states it."""
+    as sgld_update_kernel states it."""
     th = np.asarray(theta, dtype=LD)
     if model in ("svm", "lgssm"):
         full = th if model == "lgssm" else np.column_stack([th[:, 0], np.ones(len(th), dtype=LD), th[:, 1], th[:, 2]])
@@ -159,14 +159,14 @@ def prior_gradient(model, theta, hy):
 
 
 def _reflect(L, tol):
-    """reflect_chol (pfgrad.hip:356) with the other branch where L lies within tol of 0."""
+    """reflect_chol (pfg_chains.hip) with the other branch where L lies within tol of 0."""
     taken = np.where(L < 0, np.sqrt(L * L + LD(1e-16)), L)
     other = np.where(L < 0, L, np.sqrt(L * L + LD(1e-16)))
     return taken, other, np.abs(L) <= tol
 
 
 def _clip_A(A, tol):
-    """|A| > 0.9999 -> A * (0.9999 / |A|) (pfgrad.hip:399-400, pfg_chains.hip:30-31), with the other branch where |A|
+    """|A| > 0.9999 -> A * (0.9999 / |A|) (clip_ar, pfg_chains.hip), with the other branch where |A|
     lies within tol of 0.9999."""
     aa = np.abs(A)
     clipped = A * (LD(0.9999) / aa)
@@ -235,7 +235,7 @@ def sgld_expected(model, theta, ghat, hy, eps, T, seed, chain_offset, step, mome
 
 
 def sgrld_expected(theta, ghat, hy, eps, T, seed, chain_offset, step):
-    """One sgrld_update_kernel step (pfg_chains.hip:35-73) of C LGSSM chains, in long double, by the rules of
+    """One sgrld_update_kernel step (pfg_chains.hip) of C LGSSM chains, in long double, by the rules of
     lgssm_chain_rules: theta' = project(theta + sgrld_drift + sqrt(2 eps) sqrt(1 / T) noise_factor z)."""
     hy = _hy(hy)
     th = np.asarray(theta, dtype=float)[:, :4].astype(LD)
@@ -259,13 +259,13 @@ def sgrld_expected(theta, ghat, hy, eps, T, seed, chain_offset, step):
     return Expected(new, tol, other, amb)
 
 
-# ---- Gibbs: pfg_chains.hip:77-170 ----------------------------------------------------------------------------------
+# ---- Gibbs: gibbs_update_kernel (pfg_chains.hip) ----------------------------------------------------------------------------------
 K_MAX_ROUNDS = 64
 TIE_REL = 1e-12
 
 
 class ChainKeys(object):
-    """ChainKey of C chains (pfg_chains.hip:77-83, 140-141): draw(var, attempt) = Philox of
+    """ChainKey of C chains (pfg_chains.hip, as gibbs_update_kernel keys it): draw(var, attempt) = Philox of
     {gid_lo, step_lo, step_hi ^ gid_hi, 0x61B50000 | var << 8 | attempt} under (seed_lo, seed_hi)."""
 
     def __init__(self, gids, seed, step):
@@ -285,7 +285,7 @@ class ChainKeys(object):
 
 
 def gamma_draw(keys, var, shape):
-    """gamma_draw (pfg_chains.hip:89-112) of each chain: Marsaglia-Tsang on shape (shape + 1 below 1, then times
+    """gamma_draw (pfg_chains.hip) of each chain: Marsaglia-Tsang on shape (shape + 1 below 1, then times
     U^(1 / shape)), at most 64 keyed rounds, in long double.  Returns (x, tie, amp): `tie` marks a chain whose
     acceptance test differed by less than TIE_REL between its two sides in some round (double may decide it the other
     way), `amp` the relative-error amplification of the boost, 1 + |log(U) / shape|."""
@@ -327,7 +327,7 @@ def gamma_draw(keys, var, shape):
 
 
 def conjugate(df0, scale0, mean, var_col, spp, scp, scc, count):
-    """(df, scale, Spp, Scp, kappa) of one Wishart block: pfg_chains.hip:114-128 in long double.  kappa is the
+    """(df, scale, Spp, Scp, kappa) of one Wishart block: conjugate (pfg_chains.hip) in long double.  kappa is the
     condition of the scale's denominator 1 / scale0 + Scc - Scp^2 / Spp, the sum of its terms' magnitudes over its
     value: the double evaluation's relative error is kappa ulps, large when the path explains the series closely."""
     spp, scp, scc, count = (np.asarray(v, dtype=LD) for v in (spp, scp, scc, count))
@@ -341,7 +341,7 @@ def conjugate(df0, scale0, mean, var_col, spp, scp, scc, count):
 
 
 def gibbs_expected(stats, hy, seed, chain_offset, step):
-    """gibbs_update_kernel (pfg_chains.hip:130-155) of C chains with statistics stats [C, 8]: long double draws of
+    """gibbs_update_kernel (pfg_chains.hip) of C chains with statistics stats [C, 8]: long double draws of
     Qinv, Rinv and A | Q by the keyed attempts the kernel makes.  Returns (Expected, tie [C], shape_Q, shape_R)."""
     hy = _hy(hy)
     s = np.asarray(stats, dtype=float)
@@ -373,7 +373,7 @@ def gibbs_expected(stats, hy, seed, chain_offset, step):
 
 # ---- window samplers ---------------------------------------------------------------------------------------------
 def windows_one(C, T, S, buffer, strict, seed, chain_offset, step):
-    """sample_windows_kernel (pfgrad.hip:434-456): per chain (y offset, T, t1, tL, weights offset in doubles), int64."""
+    """sample_windows_kernel (pfg_windows.hip): per chain (y offset, T, t1, tL, weights offset in doubles), int64."""
     gid = chain_ids(C, chain_offset)
     s = int(step or 0)
     k0, k1 = split_seed(seed)
@@ -387,7 +387,7 @@ def windows_one(C, T, S, buffer, strict, seed, chain_offset, step):
 
 
 def windows_multi(C, bounds, K, M, S, buffer, strict, seed, chain_offset, step, weight_offsets=None):
-    """sample_windows_multi_kernel (pfg_windows.hip:23-74): [C * W] window records, chain-major (y offset in the
+    """sample_windows_multi_kernel (pfg_windows.hip): [C * W] window records, chain-major (y offset in the
     concatenated series, T, t1, tL, weights offset or -1, sequence length) and the chosen sequences [C, K]."""
     bounds = [int(v) for v in bounds]
     n_seq = len(bounds) - 1
@@ -430,7 +430,7 @@ def windows_multi(C, bounds, K, M, S, buffer, strict, seed, chain_offset, step, 
 
 
 def choose_sequences(bits, n_seq):
-    """The walk of sample_windows_multi_kernel (pfg_windows.hip:41-51): draw j is the r-th (r uniform on n_seq - j)
+    """The walk of sample_windows_multi_kernel (pfg_windows.hip): draw j is the r-th (r uniform on n_seq - j)
     sequence not chosen yet.  bits: the K 64-bit draws of the "S" tags."""
     chosen, srt = [], []
     for j, b in enumerate(bits):
@@ -444,7 +444,7 @@ def choose_sequences(bits, n_seq):
     return chosen
 
 
-# ---- the lane generator of the device-generator units: pfg_math.hpp:146-180 ----------------------------------------
+# ---- the lane generator of the device-generator units: lane_rng_init, pfg_math.hpp ----------------------------------------
 class LaneRng(object):
     """jsf32 lanes keyed by lane_rng_init(seed, stream, step, lane), vectorised over lanes."""
 
@@ -470,7 +470,7 @@ class LaneRng(object):
 
 
 def ffbs_normals(seed, stream, step, N, T):
-    """The T normals of each of N FFBS paths (pfg_ffbs.hip:126-137): lane s draws Box-Muller pairs on the f32 units, the
+    """The T normals of each of N FFBS paths (pfg_ffbs.hip): lane s draws Box-Muller pairs on the f32 units, the
     first variate for one time, the second for the next, from t = T - 1 down.  Returns z [T * N] in the reference's
     order (z[k N + s]: path s at time T - 1 - k), long double."""
     g = LaneRng(seed, stream, step, np.arange(N))

@@ -1,10 +1,12 @@
 #!/usr/bin/env python
 """Compare the device listings of two builds kernel by kernel (no GPU needed).
 
-    python tools/compare_listings.py DIR_A DIR_B [--exact 'pf_reg_kernel<0, 0, double, 256, 4, 1, false, 0, false, false>' ...]
+    python tools/compare_listings.py DIR_A DIR_B [--pool] [--exact 'pf_reg_kernel<0, 0, double, 256, 4, 1, false, 0, false, false>' ...]
 
 DIR_A / DIR_B hold one `hipcc --cuda-device-only -S` listing per instantiation unit (the recipe of
-tools/isa_histogram.py::listing without -DPFG_ISA_MARKERS), under the same file names.  Per kernel, one of
+tools/isa_histogram.py::listing without -DPFG_ISA_MARKERS), under the same file names -- or, with --pool, under any
+names: the kernels of all listings of a directory are pooled by name, so one that moved to another unit is still
+compared (a name defined twice in a directory is an error).  Per kernel, one of
   identical   the same instructions in the same order (labels, symbols of the unit id and source paths aside);
   commuted    ... up to the order of the source operands of commutative instructions;
   reordered   the same multiset of instructions (commutative operands unordered; s_nop / s_waitcnt counted apart and
@@ -38,9 +40,11 @@ def kernels(path):
         elif name and line and not line.startswith(".") and not line.endswith(":"):
             mn, _, ops = line.partition(" ")
             body.append((mn, re.sub(r"\.LBB\d+_\d+", ".LBB", ops.strip())))
+    if not out:         # a unit without device functions (c++filt would wait for names on its input)
+        return {}
     names = subprocess.run(["c++filt"] + list(out), stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()
     assert len(names) == len(out), "c++filt returned {0} names for {1} symbols".format(len(names), len(out))
-    return {n.replace("void pfg::", "").split("(")[0]: out[k] for k, n in zip(out, names)}
+    return {n.replace("void pfg::", "").replace("(anonymous namespace)::", "").split("(")[0]: out[k] for k, n in zip(out, names)}
 
 
 def canon(inst):
@@ -80,10 +84,23 @@ def main():
     ap.add_argument("dir_a")
     ap.add_argument("dir_b")
     ap.add_argument("--exact", nargs="*", default=[], help="kernels that must be identical or commuted")
+    ap.add_argument("--pool", action="store_true", help="pool the kernels of all listings of each directory by name")
     args = ap.parse_args()
     bad, tally = 0, collections.Counter()
-    for f in sorted(x for x in os.listdir(args.dir_a) if x.endswith(".s")):
-        ka, kb = kernels(os.path.join(args.dir_a, f)), kernels(os.path.join(args.dir_b, f))
+
+    def pooled(d):
+        out = {}
+        for f in sorted(x for x in os.listdir(d) if x.endswith(".s")):
+            for name, body in kernels(os.path.join(d, f)).items():
+                if name in out:
+                    raise SystemExit("{0} is defined twice in {1}".format(name, d))
+                out[name] = body
+        return out
+
+    pairs = [("pooled", pooled(args.dir_a), pooled(args.dir_b))] if args.pool else \
+            [(f, kernels(os.path.join(args.dir_a, f)), kernels(os.path.join(args.dir_b, f)))
+             for f in sorted(x for x in os.listdir(args.dir_a) if x.endswith(".s"))]
+    for f, ka, kb in pairs:
         for name in sorted(set(ka) | set(kb)):
             v, note = verdict(ka[name], kb[name]) if name in ka and name in kb else ("DIFFERENT", "in one build only")
             tally[v] += 1
