@@ -287,6 +287,8 @@ _REFUSALS = [
     ("n2", 1, dict(smoother=0), _INV, "problem 1: pf = 'poyiadjis_N2' cannot share a batch with other smoothers"),
     ("n2", 1, dict(N=16385), _UNS, "problem 1: pf = 'poyiadjis_N2' is implemented for N <= 16384"),
     ("n2_ew", 1, dict(N=5000), _UNS, "problem 1: elementwise statistics with pf = 'poyiadjis_N2' are implemented for N <= 4096"),
+    # the edge: ews_n2_step_kernel holds bw[4096] in LDS
+    ("n2_ew", 1, dict(N=4097), _UNS, "problem 1: elementwise statistics with pf = 'poyiadjis_N2' are implemented for N <= 4096"),
     ("n2", 1, dict(stat=3), _INV, "problem 1: Only can use pf = 'filter' since we are filtering"),
     ("paris", 1, dict(smoother=0), _INV, "problem 1: pf = 'paris' cannot share a batch with other smoothers"),
     ("paris", 1, dict(Ntilde=0), _INV, "problem 1: Ntilde must be in [1, 64]"),

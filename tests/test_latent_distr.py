@@ -104,15 +104,19 @@ def test_elementwise_pass_vs_oracle_nemeth(model, kernel, N, lam):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("model,kernel", [("svm", "prior"), ("garch", "optimal"), ("lgssm", "optimal")])
-@pytest.mark.parametrize("N,Ntilde,R", [(64, 2, 4), (300, 3, 2), (1100, 2, 3)])
-def test_elementwise_pass_vs_oracle_paris(model, kernel, N, Ntilde, R):
+@pytest.mark.parametrize("N,Ntilde,R,T,t1,tL", [
+    pytest.param(64, 2, 4, 8, 1, 7, id="64-2-4"), pytest.param(300, 3, 2, 8, 1, 7, id="300-3-2"),
+    pytest.param(1100, 2, 3, 8, 1, 7, id="1100-2-3"),
+    # Wd = 258: column block 1 of ews_step_kernel with Nt = 2 parents per child (the trace_paris_J buffer does not
+    # leave the device, so PaRIS stays on the oracle)
+    pytest.param(64, 2, 2, 90, 2, 88, id="64-2-2-L86")])
+def test_elementwise_pass_vs_oracle_paris(model, kernel, N, Ntilde, R, T, t1, tL):
     """pf='paris' (what the exchange-rate demos call predict(target='latent', kind='pf') with): chain of
     trust as for the PaRIS gradient -- the oracle in np.random order is bit-exact vs the reference
     (test_oracle_elementwise_matches_reference); the same oracle code on uniforms addressed by
     (timestep, j, round, particle) is what the kernel + elementwise pass are compared with here."""
     from sgmcmc_ssm_amd import _capi
     rs = np.random.RandomState(N * 3 + Ntilde)
-    T, t1, tL = 8, 1, 7
     p = default_params(model)
     np.random.seed(4)
     y = GEN[model](T=T, parameters=p)["observations"].reshape(-1)
@@ -154,6 +158,30 @@ def test_latent_var_distr_paris_no_accept_reject_seed_for_seed(model, N, T):
     kw = dict(kernel=po.DEFAULT_KERNEL[model], pf="paris", t1=2, tL=T - 3, accept_reject=False,
               prior_mean=float(np.asarray(pm).reshape(-1)[0]), prior_var=float(np.asarray(pv).reshape(-1)[0]))
     rm, rc = po.latent_var_distr(model, p.theta(), y.reshape(-1), N, rng=rng, **kw)
+    np.testing.assert_allclose(xm, rm, rtol=1e-9, atol=1e-9)
+    np.testing.assert_allclose(xc, rc, rtol=1e-8, atol=1e-9)
+    assert np.random.random_sample() == rng.random_sample()
+
+
+@pytest.mark.gpu
+def test_latent_var_distr_whole_series_seed_for_seed():
+    """The real caller's width: pf_latent_var_distr(pf='poyiadjis_N') over a whole series of T = 200, Wd = 600 columns
+    (three column blocks of the elementwise pass, the last one partly filled), against the oracle on the same seed."""
+    from sgmcmc_ssm_amd.models.lgssm import LGSSMHelper
+    model, N, T = "lgssm", 120, 200
+    np.random.seed(3)
+    p = default_params(model)
+    y = GEN[model](T=T, parameters=p)["observations"]
+    fm = dict(log_constant=0.0, mean_precision=np.zeros(1), precision=np.eye(1) / 1.7)
+    helper = LGSSMHelper(n=1, m=1, forward_message=fm)
+    np.random.seed(78)
+    xm, xc = helper.pf_latent_var_distr(observations=y, parameters=p, pf="poyiadjis_N", N=N)
+    rng = np.random.RandomState(78)
+    pm, pv, _ = helper._prior_x(fm, p)
+    kw = dict(kernel=po.DEFAULT_KERNEL[model], pf="poyiadjis_N", t1=0, tL=T,
+              prior_mean=float(np.asarray(pm).reshape(-1)[0]), prior_var=float(np.asarray(pv).reshape(-1)[0]))
+    rm, rc = po.latent_var_distr(model, p.theta(), y.reshape(-1), N, rng=rng, **kw)
+    assert xm.shape == (T, 1) and xc.shape == (T, 1, 1)
     np.testing.assert_allclose(xm, rm, rtol=1e-9, atol=1e-9)
     np.testing.assert_allclose(xc, rc, rtol=1e-8, atol=1e-9)
     assert np.random.random_sample() == rng.random_sample()
