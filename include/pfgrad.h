@@ -100,7 +100,25 @@ enum pfg_smoother { PFG_SMOOTHER_NEMETH = 0, PFG_SMOOTHER_FILTER = 1, PFG_SMOOTH
                      * the paths, [T][N] with t ascending; no other trace or final output.  `scratch`: 16 (T + 1) bytes
                      * rounded up to 256, from the whole buffer (pfg_run / pfg_run_batch allocate it; resident callers
                      * supply it).  A batch is all-FFBS or FFBS-free. */
-                    PFG_SMOOTHER_KALMAN_FFBS = 7 };
+                    PFG_SMOOTHER_KALMAN_FFBS = 7,
+                    /* EXTENSION (not in the reference): NEMETH (any lambduh; poyiadjis_N is lambduh = 1.0) with STRATIFIED
+                     * resampling: child r of a timestep searches the unchanged CDF with u'_r = (r + U_r) / N, one
+                     * U_r ~ U[0, 1) per child, r the particle index in the reference's order.  Valid in descriptors and
+                     * launches; stat = SCORE / SUFF / NONE; both generators, f64 and f32 state, N <= 16384: the 256 x 4
+                     * LDS-resident instantiation "stratified256x4" for N <= 1024, above it "mem1024_stratified" (REPLAY)
+                     * or "big4096_stratified" / "big16384_stratified" (DEVICE: the uniforms come out sorted, so the
+                     * multinomial kernel's spacing draws and second scan are compiled out).
+                     * REPLAY contract: U_r is the caller's u[t N + r] -- the stream a multinomial window consumes, so a
+                     * NumPy generator is left where the multinomial call leaves it -- and, in fp64,
+                     *     u' = ((double)r + u[t*N + r]) / (double)N         (one addition, one IEEE division)
+                     * then the unchanged cumsum; /= last; searchsorted(side='right').  The REPLAY units are built with
+                     * -ffp-contract=off: this is exactly NumPy's (np.arange(N) + u[t]) / N, and the pinned oracle fed
+                     * those uniforms is the specification, ancestors included.  DEVICE: U_r is one 32-bit uniform of the
+                     * lane that owns child r (rec_ud records u'_r in traced launches).
+                     * A batch is all-stratified or stratified-free (INVALID); together with FILTER, PARIS or POYIADJIS_N2
+                     * windows, with PFG_STAT_PREDICTIVE or with N > 16384: UNSUPPORTED, the message says which.  Whole-GPU
+                     * windows and elementwise statistics are not built for it. */
+                    PFG_SMOOTHER_NEMETH_STRATIFIED = 8 };
 /* additive statistic: *_complete_data_loglike_gradient (score), *_sufficient_statistics, zero */
 enum pfg_stat { PFG_STAT_SCORE = 0, PFG_STAT_SUFF = 1, PFG_STAT_NONE = 2,
                 /* k-step-ahead predictive log-likelihoods accumulated with the filter's
@@ -312,7 +330,7 @@ int pfg_launch_device_traced(pfg_ctx *ctx, int model, int kernel, int dtype, int
                              int n_max, int B, const pfg_dev_problem *dev_probs, void *hip_stream);
 int pfg_last_traced(pfg_ctx *ctx);
 /* as pfg_launch_device for a batch whose descriptors all have smoother = `smoother`
- * (PFG_SMOOTHER_PARIS, _NEMETH_SYSTEMATIC and _POYIADJIS_N2 have their own kernel instantiations;
+ * (PFG_SMOOTHER_PARIS, _NEMETH_SYSTEMATIC, _NEMETH_STRATIFIED and _POYIADJIS_N2 have their own kernel instantiations;
  * the plain entry point serves NEMETH / FILTER).  PFG_SMOOTHER_KALMAN: the exact-score kernel, one lane per
  * descriptor (kernel, rng and n_max are ignored; every descriptor brings its scratch).  PFG_SMOOTHER_KALMAN_FFBS: the
  * FFBS kernel, one workgroup per descriptor (n_max = the most paths N of a descriptor picks the workgroup size; every
@@ -405,7 +423,8 @@ int pfg_reduce_windows_device(pfg_ctx *ctx, int C, int num_seq_windows, int M, c
  * kernel (N <= 16384) or the whole-GPU window (N <= 4194304) needs for (model, dtype, rng, N); 0 when an LDS-resident
  * variant serves this size, -1 when N is above the supported maximum */
 int64_t pfg_scratch_bytes(int model, int dtype, int rng, int N);
-/* the same for a resident batch of `smoother` windows (PFG_SMOOTHER_NEMETH .. PFG_SMOOTHER_POYIADJIS_N) launched
+/* the same for a resident batch of `smoother` windows (PFG_SMOOTHER_NEMETH .. PFG_SMOOTHER_POYIADJIS_N, or
+ * PFG_SMOOTHER_NEMETH_STRATIFIED: the large-N kernels' state for 1024 < N <= 16384) launched
  * through pfg_launch_device_smoother: what that launch's plan sizes per descriptor -- PFG_SMOOTHER_PARIS: the
  * paris_mem1024 state for 1024 < N <= 16384, 0 where an LDS-resident variant serves -- and -1 above the one-workgroup
  * kernels' maximum (16384), for another smoother id, or for a combination that launch refuses */

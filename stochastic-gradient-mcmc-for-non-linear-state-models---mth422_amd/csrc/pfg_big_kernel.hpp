@@ -21,15 +21,22 @@ namespace pfg {
 //    immediates, slots past N hold a sentinel) and two chunks are in flight per iteration (two independent
 //    search / gather chains per lane, and both normals of a Box-Muller pair are used).
 // REPLAY (the reference's own uniforms), PaRIS and the predictive statistic stay on pf_mem_kernel.
+//  * STRAT = true, the STRATIFIED twin (PFG_SMOOTHER_NEMETH_STRATIFIED): child i's uniform is (i + U_i) / N with U_i one
+//    32-bit uniform of the lane that owns child i -- sorted by construction, so everything the sorted order costs the
+//    multinomial kernel is compiled out: the spacing draw and its -log, the second prefix scan with its two LDS arrays
+//    (red_scanE / red_offE) and its share of barrier 2b's wave, the generator snapshot and the recomputation of the
+//    spacings (one more -log and one more wave scan per child) in the sweep.  CDF, search, chunks in flight and gather
+//    are the same code.
 // ------------------------------------------------------------------------------------
-template <typename REAL>
+template <typename REAL, bool STRAT = false>
 __host__ __device__ inline size_t big_kernel_lds_bytes(int NP2) {
-    // CDF (padded) | 4 x [chunks * waves] scan totals / offsets (weights, spacings) | wave maxima | S partials | tables
-    return ((size_t)NP2 + NP2 / 32) * 8 + (size_t)(4 * (NP2 / MEM_NT) * MEM_NW + MEM_NW + PFG_MAX_STAT * MEM_NW + 8) * 8 +
+    // CDF (padded) | 4 x [chunks * waves] scan totals / offsets (weights, spacings; STRAT: 2 x, weights only) | wave maxima |
+    // S partials | tables
+    return ((size_t)NP2 + NP2 / 32) * 8 + (size_t)((STRAT ? 2 : 4) * (NP2 / MEM_NT) * MEM_NW + MEM_NW + PFG_MAX_STAT * MEM_NW + 8) * 8 +
            tab_bytes<REAL, PFG_RNG_DEVICE, true>();
 }
 
-template <int MODEL, int KERNEL, typename REAL, int NP2>
+template <int MODEL, int KERNEL, typename REAL, int NP2, bool STRAT = false>
 __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *__restrict__ probs) {
     constexpr int RNG = PFG_RNG_DEVICE;
     constexpr int NS = ModelDims<MODEL>::NS;
@@ -64,10 +71,10 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
 
     double *cdf = reinterpret_cast<double *>(smem);                 // [NP2 + NP2/32] physical
     double *red_scan = cdf + (NP2 + NP2 / 32);                      // [CH2*NW] (chunk, wave) totals of the weights
-    double *red_scanE = red_scan + CH2 * NW;                        // [CH2*NW] ... of the exponential spacings
-    double *red_off = red_scanE + CH2 * NW;                         // [CH2*NW] exclusive offsets of red_scan
-    double *red_offE = red_off + CH2 * NW;                          // [CH2*NW] ... of red_scanE
-    double *red_max = red_offE + CH2 * NW;                          // [NW]
+    double *red_scanE = red_scan + CH2 * NW;                        // [CH2*NW] ... of the exponential spacings (not STRAT)
+    double *red_off = STRAT ? red_scanE : red_scanE + CH2 * NW;     // [CH2*NW] exclusive offsets of red_scan
+    double *red_offE = red_off + CH2 * NW;                          // [CH2*NW] ... of red_scanE (not STRAT)
+    double *red_max = STRAT ? red_offE : red_offE + CH2 * NW;       // [NW]
     float *red_maxf = reinterpret_cast<float *>(red_max);
     double *red_S = red_max + NW;                                   // [H*NW]
     double *red_W = red_S + PFG_MAX_STAT * NW;                      // [8]: W, total of the spacings
@@ -147,6 +154,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
 #pragma unroll
     for (int h = 0; h < H; ++h) { filt[h] = 0.0; S[h] = 0.0; }
     double m = 0.0, W = (double)N;
+    [[maybe_unused]] const double invN = 1.0 / (double)N;           // STRAT
 
     for (int t = 0; t <= T; ++t) {
         // ---- (A) max of the log weights (f32-rounded shift, see wave_max) -------------------
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
         }
         // ---- (B,C) weights and exponential spacings: one wave scan per 1024-particle chunk each ----
         const bool needS = needS_every || (t == T);
-        const LaneRng rngE = rng;                 // the sweep recomputes this step's spacings from here
+        [[maybe_unused]] const LaneRng rngE = rng;          // the sweep recomputes this step's spacings from here
         float e_extra = 0.0f;
         {
             double part[H];
@@ -190,7 +198,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
                     const double inc = wave_incl_scan(p);
                     if (v) cdf[cdf_phys(i)] = inc;                  // wave-local; globalised in (D)
                     if (lane == WAVE - 1) red_scan[j * NW + wave] = inc;
-                    if (t < T) {
+                    if (!STRAT && t < T) {
                         // spacing of child i's sorted uniform (valid children only: N uniforms, N + 1 spacings)
                         const float ef = spacing_f32(rng.next());
                         const double incE = wave_incl_scan(v ? (double)ef : 0.0);
@@ -198,7 +206,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
                     }
                 }
             }
-            if (t < T) e_extra = spacing_f32(rng.next());           // spacing N + 1: part of the total only
+            if (!STRAT && t < T) e_extra = spacing_f32(rng.next());           // spacing N + 1: part of the total only
             if (needS) {
 #pragma unroll
                 for (int h = 0; h < H; ++h) {
@@ -208,9 +216,9 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
             }
         }
         __syncthreads();                                                        // barrier 2
-        if (wave < 2) {
+        if (wave < (STRAT ? 1 : 2)) {
             // exclusive offsets of the nchunk*NW (chunk, wave) totals (<= 256): 4 per lane + one wave scan.
-            // Wave 0: weights; wave 1: spacings.
+            // Wave 0: weights; wave 1: spacings (not STRAT).
             const double *src = wave == 0 ? red_scan : red_scanE;
             double *dst = wave == 0 ? red_off : red_offE;
             const int ntot = nchunk * NW;
@@ -234,7 +242,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
         __syncthreads();                                                        // barrier 2b
         W = uniform_f64(red_W[0]);
         const double invW = uniform_f64(1.0 / W);
-        const double invEtot = (t < T) ? uniform_f64(1.0 / red_W[1]) : 0.0;
+        [[maybe_unused]] const double invEtot = (!STRAT && t < T) ? uniform_f64(1.0 / red_W[1]) : 0.0;
         if (needS) {
 #pragma unroll
             for (int h = 0; h < H; ++h) {
@@ -270,7 +278,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
         const double wt = (inside && wv) ? wv[t - t1] : 1.0;
         const bool use_stat = inside && (stat != PFG_STAT_NONE);
         // ---- (E..H) two chunks per iteration: search, gather parent (L2), propose, publish ----
-        LaneRng rngS = rngE;                      // regenerates the words the scan above turned into spacings
+        [[maybe_unused]] LaneRng rngS = rngE;     // regenerates the words the scan above turned into spacings
         auto sweep = [&](auto stat_tag) {
             constexpr int STAT = decltype(stat_tag)::value;
             for (int j0 = 0; j0 < nchunk; j0 += G) {
@@ -285,11 +293,16 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
                     a[g] = 0;
                     u[g] = 2.0;
                     if (j0 + g < nchunk) {
+                        if constexpr (STRAT) {
+                            // child i's uniform = (i + U_i) / N straight from its lane's generator
+                            u[g] = ((double)i[g] + u01_32(rng.next())) * invN;
+                        } else {
                         // child i's uniform = the sorted uniform of rank i: the same word, spacing and wave scan
                         // as in (B,C), plus this (chunk, wave)'s offset
                         const float ef = spacing_f32(rngS.next());
                         const double incE = wave_incl_scan(v[g] ? (double)ef : 0.0);
                         u[g] = (incE + red_offE[(j0 + g) * NW + wave]) * invEtot;
+                        }
                         if (P.trace_x && P.rec_ud && v[g]) P.rec_ud[(size_t)t * N + i[g]] = u[g];
                     }
                 }

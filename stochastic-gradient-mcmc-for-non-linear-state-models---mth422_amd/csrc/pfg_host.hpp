@@ -109,6 +109,9 @@ enum class Family {
     Reg,           // LDS-resident kernel, entry (nt, ppt, pp)
     Paris, N2,     // its PaRIS / O(N^2) Poyiadjis instantiations, 256 x ppt; nt = MEM_NT: the large-N kernel's PaRIS one
     Systematic,    // its systematic-resampling instantiation (device generator), 256 x 4
+    Stratified,    // stratified resampling (PFG_SMOOTHER_NEMETH_STRATIFIED), three size classes: the LDS-resident 256 x 4
+                   // instantiation (n_max <= 1024; np2 = 0), above it the large-N kernel's twin (REPLAY; lw4: N <= 4096) or
+                   // the fast large-N kernel's twin (device generator, np2 slots)
     Mem,           // large-N kernel (state in an HBM scratch); lw4: N <= 4096, log-weights in registers
     Big,           // large-N kernel, device-generator fast path for np2 particle slots
     Grid,          // whole-GPU window above the one-workgroup kernels' maximum (pfg_grid_kernel.hpp), tile class (ppt, kmax)

@@ -144,6 +144,22 @@ int launch_big(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *
     return launch_big_one<MODEL, KERNEL, REAL, 16384>(ctx, p, B, dp, st);
 }
 
+// stratified resampling: the 256 x 4 LDS-resident instantiation (single buffer in fp64, ping-pong in f32, as systematic;
+// one instantiation that honours trace buffers serves traced and production launches), the large-N kernel's twin (REPLAY)
+// or the fast large-N kernel's twin (device generator)
+template <int MODEL, int KERNEL, typename REAL, int RNG>
+int launch_stratified(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
+    if (p.np2 == 0 && p.nt == 256)
+        return launch_one_t<MODEL, KERNEL, REAL, 256, 4, RNG, sizeof(REAL) == 4, pfg::MODE_STRATIFIED>(ctx, p, B, dp, st);
+    if constexpr (RNG == PFG_RNG_REPLAY) {
+        if (p.lw4) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, true, false, true>, pfg::MEM_NT, p, B, dp, st);
+        return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, false, false, true>, pfg::MEM_NT, p, B, dp, st);
+    } else {
+        if (p.np2 == 4096) return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 4096, true>, pfg::MEM_NT, p, B, dp, st);
+        return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 16384, true>, pfg::MEM_NT, p, B, dp, st);
+    }
+}
+
 // every kernel of one (model, proposal kernel, generator): explicitly instantiated in
 // pfg_inst_<model>_<kernel>_<rng>.hip.  The DEVICE-generator units are compiled with
 // -ffp-contract=fast (no operation-order parity to keep there), the REPLAY units with
@@ -181,6 +197,8 @@ int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *
             if (p.f64) return PFG_GRID_CASE(double);
             return PFG_GRID_CASE(float);
 #undef PFG_GRID_CASE
+        case Family::Stratified:    // (last: the kernels above keep their places in the code object)
+            return p.f64 ? launch_stratified<MODEL, KERNEL, double, RNG>(ctx, p, B, dp, st) : launch_stratified<MODEL, KERNEL, float, RNG>(ctx, p, B, dp, st);
         case Family::None:
             break;
     }

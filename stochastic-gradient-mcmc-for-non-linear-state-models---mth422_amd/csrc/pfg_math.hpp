@@ -10,7 +10,7 @@ namespace pfg {
 
 constexpr int WAVE = 64;
 // kernel instantiation modes beyond the plain filter / Nemeth path
-constexpr int MODE_PLAIN = 0, MODE_PARIS = 1, MODE_SYSTEMATIC = 2, MODE_N2 = 3;
+constexpr int MODE_PLAIN = 0, MODE_PARIS = 1, MODE_SYSTEMATIC = 2, MODE_N2 = 3, MODE_STRATIFIED = 4;
 constexpr double LOG_2PI = 1.8378770664093453;   // log(2*pi)
 
 // Pointers that arrive inside a descriptor (pfg_dev_problem) are generic to the compiler, and a generic access is a FLAT

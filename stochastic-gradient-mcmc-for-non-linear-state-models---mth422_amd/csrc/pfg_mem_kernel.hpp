@@ -84,9 +84,13 @@ __host__ __device__ inline size_t mem_kernel_lds_bytes(int N) {
 // 37.9 -> 32.1 ms per 402 windows (-15 %; the N = 10^4 kernel gains nothing: profiles/r04_ab_score1_twin.txt).  REPLAY
 // units are built without contraction: bitwise the general kernel's numbers.  A window that is not that estimator gets NaNs,
 // and so does a PFG_STAT_PREDICTIVE window in the LW4 kernel.
-template <int MODEL, int KERNEL, typename REAL, int RNG, bool PARIS = false, bool LW4 = false, bool SCORE1 = false>
+// STRAT (PFG_SMOOTHER_NEMETH_STRATIFIED, REPLAY): child i searches with (i + u[t][i]) / N instead of u[t][i] -- one
+// addition and one IEEE division on the loaded uniform, nothing else differs.  A template argument, not a branch on the
+// descriptor: the instantiations that exist keep their code, registers and numbers to the bit.
+template <int MODEL, int KERNEL, typename REAL, int RNG, bool PARIS = false, bool LW4 = false, bool SCORE1 = false, bool STRAT = false>
 __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *__restrict__ probs) {
     static_assert(!(PARIS && LW4), "LW4 is a variant of the plain kernel");
+    static_assert(!STRAT || (RNG == PFG_RNG_REPLAY && !PARIS && !SCORE1), "the stratified twin is a REPLAY instantiation of the plain kernel");
     static_assert(!SCORE1 || LW4, "the score-only twin exists for the N <= 4096 variant");
     constexpr int NS = ModelDims<MODEL>::NS;
     constexpr int H = ModelDims<MODEL>::H;
@@ -482,6 +486,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
                 REAL z;
                 if (RNG == PFG_RNG_REPLAY) { u = uv[(size_t)t * N + ii]; z = (REAL)zv[(size_t)t * N + ii]; }
                 else { REAL zb; u = u01_32(rng.next()); mth.normal_pair(rng.next(), rng.next(), z, zb); }
+                if (STRAT) u = ((double)ii + u) / (double)N;
                 int pos = 0;
                 for (int step = np2 >> 1; step >= 1; step >>= 1) {
                     const int probe = step - 1 + (step >= 32 ? (step >> 5) - 1 : 0);
@@ -586,6 +591,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
                     if (LW4 && RNG == PFG_RNG_REPLAY && PFG_MEM_PREFETCH) { u[g] = upre[g]; z[g] = zpre[g]; }
                     else if (RNG == PFG_RNG_REPLAY) { u[g] = uv[(size_t)t * N + ii]; z[g] = (REAL)zv[(size_t)t * N + ii]; }
                     else { REAL zb; u[g] = u01_32(rng.next()); mth.normal_pair(rng.next(), rng.next(), z[g], zb); }
+                    if (STRAT) u[g] = ((double)ii + u[g]) / (double)N;
                     pos[g] = 0;
                 }
                 for (int step = np2 >> 1; step >= 1; step >>= 1) {

@@ -88,7 +88,7 @@ const ParisVariant kParisVariants[] = { {64, 2, "paris64x2", reg_lds<64, 2, true
                                         {256, 1, "paris256x1", reg_lds<256, 1, true, pfg::MODE_PARIS>},
                                         {256, 4, "paris256x4", reg_lds<256, 4, true, pfg::MODE_PARIS>} };
 
-// The kernel of a plain batch (no PaRIS / systematic / O(N^2)) of `batch` windows of up to n_max particles: Reg with the
+// The kernel of a plain batch (no PaRIS / systematic / stratified / O(N^2)) of `batch` windows of up to n_max particles: Reg with the
 // kVariants index v, Mem, Grid, or None above every kernel.  force = PFGRAD_VARIANT: <tag> forces a variant (tuning /
 // tests) when it can hold n_max.
 Family pick_plain(int model, int dtype, int rng, int n_max, int batch, const char *force, int &v) {
@@ -165,6 +165,7 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
     else if (smoother == PFG_SMOOTHER_KALMAN_FFBS) p.family = Family::KalmanFfbs;
     else if (smoother == PFG_SMOOTHER_PARIS) p.family = Family::Paris;
     else if (smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) p.family = Family::Systematic;
+    else if (smoother == PFG_SMOOTHER_NEMETH_STRATIFIED) p.family = Family::Stratified;
     else if (smoother == PFG_SMOOTHER_POYIADJIS_N2) p.family = Family::N2;
     else if (predictive && n_max <= pfg::MEM_MAX_N) p.family = Family::Mem;
     else {
@@ -253,6 +254,30 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
             if (n_max > 1024) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling is built for N <= 1024");
             p.lds = (p.f64 ? reg_lds<256, 4, false, pfg::MODE_SYSTEMATIC> : reg_lds<256, 4, true, pfg::MODE_SYSTEMATIC>)(model, dtype, rng, n_max);
             if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling: state does not fit LDS");
+            break;
+        case Family::Stratified:
+            // three size classes, each a twin of the kernel that serves multinomial windows of that size (256 x 4 as
+            // systematic: single buffer in fp64, ping-pong in f32)
+            if (predictive) return refuse(p, PFG_ERR_UNSUPPORTED, "stratified resampling is not built for the predictive statistic");
+            if (n_max > pfg::MEM_MAX_N) return refuse(p, PFG_ERR_UNSUPPORTED, "stratified resampling is built for N <= 16384");
+            if (n_max <= 1024) {
+                p.name = "stratified256x4";
+                p.nt = 256; p.ppt = 4; p.pp = !p.f64;
+                p.lds = (p.f64 ? reg_lds<256, 4, false, pfg::MODE_STRATIFIED> : reg_lds<256, 4, true, pfg::MODE_STRATIFIED>)(model, dtype, rng, n_max);
+                if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, "stratified resampling: state does not fit LDS");
+            } else if (rng == PFG_RNG_DEVICE) {
+                p.np2 = n_max <= 4096 ? 4096 : 16384;
+                p.name = p.np2 == 4096 ? "big4096_stratified" : "big16384_stratified";
+                p.nt = pfg::MEM_NT;
+                p.lds = with_types(model, dtype, rng, [&](auto, auto, auto real, auto) { return pfg::big_kernel_lds_bytes<decltype(real), true>(p.np2); });
+                p.scratch = mem_scratch(false);
+            } else {
+                p.lw4 = n_max <= 4096;
+                p.name = "mem1024_stratified";
+                p.nt = pfg::MEM_NT;
+                p.lds = mem_lds();
+                p.scratch = mem_scratch(false);
+            }
             break;
         case Family::Grid: {
             // every window of the batch must fall into the same tile class; NEMETH / FILTER with the score, sufficient or
@@ -395,7 +420,9 @@ int64_t pfg_scratch_bytes(int model, int dtype, int rng, int N) {
 }
 
 int64_t pfg_scratch_bytes_smoother(int model, int dtype, int rng, int smoother, int N) {
-    if (model < 0 || model > 2 || N < 1 || smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_POYIADJIS_N) return -1;
+    if (model < 0 || model > 2 || N < 1 || smoother < PFG_SMOOTHER_NEMETH ||
+        (smoother > PFG_SMOOTHER_POYIADJIS_N && smoother != PFG_SMOOTHER_NEMETH_STRATIFIED))
+        return -1;
     const LaunchPlan p = make_plan(Caller::Device, model, dtype, rng, smoother, N, 1 << 30, false);
     return p.rc || !p.name ? -1 : (int64_t)p.scratch;
 }
@@ -415,7 +442,7 @@ int pfg_launch_device(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, i
 int pfg_launch_device_traced(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
                              const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
-    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_POYIADJIS_N)
+    if (smoother < PFG_SMOOTHER_NEMETH || (smoother > PFG_SMOOTHER_POYIADJIS_N && smoother != PFG_SMOOTHER_NEMETH_STRATIFIED))
         return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream, true);
 }
@@ -423,7 +450,7 @@ int pfg_launch_device_traced(pfg_ctx *ctx, int model, int kernel, int dtype, int
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max,
                                int B, const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
-    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_KALMAN_FFBS)
+    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_NEMETH_STRATIFIED)
         return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream);
 }

@@ -1,5 +1,5 @@
-// libpfgrad device code: pf_reg_kernel, the LDS-resident particle filter (N <= 4096) incl. its PaRIS, systematic-resampling
-// and O(N^2) instantiations.  Its build switches, derived compile-time switches and its one LDS layout: pfg_reg_traits.hpp.
+// libpfgrad device code: pf_reg_kernel, the LDS-resident particle filter (N <= 4096) incl. its PaRIS, systematic- and
+// stratified-resampling and O(N^2) instantiations.  Its build switches, derived compile-time switches and its one LDS layout: pfg_reg_traits.hpp.
 #pragma once
 #include "pfg_reg_traits.hpp"
 
@@ -537,16 +537,24 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 ll_W = mine ? W : ll_W;
                 ll_w = mine ? (counts ? wt_prev : 0.0) : ll_w;
                 ll_m = mine ? (float)m : ll_m;          // m is an f32 value
-                if ((t & (WAVE - 1)) == WAVE - 1 || t == T || PFG_TR(P.trace_ll)) {
+                // (STRATIFIED: one instantiation serves traced and production launches, so a traced running value must not
+                // move the flushes -- the parked terms are summed for the trace alone and `ll` is bitwise the production one)
+                const bool due = (t & (WAVE - 1)) == WAVE - 1 || t == T;
+                if (due || (!TR::STRATIFIED && PFG_TR(P.trace_ll))) {
                     PFG_MARK("cold loglik-flush")
                     const double term = ll_w * ((double)ll_m + (double)mth.log((REAL)(ll_W * invN)));
                     ll = uniform_f64(ll + wave_sum(term));
                     ll_w = 0.0;
+                } else if (TR::STRATIFIED && PFG_TR(P.trace_ll)) {
+                    const double term = ll_w * ((double)ll_m + (double)mth.log((REAL)(ll_W * invN)));
+                    const double run = ll + wave_sum(term);
+                    if (tid == 0) P.trace_ll[t] = run;
                 }
-            } else if (counts) {
-                ll = uniform_f64(ll + wt_prev * (m + log(W / (double)N)));
+                if ((due || !TR::STRATIFIED) && PFG_TR(P.trace_ll) && tid == 0) P.trace_ll[t] = ll;
+            } else {
+                if (counts) ll = uniform_f64(ll + wt_prev * (m + log(W / (double)N)));
+                if (PFG_TR(P.trace_ll) && tid == 0) P.trace_ll[t] = ll;
             }
-            if (PFG_TR(P.trace_ll) && tid == 0) P.trace_ll[t] = ll;
         }
         if (is_filter && t > 0) {
             PFG_MARK("cold filter")
@@ -592,10 +600,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 const double u0 = red_W0[0];
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) uu[k] = ((double)(k * NT + tid) + u0) * invN;
+            } else if (TR::STRATIFIED) {
+                // extension: child r = k NT + tid searches with (r + U_r) / N, U_r from the lane that owns it
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) uu[k] = ((double)(k * NT + tid) + u01_32(rng.next())) * invN;
+                if (PFG_TR(P.trace_x) && P.rec_ud) {          // test instrumentation: the uniforms this launch searched with
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k)
+                        if (valid[k]) P.rec_ud[(size_t)t * N + k * NT + tid] = uu[k];
+                }
             } else if (!TR::BLK) {
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) uu[k] = u01_32(rng.next());
             }
+        } else if (TR::STRATIFIED) {
+            // REPLAY: U_r is the caller's u[t][r]; one addition and one IEEE division (pfgrad.h, PFG_SMOOTHER_NEMETH_STRATIFIED)
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) uu[k] = ((double)(k * NT + tid) + uu[k]) / (double)N;
         }
         int anc[PPT];
         [[maybe_unused]] uint32_t gaddr[PPT];       // GADDR: byte offset of the parent's record in a state array

@@ -160,6 +160,7 @@ struct RegTraits {
     static constexpr int NS = ModelDims<MODEL>::NS, H = ModelDims<MODEL>::H;
     static constexpr int NW = NT / WAVE, SLOTS = NT * PPT;
     static constexpr bool PARIS = MODE == MODE_PARIS, N2 = MODE == MODE_N2, SYSTEMATIC = MODE == MODE_SYSTEMATIC;
+    static constexpr bool STRATIFIED = MODE == MODE_STRATIFIED;     // one uniform per child, (r + U_r) / N: see phase E
     static constexpr bool LWL = PARIS || N2;            // the parents' log-weights (and the PaRIS queues) in LDS
     // FAST layout = LDS math tables + sentinel-padded, bank-conflict-free cdf with an unrolled search, NT * PPT particle
     // slots whatever N is (the array stride is a compile-time constant and folds into the ds_read / ds_write immediates).

@@ -43,7 +43,7 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
     if (q.T < 0) return bad(PFG_ERR_INVALID, "T must be >= 0");
     if (q.t1 < 0 || q.tL < q.t1) return bad(PFG_ERR_INVALID, "need 0 <= t1 <= tL");
     if ((q.smoother < PFG_SMOOTHER_NEMETH || q.smoother > PFG_SMOOTHER_POYIADJIS_N2) && q.smoother != PFG_SMOOTHER_KALMAN &&
-        q.smoother != PFG_SMOOTHER_KALMAN_FFBS)
+        q.smoother != PFG_SMOOTHER_KALMAN_FFBS && q.smoother != PFG_SMOOTHER_NEMETH_STRATIFIED)
         return bad(PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     if (mixed(PFG_SMOOTHER_KALMAN_FFBS)) return bad(PFG_ERR_INVALID, "FFBS latent paths cannot share a batch with other smoothers");
     if (mixed(PFG_SMOOTHER_KALMAN)) return bad(PFG_ERR_INVALID, "the exact Kalman score cannot share a batch with particle filters");
@@ -62,6 +62,14 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
         if (ffbs && rng == PFG_RNG_REPLAY && q.T > 0 && !q.z) return bad(PFG_ERR_INVALID, "REPLAY FFBS needs z (T N normals)");
         if (ffbs && q.stat == PFG_STAT_GIBBS && q.N != 1)
             return bad(PFG_ERR_INVALID, "the Gibbs statistic (PFG_STAT_GIBBS) is of one path: N must be 1");
+    }
+    if (mixed(PFG_SMOOTHER_NEMETH_STRATIFIED)) {
+        // the id says NEMETH: the recursions it has no kernel for are named, any other mix is a caller's error
+        const int other = q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED ? first.smoother : q.smoother;
+        if (other == PFG_SMOOTHER_FILTER) return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for the NEMETH recursion, not pf = 'filter'");
+        if (other == PFG_SMOOTHER_PARIS) return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for the NEMETH recursion, not pf = 'paris'");
+        if (other == PFG_SMOOTHER_POYIADJIS_N2) return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for the NEMETH recursion, not pf = 'poyiadjis_N2'");
+        return bad(PFG_ERR_INVALID, "stratified resampling cannot share a batch with other smoothers");
     }
     if (mixed(PFG_SMOOTHER_POYIADJIS_N2)) return bad(PFG_ERR_INVALID, "pf = 'poyiadjis_N2' cannot share a batch with other smoothers");
     if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2 && q.N > pfg::MEM_MAX_N)
@@ -101,6 +109,8 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
     }
     if ((q.stat < PFG_STAT_SCORE || q.stat > PFG_STAT_PREDICTIVE) && !(ffbs && q.stat == PFG_STAT_GIBBS))
         return bad(PFG_ERR_INVALID, "bad stat id");
+    if (q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED && q.stat == PFG_STAT_PREDICTIVE)
+        return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is not built for the predictive statistic");
     if ((q.stat == PFG_STAT_PREDICTIVE) != (first.stat == PFG_STAT_PREDICTIVE))
         return bad(PFG_ERR_INVALID, "the predictive statistic cannot share a batch with others");
     if (q.stat == PFG_STAT_PREDICTIVE) {
@@ -122,6 +132,8 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
         return bad(PFG_ERR_INVALID, "systematic resampling cannot share a batch with other smoothers");
     if (q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC && (rng != PFG_RNG_DEVICE || q.N > 1024))
         return bad(PFG_ERR_UNSUPPORTED, "systematic resampling needs the DEVICE rng and N <= 1024");
+    if (q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED && q.N > pfg::MEM_MAX_N)
+        return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for N <= 16384");
     if (!(q.prior_var >= 0.0) && !(q.flags & PFG_FLAG_GARCH_STATIONARY_PRIOR) && !q.init_x)
         return bad(PFG_ERR_INVALID, "prior_var must be >= 0");
     if (model == PFG_MODEL_SVM && std::fabs(q.theta[0]) > 1.0) {
@@ -167,7 +179,7 @@ BatchSummary summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
     // the smoothers with kernels of their own fill whole batches; the rest run the plain kernels
     const int s0 = ps[0].smoother;
     if (s0 == PFG_SMOOTHER_PARIS || s0 == PFG_SMOOTHER_NEMETH_SYSTEMATIC || s0 == PFG_SMOOTHER_POYIADJIS_N2 ||
-        s0 == PFG_SMOOTHER_KALMAN || s0 == PFG_SMOOTHER_KALMAN_FFBS)
+        s0 == PFG_SMOOTHER_KALMAN || s0 == PFG_SMOOTHER_KALMAN_FFBS || s0 == PFG_SMOOTHER_NEMETH_STRATIFIED)
         s.smoother = s0;
     else if (score1 && !s.traced)
         s.smoother = PFG_SMOOTHER_POYIADJIS_N;

@@ -17,7 +17,8 @@ KERNEL = {"prior": 0, "optimal": 1}
 SMOOTHER = {"nemeth": 0, "filter": 1, "paris": 2, "nemeth_systematic": 3, "poyiadjis_n2": 4,
             "poyiadjis_n": 5,       # launch-level id only (never in a descriptor): see include/pfgrad.h
             "kalman": 6,            # the exact LGSSM score (kind='marginal'), no particles: see include/pfgrad.h
-            "kalman_ffbs": 7}       # FFBS latent paths of LGSSM and their complete-data score (kind='complete')
+            "kalman_ffbs": 7,       # FFBS latent paths of LGSSM and their complete-data score (kind='complete')
+            "nemeth_stratified": 8}  # NEMETH with stratified resampling (resampling='stratified'), N <= 16384
 STAT = {"score": 0, "suff": 1, "none": 2, "predictive": 3,
         "gibbs": 4}         # FFBS, one path: the Gibbs sufficient statistics of the buffer (include/pfgrad.h)
 DTYPE = {"f64": 0, "f32": 1}

@@ -240,13 +240,23 @@ def make_problem(model, kernel, pf, observations, theta, N, t1=0, tL=None, weigh
         # extension (the reference only resamples multinomially): one uniform per timestep
         if rng == "replay":
             raise ValueError("resampling='systematic' needs rng='device' (no reference stream to replay)")
-    elif resampling != "multinomial":
+    elif resampling not in ("multinomial", "stratified"):
         raise ValueError("Unrecognized resampling = {0}".format(resampling))
     smoother, lambduh = _smoother_of(pf, kwargs)
     if resampling == "systematic":
         if smoother != "nemeth":
             raise NotImplementedError("systematic resampling is built for pf = 'poyiadjis_N' | 'nemeth'")
         smoother = "nemeth_systematic"
+    elif resampling == "stratified":
+        # extension: child r searches with (r + U_r) / N.  rng='replay': U_r is the stream's u[t][r], drawn below exactly
+        # as for multinomial resampling (np.random ends where the multinomial call leaves it); rng='device': the lane's
+        if smoother != "nemeth":
+            raise NotImplementedError("stratified resampling is built for pf = 'poyiadjis_N' | 'nemeth'")
+        if stat == "predictive":
+            raise NotImplementedError("stratified resampling is not built for the predictive statistic")
+        if int(N) > 16384:
+            raise NotImplementedError("stratified resampling is built for N <= 16384")
+        smoother = "nemeth_stratified"
     y = np.ascontiguousarray(observations, dtype=float)
     if y.ndim == 2:
         if y.shape[1] != 1:

@@ -1,0 +1,509 @@
+"""GPU: stratified resampling (PFG_SMOOTHER_NEMETH_STRATIFIED, resampling='stratified') on every kernel that serves it.
+
+REPLAY: the pinned oracle fed (r + u[t][r]) / N in place of u (tests/helpers/stratified_model.py) is the specification,
+trajectories and ancestors included, at the tolerance of test_gpu_pf_parity.py.  DEVICE: the traced launch records the
+uniform every child searched with and its normals; the oracle replays the launch on them, in the manner of
+test_gpu_device_replay.py.  Then batch invariance, the refusals through the library, ChainEnsemble against hand-built
+launches, the variance the stratification buys, and the drop-in sampler."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import pf_oracle as po
+from sgmcmc_ssm_amd import _capi, particle_filters
+from test_host_logic import default_params, GEN, vec
+from test_gpu_device_replay import THETA, _series
+from test_gpu_batch_invariance import LAMBDAS, batch, check_alone
+from test_gpu_pf_parity import _refusal_batch
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "helpers"))
+import device_windows  # noqa: E402
+import stratified_model  # noqa: E402
+import window_reduce  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+SM = "nemeth_stratified"
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return _capi.default_context(0)
+
+
+def _prior(model):
+    if model == "garch":
+        pm, pv = po.garch_prior_x(THETA[model])
+        return pm, float(np.asarray(pv).reshape(-1)[0])
+    return 0.0, 10.0
+
+
+def _strata_ok(ud, N):
+    r = np.arange(N)
+    return bool(np.all(ud >= r / N) and np.all(ud < (r + 1) / N))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. REPLAY parity against the oracle
+# ---------------------------------------------------------------------------------------------------------------------
+RTOL, ATOL = 1e-9, 1e-9         # test_gpu_pf_parity.py
+
+
+def _resident_record(ctx, q):
+    """The same window through pfg_launch_device_smoother (descriptor and streams resident): the whole out[0..7] record,
+    whose last entry is the launch's own smallest |u' - cdf| margin (pfg_run_batch fetches out[0..4] only)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)).to(dev)
+    model, N, T = q["model"], q["N"], q["y"].shape[0]
+    th = np.zeros(_capi.MAX_THETA)
+    th[:len(q["theta"])] = q["theta"]
+    bufs = dict(y=t(q["y"]), theta=t(th), z0=t(q["z0"]), u=t(q["u"]), z=t(q["z"]), weights=t(q["weights"]))
+    out = torch.zeros(_capi.OUT_DOUBLES, dtype=torch.float64, device=dev)
+    sb = ctx.scratch_bytes_smoother(model, "f64", "replay", SM, N)
+    assert sb >= 0 and (sb > 0) == (N > 1024)
+    scratch = torch.zeros(max(sb, 1), dtype=torch.uint8, device=dev)
+    d = np.zeros(1, dtype=_capi.DEV_PROBLEM_DTYPE)
+    for k, v in bufs.items():
+        d[k] = v.data_ptr()
+    d["out"], d["scratch"] = out.data_ptr(), scratch.data_ptr() if sb > 0 else 0
+    d["prior_mean"], d["prior_var"], d["lambduh"] = q["prior_mean"], q["prior_var"], q["lambduh"]
+    d["T"], d["t1"], d["tL"], d["N"] = T, q["t1"], q["tL"], N
+    d["smoother"], d["stat"] = _capi.SMOOTHER[SM], _capi.STAT["score"]
+    desc = torch.from_numpy(d.view(np.uint8).reshape(1, -1)).to(dev)
+    ctx.launch_device_smoother(model, q["kernel"], "f64", "replay", SM, N, 1, desc.data_ptr(),
+                               torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    return out.cpu().numpy()
+
+
+def _replay_case(ctx, model, kernel, lam, N, T, window):
+    theta = THETA[model]
+    y = _series(model, T, seed=N + T)
+    t1, tL = window
+    weights = np.linspace(20.0, 30.0, tL - t1)
+    pm, pv = _prior(model)
+    z0, u, z = po.draw_streams(np.random.RandomState(5), N, T)
+    q = dict(model=model, kernel=kernel, smoother=SM, stat="score", dtype="f64", rng="replay", N=N, t1=t1, tL=tL,
+             lambduh=lam, prior_mean=pm, prior_var=pv, y=y, weights=weights, theta=theta, z0=z0, u=u, z=z)
+    o = ctx.run_batch([q], want_trace=True)[0]
+    variant = "stratified256x4" if N <= 1024 else "mem1024_stratified"
+    assert ctx.last_variant() == variant
+    ref = stratified_model.pf_window(model, theta, y, N, z0, u, z, kernel=kernel, pf="nemeth", lambduh=lam, stat="score",
+                                     t1=t1, tL=tL, weights=weights, prior_mean=pm, prior_var=pv, save_all=True)
+    rec = _resident_record(ctx, q)
+    assert ctx.last_variant() == variant
+    print("margin", model, kernel, lam, N, rec[7])
+    assert rec[7] > 1e-12, rec[7]                    # no near tie: an ancestor flip would not be a rounding matter
+    h = o["mean_stat"].shape[0]
+    assert np.array_equal(rec[:h], o["mean_stat"]) and rec[4] == o["loglik"]
+    assert int(np.sum(o["all_ancestors"] != ref["all_ancestors"])) == 0
+    np.testing.assert_allclose(o["all_x_t"], ref["all_x_t"], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(o["all_log_weights"], ref["all_log_weights"], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(o["all_loglikelihood_estimate"], ref["all_loglikelihood_estimate"], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(o["all_statistics"], ref["all_statistics"], rtol=RTOL, atol=1e-8)
+    np.testing.assert_allclose(o["mean_stat"], ref["mean_statistic"], rtol=RTOL, atol=1e-8)
+    np.testing.assert_allclose(o["loglik"], ref["loglikelihood_estimate"], rtol=RTOL, atol=ATOL)
+    # stratified, not multinomial: the ancestors of every step are sorted
+    assert np.all(np.diff(o["all_ancestors"], axis=1) >= 0)
+
+
+@pytest.mark.parametrize("N", [100, 1024, 1025, 4097])
+@pytest.mark.parametrize("lam", [1.0, 0.95])
+@pytest.mark.parametrize("model,kernel", [("svm", "prior"), ("garch", "optimal"), ("lgssm", "optimal")])
+def test_replay_parity(ctx, model, kernel, lam, N):
+    """pfg_run_batch with smoother 8 on (z0, u, z) against po.pf_window on stratified_uniforms(u): window (3, 9) of
+    T = 12 with weights; N = 100 (ragged 256 x 4), 1024 (every slot), 1025 (first size of the large-N twin), 4097 (past
+    its registers-held log-weights)."""
+    _replay_case(ctx, model, kernel, lam, N, 12, (3, 9))
+
+
+def test_replay_parity_at_the_maximum(ctx):
+    _replay_case(ctx, "svm", "prior", 1.0, 16384, 6, (1, 5))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. recorded-draw replay of the DEVICE instantiations
+# ---------------------------------------------------------------------------------------------------------------------
+DRTOL, DATOL = 1e-8, 1e-8       # test_gpu_device_replay.py
+
+DEVICE_CASES = [
+    # model, kernel, lambduh, N, T, window, variant
+    ("svm", "prior", 1.0, 100, 40, None, "stratified256x4"),
+    ("svm", "prior", 0.95, 1000, 40, (5, 30), "stratified256x4"),
+    ("garch", "optimal", 1.0, 100, 40, (5, 30), "stratified256x4"),
+    ("garch", "prior", 1.0, 1000, 40, None, "stratified256x4"),
+    ("svm", "prior", 1.0, 1025, 24, (4, 20), "big4096_stratified"),
+    ("garch", "optimal", 0.9, 4000, 24, (4, 20), "big4096_stratified"),
+    ("lgssm", "optimal", 0.95, 4097, 24, (4, 20), "big16384_stratified"),
+    ("svm", "prior", 1.0, 10000, 24, (4, 20), "big16384_stratified"),
+]
+
+
+def _device_problem(model, kernel, lam, N, T, window, dtype="f64"):
+    y = _series(model, T, seed=N + T)
+    t1, tL, weights = 0, T, None
+    if window is not None:
+        t1, tL = window
+        weights = np.linspace(20.0, 30.0, tL - t1)
+    pm, pv = _prior(model)
+    return dict(model=model, kernel=kernel, smoother=SM, stat="score", dtype=dtype, rng="device", N=N, t1=t1, tL=tL,
+                lambduh=lam, prior_mean=pm, prior_var=pv, y=y, weights=weights, theta=THETA[model], seed=20261018 + N,
+                stream=T)
+
+
+@pytest.mark.parametrize("case", DEVICE_CASES, ids=lambda c: "{0}-{1}-N{3}-{6}".format(*c))
+def test_device_kernel_replayed_by_oracle(ctx, case):
+    """The traced launch records, per step and child, the uniform it searched with (rec_ud) and its normal: every
+    uniform of child r lies in [r/N, (r+1)/N), and po.pf_window on the recorded numbers -- resampling restated by
+    stratified_model.device_ancestors -- gives the launch's trajectory at rtol 1e-8 with every ancestor equal.  The
+    production launch (no trace buffers) returns the traced launch's record bit for bit, log-likelihood included."""
+    model, kernel, lam, N, T, window, variant = case
+    q = _device_problem(model, kernel, lam, N, T, window)
+    o = ctx.run_batch([q], want_trace=True, want_draws=True)[0]
+    assert ctx.last_variant() == variant
+    plain = ctx.run_batch([dict(q)])[0]
+    assert ctx.last_variant() == variant
+    assert np.array_equal(plain["mean_stat"], o["mean_stat"]) and plain["loglik"] == o["loglik"]
+    ud, z, z0 = o["rec_ud"], o["rec_z"], o["rec_z0"]
+    assert _strata_ok(ud, N)
+    assert np.all(np.isfinite(z)) and np.all(np.isfinite(z0)) and np.any(z != 0.0)
+    # U_r itself is uniform on the 32-bit grid: mean 1/2, variance 1/12 over T N draws
+    U = ud * N - np.arange(N)
+    n = U.size
+    assert abs(U.mean() - 0.5) < 5 / np.sqrt(12 * n) and abs(U.var() - 1 / 12) < 5 * np.sqrt(1 / 180 / n)
+    ref = po.pf_window(model, q["theta"], q["y"], N, z0, None, z, kernel=kernel, pf="nemeth", lambduh=lam, stat="score",
+                       t1=q["t1"], tL=q["tL"], weights=q["weights"], prior_mean=q["prior_mean"], prior_var=q["prior_var"],
+                       save_all=True, resampler=lambda t, logw: stratified_model.device_ancestors(logw, ud[t], variant))
+    assert int(np.sum(o["all_ancestors"] != ref["all_ancestors"])) == 0
+    np.testing.assert_allclose(o["all_x_t"], ref["all_x_t"], rtol=DRTOL, atol=DATOL)
+    np.testing.assert_allclose(o["all_log_weights"], ref["all_log_weights"], rtol=DRTOL, atol=DATOL)
+    np.testing.assert_allclose(o["all_loglikelihood_estimate"], ref["all_loglikelihood_estimate"], rtol=DRTOL, atol=DATOL)
+    np.testing.assert_allclose(o["all_statistics"], ref["all_statistics"], rtol=DRTOL, atol=1e-7)
+    np.testing.assert_allclose(o["mean_stat"], ref["mean_statistic"], rtol=DRTOL, atol=1e-7)
+    np.testing.assert_allclose(o["loglik"], ref["loglikelihood_estimate"], rtol=DRTOL, atol=DATOL)
+
+
+@pytest.mark.parametrize("model,kernel,N,T,variant", [("svm", "prior", 1000, 24, "stratified256x4"),
+                                                     ("garch", "optimal", 4000, 16, "big4096_stratified"),
+                                                     ("lgssm", "optimal", 4097, 16, "big16384_stratified")])
+def test_f32_state_device_kernels_replayed(ctx, model, kernel, N, T, variant):
+    """dtype='f32', one case per unit, TEACHER-FORCED step by step at the tolerances of
+    test_gpu_device_replay.py::test_f32_state_device_kernels_replayed: particles rtol 2e-5, log-weights 2e-4, statistics
+    2e-4 of their scale, at most max(3, 2e-4 T N) ancestors off (an f32 weight moves a CDF entry by ~1e-6)."""
+    q = _device_problem(model, kernel, 1.0, N, T, None, dtype="f32")
+    o = ctx.run_batch([q], want_trace=True, want_draws=True)[0]
+    assert ctx.last_variant() == variant
+    plain = ctx.run_batch([dict(q)])[0]
+    assert np.array_equal(plain["mean_stat"], o["mean_stat"]) and plain["loglik"] == o["loglik"]
+    ud, z = o["rec_ud"], o["rec_z"]
+    assert _strata_ok(ud, N)
+    d = po.derived(model, q["theta"])
+    flips = 0
+    for t in range(T):
+        x, lw, st = o["all_x_t"][t], o["all_log_weights"][t], o["all_statistics"][t]
+        got = o["all_ancestors"][t]
+        flips += int(np.sum(stratified_model.device_ancestors(lw, ud[t], variant) != got))
+        yt = np.array([q["y"][t]])
+        xp = x[got]
+        xn = po.kernel_rv(model, kernel, d, xp, yt, z[t])
+        np.testing.assert_allclose(o["all_x_t"][t + 1], xn, rtol=2e-5, atol=2e-5)
+        np.testing.assert_allclose(o["all_log_weights"][t + 1], po.kernel_reweight(model, kernel, d, xp, xn, yt), rtol=2e-4, atol=2e-4)
+        ref_st = st[got] + po.score_statistic(model, d, xp, xn, yt)
+        assert np.max(np.abs(o["all_statistics"][t + 1] - ref_st)) < 2e-4 * np.maximum(1.0, np.abs(ref_st).max())
+    assert flips <= max(3, int(2e-4 * T * N)), flips
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. batch invariance
+# ---------------------------------------------------------------------------------------------------------------------
+def _stratified_batch(model, kernel, Ns, rng):
+    qs = batch(model, kernel, Ns, rng=rng, smoother=SM)
+    for i, q in enumerate(qs):
+        q["lambduh"] = LAMBDAS[i % len(LAMBDAS)]
+    return qs
+
+
+@pytest.mark.parametrize("rng", ["device", "replay"])
+def test_stratified_alone_equals_batched(ctx, rng):
+    """700 windows of mixed N, T (0 and 1 included), windows, theta, weights and lambduh in one launch: every window's
+    record, final particles and statistics are bitwise those of the reversed batch and of the window run alone."""
+    Ns = [(1024, 100, 1, 700, 333, 1000, 257)[i % 7] for i in range(700)]
+    check_alone(ctx, _stratified_batch("garch", "prior", Ns, rng), "stratified256x4", trace=False, every=87)
+
+
+@pytest.mark.parametrize("rng,Ns,variant", [("device", (4096, 1025, 3000, 2048), "big4096_stratified"),
+                                            ("device", (16384, 4097, 9000, 5000), "big16384_stratified"),
+                                            ("replay", (4096, 1025, 3000, 2048), "mem1024_stratified"),
+                                            ("replay", (16384, 4097, 9000), "mem1024_stratified")])
+def test_stratified_large_n_alone_equals_batched(ctx, rng, Ns, variant):
+    """The large-N twins, one size class per batch (so batch and lone window run the same instantiation): the scratch
+    stride and the LDS come from the batch's largest window, each workgroup lays out its own."""
+    check_alone(ctx, _stratified_batch("lgssm", "optimal", Ns, rng), variant)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. refusals through the library
+# ---------------------------------------------------------------------------------------------------------------------
+_INV, _UNS = _capi.PFG_ERR_INVALID, _capi.PFG_ERR_UNSUPPORTED
+_S8 = dict(smoother=8)
+_DEV = dict(smoother=8, rng=1, z0=None, u=None, z=None)
+REFUSALS = [
+    ([_S8, dict(smoother=0)], _INV, "problem 1: stratified resampling cannot share a batch with other smoothers"),
+    ([dict(smoother=0), _S8], _INV, "problem 1: stratified resampling cannot share a batch with other smoothers"),
+    ([_DEV, dict(_DEV, smoother=3)], _INV, "problem 1: stratified resampling cannot share a batch with other smoothers"),
+    ([_S8, dict(_S8, N=16385)], _UNS, "problem 1: stratified resampling is built for N <= 16384"),
+    ([_DEV, dict(_DEV, N=16385)], _UNS, "problem 1: stratified resampling is built for N <= 16384"),
+    ([_S8, dict(smoother=1)], _UNS, "problem 1: stratified resampling is built for the NEMETH recursion, not pf = 'filter'"),
+    ([_S8, dict(smoother=2, Ntilde=2, paris_man_u=32)], _UNS,
+     "problem 1: stratified resampling is built for the NEMETH recursion, not pf = 'paris'"),
+    ([_S8, dict(smoother=4)], _UNS, "problem 1: stratified resampling is built for the NEMETH recursion, not pf = 'poyiadjis_N2'"),
+    ([_S8, dict(_S8, stat=3, num_steps_ahead=1, pred_z=32)], _UNS,
+     "problem 1: stratified resampling is not built for the predictive statistic"),
+    ([dict(_S8, stat=3, num_steps_ahead=1, pred_z=32)] * 2, _UNS,
+     "problem 0: stratified resampling is not built for the predictive statistic"),
+    ([_S8, dict(_S8, elementwise=1, ew_mean=6)], _UNS, "problem 1: elementwise statistics are built for pf = 'poyiadjis_N'"),
+]
+
+
+def test_refusals_through_the_library(ctx):
+    lib, h = ctx.lib, ctx.handle
+    for faults, code, text in REFUSALS:
+        keep = []
+        ps, rs = _refusal_batch(keep, "svm", None, faults)
+        rc = lib.pfg_run_batch(h, len(ps), ps, rs)
+        msg = lib.pfg_last_error(h).decode()
+        assert (rc, text in msg) == (code, True), (faults, rc, msg)
+    # the launch and the size query refuse the same
+    import torch
+    desc = torch.zeros(_capi.DEV_PROBLEM_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+    for rng in ("replay", "device"):
+        assert ctx.scratch_bytes_smoother("svm", "f64", rng, SM, 16385) == -1
+        assert ctx.scratch_bytes_smoother("svm", "f64", rng, SM, 1024) == 0
+        assert ctx.scratch_bytes_smoother("svm", "f64", rng, SM, 1025) == ctx.scratch_bytes("svm", "f64", "replay", 1025) > 0
+        with pytest.raises(NotImplementedError, match="stratified resampling is built for N <= 16384"):
+            ctx.launch_device_smoother("svm", "prior", "f64", rng, SM, 16385, 1, desc.data_ptr())      # (never read)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. ChainEnsemble
+# ---------------------------------------------------------------------------------------------------------------------
+def _ensemble_series(model, T, seed=5):
+    np.random.seed(seed)
+    return GEN[model](T=T, parameters=default_params(model))["observations"].reshape(-1)
+
+
+def _hand_built(ens, y_host, theta_rows, step, pf, lam):
+    """ctx.run_batch of the descriptors the ensemble's latest step ran: the windows the device wrote, the chains'
+    parameters before the step, (seed, stream, step) as the resident launch keys its generator."""
+    d, yoff, woff, seq_len = device_windows.ensemble_windows(ens) if ens._multi else \
+        device_windows.decode(ens.desc_dev, ens.y_dev.data_ptr(), ens.weights_dev.data_ptr()) + (None,)
+    wtab = ens.weights_dev.cpu().numpy().reshape(-1)
+    per = ens.W if ens._multi else 1
+    probs = []
+    for i in range(ens._nd):
+        T, t1, tL = int(d["T"][i]), int(d["t1"][i]), int(d["tL"][i])
+        w = None if woff[i] < 0 else wtab[woff[i]:woff[i] + (tL - t1)]
+        kw = dict(lambduh=lam) if pf == "nemeth" else {}
+        q = particle_filters.make_problem(ens.model, ens.kernel, pf, y_host[yoff[i]:yoff[i] + T], theta_rows[i // per], ens.N,
+                                          t1=t1, tL=tL, weights=w, prior_mean=float(d["prior_mean"][i]),
+                                          prior_var=float(d["prior_var"][i]), flags=int(d["flags"][i]), dtype=ens.dtype,
+                                          rng="device", seed=ens.seed, stream=int(d["stream"][i]), resampling="stratified", **kw)
+        assert q["smoother"] == SM and int(d["smoother"][i]) == 8
+        q["step"] = step
+        probs.append(q)
+    outs = ens.ctx.run_batch(probs)
+    recs = np.zeros((len(probs), 8))
+    h = _capi.STAT_DIM[ens.model]
+    recs[:, :h] = [o["mean_stat"] for o in outs]
+    recs[:, 4] = [o["loglik"] for o in outs]
+    return recs, seq_len
+
+
+def _three_steps_equal_hand_built(ens, y_host, pf, lam, variant):
+    h = _capi.STAT_DIM[ens.model]
+    for step in range(3):
+        before = ens.theta()
+        ens.step(1)
+        ens.synchronize()
+        assert ens.ctx.last_variant() == variant
+        g, ll = ens.last_gradient_statistics()
+        recs, seq_len = _hand_built(ens, y_host, before, step, pf, lam)
+        assert ens.ctx.last_variant() == variant
+        if ens._multi:
+            win, _ = ens.window_statistics()
+            np.testing.assert_array_equal(win.reshape(-1, 8)[:, :5], recs[:, :5])
+            recs = window_reduce.reduce_windows(recs, seq_len, ens.K_eff, ens.M, ens._rescale, ens.T)
+        assert g.tobytes() == np.ascontiguousarray(recs[:, :h]).tobytes() and ll.tobytes() == np.ascontiguousarray(recs[:, 4]).tobytes()
+        assert np.all(np.isfinite(g)) and np.all(np.isfinite(ll))
+        assert not np.array_equal(before, ens.theta())
+
+
+def test_ensemble_large_n_device_windows():
+    """(a) N = 2000 (the large-N twin; its scratch from pfg_scratch_bytes_smoother), 8 chains, S = 16 / B = 4, windows
+    sampled on the device: three steps equal hand-built launches of the same descriptors bitwise, and a graph replay of
+    three steps equals three eager steps bitwise; SGHMC and a state_dict resume run on it too."""
+    from sgmcmc_ssm_amd.ensemble import ChainEnsemble
+    p = default_params("svm")
+    y = _ensemble_series("svm", 120)
+    kw = dict(num_chains=8, N=2000, epsilon=1e-3, seed=23, chain_offset=3, subsequence_length=16, buffer_length=4,
+              window_sampling="device", resampling="stratified")
+    ens = ChainEnsemble("svm", y, p, **kw)
+    assert ens._smoother == ens._launch_smoother == SM
+    assert ens.scratch_dev.numel() == 8 * ens.ctx.scratch_bytes_smoother("svm", "f64", "device", SM, 2000) > 0
+    _three_steps_equal_hand_built(ens, y, "poyiadjis_N", 1.0, "big4096_stratified")
+    eager = ChainEnsemble("svm", y, p, **kw)
+    eager.step(3)
+    graph = ChainEnsemble("svm", y, p, **kw).run(3, thin=3, graph_steps=3)
+    np.testing.assert_array_equal(graph[0], eager.theta())
+    np.testing.assert_array_equal(ens.theta(), eager.theta())
+    full = ChainEnsemble("svm", y, p, sampler="sghmc", **kw)
+    full.step(1)
+    state = full.state_dict()
+    full.step(2)
+    again = ChainEnsemble("svm", y, p, sampler="sghmc", **kw)
+    again.load_state_dict(state)
+    again.step(2)
+    np.testing.assert_array_equal(full.theta(), again.theta())
+    assert np.all(np.isfinite(full.theta()))
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_ensemble_multi_window(dtype):
+    """(b) minibatch_size = 2, N = 64, pf='nemeth': the same two checks on the multi-window path (window records and the
+    reduced records)."""
+    from sgmcmc_ssm_amd.ensemble import ChainEnsemble
+    p = default_params("garch")
+    y = _ensemble_series("garch", 90)
+    kw = dict(num_chains=12, N=64, pf="nemeth", lambduh=0.9, epsilon=1e-3, dtype=dtype, seed=31, chain_offset=2,
+              subsequence_length=16, buffer_length=4, minibatch_size=2, window_sampling="device", resampling="stratified")
+    ens = ChainEnsemble("garch", y, p, **kw)
+    assert ens._multi and ens.W == 2 and ens._smoother == SM
+    _three_steps_equal_hand_built(ens, y, "nemeth", 0.9, "stratified256x4")
+    eager = ChainEnsemble("garch", y, p, **kw)
+    eager.step(3)
+    graph = ChainEnsemble("garch", y, p, **kw).run(3, thin=3, graph_steps=3)
+    np.testing.assert_array_equal(graph[0], eager.theta())
+
+
+def test_ensemble_host_windows_and_sgrld():
+    """Host window sampling (single-window path) and the SGRLD update run stratified chains; the host-sampled chains do
+    not depend on the partition into ensembles."""
+    from sgmcmc_ssm_amd.ensemble import ChainEnsemble
+    p = default_params("lgssm")
+    y = _ensemble_series("lgssm", 80)
+    kw = dict(N=100, epsilon=1e-3, seed=7, subsequence_length=16, buffer_length=4, sampler="sgrld", resampling="stratified")
+    whole = ChainEnsemble("lgssm", y, p, num_chains=10, **kw)
+    whole.step(3)
+    lo = ChainEnsemble("lgssm", y, p, num_chains=4, chain_offset=0, **kw)
+    hi = ChainEnsemble("lgssm", y, p, num_chains=6, chain_offset=4, **kw)
+    lo.step(3)
+    hi.step(3)
+    assert whole.ctx.last_variant() == "stratified256x4"
+    np.testing.assert_array_equal(np.concatenate([lo.theta(), hi.theta()]), whole.theta())
+    assert np.all(np.isfinite(whole.theta()))
+
+
+def test_ensemble_refusals():
+    from sgmcmc_ssm_amd.ensemble import ChainEnsemble
+    y, p = _ensemble_series("svm", 40), default_params("svm")
+    with pytest.raises(NotImplementedError, match="stratified resampling is built for N <= 16384"):
+        ChainEnsemble("svm", y, p, num_chains=2, N=20000, resampling="stratified")
+    with pytest.raises(ValueError, match="multinomial"):
+        ChainEnsemble("svm", y, p, num_chains=2, N=100, pf="paris", resampling="stratified")
+    with pytest.raises(ValueError, match="needs kind='pf'"):
+        ChainEnsemble("lgssm", _ensemble_series("lgssm", 40), default_params("lgssm"), num_chains=2, kind="marginal",
+                      resampling="stratified")
+
+
+def test_stratification_cuts_the_score_variance():
+    """(c) 1024 chains at one theta, SVM, N = 100, T = 24, window [2, 22): one launch with multinomial and one with
+    stratified resampling.  Per score component var_strat / var_mult < 0.8 -- the CPU oracle measures at most 0.52 at
+    this shape and with 1024 draws the ratio's standard error is about 6 % of itself, so 0.8 is more than five standard
+    errors above the measured worst case and still fails when the stratification is lost --, and the two means agree
+    within five standard errors.  The ratio depends on the series (what is left is the proposal's own noise): on this one,
+    _series('svm', 24, seed=48) at the default parameters, the oracle with 300 seeds gives 0.43 / 0.42 / 0.45 for the three
+    score components and 0.63 for the log-likelihood (po.pf_window on stratified_uniforms(u) against u)."""
+    import torch
+    from sgmcmc_ssm_amd.ensemble import ChainEnsemble
+    C = 1024
+    p = default_params("svm")
+    y = _series("svm", 24, seed=48)
+    res = {}
+    for mode in ("multinomial", "stratified"):
+        ens = ChainEnsemble("svm", y, p, num_chains=C, N=100, epsilon=1e-3, seed=21, resampling=mode)
+        ens._desc["t1"], ens._desc["tL"] = 2, 22            # the full series as the buffered window [2, 22)
+        ens.desc_dev.copy_(torch.from_numpy(ens._desc.view(np.uint8).reshape(ens._nd, -1)))
+        ens.launch_pf()
+        ens.synchronize()
+        assert (ens.ctx.last_variant() == "stratified256x4") == (mode == "stratified")
+        g, ll = ens.last_gradient_statistics()
+        res[mode] = np.column_stack([g, ll])
+    a, b = res["multinomial"], res["stratified"]
+    assert np.all(np.isfinite(a)) and np.all(np.isfinite(b))
+    ratio = b.var(axis=0) / a.var(axis=0)
+    se = np.sqrt(a.var(axis=0) / C + b.var(axis=0) / C)
+    zs = np.abs(a.mean(axis=0) - b.mean(axis=0)) / se
+    print("variance ratios (score components, log-likelihood)", ratio, "z", zs)
+    assert np.all(ratio[:3] < 0.8), ratio
+    assert np.all(zs < 5.0), zs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. drop-in sampler
+# ---------------------------------------------------------------------------------------------------------------------
+def test_drop_in_noisy_gradient(monkeypatch):
+    """np.random.seed(3); noisy_gradient(..., N=1000, resampling='stratified') equals the same call on the oracle stand-in
+    at rtol 1e-9, and np.random stands afterwards where the multinomial call leaves it."""
+    from sgmcmc_ssm_amd.models.svm import SVMSampler
+    p = default_params("svm")
+    y = _ensemble_series("svm", 60).reshape(-1, 1)
+    sampler = SVMSampler(n=1, m=1, observations=y, parameters=p)
+    kw = dict(kind="pf", pf="poyiadjis_N", N=1000)
+    np.random.seed(3)
+    got = vec("svm", sampler.noisy_gradient(resampling="stratified", **kw))
+    after = np.random.random()
+    assert _capi.default_context().last_variant() == "stratified256x4"
+    np.random.seed(3)
+    mult = vec("svm", sampler.noisy_gradient(**kw))
+    assert np.random.random() == after
+    assert np.all(got != mult)
+    monkeypatch.setattr(particle_filters, "run_windows", stratified_model.run_windows)
+    np.random.seed(3)
+    ref = vec("svm", sampler.noisy_gradient(resampling="stratified", **kw))
+    assert np.random.random() == after
+    np.testing.assert_allclose(got, ref, rtol=1e-9)
+    monkeypatch.undo()
+    # N above the LDS-resident size and a buffered window go the same way (the large-N twin)
+    kw2 = dict(kind="pf", pf="nemeth", lambduh=0.9, N=1500, subsequence_length=16, buffer_length=4)
+    np.random.seed(8)
+    got2 = vec("svm", sampler.noisy_gradient(resampling="stratified", **kw2))
+    assert _capi.default_context().last_variant() == "mem1024_stratified"
+    monkeypatch.setattr(particle_filters, "run_windows", stratified_model.run_windows)
+    np.random.seed(8)
+    np.testing.assert_allclose(got2, vec("svm", sampler.noisy_gradient(resampling="stratified", **kw2)), rtol=1e-9)
+
+
+def test_resident_fit_passes_stratified_on():
+    """fit(iter_type='SGLD', pf_kwargs=dict(rng='device', resampling='stratified')) runs resident on a one-chain
+    stratified ensemble: reproducible under np.random.seed, another trajectory than multinomial resampling."""
+    from sgmcmc_ssm_amd.models.svm import SVMSampler
+    p = default_params("svm")
+    y = _ensemble_series("svm", 100).reshape(-1, 1)
+
+    def fit(**pf_kwargs):
+        sampler = SVMSampler(n=1, m=1, observations=y, parameters=p.copy())
+        np.random.seed(4)
+        plist = sampler.fit(iter_type="SGLD", num_iters=4, output_all=True, epsilon=0.01, subsequence_length=16,
+                            buffer_length=4, kind="pf", pf_kwargs=dict(pf="poyiadjis_N", N=200, rng="device", **pf_kwargs))
+        return np.array([q.theta() for q in plist]), _capi.default_context().last_variant()
+
+    a, va = fit(resampling="stratified")
+    b, _ = fit(resampling="stratified")
+    m, vm = fit()
+    assert va == "stratified256x4" and vm != va
+    assert a.shape == (5, 3) and np.all(np.isfinite(a))
+    np.testing.assert_array_equal(a, b)
+    assert np.all(a[1] != m[1])
