@@ -62,7 +62,13 @@ enum pfg_smoother { PFG_SMOOTHER_NEMETH = 0, PFG_SMOOTHER_FILTER = 1, PFG_SMOOTH
                     PFG_SMOOTHER_NEMETH_SYSTEMATIC = 3,
                     /* poyiadjis_smoother, the O(N^2) algorithm (pf.py:84-136): every child averages
                      * stats_j + w_t h(x_j, child) over ALL parents j with the backward weights
-                     * w_j q(child | x_j), normalised per child.  N <= 1024. */
+                     * w_j q(child | x_j), normalised per child.  N <= 1024 LDS-resident -- "n2_64x2" (one wave per
+                     * window, N <= 128), "n2_256x1" (N <= 256), "n2_256x4" -- and up to 16384 in the large-N kernel
+                     * ("n2_mem1024", state in the scratch).  The sweep over the parents is skipped on the steps before
+                     * t1 of a window without init_stats, where its result is exactly zero.  GARCH: the reference's
+                     * backward kernel (garch/kernels.py:20-37) scores only the x component of the state, so the phi /
+                     * lambda scores of this smoother (and of PaRIS) differ systematically from the O(N) ones; this
+                     * library reproduces the reference. */
                     PFG_SMOOTHER_POYIADJIS_N2 = 4,
                     /* LAUNCH-LEVEL id only (pfg_launch_device_smoother; never in a descriptor): the caller states that
                      * every descriptor of the batch is the Poyiadjis O(N) score -- smoother = NEMETH, lambduh = 1.0,
@@ -338,7 +344,10 @@ int pfg_last_traced(pfg_ctx *ctx);
  * "paris64x2" (one wave per window, 64 threads x 2 particles: n_max <= 128, the DEVICE rng and more than 64 descriptors;
  * PFGRAD_VARIANT=paris64x2 forces it wherever it holds n_max, REPLAY included), "paris256x1" (the rest of n_max <= 256),
  * "paris256x4" (n_max <= 1024) -- and "paris_mem1024" above that (state in
- * the descriptors' scratch) */
+ * the descriptors' scratch).  PFG_SMOOTHER_POYIADJIS_N2 likewise: "n2_64x2" (one wave per window: n_max <= 128, the
+ * DEVICE rng and more than 64 descriptors; PFGRAD_VARIANT=n2_64x2 forces it wherever it holds n_max, REPLAY included),
+ * "n2_256x1" (the rest of n_max <= 256), "n2_256x4" (n_max <= 1024; PFGRAD_VARIANT=n2_256x1 / n2_256x4 force those where
+ * they hold n_max), "n2_mem1024" above that (state in the descriptors' scratch) */
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother,
                                int n_max, int B, const pfg_dev_problem *dev_probs, void *hip_stream);
 /* N above the one-workgroup kernels' maximum (16384 < N <= 4194304; the reference has no limit and its bias experiments
@@ -426,7 +435,8 @@ int64_t pfg_scratch_bytes(int model, int dtype, int rng, int N);
 /* the same for a resident batch of `smoother` windows (PFG_SMOOTHER_NEMETH .. PFG_SMOOTHER_POYIADJIS_N, or
  * PFG_SMOOTHER_NEMETH_STRATIFIED: the large-N kernels' state for 1024 < N <= 16384) launched
  * through pfg_launch_device_smoother: what that launch's plan sizes per descriptor -- PFG_SMOOTHER_PARIS: the
- * paris_mem1024 state for 1024 < N <= 16384, 0 where an LDS-resident variant serves -- and -1 above the one-workgroup
+ * paris_mem1024 state for 1024 < N <= 16384, 0 where an LDS-resident variant serves; PFG_SMOOTHER_POYIADJIS_N2: the
+ * n2_mem1024 state for 1024 < N <= 16384, 0 for N <= 1024 -- and -1 above the one-workgroup
  * kernels' maximum (16384), for another smoother id, or for a combination that launch refuses */
 int64_t pfg_scratch_bytes_smoother(int model, int dtype, int rng, int smoother, int N);
 /* name of the kernel variant pfg_launch_device would pick (for profiles / logs) */

@@ -107,7 +107,7 @@ constexpr size_t kLdsLimit = 160 * 1024;
 enum class Family {
     None,
     Reg,           // LDS-resident kernel, entry (nt, ppt, pp)
-    Paris, N2,     // its PaRIS / O(N^2) Poyiadjis instantiations, 256 x ppt; nt = MEM_NT: the large-N kernel's PaRIS one
+    Paris, N2,     // its PaRIS / O(N^2) Poyiadjis instantiations, 256 x ppt or one wave (64 x 2); nt = MEM_NT: the large-N kernel's PaRIS one
     Systematic,    // its systematic-resampling instantiation (device generator), 256 x 4
     Stratified,    // stratified resampling (PFG_SMOOTHER_NEMETH_STRATIFIED), three size classes: the LDS-resident 256 x 4
                    // instantiation (n_max <= 1024; np2 = 0), above it the large-N kernel's twin (REPLAY; lw4: N <= 4096) or
@@ -174,7 +174,7 @@ int launch_ffbs(pfg_ctx *ctx, const LaunchPlan &p, int rng, int B, const pfg_dev
 // kernels only) and pfg_launch_device_grid* (whole-GPU windows).
 enum class Caller { Query, Batch, Device, Grid };
 LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B, bool traced,
-                     bool predictive = false, int t_max = 0, int phase = -1);
+                     bool predictive = false, int t_max = 0, int phase = -1, bool elementwise = false);
 int check_ids(pfg_ctx *ctx, int smoother, int model, int kernel, int dtype, int rng);
 int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, int B, const pfg_dev_problem *dp, hipStream_t st);
 // pfg_run_batch, Family::Grid: what every window of a whole-GPU batch must satisfy; plan.t_max becomes the longest T

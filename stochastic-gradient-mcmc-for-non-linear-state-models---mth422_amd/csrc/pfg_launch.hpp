@@ -114,14 +114,13 @@ int launch_v(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp
 
 // PaRIS (MODE_PARIS) / O(N^2) Poyiadjis (MODE_N2) instantiations: the ping-pong 256 x ppt variants with the parents'
 // log-weights in LDS, or (nt = MEM_NT) the large-N kernel's PaRIS instantiation (second log-weight array; state in the
-// HBM scratch, descriptors carry one); PaRIS only: one wave per window (nt = 64, 2 particles per lane, N <= 128)
+// HBM scratch, descriptors carry one); or one wave per window (nt = 64, 2 particles per lane, N <= 128: paris64x2 / n2_64x2)
 template <int MODEL, int KERNEL, typename REAL, int RNG, int MODE>
 int launch_paris(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
     if (p.nt == 256 && p.ppt == 1) return launch_one_t<MODEL, KERNEL, REAL, 256, 1, RNG, true, MODE>(ctx, p, B, dp, st);
     if (p.nt == 256) return launch_one_t<MODEL, KERNEL, REAL, 256, 4, RNG, true, MODE>(ctx, p, B, dp, st);
     if (p.nt == pfg::MEM_NT) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, true>, pfg::MEM_NT, p, B, dp, st);
-    if constexpr (MODE == pfg::MODE_PARIS)
-        if (p.nt == 64 && p.ppt == 2) return launch_one_t<MODEL, KERNEL, REAL, 64, 2, RNG, true, MODE>(ctx, p, B, dp, st);
+    if (p.nt == 64 && p.ppt == 2) return launch_one_t<MODEL, KERNEL, REAL, 64, 2, RNG, true, MODE>(ctx, p, B, dp, st);
     return fail(ctx, PFG_ERR_INVALID, "the launch plan names no PaRIS / O(N^2) kernel of this unit");
 }
 

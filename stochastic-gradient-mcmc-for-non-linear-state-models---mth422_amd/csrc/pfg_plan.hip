@@ -82,11 +82,18 @@ constexpr int kLds4096Variant = 4, kTinyVariant = 5, kGarchVariant = 6, kTiny4Va
 constexpr int kTinySingleVariant = 8, kTiny4SingleVariant = 9;
 constexpr int kLatencyVariant = 3, kLatencyBatch = 64;
 constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
-// the LDS-resident PaRIS variants (ping-pong state, the parents' log-weights in LDS); paris64x2: one wave per window
+// the LDS-resident PaRIS and O(N^2) Poyiadjis variants (ping-pong state, the parents' log-weights in LDS), in the same
+// order; paris64x2 / n2_64x2: one wave per window
 struct ParisVariant { int NT, PPT; const char *tag; size_t (*lds)(int, int, int, int); };
 const ParisVariant kParisVariants[] = { {64, 2, "paris64x2", reg_lds<64, 2, true, pfg::MODE_PARIS>},
                                         {256, 1, "paris256x1", reg_lds<256, 1, true, pfg::MODE_PARIS>},
                                         {256, 4, "paris256x4", reg_lds<256, 4, true, pfg::MODE_PARIS>} };
+const ParisVariant kN2Variants[] = { {64, 2, "n2_64x2", reg_lds<64, 2, true, pfg::MODE_N2>},
+                                     {256, 1, "n2_256x1", reg_lds<256, 1, true, pfg::MODE_N2>},
+                                     {256, 4, "n2_256x4", reg_lds<256, 4, true, pfg::MODE_N2>} };
+constexpr int kOneWaveSmoother = 0, kNumSmootherVariants = 3;
+static_assert(sizeof(kParisVariants) == sizeof(kN2Variants) && sizeof(kN2Variants) / sizeof(kN2Variants[0]) == kNumSmootherVariants,
+              "one table per smoother, the same shapes in the same order");
 
 // The kernel of a plain batch (no PaRIS / systematic / stratified / O(N^2)) of `batch` windows of up to n_max particles: Reg with the
 // kVariants index v, Mem, Grid, or None above every kernel.  force = PFGRAD_VARIANT: <tag> forces a variant (tuning /
@@ -140,10 +147,11 @@ namespace pfg_host {
 // same kernels as NEMETH, except where a unit has a twin specialised to that estimator.  traced: the descriptors may carry
 // trace_* / rec_* buffers (the plain LDS-resident kernels exist as a production twin that ignores them, see
 // pfg_reg_kernel.hpp; every other kernel always honours them).  predictive: the windows ask for the predictive statistic,
-// which only the general large-N kernel computes.  The environment variables PFGRAD_VARIANT, PFGRAD_NO_SCORE1 and
+// which only the general large-N kernel computes.  elementwise: a window of the batch asks for elementwise statistics (the
+// one-wave O(N^2) variant is not picked for those).  The environment variables PFGRAD_VARIANT, PFGRAD_NO_SCORE1 and
 // PFGRAD_CDF_SINGLE are read here and nowhere else.
 LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B, bool traced,
-                     bool predictive, int t_max, int phase) {
+                     bool predictive, int t_max, int phase, bool elementwise) {
     LaunchPlan p;
     p.f64 = dtype == PFG_F64;
     p.n_max = n_max; p.t_max = t_max; p.phase = phase;
@@ -212,28 +220,18 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
         case Family::N2: {
             const bool paris = p.family == Family::Paris;
             const std::string pf = paris ? "pf = 'paris'" : "pf = 'poyiadjis_N2'";
-            if (paris) {
-                // PaRIS in one wave per window (64 threads x 2 particles, N <= 128): picked like wg64x2s for plain
-                // windows -- device generator, more than kLatencyBatch windows; REPLAY, lone windows and N > 128 keep
-                // the 256-thread variants.
-                // PFGRAD_VARIANT=<tag> forces any PaRIS LDS-resident variant that holds n_max (tests, A/B timing).
-                const ParisVariant *pv = nullptr;
-                for (const ParisVariant &e : kParisVariants)
-                    if (force && !std::strcmp(force, e.tag) && n_max <= e.NT * e.PPT) pv = &e;
-                if (!pv && n_max <= 128 && rng == PFG_RNG_DEVICE && B > kLatencyBatch) pv = &kParisVariants[0];
-                if (pv) {
-                    p.nt = pv->NT; p.ppt = pv->PPT; p.name = pv->tag;
-                    p.lds = pv->lds(model, dtype, rng, n_max);
-                    if (p.lds > kLdsLimit)
-                        return refuse(p, PFG_ERR_UNSUPPORTED, pf + ": N = " + std::to_string(n_max) + " does not fit the LDS-resident variant");
-                    break;
-                }
-            }
-            if (n_max <= 1024) {
-                p.nt = 256; p.ppt = n_max <= 256 ? 1 : 4;
-                p.name = paris ? (p.ppt == 1 ? "paris256x1" : "paris256x4") : (p.ppt == 1 ? "n2_256x1" : "n2_256x4");
-                p.lds = (paris ? (p.ppt == 1 ? reg_lds<256, 1, true, pfg::MODE_PARIS> : reg_lds<256, 4, true, pfg::MODE_PARIS>)
-                               : (p.ppt == 1 ? reg_lds<256, 1, true, pfg::MODE_N2> : reg_lds<256, 4, true, pfg::MODE_N2>))(model, dtype, rng, n_max);
+            // One wave per window (64 threads x 2 particles, N <= 128; paris64x2 / n2_64x2): picked like wg64x2s for plain
+            // windows -- device generator, more than kLatencyBatch windows; REPLAY, small batches and N > 128 keep the
+            // 256-thread variants, and so do O(N^2) windows with elementwise statistics.
+            // PFGRAD_VARIANT=<tag> forces any LDS-resident variant of the smoother that holds n_max (tests, A/B timing).
+            const ParisVariant *const table = paris ? kParisVariants : kN2Variants, *pv = nullptr;
+            for (int i = 0; i < kNumSmootherVariants; ++i)
+                if (force && !std::strcmp(force, table[i].tag) && n_max <= table[i].NT * table[i].PPT) pv = &table[i];
+            if (!pv && n_max <= 128 && rng == PFG_RNG_DEVICE && B > kLatencyBatch && (paris || !elementwise)) pv = &table[kOneWaveSmoother];
+            if (!pv && n_max <= 1024) pv = &table[n_max <= 256 ? 1 : 2];
+            if (pv) {
+                p.nt = pv->NT; p.ppt = pv->PPT; p.name = pv->tag;
+                p.lds = pv->lds(model, dtype, rng, n_max);
                 if (p.lds > kLdsLimit)
                     return refuse(p, PFG_ERR_UNSUPPORTED, pf + ": N = " + std::to_string(n_max) + " does not fit the LDS-resident variant");
                 break;

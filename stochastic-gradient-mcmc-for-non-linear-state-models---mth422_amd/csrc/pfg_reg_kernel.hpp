@@ -537,20 +537,20 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 ll_W = mine ? W : ll_W;
                 ll_w = mine ? (counts ? wt_prev : 0.0) : ll_w;
                 ll_m = mine ? (float)m : ll_m;          // m is an f32 value
-                // (STRATIFIED: one instantiation serves traced and production launches, so a traced running value must not
+                // (STRATIFIED, N2: one instantiation serves traced and production launches, so a traced running value must not
                 // move the flushes -- the parked terms are summed for the trace alone and `ll` is bitwise the production one)
                 const bool due = (t & (WAVE - 1)) == WAVE - 1 || t == T;
-                if (due || (!TR::STRATIFIED && PFG_TR(P.trace_ll))) {
+                if (due || (!TR::TWINLESS_LL && PFG_TR(P.trace_ll))) {
                     PFG_MARK("cold loglik-flush")
                     const double term = ll_w * ((double)ll_m + (double)mth.log((REAL)(ll_W * invN)));
                     ll = uniform_f64(ll + wave_sum(term));
                     ll_w = 0.0;
-                } else if (TR::STRATIFIED && PFG_TR(P.trace_ll)) {
+                } else if (TR::TWINLESS_LL && PFG_TR(P.trace_ll)) {
                     const double term = ll_w * ((double)ll_m + (double)mth.log((REAL)(ll_W * invN)));
                     const double run = ll + wave_sum(term);
                     if (tid == 0) P.trace_ll[t] = run;
                 }
-                if ((due || !TR::STRATIFIED) && PFG_TR(P.trace_ll) && tid == 0) P.trace_ll[t] = ll;
+                if ((due || !TR::TWINLESS_LL) && PFG_TR(P.trace_ll) && tid == 0) P.trace_ll[t] = ll;
             } else {
                 if (counts) ll = uniform_f64(ll + wt_prev * (m + log(W / (double)N)));
                 if (PFG_TR(P.trace_ll) && tid == 0) P.trace_ll[t] = ll;
@@ -1211,9 +1211,22 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
         // every child averages  stats_j + w_t h(x_j, child)  over ALL parents j with the backward
         // weights  log_normalize(logw_j + log q(child | x_j)).  Every lane walks the parents in the
         // same order (LDS broadcast reads); two passes: exact per-child maximum, then exp-sums.
+        // No barrier inside: parents are read from `cur` (published behind barrier 3), children go to `nxt`; in the
+        // one-wave instantiation (64 x 2) barrier 3 itself is program order, so a timestep has no s_barrier at all.
+        // The sweep is skipped while it cannot change anything (PFG_OPT_N2SKIP): before t1 of a window that starts
+        // without init_stats every parent's statistics are +0.0 and the step adds nothing, so every child's are
+        // num / den = (sum_j e_j (0 + 0)) / den = +0.0 for any finite weights -- written directly.  Steps of the right
+        // buffer (t >= tL) carry non-zero statistics and keep the sweep.
         auto n2_slots = [&](auto stat_tag) {
             constexpr int STAT = decltype(stat_tag)::value;
-            if (RNG != PFG_RNG_REPLAY) draw_normals(zz);
+            if (RNG != PFG_RNG_REPLAY) {
+                draw_normals(zz);
+                if (PFG_TR(P.trace_x) && P.rec_z) {       // test instrumentation, as in the plain kernel
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k)
+                        if (valid[k]) P.rec_z[(size_t)t * N + k * NT + tid] = (double)zz[k];
+                }
+            }
             REAL xn[PPT][NS], lwn[PPT], aux[PPT];
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
@@ -1226,6 +1239,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
 #pragma unroll
                     for (int d = 0; d < NS; ++d) nxt[sidx(d, k * NT + tid)] = xn[k][d];
                 }
+            }
+            if (PFG_OPT_N2SKIP && t < t1 && !(P.init_x && P.init_stats)) {      // workgroup-uniform
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) {
+                    lw[k] = valid[k] ? lwn[k] : (REAL)(-INFINITY);
+                    if (valid[k]) {
+#pragma unroll
+                        for (int h = 0; h < H; ++h) nxt[sidx((NS + h), k * NT + tid)] = (REAL)0;
+                    }
+                }
+                return;
             }
             REAL mx[PPT];
 #pragma unroll

@@ -78,6 +78,11 @@ namespace pfg {
 #ifndef PFG_OPT_GATHERADDR
 #define PFG_OPT_GATHERADDR 1
 #endif
+// PFG_OPT_N2SKIP (the O(N^2) instantiations, MODE_N2): the backward sweep over all parents is skipped on the steps before t1 of a
+// window that starts without init_stats -- its result there is +0.0 exactly, see n2_slots.  -DPFG_OPT_N2SKIP=0 runs every sweep (A/B).
+#ifndef PFG_OPT_N2SKIP
+#define PFG_OPT_N2SKIP 1
+#endif
 // TRACE (template parameter of pf_reg_kernel): the instantiation honours the trace_* / rec_* buffers of its
 // descriptors (save_all trajectories, recorded generator draws: tests, elementwise statistics).  TRACE = false is
 // the production twin of the plain device-generator kernels: the same code with every trace / record test compiled
@@ -191,6 +196,8 @@ struct RegTraits {
     static constexpr bool GADDR = PFG_GATHERADDR_ON && BLK && PAIRED && NT == 256 && PPT == 4 && MODEL == PFG_MODEL_SVM && !PP;
     static_assert(!GADDR || 4 * (SLOTS + SLOTS / 32) * 993 < (1 << 23), "GADDR: rel * 993 must fit the 24-bit multiply");
     static constexpr bool LAZYLL = PFG_OPT_LAZYLL && TAB && sizeof(REAL) == 8;
+    // LAZYLL in an instantiation without a production twin: tracing the running log-likelihood must not move the flushes
+    static constexpr bool TWINLESS_LL = STRATIFIED || N2;
     static constexpr bool PIVOTS = PFG_OPT_PIVOTS && SLOTS == 1024;
     static constexpr bool RAWCAP = MODE == MODE_PARIS && RNG == PFG_RNG_REPLAY;     // PaRIS on the window's raw np.random stream
 

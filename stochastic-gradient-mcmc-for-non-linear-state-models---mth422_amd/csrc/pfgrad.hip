@@ -162,8 +162,8 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
 }
 
 // What the plan needs of a valid batch: the longest window (Kalman: of steps [t1, tL), else of particles), the longest
-// FFBS buffer, whether any window records a trajectory, and the smoother to plan for.
-struct BatchSummary { int n_max = 0, t_max = 0; bool traced = false; int smoother = PFG_SMOOTHER_NEMETH; };
+// FFBS buffer, whether any window records a trajectory or asks for elementwise statistics, and the smoother to plan for.
+struct BatchSummary { int n_max = 0, t_max = 0; bool traced = false, elementwise = false; int smoother = PFG_SMOOTHER_NEMETH; };
 BatchSummary summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
     BatchSummary s;
     bool score1 = true;         // every window the Poyiadjis O(N) score: units with a twin specialised to it run that
@@ -171,6 +171,7 @@ BatchSummary summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
         const pfg_problem &q = ps[b];
         const pfg_result &r = rs[b];
         s.traced = s.traced || r.trace_x || r.trace_ll || r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || q.elementwise;
+        s.elementwise = s.elementwise || q.elementwise;
         score1 = score1 && q.smoother == PFG_SMOOTHER_NEMETH && q.lambduh == 1.0 && q.stat == PFG_STAT_SCORE;
         const int n = q.smoother == PFG_SMOOTHER_KALMAN ? (q.tL < q.T ? q.tL : q.T) - q.t1 : q.N;
         s.n_max = n > s.n_max ? n : s.n_max;
@@ -419,7 +420,7 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     // ---- plan ---------------------------------------------------------------------------
     const BatchSummary sum = summarize(B, ps, rs);
     const bool predictive = ps[0].stat == PFG_STAT_PREDICTIVE;   // large-N kernel only (any N)
-    LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng, sum.smoother, sum.n_max, B, sum.traced, predictive, sum.t_max);
+    LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng, sum.smoother, sum.n_max, B, sum.traced, predictive, sum.t_max, -1, sum.elementwise);
     if (plan.rc && !plan.name) return fail(ctx, plan.rc, plan.err);
     if (plan.family == Family::Grid && (rc = check_grid_batch(ctx, plan, B, ps))) return rc;
     // every window of the batch gets n_max-sized state (the predictive statistic's buffers after it)

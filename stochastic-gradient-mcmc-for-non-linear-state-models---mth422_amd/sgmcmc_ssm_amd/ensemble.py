@@ -67,7 +67,12 @@ class ChainEnsemble(object):
              (sgmcmc_sampler.py:1249-1283)
       parameters: a Parameters object (all chains start there) or an array [C, P] of raw thetas
       num_chains: C (ignored when `parameters` is an array)
-      N, pf ('poyiadjis_N' | 'nemeth' | 'paris'), lambduh, kernel: particle-filter settings
+      N, pf ('poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2'), lambduh, kernel: particle-filter settings
+               pf='poyiadjis_N2' (N <= 1024; the multi-window path up to 16384): the Poyiadjis O(N^2) smoother, the score
+               with lambduh = 1, multinomial resampling, kind 'pf'; N <= 128 runs one wave per window (n2_64x2) once a
+               launch has more than 64 windows.  GARCH: the reference's backward kernel scores only the x component of the
+               state, so the O(N^2) (and PaRIS) phi / lambda scores differ systematically from the O(N) ones; this backend
+               reproduces the reference
       Ntilde, max_accept_reject, accept_reject: pf='paris' (N <= 1024): the backward draws per particle, the
                accept-reject rounds before the exact draw (default 64; accept_reject=False: none, every draw exact),
                as the Helper's device-generator path (particle_filters.make_problem)
@@ -108,7 +113,8 @@ class ChainEnsemble(object):
                T_total / sum of the chosen T_k when num_sequences != -1: pfg_reduce_windows_device) and the update.
                Passing either argument (1 included) selects this multi-window path; it samples windows on the device
                (window_sampling='device', needed whenever there is anything to draw), so it replays in hipGraphs for
-               sequence lists too, and it runs pf='paris' up to N = 16384 (paris_mem1024 above N = 1024).  Leaving
+               sequence lists too, and it runs pf='paris' and pf='poyiadjis_N2' up to N = 16384 (paris_mem1024 /
+               n2_mem1024 above N = 1024).  Leaving
                both out keeps the single-window launches described above.  Refused: sampler='gibbs' or kind != 'pf'
                with W > 1, window_sampling='host' when windows are drawn, N > 16384.
 
@@ -116,7 +122,9 @@ class ChainEnsemble(object):
       _resolve_settings: the arguments above -> kind, pf, N, lambduh, the descriptor smoother `_smoother` and the launch
                smoother `_launch_smoother`, the stat, the PaRIS fields, M / K / W, the path (`_multi`: W descriptors per
                chain, records in win_out_dev, a reduction before the update), S, B, `strict`, the sequence bounds, and
-               every refusal that needs no device.  Nothing is allocated before it returns.
+               every refusal that needs no device.  Nothing is allocated before it returns.  pf='poyiadjis_N2' is
+               resolved there to the descriptor and launch smoother 'poyiadjis_n2' (lambduh = 1, the score); from then on
+               it takes the paths of the other smoothers unchanged.
       _capi.device_descriptors: the static fields of the `_nd` = C (single-window) or C * W (multi-window, chain-major)
                records of `_desc`; stream ids chain_offset + c, or (chain_offset + c) * W + w.
       _weights_blocks: weights_dev, one row per window start of every sequence longer than S, with the offsets of the
@@ -278,6 +286,8 @@ class ChainEnsemble(object):
         if kind != "pf":
             if pf == "paris":
                 raise ValueError("pf='paris' needs kind='pf'")
+            if pf == "poyiadjis_N2":
+                raise ValueError("pf='poyiadjis_N2' needs kind='pf'")
             if resampling == "stratified":
                 raise ValueError("resampling='stratified' needs kind='pf', got kind = '{0}'".format(kind))
             smoother = {"marginal": "kalman", "complete": "kalman_ffbs"}[kind]
@@ -293,6 +303,16 @@ class ChainEnsemble(object):
             if Ntilde < 1:
                 raise ValueError("pf='paris' needs Ntilde >= 1")
             smoother, paris = "paris", dict(Ntilde=Ntilde, max_accept_reject=max_accept_reject)
+        elif pf == "poyiadjis_N2":
+            # the Poyiadjis O(N^2) smoother on the LDS-resident kernels (n2_64x2 / n2_256x1 / n2_256x4): no per-chain
+            # scratch; the multi-window path also runs n2_mem1024 (1024 < N <= 16384, its state in the descriptors' scratch)
+            if N > 1024 and not multi:
+                raise NotImplementedError("ChainEnsemble(pf='poyiadjis_N2') is built for N <= 1024 on the single-window path, "
+                                          "got N = {0}: pass minibatch_size / num_sequences for the multi-window path "
+                                          "(n2_mem1024, N <= 16384)".format(N))
+            if resampling != "multinomial":
+                raise ValueError("pf='poyiadjis_N2' resamples multinomially, got resampling = {0}".format(resampling))
+            smoother = "poyiadjis_n2"
         elif pf in ("poyiadjis_N", "nemeth"):
             if pf == "nemeth":
                 lam = 0.95 if lambduh is None else float(lambduh)
@@ -308,7 +328,7 @@ class ChainEnsemble(object):
             elif resampling != "multinomial":
                 raise ValueError("Unrecognized resampling = {0}".format(resampling))
         else:
-            raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth' | 'paris', got {0}".format(pf))
+            raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2', got {0}".format(pf))
         # every chain the Poyiadjis O(N) score (NEMETH, lambduh = 1, score): units with a twin specialised to it run that
         launch_smoother = "poyiadjis_n" if smoother == "nemeth" and lam == 1.0 else smoother
         if window_sampling not in ("host", "device"):
@@ -392,9 +412,10 @@ class ChainEnsemble(object):
         if self._smoother == "kalman_ffbs":
             # the forward messages of the longest buffer: a window and its two buffers, or the whole series
             return _capi.kalman_scratch_bytes(min(self.T, self.S + 2 * self.B) if self.S > 0 else self.T)
-        if self._multi or self._smoother in ("paris", "nemeth_stratified"):
+        if self._multi or self._smoother in ("paris", "poyiadjis_n2", "nemeth_stratified"):
             # PaRIS, N <= 1024: 0, the LDS-resident variants keep their state in LDS; above: paris_mem1024's slab.  The
             # single-window PaRIS path (N <= 1024 only) relies on that answer of 0 where it once wrote the literal.
+            # The O(N^2) smoother likewise: 0 for N <= 1024, n2_mem1024's slab above it (multi-window path only).
             # Stratified windows: 0 for N <= 1024, the large-N twin's slab up to 16384
             sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", self._smoother, self.N)
             if sb < 0:
