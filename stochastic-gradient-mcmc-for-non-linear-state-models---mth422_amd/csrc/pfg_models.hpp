@@ -221,6 +221,44 @@ __device__ __forceinline__ void particle_step(const Consts<REAL> &c, const MATH 
     }
 }
 
+// particle_step for pf_reg_kernel's STALE instantiations (SVM prior, device generator, fp64 256 x 4 on one buffer;
+// RegTraits::STEP_TUNE), whose measures take instructions out of the step.  Every other caller keeps particle_step above.
+//   PFG_STEP_SHIFTFOLD  lw comes out as lw - shift: k0_shifted = svm_logw's wave-uniform constant k0 minus the shift;
+//   PFG_STEP_SCOREDZ    the score from the proposal's noise term dz = iLQinv z, which IS x1 - A xp: x1 = fma(A, xp, dz),
+//                       add[1] = iLQinv - dz^2 LQinv = fma(-dz, z, iLQinv), add[2] = (Qinv dz) xp = ((Qinv iLQinv) z) xp.
+enum { PFG_STEP_SHIFTFOLD = 1, PFG_STEP_SCOREDZ = 2 };
+#ifdef PFG_FAST_ALGEBRA
+template <int STAT, int TUNE, typename REAL, typename MATH>
+__device__ __forceinline__ void particle_step_svm_tuned(const Consts<REAL> &c, const MATH &mth, const REAL *xp,
+                                                        REAL y, REAL z, REAL *xn, REAL &lw, REAL *add, REAL k0_shifted) {
+    const REAL half = (REAL)0.5;
+    const REAL dz = c.iLQinv * z;
+    const REAL x1 = (TUNE & PFG_STEP_SCOREDZ) ? fma(c.A, xp[0], dz) : c.iLQinv * z + xp[0] * c.A;
+    const REAL e = mth.exp_finite(-x1);          // x1 is finite
+    const REAL y2 = y * y;
+    if (TUNE & PFG_STEP_SHIFTFOLD) {
+        const REAL ke = (-half * y2) * c.Rinv;
+        lw = fma(ke, e, fma(-half, x1, k0_shifted));
+    } else {
+        lw = svm_logw(c, x1, e, y2);
+    }
+    xn[0] = x1;
+    if (STAT == PFG_STAT_SCORE) {
+        if (TUNE & PFG_STEP_SCOREDZ) {
+            add[2] = ((c.Qinv * c.iLQinv) * z) * xp[0];
+            add[1] = fma(-dz, z, c.iLQinv);
+        } else {
+            const REAL dx = x1 - c.A * xp[0];
+            add[2] = (c.Qinv * dx) * xp[0];
+            add[1] = c.iLQinv - (dx * dx) * c.LQinv;
+        }
+        add[0] = fma(-(y2 * c.LRinv), e, c.iLRinv);
+    } else {
+        add[0] = x1; add[1] = x1 * x1; add[2] = xp[0] * x1;
+    }
+}
+#endif
+
 // Additive statistic h(parent, child) alone (PaRIS evaluates it for rewired parents): the same
 // expressions as in particle_step.  `aux` carries the child's sub-expression the proposal step
 // already has (SVM: exp(-x')).

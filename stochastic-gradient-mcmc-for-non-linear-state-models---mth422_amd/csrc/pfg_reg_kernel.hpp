@@ -291,6 +291,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
         for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
         m = uniform_f64((double)mm);
         block_sync<NW>();
+        if constexpr (TR::SHIFTFOLD) {          // the log-weights cross every loop edge as lw - shift
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) lw[k] -= (REAL)m;
+        }
     }
 
     for (int t = 0; t <= T; ++t) {
@@ -311,11 +315,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             }
         }
         // ---- (A) block max of the current log weights  (log_normalize, pf.py:374-377) ----
-        float ml = (float)lw[0];
+        // (SUMSHIFT: none -- the next shift comes from the scan total behind barrier 2; SHIFTFOLD alone: the maximum of lw - shift)
+        [[maybe_unused]] float ml = 0.0f;
+        if constexpr (!TR::SUMSHIFT) {
+            ml = (float)lw[0];
 #pragma unroll
-        for (int k = 1; k < PPT; ++k) ml = fmaxf(ml, (float)lw[k]);
-        ml = wave_max(ml);
-        if (NW > 1 && lane == 0) red_maxf[wave] = ml;
+            for (int k = 1; k < PPT; ++k) ml = fmaxf(ml, (float)lw[k]);
+            ml = wave_max(ml);
+            if (NW > 1 && lane == 0) red_maxf[wave] = ml;
+        }
         PFG_PH(0)
         if constexpr (!TR::STALE) block_sync<NW>();                                 // barrier 1
         PFG_PH(1)
@@ -329,7 +337,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
         const bool needS = needS_every || (t == T);
         double cs[PPT];
 #pragma unroll
-        for (int k = 0; k < PPT; ++k) cs[k] = (double)mth.exp((REAL)(lw[k] - (REAL)m));   // exp(-inf) = 0
+        for (int k = 0; k < PPT; ++k) cs[k] = (double)mth.exp(TR::SHIFTFOLD ? lw[k] : (REAL)(lw[k] - (REAL)m));   // exp(-inf) = 0
         if (needS) {
             PFG_MARK("cold needS")
 #pragma unroll
@@ -421,21 +429,51 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             W = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(inc), NW - 1),
                                  __builtin_amdgcn_readlane(__double2loint(inc), NW - 1));
             if constexpr (TR::STALE) {
-                // this step's exact maximum: the next step's shift, and the range guard of this one (NaN, +-inf fail it)
-                float mm = red_maxf[0];
+                bool retry;
+                if constexpr (TR::SUMSHIFT) {
+                    // the range guard on W's high word (every wave holds the same bits): 2^-728 <= W < 2^728, see PFG_OPT_SUMSHIFT
+                    constexpr uint32_t W_LO = (uint32_t)(1023 - 728) << 20, W_HI = (uint32_t)(1023 + 728) << 20;
+                    retry = t > 0 && !((uint32_t)__double2hiint(W) - W_LO < W_HI - W_LO);
+                } else {
+                    // this step's exact maximum: the next step's shift, and the range guard of this one (NaN, +-inf fail it)
+                    float mm = red_maxf[0];
 #pragma unroll
-                for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
-                m_next = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mm)));
-                if (t > 0 && !(fabsf(m_next - (float)m) <= 512.0f)) {
+                    for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
+                    if constexpr (TR::SHIFTFOLD) mm += (float)m;
+                    m_next = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mm)));
+                    retry = t > 0 && !(fabsf(m_next - (float)m) <= 512.0f);
+                }
+                if (retry) {
                     PFG_MARK("cold stale-shift-retry")
                     block_sync<NW>();
-                    m = uniform_f64((double)m_next);
+                    if constexpr (!TR::SUMSHIFT) m = uniform_f64((double)m_next);
                     const REAL y_p = (REAL)yv[t - 1], y2_p = y_p * y_p;
+                    REAL lwk[PPT];
 #pragma unroll
                     for (int k = 0; k < PPT; ++k) {
                         const REAL x1 = cur[sidx(0, own[k])];
-                        const REAL lwk = valid[k] ? svm_logw(c, x1, mth.exp_finite(-x1), y2_p) : (REAL)(-INFINITY);
-                        cs[k] = (double)mth.exp((REAL)(lwk - (REAL)m));
+                        lwk[k] = valid[k] ? svm_logw(c, x1, mth.exp_finite(-x1), y2_p) : (REAL)(-INFINITY);
+                        if constexpr (!TR::SUMSHIFT) cs[k] = (double)mth.exp((REAL)(lwk[k] - (REAL)m));
+                    }
+                    if constexpr (TR::SUMSHIFT) {
+                        // the exact block maximum as the shift, as in the t = 0 prologue (red_maxf is idle in the T-loop: every
+                        // earlier read of it lies behind at least this retry's first barrier)
+                        float rl = (float)lwk[0];
+#pragma unroll
+                        for (int k = 1; k < PPT; ++k) rl = fmaxf(rl, (float)lwk[k]);
+                        rl = wave_max(rl);
+                        if (lane == 0) red_maxf[wave] = rl;
+                        block_sync<NW>();
+                        float mm = red_maxf[0];
+#pragma unroll
+                        for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red_maxf[w]);
+                        m = uniform_f64((double)mm);
+#pragma unroll
+                        for (int k = 0; k < PPT; ++k) cs[k] = (double)mth.exp((REAL)(lwk[k] - (REAL)m));
+                    }
+                    if constexpr (TR::SHIFTFOLD) {          // final_logw of a retry at t = T
+#pragma unroll
+                        for (int k = 0; k < PPT; ++k) lw[k] = lwk[k] - (REAL)m;
                     }
                     if (needS) {
 #pragma unroll
@@ -466,6 +504,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                     for (int k = 0; k < PPT; ++k) cs[k] += off2;
                     W = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(incw), NW - 1),
                                          __builtin_amdgcn_readlane(__double2loint(incw), NW - 1));
+                }
+                if constexpr (TR::SUMSHIFT) {
+                    // the next shift: s + ln2 * e, W = f 2^e with f in [0.5, 1) -- the f32 value within ln 2 above the step's
+                    // log-sum-exp.  (W out of range at t = 0 or after the retry: whatever comes out is caught by the next guard)
+                    const int e = (int)(((uint32_t)__double2hiint(W) >> 20) & 0x7ffu) - 1022;
+                    const float sn = fmaf((float)e, 0.693147180559945f, (float)m);
+                    m_next = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sn)));
                 }
             }
             if (TR::SORTED && t < T) {
@@ -739,6 +784,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
         }
 #pragma unroll
         for (int k = 0; k < PPT; ++k) anc[k] = anc[k] < last ? anc[k] : last;
+        if constexpr (TR::GADDR && TRACE) {
+            // GADDR gathers by address: the index exists for the trace alone and is stored at once, not held across phases F-H
+            if (P.trace_x && P.trace_anc) {
+#pragma unroll
+                for (int k = 0; k < PPT; ++k)
+                    if (valid[k]) P.trace_anc[(size_t)t * N + k * NT + tid] = anc[k];
+            }
+        }
 #ifdef PFG_EXP_OWNGATHER
         // knock-out (timing / counters only, NOT a valid resampler): the real search runs (its result is kept alive), but
         // every child gathers its OWN slot -- conflict-free lane <-> particle reads: what is left of SQ_LDS_BANK_CONFLICT is
@@ -805,6 +858,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             // One straight-line block per case: the case is uniform, so it is decided once per timestep and
             // not per particle, and the stores of a FAST layout are unconditional (a slot beyond N has its own
             // LDS cell and weight 0) -- the PPT particle chains stay in one basic block for the scheduler.
+#if PFG_OPT_SHIFTFOLD
+            // SHIFTFOLD (A/B builds; the closures of every kernel of such a build capture one more variable): m is already the next
+            // step's shift here; the children's log-weights are born as lw - m, the shift riding in svm_logw's constant (one add per
+            // timestep, wave-uniform: scalar registers)
+            [[maybe_unused]] REAL k0_shifted = (REAL)0;
+            if constexpr (TR::SHIFTFOLD) k0_shifted = (REAL)uniform_f64((double)(c.c0 + c.logLRinv) - m);
+#endif
             auto children = [&](auto upd_tag) {
                 constexpr int UPD = decltype(upd_tag)::value;      // 0 plain + statistic, 1 plain, no statistic, 2 general
                 if (UPD == 1) { PFG_MARK("cold children-outside-window") }
@@ -812,6 +872,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) {
                     REAL xn[NS], add[H], lwn;
+#ifdef PFG_FAST_ALGEBRA
+#if PFG_OPT_SHIFTFOLD
+                    if constexpr (TR::STEP_TUNE != 0) particle_step_svm_tuned<STAT, TR::STEP_TUNE>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add, k0_shifted);
+#else
+                    if constexpr (TR::STEP_TUNE != 0) particle_step_svm_tuned<STAT, TR::STEP_TUNE>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add, (REAL)0);
+#endif
+                    else
+#endif
                     particle_step<MODEL, KERNEL, STAT, REAL>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add);
                     lw[k] = valid[k] ? lwn : (REAL)(-INFINITY);
                     if (UPD == 0) {
@@ -1327,10 +1395,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 if (valid[k]) {
                     const int i = k * NT + tid;
                     const size_t row = (size_t)(t + 1) * N + i;
+                    if constexpr (!(TR::GADDR && TRACE)) {          // GADDR: stored behind the search
                     if (P.trace_anc) P.trace_anc[(size_t)t * N + i] = anc[k];
+                    }
 #pragma unroll
                     for (int d = 0; d < NS; ++d) P.trace_x[row * NS + d] = (double)nxt[sidx(d, i)];
-                    P.trace_logw[row] = (double)lw[k];
+                    P.trace_logw[row] = TR::SHIFTFOLD ? (double)lw[k] + m : (double)lw[k];
                     if (P.trace_stats && !is_filter) {
 #pragma unroll
                         for (int h = 0; h < H; ++h)
@@ -1385,7 +1455,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             if (i < N) {
 #pragma unroll
                 for (int d = 0; d < NS; ++d) P.final_x[(size_t)i * NS + d] = (double)cur[sidx(d, i)];
-                if (P.final_logw) P.final_logw[i] = (double)lw[k];
+                if (P.final_logw) P.final_logw[i] = TR::SHIFTFOLD ? (double)lw[k] + m : (double)lw[k];
                 if (P.final_stats && !is_filter) {
 #pragma unroll
                     for (int h = 0; h < H; ++h)

@@ -78,6 +78,41 @@ namespace pfg {
 #ifndef PFG_OPT_GATHERADDR
 #define PFG_OPT_GATHERADDR 1
 #endif
+//  The same two STALE instantiations (TRACE twins), three instruction-count measures that move no barrier:
+//  PFG_OPT_SUMSHIFT    (SUMSHIFT) no max reduction in the T-loop..  The shift of the next step comes from the scan total W_t
+//                  = sum exp(lw_t - s_t) that the CDF needs anyway: s_{t+1} = (float)(s_t + ln2 * e) with W_t = f 2^e, f in
+//                  [0.5, 1) (the binary exponent, read from W's high word with scalar integer instructions).  s_t + ln W_t
+//                  is the step's log-sum-exp, in [max, max + ln 1024], and absolute: it does not drift with s_t.  The
+//                  range guard sits on W: accepted iff 2^-728 <= W_t < 2^728 (one unsigned compare of the high word; NaN,
+//                  +-inf, 0, denormals and negatives fail it), so the true maximum of an accepted step lies in
+//                  [s_t - 728 ln2 - ln 1024, s_t + 728 ln2) = [s_t - 511.6, s_t + 504.7): stricter than |m_t - s_t| <= 512.
+//                  The t = 0 prologue keeps its exact maximum; the cold retry now forms the exact block maximum itself
+//                  (wave_max, red_maxf, one more barrier).  Phase A, the red_maxf write before barrier 2 and its read-back
+//                  behind it are gone.
+//  PFG_OPT_SHIFTFOLD   (SHIFTFOLD) the next shift is known behind barrier 2, before phase G: the children's log-weights are
+//                  born as lw - s_next (k0 - s_next in svm_logw, one wave-uniform add per timestep) and cross the loop
+//                  edge that way; phase B exponentiates them without its four v_add_f64.  Traces and final_logw add the
+//                  shift back; the retry recomputes unshifted log-weights as before.
+//  PFG_OPT_SCOREDZ     (SCOREDZ) particle_step, SVM score: dx = x1 - A xp IS iLQinv z, so x1 = fma(A, xp, dz), add[1] =
+//                  fma(-dz, z, iLQinv), add[2] = ((Qinv iLQinv) z) xp: two fp64 instructions per particle less.
+//  A/B (profiles/r06_ab_sum_shift.txt; c2 kernel ms per 12288 chains, medians of five interleaved processes per library, the
+//  parent's own max - min 0.13): parent 41.68; SCOREDZ alone 41.17 (-1.2 %, 3.8 x the spread): ON -- its outputs are the
+//  parent's to rounding (120 bench steps, 12288 chains: every chain within 5e-11).  SUMSHIFT alone 40.28 (-3.4 %), with
+//  SCOREDZ 39.75 (-4.8 %): measured and NOT kept, OFF -- another shift moves every argument of the table exp, whose cubic's
+//  error (2e-12, a function of the reduced argument) then differs per particle: the normalised weights move at 1e-12, an
+//  ancestor flips about once in ten launches of 12288 chains, and after 120 bench steps 14 of the 12288 chains had left
+//  the parent's trajectory (same distribution, not the same numbers).  SHIFTFOLD alone 41.80 (+0.3 %), on top of the other
+//  two +0.5 %: NOT kept, OFF.  Default build (SCOREDZ): 128 VGPRs, no spill, occupancy 4; the traced twin 1 spilled VGPR (the
+//  GADDR trace index is stored behind the search instead of being held across phases F-H).
+#ifndef PFG_OPT_SUMSHIFT
+#define PFG_OPT_SUMSHIFT 0
+#endif
+#ifndef PFG_OPT_SHIFTFOLD
+#define PFG_OPT_SHIFTFOLD 0
+#endif
+#ifndef PFG_OPT_SCOREDZ
+#define PFG_OPT_SCOREDZ 1
+#endif
 // PFG_OPT_N2SKIP (the O(N^2) instantiations, MODE_N2): the backward sweep over all parents is skipped on the steps before t1 of a
 // window that starts without init_stats -- its result there is +0.0 exactly, see n2_slots.  -DPFG_OPT_N2SKIP=0 runs every sweep (A/B).
 #ifndef PFG_OPT_N2SKIP
@@ -187,6 +222,9 @@ struct RegTraits {
     // STALE: the previous step's maximum as this step's shift, see PFG_OPT_STALESHIFT
     static constexpr bool STALE = PFG_OPT_STALESHIFT && BLK && MODEL == PFG_MODEL_SVM && KERNEL == PFG_KERNEL_PRIOR && NT == 256 && PPT == 4 &&
                                   !PP && sizeof(REAL) == 8;
+    // the three instruction-count measures of the STALE kernels, see PFG_OPT_SUMSHIFT; STEP_TUNE selects particle_step_svm_tuned
+    static constexpr bool SUMSHIFT = PFG_OPT_SUMSHIFT && STALE, SHIFTFOLD = PFG_OPT_SHIFTFOLD && STALE, SCOREDZ = PFG_OPT_SCOREDZ && STALE;
+    static constexpr int STEP_TUNE = (SHIFTFOLD ? PFG_STEP_SHIFTFOLD : 0) | (SCOREDZ ? PFG_STEP_SCOREDZ : 0);
     // GADDR (256 x 4): search offset -> gather byte address..  rel = 4 x physical CDF position (one pad slot per 32 entries), p4 =
     // rel - 4 (rel * 993 >> 17) = 4 x CDF position p (exact: rel * 993 < 2^23), and (p4 * 1025) & 0x3ff0 = 16 x the particle index
     // ((p & 3) << 8) | (p >> 2): p4 < 2^12, so the copies p4 << 10 and p4 do not overlap -- bits 4..11 of p4 are p >> 2 and bits
