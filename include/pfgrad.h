@@ -160,6 +160,28 @@ enum pfg_status {
                                             * parents from the exact backward categorical (REPLAY + paris_stream only) */
 #define PFG_FLAG_PARIS_RAW_STREAM 4u       /* paris_stream is the window's WHOLE np.random stream (see pfg_problem.paris_stream) */
 #define PFG_FLAG_PARIS_RAW_CARRY 8u        /* ... and its first double is the generator's cached Gaussian (has_gauss = 1) */
+/* EXTENSION (not in the reference, which resamples at every timestep): ESS-triggered (ADAPTIVE) resampling with the
+ * threshold tau in (0, 1], an IEEE binary32 whose BITS travel in `reserved`, the int32 right behind `flags` in pfg_problem
+ * and pfg_dev_problem (tau = 0.5 is 0x3F000000; memcpy(&reserved, &tau, 4); 0 without the flag).  At timestep t, with
+ * w_i = exp(logw_i - m), m = max logw and p = w / sum w (S, the shrinkage target, is sum_i p_i stats_i of the CURRENT weights
+ * as always), the step resamples iff, in fp64,
+ *     (sum w)^2 < ((double)tau * N) * sum w^2                      (ESS = 1 / sum p^2 < tau N)
+ * as today: multinomial ancestors from the unchanged CDF, the children's log-weights are new_logw.  Otherwise child i is
+ * parent i (trace_anc is the identity) and
+ *     logw_i = ((logw_i - m) - log(sum w)) + log N + new_logw_i    (log domain: an underflowed weight stays finite)
+ * so the log-likelihood increment log(mean(exp(logw))) and the final mean_stat use the carried weights.
+ * Built for: smoother NEMETH (any lambduh), stat SCORE / SUFF / NONE, both generators, f64 and f32 state, N <= 16384 --
+ * "adaptive256x4" (N <= 1024), above it "mem1024_adaptive" (REPLAY) or "big4096_adaptive" / "big16384_adaptive" (DEVICE);
+ * pfg_last_variant reports these.  A step that keeps its particles builds no CDF and runs no search.
+ * REPLAY: the window reads the streams of a multinomial window; u[t] of a step that does not resample is ignored.
+ * DEVICE: on a step that does not resample a lane of adaptive256x4 draws its normals only (no resampling word); a lane of
+ * big*_adaptive has drawn -- and drops -- the step's spacing words (they come before the decision).  Traced launches record
+ * as the multinomial kernels do (rec_ud: the uniform child i searched with; rec_z, rec_z0); what rec_ud holds for a step
+ * that did not resample is unspecified.
+ * pfg_run / pfg_run_batch route by the flag: a batch is all-adaptive or adaptive-free (INVALID); with FILTER, PARIS,
+ * POYIADJIS_N2, systematic or stratified windows, PFG_STAT_PREDICTIVE, `elementwise` or N > 16384 (whole-GPU windows):
+ * UNSUPPORTED, the message says which; tau outside (0, 1] (NaN included): INVALID.  Resident launches: pfg_launch_device_adaptive. */
+#define PFG_FLAG_ADAPTIVE_RESAMPLING 16u
 
 /* One buffered PF window, host side (all pointers are HOST pointers, C-contiguous f64). */
 typedef struct pfg_problem {
@@ -168,7 +190,7 @@ typedef struct pfg_problem {
     int32_t T;               /* timesteps of the buffered window */
     int32_t t1, tL;          /* statistic / log-likelihood accumulate on [t1, tL) */
     uint32_t flags;
-    int32_t reserved;
+    int32_t reserved;        /* PFG_FLAG_ADAPTIVE_RESAMPLING: the bits of the binary32 threshold tau in (0, 1]; else 0 */
     double lambduh;          /* Nemeth shrinkage; 1.0 = Poyiadjis O(N) */
     double prior_mean, prior_var;
     const double *y;         /* [T] observations (m = 1) */
@@ -276,7 +298,7 @@ typedef struct pfg_dev_problem {
     int32_t T, t1, tL, N;
     int32_t smoother, stat;
     uint32_t flags;
-    int32_t reserved;
+    int32_t reserved;        /* PFG_FLAG_ADAPTIVE_RESAMPLING: the bits of the binary32 threshold tau in (0, 1]; else 0 */
     const double *paris_idx_u, *paris_acc_u, *paris_man_u;   /* PaRIS REPLAY pools (see pfg_problem) */
     int32_t Ntilde, max_accept_reject;
     int32_t *trace_anc;      /* [T*N] or NULL */
@@ -350,6 +372,16 @@ int pfg_last_traced(pfg_ctx *ctx);
  * they hold n_max), "n2_mem1024" above that (state in the descriptors' scratch) */
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother,
                                int n_max, int B, const pfg_dev_problem *dev_probs, void *hip_stream);
+/* as pfg_launch_device for a batch of ADAPTIVE windows (PFG_FLAG_ADAPTIVE_RESAMPLING; the launch does not read the
+ * descriptors, so the family is stated here): NEMETH descriptors with the flag and the threshold's bits in `reserved`, n_max <= 16384.
+ * traced != 0: the launch honours trace_* / rec_* (one instantiation serves both; the `out` records are bitwise the same).
+ * A descriptor without the flag, with another smoother or with PFG_STAT_PREDICTIVE gets NaNs in out[0..7].  Scratch per
+ * descriptor (n_max > 1024): pfg_scratch_bytes(model, dtype, PFG_RNG_REPLAY, n_max) -- the large-N kernels' state, the same
+ * for both generators, and what pfg_scratch_bytes_smoother(..., PFG_SMOOTHER_NEMETH, N) answers except for the DEVICE
+ * generator and 1024 < N <= 4096, where plain windows run LDS-resident (0) and adaptive ones do not.  n_max > 16384:
+ * UNSUPPORTED. */
+int pfg_launch_device_adaptive(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int B,
+                               const pfg_dev_problem *dev_probs, void *hip_stream, int traced);
 /* N above the one-workgroup kernels' maximum (16384 < N <= 4194304; the reference has no limit and its bias experiments
  * call pf_gradient_estimate with N = 1000000: gradient_error_fig_scripts/svm_grad_compare.py:68-82): every window of the
  * batch runs as a WHOLE-GPU window -- the particle axis cut into tiles of 1024 (N <= 524288) / 2048 particles, one 256-thread workgroup each, one

@@ -27,17 +27,25 @@ namespace pfg {
 //    (red_scanE / red_offE) and its share of barrier 2b's wave, the generator snapshot and the recomputation of the
 //    spacings (one more -log and one more wave scan per child) in the sweep.  CDF, search, chunks in flight and gather
 //    are the same code.
+//  * ADAPT = true, the ADAPTIVE twin (PFG_FLAG_ADAPTIVE_RESAMPLING; "big4096_adaptive" / "big16384_adaptive"): resample only
+//    when the effective sample size is below tau N.  The sum of w^2 rides on the weight phase (one more LDS slot per wave,
+//    red_p2), wave 0 adds the slots beside its offset scan and broadcasts the total through LDS (red_W[2]), and every wave
+//    makes the SAME comparison of the same two LDS values scalar -- barrier 3 is skipped under it.  A step that resamples is
+//    the multinomial kernel's step; one that does not globalises no CDF and runs no search: child i proposes from record i
+//    (this thread's own) and its log-weight carries on (`keep`).  The spacing words of a step are drawn in (B,C), before the
+//    decision exists: a step that keeps its particles has drawn and scanned them and drops them (include/pfgrad.h).
 // ------------------------------------------------------------------------------------
-template <typename REAL, bool STRAT = false>
+template <typename REAL, bool STRAT = false, bool ADAPT = false>
 __host__ __device__ inline size_t big_kernel_lds_bytes(int NP2) {
     // CDF (padded) | 4 x [chunks * waves] scan totals / offsets (weights, spacings; STRAT: 2 x, weights only) | wave maxima |
     // S partials | tables
-    return ((size_t)NP2 + NP2 / 32) * 8 + (size_t)((STRAT ? 2 : 4) * (NP2 / MEM_NT) * MEM_NW + MEM_NW + PFG_MAX_STAT * MEM_NW + 8) * 8 +
+    return ((size_t)NP2 + NP2 / 32) * 8 + (size_t)((STRAT ? 2 : 4) * (NP2 / MEM_NT) * MEM_NW + MEM_NW + PFG_MAX_STAT * MEM_NW + 8 + (ADAPT ? MEM_NW : 0)) * 8 +
            tab_bytes<REAL, PFG_RNG_DEVICE, true>();
 }
 
-template <int MODEL, int KERNEL, typename REAL, int NP2, bool STRAT = false>
+template <int MODEL, int KERNEL, typename REAL, int NP2, bool STRAT = false, bool ADAPT = false>
 __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *__restrict__ probs) {
+    static_assert(!(STRAT && ADAPT), "adaptive resampling draws multinomially");
     constexpr int RNG = PFG_RNG_DEVICE;
     constexpr int NS = ModelDims<MODEL>::NS;
     constexpr int H = ModelDims<MODEL>::H;
@@ -61,6 +69,14 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
     const int nchunk = (N + NT - 1) / NT;                           // <= CH2
+    if constexpr (ADAPT) {
+        // a descriptor that does not ask for adaptive resampling, or asks for what it is not built for: NaNs
+        if (!(P.flags & PFG_FLAG_ADAPTIVE_RESAMPLING) || P.smoother != PFG_SMOOTHER_NEMETH || P.stat == PFG_STAT_PREDICTIVE) {
+            if (threadIdx.x < PFG_OUT_DOUBLES && P.out) P.out[threadIdx.x] = __builtin_nan("");
+            return;
+        }
+    }
+    [[maybe_unused]] const double tauN = ADAPT ? (double)ess_threshold_of(P.reserved) * (double)N : 0.0;
     const bool is_filter = (P.smoother == PFG_SMOOTHER_FILTER);
     const int stat = P.stat;
     const double lam_d = is_filter ? 0.0 : P.lambduh;
@@ -77,8 +93,9 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
     double *red_max = STRAT ? red_offE : red_offE + CH2 * NW;       // [NW]
     float *red_maxf = reinterpret_cast<float *>(red_max);
     double *red_S = red_max + NW;                                   // [H*NW]
-    double *red_W = red_S + PFG_MAX_STAT * NW;                      // [8]: W, total of the spacings
-    double *tabmem = red_W + 8;
+    double *red_W = red_S + PFG_MAX_STAT * NW;                      // [8]: W, total of the spacings, (ADAPT) sum of w^2
+    [[maybe_unused]] double *red_p2 = red_W + 8;                    // [NW] the waves' sums of w^2 (ADAPT only)
+    double *tabmem = red_W + 8 + (ADAPT ? NW : 0);
 
     constexpr int REC = mem_rec_len<MODEL, REAL>();
     gptr<REAL> lwg = global_ptr(reinterpret_cast<REAL *>(P.scratch));    // [N]
@@ -180,6 +197,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
         float e_extra = 0.0f;
         {
             double part[H];
+            [[maybe_unused]] double p2 = 0.0;                       // ADAPT: sum of w^2
 #pragma unroll
             for (int h = 0; h < H; ++h) part[h] = 0.0;
 #pragma unroll 2
@@ -191,6 +209,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
                     const REAL lwv = LWREG ? lwr[LWREG ? j : 0] : lwg[ii];
                     double p = (double)mth.exp((REAL)(lwv - (REAL)m));
                     p = v ? p : 0.0;
+                    if (ADAPT) p2 += p * p;
                     if (needS) {
 #pragma unroll
                         for (int h = 0; h < H; ++h) part[h] += (double)cur[(size_t)ii * REC + NS + h] * p;
@@ -207,6 +226,10 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
                 }
             }
             if (!STRAT && t < T) e_extra = spacing_f32(rng.next());           // spacing N + 1: part of the total only
+            if (ADAPT && t < T) {
+                p2 = wave_sum(p2);
+                if (lane == 0) red_p2[wave] = p2;
+            }
             if (needS) {
 #pragma unroll
                 for (int h = 0; h < H; ++h) {
@@ -238,11 +261,22 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
                 run += v4[q];
             }
             if (lane == WAVE - 1) red_W[wave] = inc + (wave == 1 ? (double)e_extra : 0.0);
+            if (ADAPT && wave == 0 && t < T) {
+                double W2 = red_p2[0];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) W2 += red_p2[w];
+                if (lane == WAVE - 1) red_W[2] = W2;
+            }
         }
         __syncthreads();                                                        // barrier 2b
         W = uniform_f64(red_W[0]);
         const double invW = uniform_f64(1.0 / W);
         [[maybe_unused]] const double invEtot = (!STRAT && t < T) ? uniform_f64(1.0 / red_W[1]) : 0.0;
+        // ADAPT: resample iff ESS = W^2 / sum w^2 < tau N -- one comparison of two LDS values every wave reads alike, made scalar
+        [[maybe_unused]] bool resample = true;
+        if constexpr (ADAPT) {
+            if (t < T) resample = __builtin_amdgcn_readfirstlane((int)(W * W < tauN * red_W[2])) != 0;
+        }
         if (needS) {
 #pragma unroll
             for (int h = 0; h < H; ++h) {
@@ -263,6 +297,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
         if (t == T) break;
 
         // ---- (D) globalise + normalise the own CDF entries ---------------------------------
+        if (!ADAPT || resample) {
 #pragma unroll 2
         for (int j = 0; j < CH2; ++j) {
             const int i = j * NT + tid;
@@ -272,6 +307,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
             }
         }
         __syncthreads();                                                        // barrier 3
+        }
 
         const double y_t = yv[t];
         const bool inside = (t >= t1) && (t < tL);
@@ -369,7 +405,84 @@ __global__ __launch_bounds__(MEM_NT) void pf_big_kernel(const pfg_dev_problem *_
                 }
             }
         };
-        if (stat == PFG_STAT_SCORE) sweep(std::integral_constant<int, PFG_STAT_SCORE>{});
+        // ADAPT, ESS >= tau N: child i proposes from record i (this thread's own) with the normals the sweep would have given
+        // it, and its log-weight carries on, base = (logw - m) - log(sum exp(logw - m)) + log N in the log domain
+        [[maybe_unused]] auto keep = [&](auto stat_tag) {
+            constexpr int STAT = decltype(stat_tag)::value;
+            const double lse = uniform_f64(log(W)), lgN = uniform_f64(log((double)N));
+            for (int j0 = 0; j0 < nchunk; j0 += G) {
+                int i[G];
+                bool v[G];
+                REAL z[G], lwo[G];
+                alignas(16) REAL rec[G][REC];
+                // the G own records (and log-weights) are in flight together, as the sweep's gathers are
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    i[g] = (j0 + g) * NT + tid;
+                    v[g] = i[g] < N;
+                    const int ii = v[g] ? i[g] : N - 1;
+                    rec_load<REC, REAL>(rec[g], cur + (size_t)ii * REC);
+                    lwo[g] = (REAL)(-INFINITY);
+                    if (LWREG) {
+#pragma unroll
+                        for (int q = 0; q < (LWREG ? CH2 : 1); ++q) lwo[g] = (q == j0 + g) ? lwr[q] : lwo[g];
+                    } else {
+                        lwo[g] = lwg[ii];
+                    }
+                }
+#pragma unroll
+                for (int g = 0; g < G; g += 2) mth.normal_pair(rng.next(), rng.next(), z[g], z[g + 1]);
+                if (P.trace_x && P.rec_z) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g)
+                        if (v[g]) P.rec_z[(size_t)t * N + i[g]] = (double)z[g];
+                }
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    REAL xp[NS], sp[H], xn[NS], add[H], lwn;
+#pragma unroll
+                    for (int d = 0; d < NS; ++d) xp[d] = rec[g][d];
+#pragma unroll
+                    for (int h = 0; h < H; ++h) sp[h] = rec[g][NS + h];
+                    particle_step<MODEL, KERNEL, STAT, REAL>(c, mth, xp, (REAL)y_t, z[g], xn, lwn, add);
+#pragma unroll
+                    for (int h = 0; h < H; ++h) {
+                        const REAL av = use_stat ? add[h] * (REAL)wt : (REAL)0;
+                        sp[h] = (lam * sp[h] + oml * (REAL)S[h]) + av;
+                    }
+                    lwn = v[g] ? (REAL)(((((double)lwo[g] - m) - lse) + lgN) + (double)lwn) : (REAL)(-INFINITY);
+                    if (LWREG) {
+#pragma unroll
+                        for (int q = 0; q < (LWREG ? CH2 : 1); ++q) lwr[q] = (q == j0 + g) ? lwn : lwr[q];
+                    }
+                    if (v[g]) {
+                        if (!LWREG) lwg[i[g]] = lwn;
+#pragma unroll
+                        for (int d = 0; d < NS; ++d) rec[g][d] = xn[d];
+#pragma unroll
+                        for (int h = 0; h < H; ++h) rec[g][NS + h] = sp[h];
+                        rec_store<REC, REAL>(nxt + (size_t)i[g] * REC, rec[g]);
+                        if (P.trace_x) {
+                            const size_t row = (size_t)(t + 1) * N + i[g];
+                            if (P.trace_anc) P.trace_anc[(size_t)t * N + i[g]] = i[g];
+#pragma unroll
+                            for (int d = 0; d < NS; ++d) P.trace_x[row * NS + d] = (double)xn[d];
+                            P.trace_logw[row] = (double)lwn;
+                            if (P.trace_stats) {
+#pragma unroll
+                                for (int h = 0; h < H; ++h) P.trace_stats[row * H + h] = (double)sp[h];
+                            }
+                        }
+                    }
+                }
+            }
+        };
+        if (ADAPT && !resample) {
+            if constexpr (ADAPT) {
+                if (stat == PFG_STAT_SCORE) keep(std::integral_constant<int, PFG_STAT_SCORE>{});
+                else keep(std::integral_constant<int, PFG_STAT_SUFF>{});
+            }
+        } else if (stat == PFG_STAT_SCORE) sweep(std::integral_constant<int, PFG_STAT_SCORE>{});
         else sweep(std::integral_constant<int, PFG_STAT_SUFF>{});
         { gptr<REAL> tmp = cur; cur = nxt; nxt = tmp; }
         wt_prev = wt;

@@ -112,6 +112,8 @@ enum class Family {
     Stratified,    // stratified resampling (PFG_SMOOTHER_NEMETH_STRATIFIED), three size classes: the LDS-resident 256 x 4
                    // instantiation (n_max <= 1024; np2 = 0), above it the large-N kernel's twin (REPLAY; lw4: N <= 4096) or
                    // the fast large-N kernel's twin (device generator, np2 slots)
+    Adaptive,      // ESS-triggered resampling (PFG_FLAG_ADAPTIVE_RESAMPLING), the same three size classes as Stratified: the
+                   // 256 x 4 LDS-resident instantiation, the large-N kernel's twin (REPLAY) or the fast large-N kernel's (device)
     Mem,           // large-N kernel (state in an HBM scratch); lw4: N <= 4096, log-weights in registers
     Big,           // large-N kernel, device-generator fast path for np2 particle slots
     Grid,          // whole-GPU window above the one-workgroup kernels' maximum (pfg_grid_kernel.hpp), tile class (ppt, kmax)
@@ -173,6 +175,9 @@ int launch_ffbs(pfg_ctx *ctx, const LaunchPlan &p, int rng, int B, const pfg_dev
 // (N above the one-workgroup kernels, or PFGRAD_VARIANT=grid, runs as whole-GPU windows), pfg_launch_device* (one-workgroup
 // kernels only) and pfg_launch_device_grid* (whole-GPU windows).
 enum class Caller { Query, Batch, Device, Grid };
+// make_plan's `smoother` for a batch of adaptive windows (PFG_FLAG_ADAPTIVE_RESAMPLING): a planner-level id like
+// PFG_SMOOTHER_POYIADJIS_N is a launch-level one, outside the ABI's enum -- the descriptors say NEMETH and carry the flag
+constexpr int kPlanAdaptive = 1000;
 LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B, bool traced,
                      bool predictive = false, int t_max = 0, int phase = -1, bool elementwise = false);
 int check_ids(pfg_ctx *ctx, int smoother, int model, int kernel, int dtype, int rng);

@@ -159,6 +159,21 @@ int launch_stratified(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_pr
     }
 }
 
+// adaptive (ESS-triggered) resampling: the same three size classes, each a twin of the kernel that serves multinomial
+// windows of that size
+template <int MODEL, int KERNEL, typename REAL, int RNG>
+int launch_adaptive(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
+    if (p.np2 == 0 && p.nt == 256)
+        return launch_one_t<MODEL, KERNEL, REAL, 256, 4, RNG, sizeof(REAL) == 4, pfg::MODE_ADAPTIVE>(ctx, p, B, dp, st);
+    if constexpr (RNG == PFG_RNG_REPLAY) {
+        if (p.lw4) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, true, false, false, true>, pfg::MEM_NT, p, B, dp, st);
+        return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, false, false, false, true>, pfg::MEM_NT, p, B, dp, st);
+    } else {
+        if (p.np2 == 4096) return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 4096, false, true>, pfg::MEM_NT, p, B, dp, st);
+        return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 16384, false, true>, pfg::MEM_NT, p, B, dp, st);
+    }
+}
+
 // every kernel of one (model, proposal kernel, generator): explicitly instantiated in
 // pfg_inst_<model>_<kernel>_<rng>.hip.  The DEVICE-generator units are compiled with
 // -ffp-contract=fast (no operation-order parity to keep there), the REPLAY units with
@@ -198,6 +213,8 @@ int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *
 #undef PFG_GRID_CASE
         case Family::Stratified:    // (last: the kernels above keep their places in the code object)
             return p.f64 ? launch_stratified<MODEL, KERNEL, double, RNG>(ctx, p, B, dp, st) : launch_stratified<MODEL, KERNEL, float, RNG>(ctx, p, B, dp, st);
+        case Family::Adaptive:      // (behind Stratified, for the same reason)
+            return p.f64 ? launch_adaptive<MODEL, KERNEL, double, RNG>(ctx, p, B, dp, st) : launch_adaptive<MODEL, KERNEL, float, RNG>(ctx, p, B, dp, st);
         case Family::None:
             break;
     }

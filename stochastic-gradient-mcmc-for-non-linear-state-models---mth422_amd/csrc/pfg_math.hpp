@@ -10,7 +10,9 @@ namespace pfg {
 
 constexpr int WAVE = 64;
 // kernel instantiation modes beyond the plain filter / Nemeth path
-constexpr int MODE_PLAIN = 0, MODE_PARIS = 1, MODE_SYSTEMATIC = 2, MODE_N2 = 3, MODE_STRATIFIED = 4;
+constexpr int MODE_PLAIN = 0, MODE_PARIS = 1, MODE_SYSTEMATIC = 2, MODE_N2 = 3, MODE_STRATIFIED = 4, MODE_ADAPTIVE = 5;
+// the threshold of PFG_FLAG_ADAPTIVE_RESAMPLING: a binary32 whose bits travel in the descriptors' `reserved` word (pfgrad.h)
+__host__ __device__ inline float ess_threshold_of(int32_t reserved) { return __builtin_bit_cast(float, reserved); }
 constexpr double LOG_2PI = 1.8378770664093453;   // log(2*pi)
 
 // Pointers that arrive inside a descriptor (pfg_dev_problem) are generic to the compiler, and a generic access is a FLAT

@@ -87,9 +87,16 @@ __host__ __device__ inline size_t mem_kernel_lds_bytes(int N) {
 // STRAT (PFG_SMOOTHER_NEMETH_STRATIFIED, REPLAY): child i searches with (i + u[t][i]) / N instead of u[t][i] -- one
 // addition and one IEEE division on the loaded uniform, nothing else differs.  A template argument, not a branch on the
 // descriptor: the instantiations that exist keep their code, registers and numbers to the bit.
-template <int MODEL, int KERNEL, typename REAL, int RNG, bool PARIS = false, bool LW4 = false, bool SCORE1 = false, bool STRAT = false>
+// ADAPT (PFG_FLAG_ADAPTIVE_RESAMPLING, REPLAY; "mem1024_adaptive"): resample only when the effective sample size is below
+// tau N.  The sum of w^2 rides on the weight phase (one LDS slot per wave, red_pt: the predictive statistic is refused),
+// wave 0 adds the slots beside its offset scan and broadcasts the total through LDS, and every wave makes the SAME comparison
+// of the same two LDS values scalar -- barrier 3 is skipped under it.  A step that keeps its particles builds no CDF and runs
+// no search: child i proposes from record i and its log-weight carries on (`keep` below).  A template argument, like STRAT.
+template <int MODEL, int KERNEL, typename REAL, int RNG, bool PARIS = false, bool LW4 = false, bool SCORE1 = false, bool STRAT = false,
+          bool ADAPT = false>
 __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *__restrict__ probs) {
     static_assert(!(PARIS && LW4), "LW4 is a variant of the plain kernel");
+    static_assert(!ADAPT || (RNG == PFG_RNG_REPLAY && !PARIS && !SCORE1 && !STRAT), "the adaptive twin is a REPLAY instantiation of the plain kernel");
     static_assert(!STRAT || (RNG == PFG_RNG_REPLAY && !PARIS && !SCORE1), "the stratified twin is a REPLAY instantiation of the plain kernel");
     static_assert(!SCORE1 || LW4, "the score-only twin exists for the N <= 4096 variant");
     constexpr int NS = ModelDims<MODEL>::NS;
@@ -119,6 +126,14 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
             return;
         }
     }
+    if constexpr (ADAPT) {
+        // a descriptor that does not ask for adaptive resampling, or asks for what it is not built for: NaNs
+        if (!(P.flags & PFG_FLAG_ADAPTIVE_RESAMPLING) || P.smoother != PFG_SMOOTHER_NEMETH || P.stat == PFG_STAT_PREDICTIVE) {
+            if (threadIdx.x < PFG_OUT_DOUBLES && P.out) P.out[threadIdx.x] = __builtin_nan("");
+            return;
+        }
+    }
+    [[maybe_unused]] const double tauN = ADAPT ? (double)ess_threshold_of(P.reserved) * (double)N : 0.0;
     const bool is_filter = !SCORE1 && (P.smoother == PFG_SMOOTHER_FILTER);
     const int stat = SCORE1 ? (int)PFG_STAT_SCORE : P.stat;
     const double lam_d = SCORE1 ? 1.0 : is_filter ? 0.0 : (PARIS ? 1.0 : P.lambduh);
@@ -368,6 +383,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
         const bool needS = needS_every || (t == T);
         {
             double ptot = 0.0;
+            [[maybe_unused]] double p2 = 0.0;                       // ADAPT: sum of w^2
             double part[H];
 #pragma unroll
             for (int h = 0; h < H; ++h) part[h] = 0.0;
@@ -380,6 +396,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
                 const REAL lwv = LW4 ? lwr[LW4 ? j : 0] : lwg[ii];
                 double p = (double)mth.exp((REAL)(lwv - (REAL)m));
                 p = v ? p : 0.0;
+                if (ADAPT) p2 += p * p;
                 if (needS) {
 #pragma unroll
                     for (int h = 0; h < H; ++h) part[h] += (double)cur[(size_t)ii * REC + NS + h] * p;
@@ -399,6 +416,10 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
             if (pred_upd) {
                 ptot = wave_sum(ptot);
                 if (lane == 0) red_pt[wave] = ptot;
+            }
+            if (ADAPT && t < T) {
+                p2 = wave_sum(p2);
+                if (lane == 0) red_pt[wave] = p2;
             }
             if (needS) {
 #pragma unroll
@@ -428,10 +449,21 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
                 run += v4[q];
             }
             if (lane == WAVE - 1) red_W[0] = inc;
+            if (ADAPT && t < T) {
+                double W2 = red_pt[0];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) W2 += red_pt[w];
+                if (lane == WAVE - 1) red_W[5] = W2;
+            }
         }
         __syncthreads();                                                        // barrier 2b
         W = red_W[0];
         const double invW = 1.0 / W;
+        // ADAPT: resample iff ESS = W^2 / sum w^2 < tau N -- one comparison of two LDS values every wave reads alike, made scalar
+        [[maybe_unused]] bool resample = true;
+        if constexpr (ADAPT) {
+            if (t < T) resample = __builtin_amdgcn_readfirstlane((int)(W * W < tauN * red_W[5])) != 0;
+        }
         if (needS) {
 #pragma unroll
             for (int h = 0; h < H; ++h) {
@@ -461,6 +493,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
         if (t == T) break;
 
         // ---- (D) normalise the CDF in place (own entries) -------------------------------------
+        if (!ADAPT || resample) {
         for (int j = 0; j < nchunk; ++j) {
             const int i = j * NT + tid;
             if (i < N) {
@@ -469,6 +502,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
             }
         }
         __syncthreads();                                                        // barrier 3
+        }
 
         const double y_t = yv[t];
         const bool inside = (t >= t1) && (t < tL);
@@ -1111,7 +1145,57 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
             }
             { REAL *tmp = lwg; lwg = lwn_g; lwn_g = tmp; }
         };
-        if constexpr (PARIS) {
+        // ADAPT, ESS >= tau N: child i proposes from record i (this thread's own) and its log-weight carries on,
+        // base = (logw - m) - log(sum exp(logw - m)) + log N in the log domain; no CDF, no search, no gather
+        [[maybe_unused]] auto keep = [&](auto stat_tag) {
+            constexpr int STAT = decltype(stat_tag)::value;
+            const double lse = log(W), lgN = log((double)N);
+#pragma unroll (LW4 ? 4 : 1)
+            for (int j = 0; j < (LW4 ? 4 : nchunk); ++j) {
+                const int i = j * NT + tid;
+                if (i >= N) continue;
+                const REAL z = (REAL)zv[(size_t)t * N + i];
+                REAL xp[NS], sp[H], xn[NS], add[H], lwn;
+                alignas(16) REAL rec[REC];
+                rec_load<REC, REAL>(rec, cur + (size_t)i * REC);
+#pragma unroll
+                for (int d = 0; d < NS; ++d) xp[d] = rec[d];
+#pragma unroll
+                for (int h = 0; h < H; ++h) sp[h] = rec[NS + h];
+                particle_step<MODEL, KERNEL, STAT, REAL>(c, mth, xp, (REAL)y_t, z, xn, lwn, add);
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    const REAL av = use_stat ? add[h] * (REAL)wt : (REAL)0;
+                    sp[h] = (lam * sp[h] + oml * (REAL)S[h]) + av;
+                }
+                const REAL lwo = LW4 ? lwr[LW4 ? j : 0] : lwg[i];
+                lwn = (REAL)(((((double)lwo - m) - lse) + lgN) + (double)lwn);
+                if (LW4) lwr[LW4 ? j : 0] = lwn;
+                else lwg[i] = lwn;
+#pragma unroll
+                for (int d = 0; d < NS; ++d) rec[d] = xn[d];
+#pragma unroll
+                for (int h = 0; h < H; ++h) rec[NS + h] = sp[h];
+                rec_store<REC, REAL>(nxt + (size_t)i * REC, rec);
+                if (P.trace_x) {
+                    const size_t row = (size_t)(t + 1) * N + i;
+                    if (P.trace_anc) P.trace_anc[(size_t)t * N + i] = i;
+#pragma unroll
+                    for (int d = 0; d < NS; ++d) P.trace_x[row * NS + d] = (double)xn[d];
+                    P.trace_logw[row] = (double)lwn;
+                    if (P.trace_stats) {
+#pragma unroll
+                        for (int h = 0; h < H; ++h) P.trace_stats[row * H + h] = (double)sp[h];
+                    }
+                }
+            }
+        };
+        if (ADAPT && !resample) {
+            if constexpr (ADAPT) {
+                if (stat == PFG_STAT_SCORE) keep(std::integral_constant<int, PFG_STAT_SCORE>{});
+                else keep(std::integral_constant<int, PFG_STAT_SUFF>{});
+            }
+        } else if constexpr (PARIS) {
             if (P.smoother == PFG_SMOOTHER_POYIADJIS_N2) {
                 if (stat == PFG_STAT_SCORE) n2_sweep(std::integral_constant<int, PFG_STAT_SCORE>{});
                 else n2_sweep(std::integral_constant<int, PFG_STAT_SUFF>{});

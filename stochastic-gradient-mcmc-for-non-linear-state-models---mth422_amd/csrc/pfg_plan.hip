@@ -174,6 +174,7 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
     else if (smoother == PFG_SMOOTHER_PARIS) p.family = Family::Paris;
     else if (smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) p.family = Family::Systematic;
     else if (smoother == PFG_SMOOTHER_NEMETH_STRATIFIED) p.family = Family::Stratified;
+    else if (smoother == kPlanAdaptive) p.family = Family::Adaptive;
     else if (smoother == PFG_SMOOTHER_POYIADJIS_N2) p.family = Family::N2;
     else if (predictive && n_max <= pfg::MEM_MAX_N) p.family = Family::Mem;
     else {
@@ -272,6 +273,30 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
             } else {
                 p.lw4 = n_max <= 4096;
                 p.name = "mem1024_stratified";
+                p.nt = pfg::MEM_NT;
+                p.lds = mem_lds();
+                p.scratch = mem_scratch(false);
+            }
+            break;
+        case Family::Adaptive:
+            // as Stratified: three size classes, each a twin of the kernel that serves multinomial windows of that size
+            if (predictive) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for the predictive statistic");
+            if (elementwise) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for elementwise statistics");
+            if (n_max > pfg::MEM_MAX_N) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling is built for N <= 16384 (no whole-GPU windows)");
+            if (n_max <= 1024) {
+                p.name = "adaptive256x4";
+                p.nt = 256; p.ppt = 4; p.pp = !p.f64;
+                p.lds = (p.f64 ? reg_lds<256, 4, false, pfg::MODE_ADAPTIVE> : reg_lds<256, 4, true, pfg::MODE_ADAPTIVE>)(model, dtype, rng, n_max);
+                if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling: state does not fit LDS");
+            } else if (rng == PFG_RNG_DEVICE) {
+                p.np2 = n_max <= 4096 ? 4096 : 16384;
+                p.name = p.np2 == 4096 ? "big4096_adaptive" : "big16384_adaptive";
+                p.nt = pfg::MEM_NT;
+                p.lds = with_types(model, dtype, rng, [&](auto, auto, auto real, auto) { return pfg::big_kernel_lds_bytes<decltype(real), false, true>(p.np2); });
+                p.scratch = mem_scratch(false);
+            } else {
+                p.lw4 = n_max <= 4096;
+                p.name = "mem1024_adaptive";
                 p.nt = pfg::MEM_NT;
                 p.lds = mem_lds();
                 p.scratch = mem_scratch(false);
@@ -451,6 +476,12 @@ int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, i
     if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_NEMETH_STRATIFIED)
         return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
     return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream);
+}
+
+int pfg_launch_device_adaptive(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int B,
+                               const pfg_dev_problem *dev_probs, void *hip_stream, int traced) {
+    if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
+    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, kPlanAdaptive, n_max, B, dev_probs, (hipStream_t)hip_stream, traced != 0);
 }
 
 int pfg_launch_device_grid(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int T_max, int B,

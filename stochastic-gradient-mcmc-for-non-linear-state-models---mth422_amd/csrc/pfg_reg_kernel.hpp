@@ -1,5 +1,5 @@
-// libpfgrad device code: pf_reg_kernel, the LDS-resident particle filter (N <= 4096) incl. its PaRIS, systematic- and
-// stratified-resampling and O(N^2) instantiations.  Its build switches, derived compile-time switches and its one LDS layout: pfg_reg_traits.hpp.
+// libpfgrad device code: pf_reg_kernel, the LDS-resident particle filter (N <= 4096) incl. its PaRIS, systematic-,
+// stratified- and adaptive-resampling and O(N^2) instantiations.  Its build switches, derived compile-time switches and its one LDS layout: pfg_reg_traits.hpp.
 #pragma once
 #include "pfg_reg_traits.hpp"
 
@@ -57,6 +57,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             return;
         }
     }
+    // ADAPTIVE (pfg_launch_device_adaptive, flagged batches of pfg_run_batch): a descriptor that does not ask for it -- or
+    // asks for a recursion this instantiation has no skip path for -- gets NaNs, as in the score-only twins
+    if constexpr (TR::ADAPTIVE) {
+        if (!(P.flags & PFG_FLAG_ADAPTIVE_RESAMPLING) || P.smoother != PFG_SMOOTHER_NEMETH || P.stat == PFG_STAT_PREDICTIVE) {
+            if (threadIdx.x < PFG_OUT_DOUBLES && P.out) P.out[threadIdx.x] = __builtin_nan("");
+            return;
+        }
+    }
+    [[maybe_unused]] const double tauN = TR::ADAPTIVE ? (double)ess_threshold_of(P.reserved) * (double)N : 0.0;
     const bool is_filter = !ONLY_SCORE1 && (P.smoother == PFG_SMOOTHER_FILTER);
     const int stat = ONLY_SCORE1 ? (int)PFG_STAT_SCORE : P.stat;
     const double lam_d = ONLY_SCORE1 ? 1.0 : is_filter ? 0.0 : ((P.smoother == PFG_SMOOTHER_PARIS || TR::N2) ? 1.0 : P.lambduh);
@@ -254,6 +263,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                         for (int h = 0; h < H; ++h) P.trace_stats[(size_t)i * H + h] = (double)s[h];
                     }
                 }
+            } else if (TR::ADAPTIVE && TR::FAST) {
+                // a slot beyond N reads its OWN cell on a step that does not resample (no other thread's): give it a value
+#pragma unroll
+                for (int d = 0; d < NS + H; ++d) cur[sidx(d, i)] = (REAL)0;
             }
         }
     }
@@ -347,6 +360,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 for (int k = 0; k < PPT; ++k) part += (double)cur[sidx((NS + h), own[k])] * cs[k];
                 part = wave_sum(part);
                 if (lane == 0) red_S[h * NW + wave] = part;
+            }
+        }
+        if constexpr (TR::ADAPTIVE) {
+            // sum of w^2 for the effective sample size: rides on this reduction phase, one LDS slot per wave, no barrier of its own
+            if (t < T) {
+                double q2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) q2 += cs[k] * cs[k];
+                q2 = wave_sum(q2);
+                if (lane == 0) red_W0[4 + wave] = q2;
             }
         }
         double wave_inc = 0.0;          // BLK: this wave's inclusive scan (lane 63 = the wave total)
@@ -562,6 +585,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             W = uniform_f64(run);
         }
         const double invW = uniform_f64(PFG_OPT_RCPW ? rcp_newton2(W) : 1.0 / W);
+        // ADAPTIVE: resample iff ESS = W^2 / sum w^2 < tau N.  Workgroup-uniform by construction: every wave adds the same NW
+        // LDS slots in the same order, W is the same scan of the same LDS totals in every wave, and the result is made scalar
+        // -- barriers 3 and 4 are skipped under it
+        [[maybe_unused]] bool resample = true;
+        if constexpr (TR::ADAPTIVE) {
+            if (t < T) {
+                double W2 = red_W0[4];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) W2 += red_W0[4 + w];
+                resample = __builtin_amdgcn_readfirstlane((int)(W * W < tauN * W2)) != 0;
+            }
+        }
         if (needS) {
             PFG_MARK("cold needS")
 #pragma unroll
@@ -615,6 +650,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
         const double wt = (inside && wv) ? wv[t - t1] : 1.0;
         const bool use_stat = inside && (stat != PFG_STAT_NONE);
         const bool plain = !needS_every;                 // not filter and lambda == 1
+        if (!TR::ADAPTIVE || resample) {            // (ADAPTIVE: phases D and E only on a step that resamples)
         if (TR::BLK) {
             // all PPT positions: slots beyond N carry weight 0 (flat CDF, never selected)
             {
@@ -657,16 +693,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             } else if (!TR::BLK) {
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) uu[k] = u01_32(rng.next());
+                if (TR::ADAPTIVE && PFG_TR(P.trace_x) && P.rec_ud) {      // test instrumentation, as for STRATIFIED
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k)
+                        if (valid[k]) P.rec_ud[(size_t)t * N + k * NT + tid] = uu[k];
+                }
             }
         } else if (TR::STRATIFIED) {
             // REPLAY: U_r is the caller's u[t][r]; one addition and one IEEE division (pfgrad.h, PFG_SMOOTHER_NEMETH_STRATIFIED)
 #pragma unroll
             for (int k = 0; k < PPT; ++k) uu[k] = ((double)(k * NT + tid) + uu[k]) / (double)N;
         }
+        }
         int anc[PPT];
         [[maybe_unused]] uint32_t gaddr[PPT];       // GADDR: byte offset of the parent's record in a state array
 #pragma unroll
         for (int k = 0; k < PPT; ++k) { anc[k] = 0; gaddr[k] = 0u; }
+        if (!TR::ADAPTIVE || resample) {
         if (TR::BLK) {
             uint32_t ua[PPT];
 #pragma unroll
@@ -809,6 +852,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 tie = (valid[k] && mg < tie) ? mg : tie;
             }
         }
+        } else {
+            // ADAPTIVE, ESS >= tau N: child i is parent i -- thread and particle coincide, so the state is read from and
+            // written to this thread's own cells (slots beyond N: their own cell too) and no barrier orders anything
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) { anc[k] = (TR::FAST || valid[k]) ? k * NT + tid : last; gaddr[k] = 0u; }
+        }
+        // ... and its log-weight carries on: base = (logw - m) - log(sum exp(logw - m)) + log N, in the log domain
+        [[maybe_unused]] double lse = 0.0, lgN = 0.0;
+        if constexpr (TR::ADAPTIVE) {
+            if (!resample) { lse = uniform_f64(log(W)); lgN = uniform_f64(log((double)N)); }
+        }
         PFG_PH(6)
         // ---- (F) gather parents, (G) propose / weight / statistic, (H) publish children ---
         auto slots = [&](auto stat_tag) {
@@ -845,7 +899,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             PFG_PH(7)
             if (TR::PRIO == 1) __builtin_amdgcn_s_setprio(0);
             if (TR::PRIO == 2) __builtin_amdgcn_s_setprio(2);
-            if (!PP) block_sync<NW>();                                          // barrier 4 (single buffer)
+            if (!PP && (!TR::ADAPTIVE || resample)) block_sync<NW>();           // barrier 4 (single buffer)
             PFG_PH(8)
             if (RNG != PFG_RNG_REPLAY) {
                 draw_normals(zz);
@@ -881,6 +935,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                     else
 #endif
                     particle_step<MODEL, KERNEL, STAT, REAL>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add);
+                    if constexpr (TR::ADAPTIVE) {
+                        if (!resample) lwn = (REAL)(((((double)lw[k] - m) - lse) + lgN) + (double)lwn);
+                    }
                     lw[k] = valid[k] ? lwn : (REAL)(-INFINITY);
                     if (UPD == 0) {
                         // Poyiadjis O(N), lambda = 1: 1*s[a] + 0*S + w_t h = s[a] + w_t h exactly

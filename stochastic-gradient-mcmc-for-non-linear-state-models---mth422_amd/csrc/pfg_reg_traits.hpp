@@ -201,6 +201,10 @@ struct RegTraits {
     static constexpr int NW = NT / WAVE, SLOTS = NT * PPT;
     static constexpr bool PARIS = MODE == MODE_PARIS, N2 = MODE == MODE_N2, SYSTEMATIC = MODE == MODE_SYSTEMATIC;
     static constexpr bool STRATIFIED = MODE == MODE_STRATIFIED;     // one uniform per child, (r + U_r) / N: see phase E
+    // ESS-triggered resampling (PFG_FLAG_ADAPTIVE_RESAMPLING): a step whose effective sample size is at least tau N keeps
+    // every particle where it is -- no CDF, no search, no gather -- and carries its normalised log-weight on
+    static constexpr bool ADAPTIVE = MODE == MODE_ADAPTIVE;
+    static_assert(!ADAPTIVE || NT / WAVE <= 4, "the per-wave sums of w^2 sit in red_W0[4 .. 4 + NW)");
     static constexpr bool LWL = PARIS || N2;            // the parents' log-weights (and the PaRIS queues) in LDS
     // FAST layout = LDS math tables + sentinel-padded, bank-conflict-free cdf with an unrolled search, NT * PPT particle
     // slots whatever N is (the array stride is a compile-time constant and folds into the ds_read / ds_write immediates).
@@ -235,7 +239,7 @@ struct RegTraits {
     static_assert(!GADDR || 4 * (SLOTS + SLOTS / 32) * 993 < (1 << 23), "GADDR: rel * 993 must fit the 24-bit multiply");
     static constexpr bool LAZYLL = PFG_OPT_LAZYLL && TAB && sizeof(REAL) == 8;
     // LAZYLL in an instantiation without a production twin: tracing the running log-likelihood must not move the flushes
-    static constexpr bool TWINLESS_LL = STRATIFIED || N2;
+    static constexpr bool TWINLESS_LL = STRATIFIED || N2 || ADAPTIVE;
     static constexpr bool PIVOTS = PFG_OPT_PIVOTS && SLOTS == 1024;
     static constexpr bool RAWCAP = MODE == MODE_PARIS && RNG == PFG_RNG_REPLAY;     // PaRIS on the window's raw np.random stream
 

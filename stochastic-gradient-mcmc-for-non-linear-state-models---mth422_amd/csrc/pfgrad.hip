@@ -63,6 +63,23 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
         if (ffbs && q.stat == PFG_STAT_GIBBS && q.N != 1)
             return bad(PFG_ERR_INVALID, "the Gibbs statistic (PFG_STAT_GIBBS) is of one path: N must be 1");
     }
+    // adaptive (ESS-triggered) resampling: the flag fills a batch or is absent from it; what it is not built for is named
+    const bool adaptive = (q.flags & PFG_FLAG_ADAPTIVE_RESAMPLING) != 0;
+    if (adaptive != ((first.flags & PFG_FLAG_ADAPTIVE_RESAMPLING) != 0))
+        return bad(PFG_ERR_INVALID, "adaptive resampling (PFG_FLAG_ADAPTIVE_RESAMPLING) cannot share a batch with windows that resample at every step");
+    if (adaptive) {
+        if (q.smoother == PFG_SMOOTHER_FILTER) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for the NEMETH recursion, not pf = 'filter'");
+        if (q.smoother == PFG_SMOOTHER_PARIS) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for the NEMETH recursion, not pf = 'paris'");
+        if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for the NEMETH recursion, not pf = 'poyiadjis_N2'");
+        if (q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC || q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED)
+            return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for multinomial draws, not systematic or stratified ones");
+        if (q.smoother != PFG_SMOOTHER_NEMETH) return bad(PFG_ERR_INVALID, "adaptive resampling needs a particle filter (smoother NEMETH)");
+        if (q.stat == PFG_STAT_PREDICTIVE) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for the predictive statistic");
+        if (q.elementwise) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for elementwise statistics");
+        if (q.N > pfg::MEM_MAX_N) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for N <= 16384 (no whole-GPU windows)");
+        const float tau = pfg::ess_threshold_of(q.reserved);
+        if (!(tau > 0.0f && tau <= 1.0f)) return bad(PFG_ERR_INVALID, "ess_threshold must be in (0, 1]");
+    }
     if (mixed(PFG_SMOOTHER_NEMETH_STRATIFIED)) {
         // the id says NEMETH: the recursions it has no kernel for are named, any other mix is a caller's error
         const int other = q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED ? first.smoother : q.smoother;
@@ -179,7 +196,9 @@ BatchSummary summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
     }
     // the smoothers with kernels of their own fill whole batches; the rest run the plain kernels
     const int s0 = ps[0].smoother;
-    if (s0 == PFG_SMOOTHER_PARIS || s0 == PFG_SMOOTHER_NEMETH_SYSTEMATIC || s0 == PFG_SMOOTHER_POYIADJIS_N2 ||
+    if (ps[0].flags & PFG_FLAG_ADAPTIVE_RESAMPLING)        // (NEMETH windows, checked: their own kernels)
+        s.smoother = kPlanAdaptive;
+    else if (s0 == PFG_SMOOTHER_PARIS || s0 == PFG_SMOOTHER_NEMETH_SYSTEMATIC || s0 == PFG_SMOOTHER_POYIADJIS_N2 ||
         s0 == PFG_SMOOTHER_KALMAN || s0 == PFG_SMOOTHER_KALMAN_FFBS || s0 == PFG_SMOOTHER_NEMETH_STRATIFIED)
         s.smoother = s0;
     else if (score1 && !s.traced)
@@ -313,6 +332,7 @@ void describe_window(Layout &L, const pfg_problem &q, pfg_result &r, pfg_dev_pro
     d.seed = q.seed; d.stream = q.stream;
     d.T = q.T; d.t1 = q.t1; d.tL = tL; d.N = q.N;
     d.smoother = q.smoother; d.stat = q.stat; d.flags = q.flags;
+    d.reserved = (q.flags & PFG_FLAG_ADAPTIVE_RESAMPLING) ? q.reserved : 0;      // the threshold's bits
 }
 }  // namespace
 

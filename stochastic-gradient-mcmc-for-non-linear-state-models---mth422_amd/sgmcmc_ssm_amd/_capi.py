@@ -27,10 +27,20 @@ FLAG_GARCH_STATIONARY_PRIOR = 1
 FLAG_PARIS_NO_ACCEPT_REJECT = 2
 FLAG_PARIS_RAW_STREAM = 4        # paris_stream = the window's whole np.random stream of doubles (pfgrad.h)
 FLAG_PARIS_RAW_CARRY = 8         # ... whose first entry is the generator's pending cached Gaussian
+FLAG_ADAPTIVE_RESAMPLING = 16    # resample only when ESS < ess_threshold * N (extension; include/pfgrad.h)
 MAX_STAT, MAX_THETA, OUT_DOUBLES, MAX_PRED, STAMP_WORDS = 4, 4, 8, 16, 16
 MAX_DRAWN_SEQUENCES = 1024       # PFG_MAX_DRAWN_SEQUENCES: sequences a chain draws per step (num_sequences != -1)
 STATE_DIM = {"svm": 1, "garch": 2, "lgssm": 1}
 STAT_DIM = {"svm": 3, "garch": 4, "lgssm": 4}
+
+
+def ess_threshold_bits(tau):
+    """The `reserved` word of a PFG_FLAG_ADAPTIVE_RESAMPLING descriptor: the bits of tau as an IEEE binary32 (0: off)."""
+    return int(np.array(tau or 0.0, dtype=np.float32).view(np.int32))
+
+
+def ess_threshold_from_bits(bits):
+    return float(np.array(bits, dtype=np.int32).view(np.float32))
 
 
 def kalman_scratch_bytes(L):
@@ -141,7 +151,7 @@ DEV_PROBLEM_DTYPE = np.dtype([
 
 
 def device_descriptors(n, *, theta, row, out, step_ctr, scratch, scratch_bytes, stream, prior_mean, prior_var, lambduh, seed,
-                       N, smoother, stat="score", flags=0, Ntilde=0, max_accept_reject=0):
+                       N, smoother, stat="score", flags=0, Ntilde=0, max_accept_reject=0, ess_threshold=None):
     """The static fields of n pfg_dev_problem records (the windows -- y, T, t1, tL, weights -- are the caller's):
     descriptor i reads row `row[i]` of the tensor theta [*, MAX_THETA], writes record i of out [n, OUT_DOUBLES], owns bytes
     [i * scratch_bytes, (i + 1) * scratch_bytes) of `scratch` (None: no scratch) and draws from the stream id `stream[i]`."""
@@ -157,6 +167,9 @@ def device_descriptors(n, *, theta, row, out, step_ctr, scratch, scratch_bytes, 
     d["stream"] = stream
     d["N"], d["smoother"], d["stat"], d["flags"] = N, SMOOTHER[smoother], STAT[stat], int(flags)
     d["Ntilde"], d["max_accept_reject"] = Ntilde, max_accept_reject
+    if ess_threshold:       # adaptive resampling (pfg_launch_device_adaptive): the flag and tau travel in every descriptor
+        d["flags"] |= FLAG_ADAPTIVE_RESAMPLING
+        d["reserved"] = ess_threshold_bits(ess_threshold)
     return d
 
 
@@ -166,7 +179,8 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_last_variant", "pfg_legacy_streams", "pfg_host_register", "pfg_host_unregister",
            "pfg_launch_device_traced", "pfg_last_traced", "pfg_launch_device_grid", "pfg_launch_device_grid_phase",
            "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device",
-           "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother")
+           "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
+           "pfg_launch_device_adaptive")
 
 _lib = None
 
@@ -283,6 +297,8 @@ def load_library():
     lib.pfg_reduce_windows_device.restype = C.c_int
     lib.pfg_scratch_bytes_smoother.argtypes = [C.c_int] * 5
     lib.pfg_scratch_bytes_smoother.restype = C.c_int64
+    lib.pfg_launch_device_adaptive.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int]
+    lib.pfg_launch_device_adaptive.restype = C.c_int
     _lib = lib
     return lib
 
@@ -435,6 +451,7 @@ class Context:
             tL = q.get("tL", None)
             p.tL = T if tL is None else int(tL)
             p.flags = int(q.get("flags", 0))
+            p.reserved = ess_threshold_bits(q.get("ess_threshold", None))
             p.lambduh = float(q.get("lambduh", 1.0))
             p.prior_mean = float(q.get("prior_mean", 0.0))
             p.prior_var = float(q.get("prior_var", 1.0))
@@ -568,6 +585,7 @@ class Context:
         tL = [q.get("tL", None) for q in problems]
         ps["tL"] = tL = np.array([t if v is None else v for v, t in zip(tL, T)], dtype=np.int64)
         ps["flags"] = [q.get("flags", 0) for q in problems]
+        ps["reserved"] = [ess_threshold_bits(q.get("ess_threshold", None)) for q in problems]
         ps["lambduh"] = [q.get("lambduh", 1.0) for q in problems]
         ps["prior_mean"] = [q.get("prior_mean", 0.0) for q in problems]
         ps["prior_var"] = [q.get("prior_var", 1.0) for q in problems]
@@ -625,6 +643,13 @@ class Context:
         self._check(self.lib.pfg_launch_device_traced(
             self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], SMOOTHER[smoother], int(n_max),
             int(B), C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr))))
+
+    def launch_device_adaptive(self, model, kernel, dtype, rng, n_max, B, dev_probs_ptr, stream_ptr=0, traced=False):
+        """A batch of adaptive-resampling windows (descriptors with FLAG_ADAPTIVE_RESAMPLING and ess_threshold):
+        pfg_launch_device_adaptive; traced: honour the trace_* / rec_* buffers."""
+        self._check(self.lib.pfg_launch_device_adaptive(
+            self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], int(n_max), int(B),
+            C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr)), int(bool(traced))))
 
     def last_traced(self):
         return bool(self.lib.pfg_last_traced(self.handle))
@@ -695,6 +720,12 @@ class Context:
     def scratch_bytes_smoother(self, model, dtype, rng, smoother, N):
         """Per-descriptor scratch of a pfg_launch_device_smoother batch of `smoother` windows (-1: above its maximum)."""
         return int(self.lib.pfg_scratch_bytes_smoother(MODEL[model], DTYPE[dtype], RNG[rng], SMOOTHER[smoother], int(N)))
+
+    def scratch_bytes_adaptive(self, model, dtype, N):
+        """Per-descriptor scratch of a pfg_launch_device_adaptive batch: 0 for N <= 1024, above it the large-N kernels' state,
+        the same for both generators -- pfg_scratch_bytes of the REPLAY plan (include/pfgrad.h; the DEVICE plan of plain
+        windows keeps N <= 4096 in LDS and answers 0 there).  -1 above N = 16384."""
+        return -1 if int(N) > 16384 else self.scratch_bytes(model, dtype, "replay", N)
 
     def imq_ksd(self, x, gradlogp, c=1.0, beta=0.5):
         x, g = _as_f64(x), _as_f64(gradlogp)

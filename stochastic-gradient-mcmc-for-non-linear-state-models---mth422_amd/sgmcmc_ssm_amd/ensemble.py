@@ -84,6 +84,13 @@ class ChainEnsemble(object):
                'stratified' (extension: child r of a step resamples with (r + U_r) / N, one uniform per child -- the
                score's variance falls to 0.2-0.5 of the multinomial one at the same N; pf 'poyiadjis_N' | 'nemeth',
                kind 'pf', N <= 16384, every path those serve: single- and multi-window, host and device windows, graphs)
+      ess_threshold: None | tau in (0, 1] (extension: ESS-triggered, "adaptive" resampling -- a timestep resamples only
+               when the effective sample size 1 / sum p_i^2 is below tau N; otherwise every particle stays where it is and
+               carries its normalised weight on, so the genealogy is thinned less often: at tau = 0.5 the score's variance
+               falls to about 0.5-0.7 of the always-resampling one and some 70-80 % of the steps run no CDF, search or
+               gather; pf 'poyiadjis_N' | 'nemeth', kind 'pf', resampling 'multinomial', N <= 16384, every path those
+               serve: single- and multi-window, host and device windows, graphs, every sampler; None or 0 = resample at
+               every step, today's kernels and numbers; include/pfgrad.h: PFG_FLAG_ADAPTIVE_RESAMPLING)
       sampler: 'sgld' (sample_sgld + project_parameters) | 'sghmc' (extension: momentum with
                friction `friction` in (0,1]; friction = 1 is SGLD) | 'sgrld' (model 'lgssm': sample_sgrld with the
                LGSSM preconditioner + project_parameters, pfg_sgrld_update_device; every kind, pf and dtype) |
@@ -143,13 +150,14 @@ class ChainEnsemble(object):
                  buffer_length=-1, dtype="f64", seed=0, chain_offset=0, device=None,
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
-                 Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None):
+                 Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
+                 ess_threshold=None):
         s = self._resolve_settings(
             model, observations, parameters, num_chains=num_chains, N=N, pf=pf, lambduh=lambduh,
             subsequence_length=subsequence_length, buffer_length=buffer_length, dtype=dtype, partition_style=partition_style,
             resampling=resampling, sampler=sampler, window_sampling=window_sampling, kind=kind, num_samples=num_samples,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, accept_reject=accept_reject, minibatch_size=minibatch_size,
-            num_sequences=num_sequences)
+            num_sequences=num_sequences, ess_threshold=ess_threshold)
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         Parameters, Prior, Helper = _model_info(model)
@@ -158,6 +166,7 @@ class ChainEnsemble(object):
         self._smoother, self._launch_smoother = s.smoother, s.launch_smoother
         self.Ntilde, self.max_accept_reject = s.Ntilde, s.max_accept_reject
         self.resampling, self.sampler, self.friction = resampling, sampler, float(friction)
+        self.ess_threshold = s.ess_threshold        # None: resample at every step
         self.window_sampling, self.partition_style, self.strict = window_sampling, partition_style, s.strict
         self._multi, self.W, self.segments, self.T, self.S, self.B = s.multi, s.W, s.segments, s.T, s.S, s.B
         self.P, self.C = s.theta0.shape[1], s.theta0.shape[0]
@@ -226,7 +235,8 @@ class ChainEnsemble(object):
         self._desc = _capi.device_descriptors(
             self._nd, theta=self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
             scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv, lambduh=self.lambduh, seed=self.seed, N=self.N,
-            smoother=s.smoother, stat=s.stat, flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0, **s.paris)
+            smoother=s.smoother, stat=s.stat, flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0,
+            ess_threshold=s.ess_threshold, **s.paris)
         if not self._multi:
             self._set_windows(first=True)
         self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)).to(dev)
@@ -237,14 +247,33 @@ class ChainEnsemble(object):
     def _resolve_settings(model, observations, parameters=None, num_chains=None, N=1000, pf="poyiadjis_N", lambduh=None,
                           subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
                           resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
-                          Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None):
+                          Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
+                          ess_threshold=None):
         """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
         device is made here and nowhere else, so it runs (and is tested) without a GPU.
 
         kind, pf, N (kind='complete': num_samples), lambduh; smoother (what the descriptors say) and launch_smoother (what the
         launch states: 'poyiadjis_n' for 'nemeth' with lambduh = 1); stat; paris (the descriptors' PaRIS fields, {} otherwise),
         Ntilde, max_accept_reject; M, K, W, multi; S, B, strict; y (the concatenated series), T, segments ([K+1] offsets
-        into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto."""
+        into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto;
+        ess_threshold (None unless adaptive resampling is on)."""
+        tau = None
+        if ess_threshold is not None and ess_threshold != 0:
+            # adaptive resampling (extension, include/pfgrad.h): what it is not built for is refused by name
+            tau = float(ess_threshold)
+            if not 0.0 < tau <= 1.0:
+                raise ValueError("ess_threshold must be in (0, 1] (None or 0: resample at every step), got {0}".format(ess_threshold))
+            if kind != "pf" or sampler == "gibbs":
+                raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
+            if pf not in ("poyiadjis_N", "nemeth"):
+                raise NotImplementedError("adaptive resampling (ess_threshold) is built for pf = 'poyiadjis_N' | 'nemeth', "
+                                          "got pf = '{0}'".format(pf))
+            if resampling != "multinomial":
+                raise NotImplementedError("adaptive resampling (ess_threshold) is built for resampling='multinomial', "
+                                          "got '{0}'".format(resampling))
+            if int(N) > 16384:
+                raise NotImplementedError("adaptive resampling (ess_threshold) is built for N <= 16384 "
+                                          "(no whole-GPU windows), got N = {0}".format(int(N)))
         if sampler not in ("sgld", "sghmc", "sgrld", "gibbs"):
             raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld' or 'gibbs'")
         M, K, W = ChainEnsemble._window_counts(observations, minibatch_size, num_sequences)
@@ -383,7 +412,7 @@ class ChainEnsemble(object):
         return types.SimpleNamespace(
             kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, M=M, K=K, W=W, multi=multi, S=S, B=B, strict=strict, y=y, T=T,
-            segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto)
+            segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau)
 
     @staticmethod
     def _window_counts(observations, minibatch_size, num_sequences):
@@ -412,6 +441,13 @@ class ChainEnsemble(object):
         if self._smoother == "kalman_ffbs":
             # the forward messages of the longest buffer: a window and its two buffers, or the whole series
             return _capi.kalman_scratch_bytes(min(self.T, self.S + 2 * self.B) if self.S > 0 else self.T)
+        if self.ess_threshold:
+            # adaptive windows: 0 for N <= 1024, the large-N twins' slab up to 16384 (also where plain device-generator
+            # windows would run LDS-resident, 1024 < N <= 4096)
+            sb = self.ctx.scratch_bytes_adaptive(self.model, self.dtype, self.N)
+            if sb < 0:
+                raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(self.N))
+            return sb
         if self._multi or self._smoother in ("paris", "poyiadjis_n2", "nemeth_stratified"):
             # PaRIS, N <= 1024: 0, the LDS-resident variants keep their state in LDS; above: paris_mem1024's slab.  The
             # single-window PaRIS path (N <= 1024 only) relies on that answer of 0 where it once wrote the literal.
@@ -539,6 +575,9 @@ class ChainEnsemble(object):
         none: 1) in each of _nd descriptors."""
         if traced and self.kind != "pf":
             raise ValueError("kind='{0}' has no particles to trace".format(self.kind))
+        if self.ess_threshold:      # adaptive resampling: its own kernels, the family stated at launch level
+            return self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.N, self._nd,
+                                                   self.desc_dev.data_ptr(), self._stream(stream), traced=traced)
         launch, smoother = self.ctx.launch_device_smoother, self._launch_smoother
         if traced and self.pf != "paris":       # the PaRIS kernels always honour trace buffers: traced or not, the same launch
             launch, smoother = self.ctx.launch_device_traced, self._smoother
@@ -658,13 +697,16 @@ class ChainEnsemble(object):
         return dict(theta=self.theta_dev.cpu().numpy(), momentum=self.momentum_dev.cpu().numpy(),
                     step_ctr=int(self.step_ctr.item()), steps_done=int(self.steps_done),
                     seed=self.seed, chain_offset=self.chain_offset,
-                    model=self.model, N=self.N, C=self.C)
+                    model=self.model, N=self.N, C=self.C, ess_threshold=self.ess_threshold)
 
     def load_state_dict(self, state):
         for key in ("model", "N", "C", "seed", "chain_offset"):
             if state[key] != getattr(self, key):
                 raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(
                     key, state[key], getattr(self, key)))
+        if state.get("ess_threshold", None) != self.ess_threshold:      # (checkpoints from before the option: None)
+            raise ValueError("checkpoint ess_threshold = {0} does not match the ensemble ({1})".format(
+                state.get("ess_threshold", None), self.ess_threshold))
         self.theta_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["theta"])))
         self.momentum_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["momentum"])))
         self.step_ctr.fill_(int(state["step_ctr"]))

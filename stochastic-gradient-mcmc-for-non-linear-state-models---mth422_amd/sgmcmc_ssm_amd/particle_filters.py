@@ -243,6 +243,27 @@ def make_problem(model, kernel, pf, observations, theta, N, t1=0, tL=None, weigh
     elif resampling not in ("multinomial", "stratified"):
         raise ValueError("Unrecognized resampling = {0}".format(resampling))
     smoother, lambduh = _smoother_of(pf, kwargs)
+    # extension (include/pfgrad.h, PFG_FLAG_ADAPTIVE_RESAMPLING): resample only when ESS < ess_threshold * N.  None or 0: off,
+    # this function returns what it always has.  rng='replay' draws the streams of a multinomial window below (u[t] of a
+    # step that does not resample is ignored), so np.random ends where the multinomial call leaves it
+    ess_threshold = kwargs.pop("ess_threshold", None)
+    if ess_threshold is not None and ess_threshold != 0:
+        ess_threshold = float(ess_threshold)
+        if not 0.0 < ess_threshold <= 1.0:
+            raise ValueError("ess_threshold must be in (0, 1] (None or 0: resample at every step), got {0}".format(ess_threshold))
+        if smoother != "nemeth":
+            raise NotImplementedError("adaptive resampling (ess_threshold) is built for pf = 'poyiadjis_N' | 'nemeth', "
+                                      "got pf = '{0}'".format(pf))
+        if resampling != "multinomial":
+            raise NotImplementedError("adaptive resampling (ess_threshold) is built for resampling='multinomial', "
+                                      "got '{0}'".format(resampling))
+        if stat == "predictive":
+            raise NotImplementedError("adaptive resampling (ess_threshold) is not built for the predictive statistic")
+        if int(N) > 16384:
+            raise NotImplementedError("adaptive resampling (ess_threshold) is built for N <= 16384 (no whole-GPU windows)")
+        flags = int(flags) | _capi.FLAG_ADAPTIVE_RESAMPLING
+    else:
+        ess_threshold = None
     if resampling == "systematic":
         if smoother != "nemeth":
             raise NotImplementedError("systematic resampling is built for pf = 'poyiadjis_N' | 'nemeth'")
@@ -310,6 +331,8 @@ def make_problem(model, kernel, pf, observations, theta, N, t1=0, tL=None, weigh
              prior_mean=float(np.asarray(prior_mean).reshape(-1)[0]),
              prior_var=float(np.asarray(prior_var).reshape(-1)[0]),
              y=y, weights=weights, theta=theta, flags=flags)
+    if ess_threshold is not None:
+        q["ess_threshold"] = ess_threshold
     if stat == "predictive":
         if smoother != "filter":
             raise ValueError("Only can use pf = 'filter' since we are filtering")

@@ -206,6 +206,9 @@ class PFHelper(object):
         if pf not in ("poyiadjis_N", "nemeth", "paris", "poyiadjis_N2"):
             raise ValueError("Unrecognized pf = {0}".format(pf))
         kwargs.pop("tqdm", None)
+        if kwargs.get("ess_threshold", None):
+            raise NotImplementedError("adaptive resampling (ess_threshold) is not built for elementwise statistics "
+                                      "(pf_latent_var_distr)")
         q = self.pf_problem(observations, parameters, subsequence_start, subsequence_end, weights,
                             pf, N, kernel, forward_message, stat="none", **kwargs)
         if "_result" in q:
@@ -680,7 +683,7 @@ class SGMCMCSampler(object):
         return names * steps_per_iteration, kws * steps_per_iteration
 
     # -- resident fit: rng='device' SGLD runs on the GPU without the host in the loop ----------------------------
-    _RESIDENT_PF_KEYS = frozenset(("pf", "N", "kernel", "lambduh", "rng", "dtype", "resampling", "tqdm", "resident"))
+    _RESIDENT_PF_KEYS = frozenset(("pf", "N", "kernel", "lambduh", "rng", "dtype", "resampling", "ess_threshold", "tqdm", "resident"))
 
     def _resident_plan(self, iter_type, kwargs):
         """fit / fit_timed / fit_evaluate with iter_type='SGLD' and pf_kwargs=dict(rng='device', ...): the step
@@ -709,7 +712,8 @@ class SGMCMCSampler(object):
             return None
         return dict(N=int(pfkw.get("N", 1000)), pf=pfkw.get("pf", "poyiadjis_N"), lambduh=pfkw.get("lambduh", None),
                     kernel=pfkw.get("kernel", None), dtype=pfkw.get("dtype", "f64"),
-                    resampling=pfkw.get("resampling", "multinomial"), epsilon=float(kwargs["epsilon"]),
+                    resampling=pfkw.get("resampling", "multinomial"), ess_threshold=pfkw.get("ess_threshold", None),
+                    epsilon=float(kwargs["epsilon"]),
                     S=int(kwargs["subsequence_length"]), B=int(kwargs["buffer_length"]),
                     spi=int(kwargs.get("steps_per_iteration", 1)), is_list=is_list)
 
@@ -723,7 +727,8 @@ class SGMCMCSampler(object):
                              pf=plan["pf"], lambduh=plan["lambduh"], kernel=plan["kernel"], epsilon=plan["epsilon"],
                              prior=self.prior, subsequence_length=plan["S"], buffer_length=plan["B"], dtype=plan["dtype"],
                              seed=seed, chain_offset=0, forward_message=getattr(self, "forward_message", None),
-                             resampling=plan["resampling"], window_sampling="host" if plan["is_list"] else "device")
+                             resampling=plan["resampling"], ess_threshold=plan["ess_threshold"],
+                             window_sampling="host" if plan["is_list"] else "device")
 
     @staticmethod
     def _graph_steps(ens, thin):

@@ -25,7 +25,7 @@ BENCH = {
     "pf_reg_kernel<0, 0, double, 256, 4, 1, false, 0, false, false>": "c2 wg256x4s (SVM, headline)",
     "pf_reg_kernel<1, 1, double, 512, 2, 1, false, 0, false, false>": "c3 wg512x2s (GARCH optimal)",
     "pf_reg_kernel<0, 0, double, 1024, 4, 1, false, 0, false, true>": "c4 wg1024x4s_score1 (SVM N=4000)",
-    "pf_big_kernel<0, 0, double, 16384, false>": "c5 big16384 (SVM N=10000)",
+    "pf_big_kernel<0, 0, double, 16384, false, false>": "c5 big16384 (SVM N=10000)",
     "pfg_grid_step_dev_kernel<0, 0, double, 256, 8, 2>": "g1 grid2048 (SVM N=10^6)",
 }
 
