@@ -528,6 +528,38 @@ int pfg_gibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const
                             const pfg_prior_hyper *hyper, uint64_t seed, uint64_t chain_offset,
                             uint64_t *step_ctr, void *hip_stream);
 
+/* EXTENSION (not in the reference): particle marginal Metropolis-Hastings (Andrieu, Doucet and Holenstein 2010) for B
+ * resident chains -- a random-walk proposal, a launch that leaves a log-likelihood estimate of the WHOLE data set at the
+ * proposal in out[4] (a particle filter, whatever its N, or the Kalman launch), and an accept / reject step.  All
+ * arrays are DEVICE memory; the draws of chain b are Philox4x32-10 keyed by (seed, chain_offset + b, *step_ctr) with
+ * tags of their own (csrc/pfg_chains.hip), so a chain depends on its GLOBAL index only.
+ *
+ * pfg_logprior_device: logprior[b] = Prior.logprior of the raw row theta[b] (SVM (A, LQinv, LRinv), LGSSM (A, C, LQinv,
+ * LRinv), GARCH (log_mu, logit_phi, logit_lambduh, LRinv)), without Jacobian terms and up to a constant of the
+ * hyper-parameters: differences of it are differences of the host's log-prior.
+ *
+ * pfg_pmmh_propose_device: theta_prop[b] = theta[b] + scale (.) z, scale [PFG_MAX_THETA] doubles, z standard normals
+ * (LGSSM: C stays 1 whatever scale[1] is).  The support is what project_parameters leaves unchanged: |A| <= 0.9999 and
+ * every Cholesky factor > 0.  valid[b] = 1 inside it; outside, valid[b] = 0 and theta_prop[b] = theta[b], so the launch
+ * that follows runs on a legal parameter vector.  *step_ctr is read, not incremented.
+ *
+ * pfg_pmmh_accept_device: outs [B][PFG_OUT_DOUBLES], out[4] the estimate at theta_prop.  init != 0: ll_cur[b] = out[4],
+ * nothing else changes, *step_ctr is left as it is.  Otherwise
+ *   log alpha = (out[4] + logprior(theta_prop)) - (ll_cur + logprior(theta)),  u uniform in (0, 1),
+ * and chain b accepts iff valid[b], out[4] is finite and log(u) < log alpha (a NaN log alpha rejects): theta[b] =
+ * theta_prop[b], ll_cur[b] = out[4], n_accept[b] += 1.  A chain that rejects keeps theta AND ll_cur -- the estimate is
+ * never refreshed, which is what makes the chain exact for every N.  *step_ctr is incremented afterwards.
+ * A bad model id, B < 0 or a NULL array: PFG_ERR_INVALID (step_ctr may be NULL: counter 0, no increment). */
+int pfg_logprior_device(pfg_ctx *ctx, int model, int B, const double *theta, const pfg_prior_hyper *hyper,
+                        double *logprior, void *hip_stream);
+int pfg_pmmh_propose_device(pfg_ctx *ctx, int model, int B, const double *theta, double *theta_prop, int32_t *valid,
+                            const double *scale, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr,
+                            void *hip_stream);
+int pfg_pmmh_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const double *theta_prop,
+                           const int32_t *valid, const double *outs, double *ll_cur, uint64_t *n_accept,
+                           const pfg_prior_hyper *hyper, int init, uint64_t seed, uint64_t chain_offset,
+                           uint64_t *step_ctr, void *hip_stream);
+
 /* Inverse-multiquadric kernel Stein discrepancy of K points x[K][d] with score estimates
  * g[K][d] (HOST pointers, d <= 8): sqrt(sum_{i,j} k0(x_i,x_j)) / K for
  * k(x,y) = (c^2 + |x-y|^2)^(-beta) -- IMQ_KSD of sgmcmc_ssm/trace_metric_functions.py:20-81

@@ -17,6 +17,25 @@
 //          chi2(df) = 2 Gamma(df / 2), Gamma by Marsaglia-Tsang (shape >= 1) or Gamma(a + 1) U^(1/a) (shape < 1); every
 //          attempt is keyed by (seed, chain, *step_ctr, variable, attempt), so a draw is a pure function of its key.
 //          A variable still rejected after kMaxRounds attempts is NaN.
+//   pmmh   particle marginal Metropolis-Hastings (Andrieu, Doucet and Holenstein 2010), two kernels around a particle
+//          filter (or Kalman) launch that leaves its log-likelihood estimate in out[4]:
+//            propose  theta' = theta + scale (.) z in the raw parameterisation (SVM A, LQinv, LRinv; LGSSM A, C, LQinv, LRinv
+//                     with C' = 1 whatever scale_C is; GARCH log_mu, logit_phi, logit_lambduh, LRinv).  Support: what
+//                     project_parameters leaves unchanged, |A| <= 0.9999 and every Cholesky factor > 0 (and finite
+//                     numbers).  Outside it valid = 0 and theta' = theta, so the launch that follows never sees an
+//                     illegal parameter vector.
+//            accept   log alpha = (out[4] + logprior(theta')) - (ll_cur + logprior(theta)); accepted iff valid, out[4] is
+//                     finite and log(u) < log alpha (a NaN log alpha rejects).  ll_cur is NEVER refreshed for a chain that
+//                     rejects: the estimate a chain was accepted with is part of its state, and that is what makes the
+//                     chain exact for every N.
+//          logprior is Prior.logprior (base_parameters.py) of the raw theta row without Jacobian terms and without the
+//          terms that depend on the hyper-parameters only (they cancel in log alpha).
+//          Draws: Philox4x32-10, counter {gid_lo, step_lo, step_hi ^ gid_hi, tag} under key (seed_lo, seed_hi), gid =
+//          chain_offset + b, step = *step_ctr -- the layout of the 0x5A11 / 0x5A12 normals above with tags of their own:
+//            0x504D0001  normal_pair(r.x, r.y) -> z0, z1      0x504D0002  normal_pair(r.x, r.y) -> z2, z3
+//            0x504D0003  uniform53(r.x, r.y)   -> u, the accept uniform in (0, 1)
+//          (SVM: z0, z1, z2 for A, LQinv, LRinv; LGSSM: z0, z2, z3 for A, LQinv, LRinv; GARCH: z0..z3 in theta order).
+//          Disjoint from 0x5A11 / 0x5A12, the Gibbs tags 0x61B5vvaa and the window tags 0x53...... / 0x57.......
 // Built with -ffp-contract=off; IEEE division and ::sqrt / ::log throughout.
 #include "pfg_host.hpp"
 #include "pfg_math.hpp"
@@ -232,6 +251,100 @@ __global__ void gibbs_update_kernel(int B, double *__restrict__ theta, const dou
     lgssm_project_store(th, A, LQ, LR);
 }
 
+// ---- PMMH: the log-prior value, propose, accept ----
+// log-density of a Cholesky factor L of a 1 x 1 Wishart precision at P = L^2 + 1e-16 (scipy.stats.wishart.logpdf,
+// base_parameters.py WishartPrecisionPrior.logprior), less its terms in (df, scale) alone ...
+__device__ __forceinline__ double chol_logprior(double L, double df, double scale) {
+    const double P = L * L + 1e-16;
+    return (0.5 * (df - 2.0)) * ::log(P) - (0.5 * P) / scale;
+}
+// ... and of the coefficient x paired with the factor L (MatrixNormalPrior.logprior, 1 x 1), less its constants
+__device__ __forceinline__ double coef_logprior(double L, double x, double mean, double var_col) {
+    const double r = L * (x - mean);
+    return -0.5 * ((r * r) / var_col) + ::log(L);
+}
+// Prior.logprior of one raw theta row, up to a constant of the hyper-parameters.  GARCH (GARCHVarsPrior.logprior):
+// mu ~ InvGamma, (1 + phi) / 2 and (1 + lambduh) / 2 ~ Beta with phi = expit(logit_phi), as the host evaluates them
+__device__ double logprior_value(int model, const double *th, const pfg_prior_hyper &hy) {
+    if (model == PFG_MODEL_SVM)
+        return chol_logprior(th[1], hy.df_Qinv, hy.scale_Qinv) + chol_logprior(th[2], hy.df_Rinv, hy.scale_Rinv) +
+               coef_logprior(th[1], th[0], hy.mean_A, hy.var_col_A);
+    if (model == PFG_MODEL_LGSSM)
+        return chol_logprior(th[2], hy.df_Qinv, hy.scale_Qinv) + chol_logprior(th[3], hy.df_Rinv, hy.scale_Rinv) +
+               coef_logprior(th[2], th[0], hy.mean_A, hy.var_col_A) + coef_logprior(th[3], th[1], hy.mean_C, hy.var_col_C);
+    const double mu = ::exp(th[0]);
+    const double xp = (1.0 + 1.0 / (1.0 + ::exp(-th[1]))) / 2.0, xl = (1.0 + 1.0 / (1.0 + ::exp(-th[2]))) / 2.0;
+    double lp = -(hy.shape_mu + 1.0) * th[0] - hy.scale_mu / mu;
+    lp = lp + ((hy.alpha_phi - 1.0) * ::log(xp) + (hy.beta_phi - 1.0) * ::log1p(-xp));
+    lp = lp + ((hy.alpha_lambduh - 1.0) * ::log(xl) + (hy.beta_lambduh - 1.0) * ::log1p(-xl));
+    return lp + chol_logprior(th[3], hy.df_Rinv, hy.scale_Rinv);
+}
+
+__global__ void logprior_kernel(int model, int B, const double *__restrict__ theta, pfg_prior_hyper hy,
+                                double *__restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    out[b] = logprior_value(model, theta + (size_t)b * PFG_MAX_THETA, hy);
+}
+
+__global__ void pmmh_propose_kernel(int model, int B, const double *__restrict__ theta, double *__restrict__ theta_prop,
+                                    int32_t *__restrict__ valid, const double *__restrict__ scale, uint64_t seed,
+                                    uint64_t chain_offset, const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double *th = theta + (size_t)b * PFG_MAX_THETA;
+    double *tp = theta_prop + (size_t)b * PFG_MAX_THETA;
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const uint32_t c1 = (uint32_t)step, c2 = (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32);
+    const pfg::u32x4 r0 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x504D0001u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const pfg::u32x4 r1 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x504D0002u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    double z[4];
+    const pfg::Math<double, false> mth = {};
+    mth.normal_pair(r0.x, r0.y, z[0], z[1]);
+    mth.normal_pair(r1.x, r1.y, z[2], z[3]);
+    double p[PFG_MAX_THETA];
+    bool ok;
+    if (model == PFG_MODEL_SVM) {
+        p[0] = th[0] + scale[0] * z[0]; p[1] = th[1] + scale[1] * z[1]; p[2] = th[2] + scale[2] * z[2]; p[3] = th[3];
+        ok = fabs(p[0]) <= 0.9999 && p[1] > 0.0 && p[1] < INFINITY && p[2] > 0.0 && p[2] < INFINITY;
+    } else if (model == PFG_MODEL_LGSSM) {
+        p[0] = th[0] + scale[0] * z[0]; p[1] = 1.0; p[2] = th[2] + scale[2] * z[2]; p[3] = th[3] + scale[3] * z[3];
+        ok = fabs(p[0]) <= 0.9999 && p[2] > 0.0 && p[2] < INFINITY && p[3] > 0.0 && p[3] < INFINITY;
+    } else {
+        for (int j = 0; j < 4; ++j) p[j] = th[j] + scale[j] * z[j];
+        ok = fabs(p[0]) < INFINITY && fabs(p[1]) < INFINITY && fabs(p[2]) < INFINITY && p[3] > 0.0 && p[3] < INFINITY;
+    }
+    valid[b] = ok ? 1 : 0;
+    for (int j = 0; j < PFG_MAX_THETA; ++j) tp[j] = ok ? p[j] : th[j];
+}
+
+// init != 0: ll_cur = out[4], nothing else.  Otherwise the accept / reject step; a chain that rejects keeps theta AND
+// ll_cur, the estimate it was accepted with (never a fresh one: see the header)
+__global__ void pmmh_accept_kernel(int model, int B, double *__restrict__ theta, const double *__restrict__ theta_prop,
+                                   const int32_t *__restrict__ valid, const double *__restrict__ outs,
+                                   double *__restrict__ ll_cur, uint64_t *__restrict__ n_accept, pfg_prior_hyper hy, int init,
+                                   uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double ll_prop = outs[(size_t)b * PFG_OUT_DOUBLES + 4];
+    if (init) { ll_cur[b] = ll_prop; return; }
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    const double *tp = theta_prop + (size_t)b * PFG_MAX_THETA;
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const uint32_t c1 = (uint32_t)step, c2 = (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32);
+    const pfg::u32x4 r = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x504D0003u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u = uniform53(r.x, r.y);
+    const double log_alpha = (ll_prop + logprior_value(model, tp, hy)) - (ll_cur[b] + logprior_value(model, th, hy));
+    const bool finite = fabs(ll_prop) < INFINITY;        // false for a NaN as well
+    if (valid[b] != 0 && finite && ::log(u) < log_alpha) {
+        for (int j = 0; j < PFG_MAX_THETA; ++j) th[j] = tp[j];
+        ll_cur[b] = ll_prop;
+        n_accept[b] += 1;
+    }
+}
+
 // ---- the entry points: one prologue, one epilogue ----
 // What every rule checks of its arguments (`what` names the entry point).  lgssm_only: how SGRLD and Gibbs refuse other
 // models' chains (the reference's one preconditioner and conjugate prior).  Gibbs has no step size: the defaults pass.
@@ -290,4 +403,37 @@ int pfg_gibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const
     if (const int rc = check_update(ctx, __func__, model, theta, outs, hyper, ": no conjugate Gibbs draw for ")) return rc;
     return run_update(ctx, B, step_ctr, hip_stream, gibbs_update_kernel, B, theta, outs, *hyper, seed, chain_offset,
                       (const uint64_t *)step_ctr);
+}
+
+int pfg_logprior_device(pfg_ctx *ctx, int model, int B, const double *theta, const pfg_prior_hyper *hyper, double *logprior,
+                        void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (!theta || !hyper || !logprior) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+    if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
+    return run_update(ctx, B, nullptr, hip_stream, logprior_kernel, model, B, theta, *hyper, logprior);
+}
+
+int pfg_pmmh_propose_device(pfg_ctx *ctx, int model, int B, const double *theta, double *theta_prop, int32_t *valid,
+                            const double *scale, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr,
+                            void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (!theta || !theta_prop || !valid || !scale) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+    if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
+    // (no bump: the accept step that closes the PMMH step advances the counter)
+    return run_update(ctx, B, nullptr, hip_stream, pmmh_propose_kernel, model, B, theta, theta_prop, valid, scale, seed,
+                      chain_offset, step_ctr);
+}
+
+int pfg_pmmh_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const double *theta_prop, const int32_t *valid,
+                           const double *outs, double *ll_cur, uint64_t *n_accept, const pfg_prior_hyper *hyper, int init,
+                           uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (!theta || !theta_prop || !valid || !outs || !ll_cur || !n_accept || !hyper)
+        return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+    if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
+    return run_update(ctx, B, init ? nullptr : step_ctr, hip_stream, pmmh_accept_kernel, model, B, theta, theta_prop, valid,
+                      outs, ll_cur, n_accept, *hyper, init, seed, chain_offset, (const uint64_t *)step_ctr);
 }

@@ -180,7 +180,7 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_launch_device_traced", "pfg_last_traced", "pfg_launch_device_grid", "pfg_launch_device_grid_phase",
            "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device",
            "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
-           "pfg_launch_device_adaptive")
+           "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device")
 
 _lib = None
 
@@ -282,6 +282,15 @@ def load_library():
     lib.pfg_gibbs_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                             C.POINTER(PriorHyper), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.pfg_gibbs_update_device.restype = C.c_int
+    lib.pfg_logprior_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(PriorHyper), C.c_void_p, C.c_void_p]
+    lib.pfg_logprior_device.restype = C.c_int
+    lib.pfg_pmmh_propose_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pfg_pmmh_propose_device.restype = C.c_int
+    lib.pfg_pmmh_accept_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(PriorHyper), C.c_int, C.c_uint64, C.c_uint64,
+                                           C.c_void_p, C.c_void_p]
+    lib.pfg_pmmh_accept_device.restype = C.c_int
     lib.pfg_imq_ksd.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp]
     lib.pfg_imq_ksd.restype = C.c_int
     lib.pfg_sample_windows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -713,6 +722,32 @@ class Context:
             self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper),
             C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
             C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def logprior_device(self, model, B, theta_ptr, hyper, logprior_ptr, stream_ptr=0):
+        """pfg_logprior_device: logprior[b] = Prior.logprior of the raw row theta[b], up to a constant of the hyper-parameters."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_logprior_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.byref(hyper) if hyper is not None else None,
+            C.c_void_p(logprior_ptr or 0), C.c_void_p(int(stream_ptr))))
+
+    def pmmh_propose_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, scale_ptr, seed, chain_offset=0,
+                            step_ctr_ptr=None, stream_ptr=0):
+        """pfg_pmmh_propose_device: theta_prop = theta + scale (.) z, or theta and valid = 0 outside the support."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_pmmh_propose_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
+            C.c_void_p(scale_ptr or 0), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def pmmh_accept_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, n_accept_ptr, hyper, init,
+                           seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
+        """pfg_pmmh_accept_device: the accept / reject step on out[4] (init: ll = out[4] only); bumps *step_ctr unless init."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_pmmh_accept_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
+            C.c_void_p(outs_ptr or 0), C.c_void_p(ll_ptr or 0), C.c_void_p(n_accept_ptr or 0),
+            C.byref(hyper) if hyper is not None else None, int(bool(init)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
 
     def scratch_bytes(self, model, dtype, rng, N):
         return int(self.lib.pfg_scratch_bytes(MODEL[model], DTYPE[dtype], RNG[rng], int(N)))

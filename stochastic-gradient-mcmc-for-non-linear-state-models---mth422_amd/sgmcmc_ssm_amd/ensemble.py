@@ -1,4 +1,4 @@
-"""ChainEnsemble: many independent SGLD / SGHMC / SGRLD / Gibbs chains resident on one MI355X.
+"""ChainEnsemble: many independent SGLD / SGHMC / SGRLD / Gibbs / PMMH chains resident on one MI355X.
 
 The reference runs one chain in one Python thread; its experiment grid fans chains / settings
 out over processes (driver_utils.py:69-111).  On an MI355X one chain keeps one workgroup (one
@@ -97,7 +97,25 @@ class ChainEnsemble(object):
                'gibbs' (model 'lgssm', dtype 'f64', subsequence_length = buffer_length = -1: the blocked Gibbs sampler
                of sample_gibbs -- one FFBS path of the whole series with the PFG_STAT_GIBBS statistics, then the
                conjugate draw of pfg_gibbs_update_device; kind, N, pf, num_samples and epsilon are ignored, sequence
-               lists are refused, and last_gradient_statistics() returns the sufficient statistics)
+               lists are refused, and last_gradient_statistics() returns the sufficient statistics) |
+               'pmmh' (extension: particle marginal Metropolis-Hastings, Andrieu, Doucet and Holenstein 2010 -- a step
+               proposes theta' = theta + proposal_scale (.) z in the raw parameterisation (pfg_pmmh_propose_device; outside
+               the support of project_parameters the proposal is rejected unseen), runs the launch of the resolved kind
+               on theta' and accepts on its log-likelihood estimate out[4] plus the log-prior (pfg_pmmh_accept_device).
+               The chain keeps the estimate it was accepted with, so it samples the posterior exactly for every N.  It
+               needs the whole data set in every step: a single series with subsequence_length = buffer_length = -1, or
+               a list on the multi-window path with num_sequences = -1 and whole sequences (subsequence_length = -1), the
+               reduced out[4] being the sum over the sequences.  kind 'pf' with pf 'poyiadjis_N' | 'nemeth', any
+               resampling and ess_threshold (the statistic is not computed: stat 'none'), or kind 'marginal' (LGSSM, f64:
+               Metropolis-Hastings on the Kalman likelihood).  The target is prior.logprior(theta) in the raw coordinates
+               WITHOUT Jacobian terms -- the density whose gradient SGLD uses.  epsilon, friction and lambduh are
+               ignored; loglik() and acceptance_rate() read the chains' estimates and acceptance; the constructor runs
+               one launch at the initial parameters (the init pass: it consumes counter value 0, step s draws with
+               counter s + 1) and refuses a chain whose initial log-likelihood is not finite)
+      proposal_scale: sampler='pmmh' (required there, refused elsewhere): the random walk's standard deviations in raw-theta
+               units, a positive scalar or a length-P vector (LGSSM: C stays 1 whatever its entry)
+      pmmh_stat: sampler='pmmh', kind='pf': None | 'none' (the launch computes no statistic, the default) | 'score' (the
+               score launch of the same shape, its score ignored: tools/pmmh_time.py measures one against the other)
       kind: 'pf' (the particle-filter score) | 'marginal' (LGSSM, dtype 'f64': the exact Kalman score of
                every window, PFG_SMOOTHER_KALMAN -- the reference's kind='marginal', the KF baseline of its
                LGSSM experiment; N, pf and resampling are ignored) | 'complete' (LGSSM, dtype 'f64': the
@@ -142,7 +160,8 @@ class ChainEnsemble(object):
                null weights pointer, a whole short sequence of a list points at its row of T_total / T_k.
       _scratch_bytes: the scratch per descriptor of the resolved smoother.
       launch_windows / launch_pf / launch_reduce / launch_update: the launches of a step on one stream (_stream);
-               _enqueue_step orders them, step / run / _graph drive them.
+               _enqueue_step orders them, step / run / _graph drive them.  sampler='pmmh': launch_propose before
+               launch_pf, launch_accept as the update; _pmmh_init is the init pass.
     """
 
     def __init__(self, model, observations, parameters, num_chains=None, N=1000, pf="poyiadjis_N",
@@ -151,13 +170,13 @@ class ChainEnsemble(object):
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
                  Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                 ess_threshold=None):
+                 ess_threshold=None, proposal_scale=None, pmmh_stat=None):
         s = self._resolve_settings(
             model, observations, parameters, num_chains=num_chains, N=N, pf=pf, lambduh=lambduh,
             subsequence_length=subsequence_length, buffer_length=buffer_length, dtype=dtype, partition_style=partition_style,
             resampling=resampling, sampler=sampler, window_sampling=window_sampling, kind=kind, num_samples=num_samples,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, accept_reject=accept_reject, minibatch_size=minibatch_size,
-            num_sequences=num_sequences, ess_threshold=ess_threshold)
+            num_sequences=num_sequences, ess_threshold=ess_threshold, proposal_scale=proposal_scale, pmmh_stat=pmmh_stat)
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         Parameters, Prior, Helper = _model_info(model)
@@ -201,6 +220,14 @@ class ChainEnsemble(object):
         self.out_dev = torch.zeros((C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         self.momentum_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
+        self.proposal_scale = s.proposal_scale
+        if sampler == "pmmh":
+            # the proposal the launch reads, its validity, each chain's current estimate and acceptance count
+            self.theta_prop_dev = self.theta_dev.clone()
+            self.valid_dev = torch.ones(C, dtype=torch.int32, device=dev)
+            self.ll_dev = torch.zeros(C, dtype=torch.float64, device=dev)
+            self.accept_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
+            self.scale_dev = torch.from_numpy(s.proposal_scale).to(dev)
         # one weights row per window start of every sequence longer than S.  Single-window lists: every row times
         # T_total / T_sequence, the Seq sampler's rescaling of a one-sequence gradient, whole short sequences a row of it;
         # the multi-window path leaves that rescaling to the reduction
@@ -233,7 +260,7 @@ class ChainEnsemble(object):
             self.scratch_dev = torch.empty(self._nd * sb, dtype=torch.uint8, device=dev)
         garch_stationary = model == "garch" and self.helper.default_forward_message is None
         self._desc = _capi.device_descriptors(
-            self._nd, theta=self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
+            self._nd, theta=self.theta_prop_dev if sampler == "pmmh" else self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
             scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv, lambduh=self.lambduh, seed=self.seed, N=self.N,
             smoother=s.smoother, stat=s.stat, flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0,
             ess_threshold=s.ess_threshold, **s.paris)
@@ -242,13 +269,15 @@ class ChainEnsemble(object):
         self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)).to(dev)
         if self._multi and not self._draws:
             self.launch_windows()           # static windows: written once, no draw
+        if sampler == "pmmh":
+            self._pmmh_init()
 
     @staticmethod
     def _resolve_settings(model, observations, parameters=None, num_chains=None, N=1000, pf="poyiadjis_N", lambduh=None,
                           subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
                           resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
                           Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                          ess_threshold=None):
+                          ess_threshold=None, proposal_scale=None, pmmh_stat=None):
         """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
         device is made here and nowhere else, so it runs (and is tested) without a GPU.
 
@@ -256,7 +285,8 @@ class ChainEnsemble(object):
         launch states: 'poyiadjis_n' for 'nemeth' with lambduh = 1); stat; paris (the descriptors' PaRIS fields, {} otherwise),
         Ntilde, max_accept_reject; M, K, W, multi; S, B, strict; y (the concatenated series), T, segments ([K+1] offsets
         into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto;
-        ess_threshold (None unless adaptive resampling is on)."""
+        ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
+        'pmmh')."""
         tau = None
         if ess_threshold is not None and ess_threshold != 0:
             # adaptive resampling (extension, include/pfgrad.h): what it is not built for is refused by name
@@ -274,8 +304,35 @@ class ChainEnsemble(object):
             if int(N) > 16384:
                 raise NotImplementedError("adaptive resampling (ess_threshold) is built for N <= 16384 "
                                           "(no whole-GPU windows), got N = {0}".format(int(N)))
-        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs"):
-            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld' or 'gibbs'")
+        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh"):
+            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'gibbs' or 'pmmh'")
+        scale = None
+        if sampler != "pmmh":
+            if proposal_scale is not None:
+                raise ValueError("proposal_scale is the random walk of sampler='pmmh', got sampler = '{0}'".format(sampler))
+            if pmmh_stat is not None:
+                raise ValueError("pmmh_stat belongs to sampler='pmmh', got sampler = '{0}'".format(sampler))
+        else:
+            # particle marginal Metropolis-Hastings (extension): what it is not built for is refused by name
+            if proposal_scale is None:
+                raise ValueError("sampler='pmmh' needs proposal_scale: a positive scalar or a length-P vector in raw-theta units")
+            P = _capi.THETA_DIM[model]
+            ps = np.asarray(proposal_scale, dtype=np.float64).reshape(-1)
+            if ps.size not in (1, P) or not np.all(np.isfinite(ps)) or not np.all(ps > 0.0):
+                raise ValueError("proposal_scale must be a positive scalar or a positive vector of length {0}, got {1}".format(
+                    P, proposal_scale))
+            scale = np.zeros(_capi.MAX_THETA)
+            scale[:P] = ps
+            if kind == "complete":
+                raise NotImplementedError("sampler='pmmh' accepts on a log-likelihood estimate: kind='pf' or kind='marginal' "
+                                          "(kind='complete' samples paths and has none)")
+            if kind == "pf" and pf not in ("poyiadjis_N", "nemeth"):
+                raise NotImplementedError("sampler='pmmh' reads the filter's log-likelihood only: pf = 'poyiadjis_N' | 'nemeth' "
+                                          "(the smoothing of pf = '{0}' would be thrown away)".format(pf))
+            if kind == "pf" and int(N) > 16384:
+                raise NotImplementedError("sampler='pmmh' is built for N <= 16384 (no whole-GPU windows), got N = {0}".format(int(N)))
+            if pmmh_stat not in (None, "none", "score"):
+                raise ValueError("pmmh_stat must be None, 'none' or 'score'")
         M, K, W = ChainEnsemble._window_counts(observations, minibatch_size, num_sequences)
         if W > 1 and sampler == "gibbs":
             raise NotImplementedError("sampler='gibbs' draws one FFBS path per chain and step: W = 1 window "
@@ -289,6 +346,8 @@ class ChainEnsemble(object):
             raise NotImplementedError("No Default Preconditioner for {0}: sampler='sgrld' is built for model 'lgssm'".format(
                 dict(svm="SVMSampler", garch="GARCHSampler").get(model, model)))
         stat = "score"
+        if sampler == "pmmh" and kind == "pf":
+            stat = pmmh_stat or "none"      # the launch computes no statistic: PMMH reads out[4] alone
         if sampler == "gibbs":
             if model != "lgssm" or dtype != "f64":
                 raise NotImplementedError("sampler='gibbs' (FFBS paths, conjugate draws) is built for model 'lgssm', dtype 'f64'")
@@ -359,7 +418,8 @@ class ChainEnsemble(object):
         else:
             raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2', got {0}".format(pf))
         # every chain the Poyiadjis O(N) score (NEMETH, lambduh = 1, score): units with a twin specialised to it run that
-        launch_smoother = "poyiadjis_n" if smoother == "nemeth" and lam == 1.0 else smoother
+        # (their kernels answer NaN to a window that asks for another statistic: stat 'none' launches the general unit)
+        launch_smoother = "poyiadjis_n" if smoother == "nemeth" and lam == 1.0 and stat == "score" else smoother
         if window_sampling not in ("host", "device"):
             raise ValueError("window_sampling must be 'host' or 'device'")
 
@@ -409,8 +469,19 @@ class ChainEnsemble(object):
             if N > 16384:
                 raise NotImplementedError("the multi-window path is built for N <= 16384 (one workgroup per window), "
                                           "got N = {0}".format(N))
+        if sampler == "pmmh":
+            # every step needs the likelihood of the whole data set: no window is drawn, nothing is rescaled
+            whole = "pmmh needs the whole series in every step: "
+            if segments is None and (S != -1 or int(buffer_length) != -1):
+                raise NotImplementedError(whole + "subsequence_length = buffer_length = -1, got {0} / {1}".format(
+                    int(subsequence_length), int(buffer_length)))
+            if segments is not None and (not multi or K != -1 or int(subsequence_length) != -1 or M != 1 or draws or rescale):
+                raise NotImplementedError(whole + "a list of sequences takes num_sequences = -1, subsequence_length = -1, "
+                                          "buffer_length = 0 and minibatch_size 1 (every sequence whole, out[4] summed)")
+            if multi and (M != 1 or draws or rescale):
+                raise NotImplementedError(whole + "minibatch_size = 1 (an average of log-likelihoods is no estimate of one)")
         return types.SimpleNamespace(
-            kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
+            proposal_scale=scale, kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, M=M, K=K, W=W, multi=multi, S=S, B=B, strict=strict, y=y, T=T,
             segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau)
 
@@ -587,7 +658,9 @@ class ChainEnsemble(object):
     def launch_update(self, stream=None):
         theta, out = (self.model, self.C, self.theta_dev.data_ptr()), (self.out_dev.data_ptr(), self.hyper)
         key = (self.seed ^ 0x5DEECE66D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
-        if self.sampler == "sgrld":
+        if self.sampler == "pmmh":
+            self.launch_accept(stream)
+        elif self.sampler == "sgrld":
             self.ctx.sgrld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
         elif self.sampler == "gibbs":
             self.ctx.gibbs_update_device(*theta, *out, *key)
@@ -596,6 +669,35 @@ class ChainEnsemble(object):
                                          float(self.T), *key)
         else:
             self.ctx.sgld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
+
+    def _pmmh_key(self, stream):
+        return (self.seed ^ 0x5DEECE66D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
+
+    def launch_propose(self, stream=None):
+        """sampler='pmmh': theta_prop_dev = theta_dev + proposal_scale (.) z, valid_dev (pfg_pmmh_propose_device)."""
+        self.ctx.pmmh_propose_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
+                                     self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), *self._pmmh_key(stream))
+
+    def launch_accept(self, stream=None, init=False):
+        """sampler='pmmh': accept / reject on out_dev[:, 4] and the log-prior; bumps the counter (pfg_pmmh_accept_device)."""
+        self.ctx.pmmh_accept_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
+                                    self.valid_dev.data_ptr(), self.out_dev.data_ptr(), self.ll_dev.data_ptr(),
+                                    self.accept_dev.data_ptr(), self.hyper, init, *self._pmmh_key(stream))
+
+    def _pmmh_init(self):
+        """The init pass, the constructor's last act: the launch at the initial parameters, ll_dev = its out[4].  It
+        consumes counter value 0 -- the counter is 1 afterwards, step s (from 0) draws with s + 1 -- so that no step's
+        particle filter repeats the draws the initial estimate was made with."""
+        self.theta_prop_dev.copy_(self.theta_dev)
+        self.launch_pf()
+        if self._multi:
+            self.launch_reduce()
+        self.launch_accept(init=True)
+        self.step_ctr.fill_(1)
+        self.synchronize()
+        bad = np.flatnonzero(~np.isfinite(self.ll_dev.cpu().numpy()))
+        if bad.size:
+            raise ValueError("pmmh: the initial log-likelihood of chain {0} is not finite".format(int(bad[0]) + self.chain_offset))
 
     def launch_windows(self, stream=None):
         """Device-side window sampling (window_sampling='device'): rewrite y / T / t1 / tL / weights of
@@ -619,14 +721,19 @@ class ChainEnsemble(object):
                                        self._rescale, float(self.T), self.out_dev.data_ptr(), self._stream(stream))
 
     def _enqueue_step(self):
+        pmmh = self.sampler == "pmmh"       # (its windows are static: nothing to draw on either path)
         if self._multi:
             if self._draws:
                 self.launch_windows()
+            if pmmh:
+                self.launch_propose()
             self.launch_pf()
             self.launch_reduce()
             self.launch_update()
             return
-        if self.window_sampling == "device":
+        if pmmh:
+            self.launch_propose()
+        elif self.window_sampling == "device":
             self.launch_windows()
         elif self.steps_done > 0 and self._set_windows():
             self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self.C, -1)),
@@ -652,10 +759,13 @@ class ChainEnsemble(object):
         if g is None:
             # one eager step first (code-object load, LDS-size attributes), undone afterwards so
             # that building the graph does not advance the chains
-            snap = [t.clone() for t in (self.theta_dev, self.momentum_dev, self.step_ctr, self.desc_dev)]
+            state = (self.theta_dev, self.momentum_dev, self.step_ctr, self.desc_dev)
+            if self.sampler == "pmmh":
+                state += (self.theta_prop_dev, self.valid_dev, self.ll_dev, self.accept_dev)
+            snap = [t.clone() for t in state]
             self._enqueue_step()
             self.synchronize()
-            for t, c in zip((self.theta_dev, self.momentum_dev, self.step_ctr, self.desc_dev), snap):
+            for t, c in zip(state, snap):
                 t.copy_(c)
             self.synchronize()
             g = torch.cuda.CUDAGraph()
@@ -694,10 +804,13 @@ class ChainEnsemble(object):
     #    svm/driver.py:362-408; here the whole ensemble state is a few small arrays) -------------
     def state_dict(self):
         self.synchronize()
-        return dict(theta=self.theta_dev.cpu().numpy(), momentum=self.momentum_dev.cpu().numpy(),
-                    step_ctr=int(self.step_ctr.item()), steps_done=int(self.steps_done),
-                    seed=self.seed, chain_offset=self.chain_offset,
-                    model=self.model, N=self.N, C=self.C, ess_threshold=self.ess_threshold)
+        state = dict(theta=self.theta_dev.cpu().numpy(), momentum=self.momentum_dev.cpu().numpy(),
+                     step_ctr=int(self.step_ctr.item()), steps_done=int(self.steps_done),
+                     seed=self.seed, chain_offset=self.chain_offset,
+                     model=self.model, N=self.N, C=self.C, ess_threshold=self.ess_threshold)
+        if self.sampler == "pmmh":      # the estimate a chain was accepted with is part of its state
+            state.update(ll=self.ll_dev.cpu().numpy(), n_accept=self.accept_dev.cpu().numpy())
+        return state
 
     def load_state_dict(self, state):
         for key in ("model", "N", "C", "seed", "chain_offset"):
@@ -710,6 +823,9 @@ class ChainEnsemble(object):
         self.theta_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["theta"])))
         self.momentum_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["momentum"])))
         self.step_ctr.fill_(int(state["step_ctr"]))
+        if self.sampler == "pmmh":
+            self.ll_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["ll"], dtype=np.float64)))
+            self.accept_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["n_accept"], dtype=np.int64)))
         self.steps_done = int(state["steps_done"])       # host window draws are keyed by (seed, chain, steps_done)
         self.synchronize()
 
@@ -754,7 +870,24 @@ class ChainEnsemble(object):
         out = self.out_dev.cpu().numpy()
         if self.sampler == "gibbs":
             return out[:, :7], None
+        if self.sampler == "pmmh":      # no score is computed: (None, the log-likelihood estimates at the latest PROPOSALS)
+            return None, out[:, 4]
         return out[:, :_capi.STAT_DIM[self.model]], out[:, 4]
+
+    def loglik(self):
+        """sampler='pmmh': [C] log-likelihood estimates the chains hold, each the one its current state was accepted with."""
+        self._need_pmmh("loglik")
+        return self.ll_dev.cpu().numpy()
+
+    def acceptance_rate(self):
+        """sampler='pmmh': [C] accepted proposals / steps done (nan before the first step)."""
+        self._need_pmmh("acceptance_rate")
+        n = self.accept_dev.cpu().numpy().astype(np.float64)
+        return n / self.steps_done if self.steps_done else np.full(self.C, np.nan)
+
+    def _need_pmmh(self, what):
+        if self.sampler != "pmmh":
+            raise ValueError("{0}() belongs to sampler='pmmh', this ensemble runs '{1}'".format(what, self.sampler))
 
     def window_statistics(self):
         """Multi-window path: the latest launch's [C, W, 8] window records and [C, W] sequence lengths."""
