@@ -226,7 +226,23 @@ __device__ __forceinline__ void particle_step(const Consts<REAL> &c, const MATH 
 //   PFG_STEP_SHIFTFOLD  lw comes out as lw - shift: k0_shifted = svm_logw's wave-uniform constant k0 minus the shift;
 //   PFG_STEP_SCOREDZ    the score from the proposal's noise term dz = iLQinv z, which IS x1 - A xp: x1 = fma(A, xp, dz),
 //                       add[1] = iLQinv - dz^2 LQinv = fma(-dz, z, iLQinv), add[2] = (Qinv dz) xp = ((Qinv iLQinv) z) xp.
-enum { PFG_STEP_SHIFTFOLD = 1, PFG_STEP_SCOREDZ = 2 };
+//   PFG_STEP_RAWSCORE   (STAT = score) add[] comes out as the RAW factors {e, z, xp} of the three sums r0 += (w y^2) e, r1 += (w z) z,
+//                       r2 += (w z) xp (RegTraits::RAWSCORE; raw_score_in / raw_score_out map them from / to the score's scale).
+//                       pf_reg_kernel sets the bit for the children block of a raw window's statistic steps alone.
+enum { PFG_STEP_SHIFTFOLD = 1, PFG_STEP_SCOREDZ = 2, PFG_STEP_RAWSCORE = 4 };
+// the SVM score from the raw sums (r[0..2], Cw = the sum of the window weights added so far) and back (Cw = 0)
+template <typename REAL>
+__device__ __forceinline__ void raw_score_out(const Consts<REAL> &c, REAL Cw, const REAL *r, REAL *s) {
+    s[0] = fma(-c.LRinv, r[0], c.iLRinv * Cw);
+    s[1] = c.iLQinv * (Cw - r[1]);
+    s[2] = (c.Qinv * c.iLQinv) * r[2];
+}
+template <typename REAL>
+__device__ __forceinline__ void raw_score_in(const Consts<REAL> &c, const REAL *s, REAL *r) {
+    r[0] = -s[0] / c.LRinv;
+    r[1] = -s[1] / c.iLQinv;
+    r[2] = s[2] / (c.Qinv * c.iLQinv);
+}
 #ifdef PFG_FAST_ALGEBRA
 template <int STAT, int TUNE, typename REAL, typename MATH>
 __device__ __forceinline__ void particle_step_svm_tuned(const Consts<REAL> &c, const MATH &mth, const REAL *xp,
@@ -243,7 +259,9 @@ __device__ __forceinline__ void particle_step_svm_tuned(const Consts<REAL> &c, c
         lw = svm_logw(c, x1, e, y2);
     }
     xn[0] = x1;
-    if (STAT == PFG_STAT_SCORE) {
+    if (STAT == PFG_STAT_SCORE && (TUNE & PFG_STEP_RAWSCORE)) {
+        add[0] = e; add[1] = z; add[2] = xp[0];
+    } else if (STAT == PFG_STAT_SCORE) {
         if (TUNE & PFG_STEP_SCOREDZ) {
             add[2] = ((c.Qinv * c.iLQinv) * z) * xp[0];
             add[1] = fma(-dz, z, c.iLQinv);

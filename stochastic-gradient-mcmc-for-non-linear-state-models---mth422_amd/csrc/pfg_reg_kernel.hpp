@@ -71,6 +71,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
     const double lam_d = ONLY_SCORE1 ? 1.0 : is_filter ? 0.0 : ((P.smoother == PFG_SMOOTHER_PARIS || TR::N2) ? 1.0 : P.lambduh);
     const REAL lam = (REAL)lam_d, oml = (REAL)(1.0 - lam_d);
     const bool needS_every = is_filter || (lam_d != 1.0);
+    // RAWSCORE: a plain window whose statistic is the score carries it as raw sums (see PFG_OPT_RAWSCORE); window-uniform
+    [[maybe_unused]] const bool raw_score = TR::RAWSCORE && !needS_every && stat == PFG_STAT_SCORE;
     const gptr<const double> yv = global_ptr(P.y);
     const gptr<const double> wv = global_ptr(P.weights);
     const gptr<const double> uv = global_ptr(P.u);
@@ -252,8 +254,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 }
 #pragma unroll
                 for (int d = 0; d < NS; ++d) cur[sidx(d, i)] = x[d];
+                if constexpr (TR::RAWSCORE) {
+                    REAL r[H];
+#pragma unroll
+                    for (int h = 0; h < H; ++h) r[h] = s[h];
+                    if (raw_score && P.init_x && P.init_stats) raw_score_in(c, s, r);      // Cw = 0 (zeros stay +0 without it)
+#pragma unroll
+                    for (int h = 0; h < H; ++h) cur[sidx((NS + h), i)] = r[h];
+                } else {
 #pragma unroll
                 for (int h = 0; h < H; ++h) cur[sidx((NS + h), i)] = s[h];
+                }
                 if (PFG_TR(P.trace_x)) {
 #pragma unroll
                     for (int d = 0; d < NS; ++d) P.trace_x[(size_t)i * NS + d] = (double)x[d];
@@ -272,6 +283,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
     }
 
     double ll = 0.0, wt_prev = 1.0, tie = 1.0;
+    [[maybe_unused]] double Cw = 0.0;       // RAWSCORE: the window weights of the statistic steps so far
     double ll_W = 1.0, ll_w = 0.0;          // LAZYLL: lane t % 64 of wave 0 holds step t's (W, w, m)
     float ll_m = 0.0f;
     double filt[H], S[H];
@@ -921,6 +933,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
 #endif
             auto children = [&](auto upd_tag) {
                 constexpr int UPD = decltype(upd_tag)::value;      // 0 plain + statistic, 1 plain, no statistic, 2 general
+                // RAWSCORE: plain + statistic with STAT = score IS the statistic step of a raw window; the step hands out the raw factors
+                constexpr bool RAWUPD = TR::RAWSCORE && STAT == PFG_STAT_SCORE && UPD == 0;
+                [[maybe_unused]] constexpr int TUNE = RAWUPD ? TR::STEP_TUNE : (TR::STEP_TUNE & ~PFG_STEP_RAWSCORE);
                 if (UPD == 1) { PFG_MARK("cold children-outside-window") }
                 if (UPD == 2) { PFG_MARK("cold children-general") }
 #pragma unroll
@@ -928,9 +943,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                     REAL xn[NS], add[H], lwn;
 #ifdef PFG_FAST_ALGEBRA
 #if PFG_OPT_SHIFTFOLD
-                    if constexpr (TR::STEP_TUNE != 0) particle_step_svm_tuned<STAT, TR::STEP_TUNE>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add, k0_shifted);
+                    if constexpr (TR::STEP_TUNE != 0) particle_step_svm_tuned<STAT, TUNE>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add, k0_shifted);
 #else
-                    if constexpr (TR::STEP_TUNE != 0) particle_step_svm_tuned<STAT, TR::STEP_TUNE>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add, (REAL)0);
+                    if constexpr (TR::STEP_TUNE != 0) particle_step_svm_tuned<STAT, TUNE>(c, mth, xp[k], (REAL)y_t, zz[k], xn, lwn, add, (REAL)0);
 #endif
                     else
 #endif
@@ -939,7 +954,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                         if (!resample) lwn = (REAL)(((((double)lw[k] - m) - lse) + lgN) + (double)lwn);
                     }
                     lw[k] = valid[k] ? lwn : (REAL)(-INFINITY);
-                    if (UPD == 0) {
+                    if constexpr (RAWUPD) {
+                        // raw sums: r0 += (w_t y^2) e, r1 += (w_t z) z, r2 += (w_t z) xp
+                        const REAL y2 = (REAL)y_t * (REAL)y_t, wy2 = (REAL)wt * y2;     // wave-uniform: once per timestep
+                        const REAL zw = (REAL)wt * add[1];
+                        sp[k][0] = fma(wy2, add[0], sp[k][0]);
+                        sp[k][1] = fma(zw, add[1], sp[k][1]);
+                        sp[k][2] = fma(zw, add[2], sp[k][2]);
+                    } else if (UPD == 0) {
                         // Poyiadjis O(N), lambda = 1: 1*s[a] + 0*S + w_t h = s[a] + w_t h exactly
 #pragma unroll
                         for (int h = 0; h < H; ++h) sp[k][h] = sp[k][h] + add[h] * (REAL)wt;
@@ -1445,6 +1467,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             if (stat == PFG_STAT_SCORE) slots(std::integral_constant<int, PFG_STAT_SCORE>{});
             else slots(std::integral_constant<int, PFG_STAT_SUFF>{});
         }
+        if constexpr (TR::RAWSCORE) {
+            if (raw_score && use_stat) Cw = uniform_f64(Cw + wt);
+        }
         if (PFG_TR(P.trace_x)) {
             // own children back from LDS (written by this thread: no barrier needed)
 #pragma unroll
@@ -1459,9 +1484,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                     for (int d = 0; d < NS; ++d) P.trace_x[row * NS + d] = (double)nxt[sidx(d, i)];
                     P.trace_logw[row] = TR::SHIFTFOLD ? (double)lw[k] + m : (double)lw[k];
                     if (P.trace_stats && !is_filter) {
+                        if constexpr (TR::RAWSCORE) {          // a raw window's slots leave in the score's scale, with this step's Cw
+                            REAL r[H], sv[H];
+#pragma unroll
+                            for (int h = 0; h < H; ++h) r[h] = sv[h] = nxt[sidx((NS + h), i)];
+                            if (raw_score) raw_score_out(c, (REAL)Cw, r, sv);
+#pragma unroll
+                            for (int h = 0; h < H; ++h) P.trace_stats[row * H + h] = (double)sv[h];
+                        } else {
 #pragma unroll
                         for (int h = 0; h < H; ++h)
                             P.trace_stats[row * H + h] = (double)nxt[sidx((NS + h), i)];
+                        }
                     }
                 }
             }
@@ -1494,6 +1528,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
         // RAW: a cached Gaussian is pending -> how far back from the end of the consumption its pair of doubles starts
         P.paris_consumed[1] = (TR::RAWCAP && raw && carry_has && !paris_overflow) ? paris_cursor - raw_slots[1] : 0ll;
     }
+    if constexpr (TR::RAWSCORE) {
+        // the weighted sums of t == T ran over raw slots: to the score's scale, once
+        if (raw_score) {
+            REAL r[H], sv[H];
+#pragma unroll
+            for (int h = 0; h < H; ++h) r[h] = (REAL)S[h];
+            raw_score_out(c, (REAL)Cw, r, sv);
+#pragma unroll
+            for (int h = 0; h < H; ++h) S[h] = (double)sv[h];
+        }
+    }
     if (tid == 0 && P.out) {
 #pragma unroll
         for (int h = 0; h < PFG_MAX_STAT; ++h) P.out[h] = 0.0;
@@ -1514,9 +1559,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 for (int d = 0; d < NS; ++d) P.final_x[(size_t)i * NS + d] = (double)cur[sidx(d, i)];
                 if (P.final_logw) P.final_logw[i] = TR::SHIFTFOLD ? (double)lw[k] + m : (double)lw[k];
                 if (P.final_stats && !is_filter) {
+                    if constexpr (TR::RAWSCORE) {
+                        REAL r[H], sv[H];
+#pragma unroll
+                        for (int h = 0; h < H; ++h) r[h] = sv[h] = cur[sidx((NS + h), i)];
+                        if (raw_score) raw_score_out(c, (REAL)Cw, r, sv);
+#pragma unroll
+                        for (int h = 0; h < H; ++h) P.final_stats[(size_t)i * H + h] = (double)sv[h];
+                    } else {
 #pragma unroll
                     for (int h = 0; h < H; ++h)
                         P.final_stats[(size_t)i * H + h] = (double)cur[sidx((NS + h), i)];
+                    }
                 }
             }
         }

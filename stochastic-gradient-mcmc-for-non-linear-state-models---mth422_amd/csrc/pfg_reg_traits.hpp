@@ -113,6 +113,31 @@ namespace pfg {
 #ifndef PFG_OPT_SCOREDZ
 #define PFG_OPT_SCOREDZ 1
 #endif
+//  PFG_OPT_RAWSCORE    (RAWSCORE; the same two STALE instantiations) the Poyiadjis O(N) score of a `raw` window -- plain (no filter,
+//                  lambda = 1) with stat = score, both window-uniform and fixed for the whole T-loop -- is carried along the
+//                  genealogy as RAW SUMS and scaled where a statistic leaves the kernel.  With normalised weights sum_i W_i (a +
+//                  b r_i) = a + b sum_i W_i r_i, and of the score's terms  w_t (iLRinv - y^2 LRinv e),  w_t iLQinv (1 - z^2),
+//                  w_t (Qinv iLQinv) z xp  the constants iLRinv, iLQinv, the factors LRinv, iLQinv, Qinv iLQinv and w_t are the
+//                  same for every particle of the window.  The three statistic slots of a raw window's LDS records hold
+//                    r0 += (w_t y^2) e,   r1 += (w_t z) z,   r2 += (w_t z) xp       (w_t y^2 wave-uniform; zw = w_t z)
+//                  and Cw += w_t (uniform; on the steps that add a statistic) rides in scalar registers:
+//                    s0 = iLRinv Cw - LRinv r0,   s1 = iLQinv (Cw - r1),   s2 = (Qinv iLQinv) r2          (raw_score_out)
+//                  on P.trace_stats (per step, with that step's Cw), P.final_stats and the three uniform sums S[h] before P.out;
+//                  P.init_stats enters as r0 = -s0 / LRinv, r1 = -s1 / iLQinv, r2 = s2 / (Qinv iLQinv) with Cw = 0 (raw_score_in:
+//                  converted, not sent down the general path -- a fallback would keep one more children block in the loop body).
+//                  One multiply and three fma per particle instead of seven fp64 instructions; x', the log-weight and everything on
+//                  the weight path are instruction for instruction what they were.  Record layout, pairs, gathers and stores do not
+//                  change; every other window (lambda != 1, filter, stat suff / none) keeps the general path in the original scale.
+//                  Accuracy: s1 = iLQinv (Cw - r1) cancels -- r1 is about Cw +- sqrt(2 Cw) -- so it loses about log10(sqrt(Cw / 2))
+//                  digits (1.3 at Cw = 1000); Cw grows with the window length, the window weights and every warm start that
+//                  carries statistics on.  Harmless at T = 1000; a caller with windows orders of magnitude longer builds with
+//                  -DPFG_OPT_RAWSCORE=0.
+//                  Measured and not kept (no longer in the source): a children block of its own for steps with w_t == 1, without the
+//                  multiply zw = w_t z: -0.1 ... -0.3 % against the general form, under its gate.
+//  A/B: profiles/r07_ab_raw_score.txt.
+#ifndef PFG_OPT_RAWSCORE
+#define PFG_OPT_RAWSCORE 1
+#endif
 // PFG_OPT_N2SKIP (the O(N^2) instantiations, MODE_N2): the backward sweep over all parents is skipped on the steps before t1 of a
 // window that starts without init_stats -- its result there is +0.0 exactly, see n2_slots.  -DPFG_OPT_N2SKIP=0 runs every sweep (A/B).
 #ifndef PFG_OPT_N2SKIP
@@ -228,7 +253,9 @@ struct RegTraits {
                                   !PP && sizeof(REAL) == 8;
     // the three instruction-count measures of the STALE kernels, see PFG_OPT_SUMSHIFT; STEP_TUNE selects particle_step_svm_tuned
     static constexpr bool SUMSHIFT = PFG_OPT_SUMSHIFT && STALE, SHIFTFOLD = PFG_OPT_SHIFTFOLD && STALE, SCOREDZ = PFG_OPT_SCOREDZ && STALE;
-    static constexpr int STEP_TUNE = (SHIFTFOLD ? PFG_STEP_SHIFTFOLD : 0) | (SCOREDZ ? PFG_STEP_SCOREDZ : 0);
+    // RAWSCORE: the score of a raw window as raw sums, see PFG_OPT_RAWSCORE
+    static constexpr bool RAWSCORE = PFG_OPT_RAWSCORE && STALE;
+    static constexpr int STEP_TUNE = (SHIFTFOLD ? PFG_STEP_SHIFTFOLD : 0) | (SCOREDZ ? PFG_STEP_SCOREDZ : 0) | (RAWSCORE ? PFG_STEP_RAWSCORE : 0);
     // GADDR (256 x 4): search offset -> gather byte address..  rel = 4 x physical CDF position (one pad slot per 32 entries), p4 =
     // rel - 4 (rel * 993 >> 17) = 4 x CDF position p (exact: rel * 993 < 2^23), and (p4 * 1025) & 0x3ff0 = 16 x the particle index
     // ((p & 3) << 8) | (p >> 2): p4 < 2^12, so the copies p4 << 10 and p4 do not overlap -- bits 4..11 of p4 are p >> 2 and bits
