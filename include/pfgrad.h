@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PFG_VERSION 125          /* 0.1.25 */
+#define PFG_VERSION 126          /* 0.1.26 */
 #define PFG_MAX_STAT 4           /* widest additive statistic (GARCH / LGSSM score) */
 #define PFG_MAX_THETA 4          /* raw parameters per model */
 #define PFG_OUT_DOUBLES 8        /* doubles in one result record (see pfg_dev_problem.out) */
@@ -276,6 +276,11 @@ typedef struct pfg_result {
      * ew_stats [N * 3 (tL-t1)] = its per-particle statistics, row-major (optional) */
     double *ew_mean, *ew_stats;
     int64_t paris_consumed;  /* doubles of pfg_problem.paris_stream the window consumed; -1 = stream too short */
+    /* PARIS + trace_x only (test instrumentation, both generators; NULL = not wanted): [T][Ntilde][N] int32, the
+     * backward-sampled parent of child i's draw j at step t at (t Ntilde + j) N + i -- what the accept-reject rounds or
+     * the exact categorical fallback returned, in [0, N).  With the trajectories it determines the statistics.  Not with
+     * `elementwise` (that pass owns the buffer as a work piece): INVALID. */
+    int32_t *trace_paris_J;
 } pfg_result;
 
 /* Device-side descriptor: one per workgroup, resident in HBM.  All pointers are DEVICE

@@ -435,7 +435,7 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
               prior_mean=0.0, prior_var=1.0, save_all=False,
               Ntilde=2, max_accept_reject=None, manual_sample_threshold=None, paris_draws=None,
               elementwise_statistic=False, num_steps_ahead=5, pred_normals=None, resampler=None,
-              accept_reject=True):
+              accept_reject=True, paris_parents=None):
     """One buffered PF window.
 
     Args:
@@ -447,6 +447,10 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
       resampler: None = the reference's np.random.choice semantics on u[t]; else a callable
           (t, logw) -> ancestors (tests of the device-generator kernels: `device_ancestors` on the
           words the launch recorded), u is then unused
+      paris_parents: pf='paris' only.  None = the backward draws come from paris_draws (accept-reject rounds and the
+          exact fallback, or accept_reject=False); else a callable t -> J[N, Ntilde], the backward-sampled parents of step
+          t as given (tests of the device-generator kernels: the parents the launch traced).  It replaces the draw and
+          nothing else; paris_draws is then unused
     Returns dict(x_t, log_weights, statistics, loglikelihood_estimate[, mean_statistic, all_*])
     """
     y = np.asarray(y, dtype=float).reshape(-1, 1)   # y[t] is a (1,) array as in the reference
@@ -460,8 +464,8 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
     elif pf == "nemeth":
         lambduh = 0.95 if lambduh is None else lambduh
     elif pf == "paris":
-        if paris_draws is None:
-            raise ValueError("pf='paris' needs paris_draws (NpDraws or PoolDraws)")
+        if paris_draws is None and paris_parents is None:
+            raise ValueError("pf='paris' needs paris_draws (NpDraws or PoolDraws) or paris_parents")
     elif pf == "poyiadjis_N2":
         pass
     elif pf != "filter":
@@ -491,6 +495,7 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
     stats = np.zeros(h) if is_filter else np.zeros((N, h))
     if save_all:
         all_x, all_lw, all_s, all_ll, all_anc = [x], [logw], [stats], [loglik], []
+        all_J = []
 
     def widen(add, t):
         """elementwise_statistic_wrapper (buffered_smoother.py:201-210): the h_base columns of step t
@@ -546,7 +551,9 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
             continue
         if is_paris:
             # paris_smoother (pf.py:183-258): rewire Ntilde backward-sampled parents per child
-            if accept_reject:
+            if paris_parents is not None:
+                J = np.array(paris_parents(t), dtype=int).reshape(N, Ntilde)
+            elif accept_reject:
                 J = paris_backward_indices(model, d, x, logw, x_next, Ntilde, paris_draws, t,
                                            max_accept_reject, manual_sample_threshold)
             else:
@@ -556,6 +563,8 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
                 for i in range(N):
                     child_ll = prior_log_density(model, d, x, np.outer(np.ones(N), x_next[i]))
                     J[i] = multinomial_ancestors(log_normalize(logw + child_ll), paris_draws.child_uniforms(t, i, Ntilde))
+            if save_all:
+                all_J.append(J)
             flat = J.flatten()
             rew_parents = x[flat]
             xi_next = x_next[np.array([ii for ii in range(N) for _ in range(Ntilde)])]
@@ -618,6 +627,8 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
         out["all_statistics"] = np.array(all_s)
         out["all_loglikelihood_estimate"] = np.array(all_ll)
         out["all_ancestors"] = np.array(all_anc, dtype=int).reshape(-1, N)
+        if is_paris:
+            out["all_paris_J"] = np.array(all_J, dtype=int).reshape(-1, N, Ntilde)      # [T, N, Ntilde]
     return out
 
 

@@ -1017,7 +1017,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
             int *queue = paris_queue;                               // [<= N] children left to the fallback
             int *qcount = reinterpret_cast<int *>(red_max) + NW;    // behind the NW floats of red_maxf
             // ---- 1. propose every child from its filter ancestor and publish x' -------------
-            if (RNG != PFG_RNG_REPLAY) draw_normals(zz);
+            if (RNG != PFG_RNG_REPLAY) {
+                draw_normals(zz);
+                if (PFG_TR(P.trace_x) && P.rec_z) {       // test instrumentation, as in the plain kernel
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k)
+                        if (valid[k]) P.rec_z[(size_t)t * N + k * NT + tid] = (double)zz[k];
+                }
+            }
             REAL xn[PPT][NS], lwn[PPT], aux[PPT], sacc[PPT][H];
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {

@@ -266,7 +266,7 @@ struct RegTraits {
     static_assert(!GADDR || 4 * (SLOTS + SLOTS / 32) * 993 < (1 << 23), "GADDR: rel * 993 must fit the 24-bit multiply");
     static constexpr bool LAZYLL = PFG_OPT_LAZYLL && TAB && sizeof(REAL) == 8;
     // LAZYLL in an instantiation without a production twin: tracing the running log-likelihood must not move the flushes
-    static constexpr bool TWINLESS_LL = STRATIFIED || N2 || ADAPTIVE;
+    static constexpr bool TWINLESS_LL = STRATIFIED || N2 || ADAPTIVE || PARIS;
     static constexpr bool PIVOTS = PFG_OPT_PIVOTS && SLOTS == 1024;
     static constexpr bool RAWCAP = MODE == MODE_PARIS && RNG == PFG_RNG_REPLAY;     // PaRIS on the window's raw np.random stream
 

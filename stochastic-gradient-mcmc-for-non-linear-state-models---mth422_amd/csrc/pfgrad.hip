@@ -56,7 +56,7 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
             return bad(PFG_ERR_INVALID, ffbs ? "FFBS latent paths take no warm start or elementwise statistic; stat is score, none or gibbs"
                                              : "the exact Kalman score takes no warm start, elementwise or predictive statistic");
         if (r.x_T || r.logw_T || r.stats_T || (kalman && r.trace_x) || r.trace_logw || r.trace_stats || r.trace_ll || r.trace_anc ||
-            r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats)
+            r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.ew_mean || r.ew_stats || r.trace_paris_J)
             return bad(PFG_ERR_INVALID, ffbs ? "FFBS latent paths have no particles: only the result record and trace_x (the paths)"
                                              : "the exact Kalman score has no particles: only the result record");
         if (ffbs && rng == PFG_RNG_REPLAY && q.T > 0 && !q.z) return bad(PFG_ERR_INVALID, "REPLAY FFBS needs z (T N normals)");
@@ -163,7 +163,7 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
             return bad(PFG_ERR_UNSUPPORTED, "elementwise statistics are built for pf = 'poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2'");
         if (q.stat == PFG_STAT_PREDICTIVE) return bad(PFG_ERR_INVALID, "elementwise statistics do not combine with the predictive statistic");
         if (!r.ew_mean) return bad(PFG_ERR_INVALID, "elementwise needs ew_mean");
-        if (r.trace_x || r.trace_logw || r.trace_stats || r.trace_anc || r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud)
+        if (r.trace_x || r.trace_logw || r.trace_stats || r.trace_anc || r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud || r.trace_paris_J)
             return bad(PFG_ERR_INVALID, "elementwise statistics cannot be combined with trace outputs");
         if ((q.tL < q.T ? q.tL : q.T) - q.t1 < 1) return bad(PFG_ERR_INVALID, "elementwise needs a non-empty window [t1, tL)");
     } else if (r.ew_mean || r.ew_stats) {
@@ -172,6 +172,8 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
     if ((r.rec_u || r.rec_z || r.rec_z0 || r.rec_ud) && (rng != PFG_RNG_DEVICE || !r.trace_x))
         return bad(PFG_ERR_INVALID, "rec_u / rec_z / rec_z0 record the DEVICE generator's draws and need trace_x");
     if (r.trace_anc && !r.trace_x) return bad(PFG_ERR_INVALID, "trace_anc needs trace_x");
+    if (r.trace_paris_J && (!r.trace_x || q.smoother != PFG_SMOOTHER_PARIS))
+        return bad(PFG_ERR_INVALID, "trace_paris_J needs trace_x and pf = 'paris'");
     if ((r.logw_T || r.stats_T) && !r.x_T) return bad(PFG_ERR_INVALID, "logw_T/stats_T need x_T");
     if (!ffbs && (r.trace_logw == nullptr) != (r.trace_x == nullptr)) return bad(PFG_ERR_INVALID, "trace_x and trace_logw go together");
     if (r.trace_stats && !r.trace_x) return bad(PFG_ERR_INVALID, "trace_stats needs trace_x");
@@ -307,6 +309,7 @@ void describe_window(Layout &L, const pfg_problem &q, pfg_result &r, pfg_dev_pro
     L.want(r.trace_stats, d.trace_stats, (T + 1) * N * H);
     L.want(r.trace_ll, d.trace_ll, T + 1);
     L.want(r.trace_anc, d.trace_anc, (TN + 1) / 2, TN * 4);         // int32 pairs in f64 slots
+    if (paris) L.want(r.trace_paris_J, d.trace_paris_J, (TN * q.Ntilde + 1) / 2, TN * q.Ntilde * 4);     // packed int32 likewise
     if (q.elementwise) {
         e.Wd = 3 * (size_t)(tL - q.t1);
         e.Nt = paris ? q.Ntilde : 1;

@@ -86,6 +86,7 @@ class Result(C.Structure):
         ("rec_ud", _dp),
         ("ew_mean", _dp), ("ew_stats", _dp),
         ("paris_consumed", C.c_int64),
+        ("trace_paris_J", C.POINTER(C.c_int32)),
     ]
 
 
@@ -110,7 +111,7 @@ RESULT_DTYPE = np.dtype([
     ("status", "i4"), ("paris_carry_back", "i4"), ("trace_anc", "u8"),
     ("pred", "f8", (MAX_PRED,)),
     ("rec_u", "u8"), ("rec_z", "u8"), ("rec_z0", "u8"), ("rec_ud", "u8"), ("ew_mean", "u8"), ("ew_stats", "u8"),
-    ("paris_consumed", "i8")], align=True)
+    ("paris_consumed", "i8"), ("trace_paris_J", "u8")], align=True)
 assert PROBLEM_DTYPE.itemsize == C.sizeof(Problem) and RESULT_DTYPE.itemsize == C.sizeof(Result)
 assert all(PROBLEM_DTYPE.fields[n][1] == getattr(Problem, n).offset for n, _ in Problem._fields_)
 assert all(RESULT_DTYPE.fields[n][1] == getattr(Result, n).offset for n, _ in Result._fields_)
@@ -537,6 +538,10 @@ class Context:
                 o["all_loglikelihood_estimate"] = np.zeros(T + 1)
                 o["all_ancestors"] = np.zeros((T, N), dtype=np.int32)
                 r.trace_anc = o["all_ancestors"].ctypes.data_as(C.POINTER(C.c_int32))
+                if p.smoother == SMOOTHER["paris"]:
+                    # test instrumentation: the backward-sampled parent of every child and draw (both generators)
+                    o["all_paris_J"] = np.zeros((T, p.Ntilde, N), dtype=np.int32)
+                    r.trace_paris_J = o["all_paris_J"].ctypes.data_as(C.POINTER(C.c_int32))
                 r.trace_x, r.trace_logw = _ptr(o["all_x_t"]), _ptr(o["all_log_weights"])
                 r.trace_ll = _ptr(o["all_loglikelihood_estimate"])
                 if not is_filter:

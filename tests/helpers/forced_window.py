@@ -9,7 +9,13 @@ po.prior_log_density, po.log_normalize, po.score_statistic and po.sufficient_sta
 at a time; nothing of one recomputed step enters the next.  The proposal itself (x_{t+1} from its normal) is NOT checked
 here: that needs the recorded normals.
 
-`ancestor_law_z` is a z-score of one resampling step against the multinomial law."""
+`ancestor_law_z` is a z-score of one resampling step against the multinomial law.
+
+`forced_paris_steps` is the same for a PaRIS window (pf.py:183-258): the statistics of step t + 1 are the reference's rewiring
+mean_j(stats_t[J_ij] + weight_t h(x_t[J_ij], x_{t+1}[i])) over the Ntilde backward-sampled parents J the launch traced.
+The parents themselves cannot be recomputed without the launch's uniforms; `backward_law_scores` tests their LAW: given the
+traced particles and log-weights every J_ij is an independent draw from the exact backward law of child i, whether it left
+an accept-reject round or the categorical fallback."""
 import numpy as np
 
 from oracle import pf_oracle as po
@@ -82,3 +88,96 @@ def ancestor_law_score(all_logw, all_anc):
     zs = [z for z in zs if z is not None]
     assert zs, "no step with varying weights"
     return abs(float(np.sum(zs))) / np.sqrt(len(zs)), len(zs)
+
+
+def forced_paris_step(model, kernel, d, x, logw, stats, anc, J, x_next, y_t, stat, inside, weight_t):
+    """(log-weights, statistics [N, h], log-likelihood increment) of step t + 1 of a PaRIS window from the traced step t.
+
+    As forced_step, with J [N, Ntilde]: the backward-sampled parents of every child (row i: child i).  The rewiring reads
+    the parents' particles and statistics, not their log-weights: logw is taken for symmetry with forced_step only."""
+    x, x_next = np.asarray(x, dtype=np.float64), np.asarray(x_next, dtype=np.float64)
+    stats = np.asarray(stats, dtype=np.float64)
+    N, h = stats.shape
+    J = np.asarray(J).reshape(N, -1)
+    Ntilde = J.shape[1]
+    y_t = np.asarray(y_t, dtype=np.float64).reshape(1)
+    new_logw = po.kernel_reweight(model, kernel, d, x[np.asarray(anc)], x_next, y_t)
+    flat = J.reshape(-1)                        # row i * Ntilde + j: child i, draw j
+    child = np.repeat(np.arange(N), Ntilde)
+    if inside and stat == "score":
+        add = po.score_statistic(model, d, x[flat], x_next[child], y_t)
+    elif inside and stat == "suff":
+        add = po.sufficient_statistic(model, x[flat], x_next[child])
+    else:
+        add = np.zeros((N * Ntilde, h))
+    add = add[:, :h] * float(weight_t)
+    new_stats = np.mean(np.reshape(stats[flat] + add, (N, Ntilde, h)), axis=1)
+    dll = float(weight_t) * np.log(np.mean(np.exp(new_logw))) if inside else 0.0
+    return new_logw, new_stats, dll
+
+
+def forced_paris_steps(model, kernel, theta, y, all_x, all_logw, all_stats, all_anc, all_J, stat="score", t1=0, tL=None,
+                       weights=None):
+    """forced_paris_step for t = 0 .. T - 1 on a PaRIS window's trace (as forced_steps; all_J [T, N, Ntilde]) ->
+    (log-weights [T, N], statistics [T, N, h], log-likelihood increments [T]); entry t is what the trace must hold at
+    t + 1.  Every step starts from the trace: nothing of one recomputed step enters the next."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    T = y.shape[0]
+    tL = T if tL is None else tL
+    d = po.derived(model, theta)
+    lws, sts, dlls = [], [], []
+    for t in range(T):
+        inside = t1 <= t < tL
+        wt = float(weights[t - t1]) if inside and weights is not None else 1.0
+        lw, st, dll = forced_paris_step(model, kernel, d, all_x[t], all_logw[t], all_stats[t], all_anc[t], all_J[t],
+                                        all_x[t + 1], y[t], stat, inside, wt)
+        lws.append(lw); sts.append(st); dlls.append(dll)
+    return np.array(lws), np.array(sts), np.array(dlls)
+
+
+def backward_law(model, d, x, logw, x_next):
+    """beta [N children, N parents]: row i is the exact backward law of child i,
+    log_normalize(logw + prior_log_density(x -> x_next[i])) (pf.py:226-236, :329-338)."""
+    x, x_next = np.asarray(x, dtype=np.float64), np.asarray(x_next, dtype=np.float64)
+    logw = np.asarray(logw, dtype=np.float64)
+    N = x.shape[0]
+    parent = np.tile(np.arange(N), N)           # row i * N + k: child i, parent k
+    child = np.repeat(np.arange(N), N)
+    lb = logw[None, :] + np.reshape(po.prior_log_density(model, d, x[parent], x_next[child]), (N, N))
+    b = np.exp(lb - np.max(lb, axis=1, keepdims=True))
+    return b / np.sum(b, axis=1, keepdims=True)
+
+
+def backward_law_scores(model, d, all_x, all_logw, all_J):
+    """(Z_p, Z_x, #terms) of a PaRIS trace against the exact backward law; all_J [T, N, Ntilde].
+
+    Given the traced particles and log-weights, J_ij of step t is a draw from beta_i = backward_law(...)[i], independent
+    over (t, i, j).  With f(k) = beta_i(k), f(J) has mean sum_k beta_i(k)^2 and variance sum beta^3 - (sum beta^2)^2; with
+    f(k) = x_t[k, 0] -- the conditional mean the score is carried through -- the mean is sum_k beta_i(k) x_t[k, 0] and the
+    variance Var_beta(x).  The centred sums over all (t, j, i), divided by the root of the summed variances,
+        Z_p = sum (beta_i[J] - sum_k beta_i(k)^2) / sqrt(sum (sum beta^3 - (sum beta^2)^2))
+        Z_x = sum (x_t[J, 0] - sum_k beta_i(k) x_t[k, 0]) / sqrt(sum Var_beta(x))
+    are asymptotically N(0, 1).  A term whose variance vanishes in either sum (beta_i uniform or a point mass, all
+    parents equal) is constant and enters neither; #terms counts the rest."""
+    all_J = np.asarray(all_J)
+    T, N, Ntilde = all_J.shape
+    num_p = num_x = var_p = var_x = 0.0
+    terms = 0
+    for t in range(T):
+        beta = backward_law(model, d, all_x[t], all_logw[t], all_x[t + 1])
+        xk = np.asarray(all_x[t], dtype=np.float64)[:, 0]
+        s2, s3 = np.sum(beta ** 2, axis=1), np.sum(beta ** 3, axis=1)
+        vp = s3 - s2 ** 2
+        mx = beta @ xk
+        vx = beta @ (xk ** 2) - mx ** 2
+        ok = (vp > 1e-12 * s2 ** 2) & (vx > 1e-12 * np.maximum(beta @ (xk ** 2), 1e-300))
+        rows = np.arange(N)
+        for j in range(Ntilde):
+            Jj = all_J[t][:, j]
+            num_p += np.sum((beta[rows, Jj] - s2)[ok])
+            num_x += np.sum((xk[Jj] - mx)[ok])
+        var_p += Ntilde * np.sum(vp[ok])
+        var_x += Ntilde * np.sum(vx[ok])
+        terms += Ntilde * int(np.sum(ok))
+    assert terms > 0, "no term with a varying backward law"
+    return float(num_p / np.sqrt(var_p)), float(num_x / np.sqrt(var_x)), terms

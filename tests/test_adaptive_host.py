@@ -153,14 +153,16 @@ def test_resolve_settings_adaptive_refusals():
             resolve("svm", np.zeros(40), svm, num_chains=2, N=100, ess_threshold=tau)
 
 
-def test_header_and_binding_agree_on_the_flag_and_the_abi_is_unchanged():
+def test_header_and_binding_agree_on_the_flag_and_the_abi_only_grew_at_the_end():
     src = open(os.path.join(ROOT, "include", "pfgrad.h")).read()
     m = re.search(r"#define\s+PFG_FLAG_ADAPTIVE_RESAMPLING\s+(\d+)u", src)
     assert m and int(m.group(1)) == 16 == _capi.FLAG_ADAPTIVE_RESAMPLING
     assert re.search(r"int\s+pfg_launch_device_adaptive\s*\(", src) and "pfg_launch_device_adaptive" in _capi.EXPORTS
-    # no new smoother id, no version bump, the same struct sizes; the threshold sits where `reserved` sat
+    # no new smoother id, the same problem / descriptor sizes; the threshold sits where `reserved` sat.  (The flag came
+    # without a version bump, at 125; 126 is pfg_result.trace_paris_J, appended behind everything that was there.)
     assert sorted(_capi.SMOOTHER.values()) == list(range(9))
-    assert re.search(r"#define\s+PFG_VERSION\s+125\b", src)
+    assert re.search(r"#define\s+PFG_VERSION\s+126\b", src)
+    assert _capi.Result.trace_paris_J.offset == _capi.Result.paris_consumed.offset + 8 == C.sizeof(_capi.Result) - 8
     assert _capi.DEV_PROBLEM_DTYPE.itemsize == 376 and _capi.PROBLEM_DTYPE.itemsize == C.sizeof(_capi.Problem)
     assert _capi.Problem.reserved.offset == _capi.Problem.flags.offset + 4 == _capi.PROBLEM_DTYPE.fields["reserved"][1]
     assert _capi.Problem.reserved.size == 4 and _capi.Problem.lambduh.offset == _capi.Problem.flags.offset + 8

@@ -36,7 +36,7 @@ def test_binding_struct_sizes_version_and_grid_scratch():
     to the Python mirror of its layout on both sides of every tile-class and coarse-stride boundary.  (The REPLAY layout
     reserves min(16384, ceil(N / 64)) coarse entries, so the sizes above 2^20 are those of a layout monotone in N.)"""
     lib = _capi.load_library()          # asserts the struct sizes against pfg_struct_size()
-    assert lib.pfg_version() == 125
+    assert lib.pfg_version() == 126
     assert lib.pfg_struct_size(2) == _capi.DEV_PROBLEM_DTYPE.itemsize == 376
     assert lib.pfg_struct_size(99) == -1
     assert lib.pfg_variant_name(0, 0, 0, 1, 1000) == b"wg256x4s"

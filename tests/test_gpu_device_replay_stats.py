@@ -18,8 +18,8 @@ lambduh = 0.9 (branch 2) and the filter.  Then three f32 teacher-forced cases, a
 windows: pfg_run_batch must plan the general kernel for them (the score-only `_score1` twins answer any other window with
 NaNs) and every window must equal itself run alone, bit for bit.
 
-Not covered: PaRIS on the device generator.  Its backward draws are not recorded, and recording them needs a new
-descriptor field.  The O(N^2) units are in tests/test_gpu_n2_device_replay.py."""
+PaRIS on the device generator is in tests/test_gpu_paris_device_replay.py (replayed from the backward parents its traced
+launch returns), the O(N^2) units are in tests/test_gpu_n2_device_replay.py."""
 import os
 import sys
 

@@ -15,28 +15,35 @@ def _series(model, T, seed=5):
     return GEN[model](T=T, parameters=default_params(model))["observations"]
 
 
-@pytest.mark.parametrize("model,dtype", [("svm", "f64"), ("garch", "f64"), ("lgssm", "f32")])
-def test_one_step_equals_run_batch(model, dtype):
+@pytest.mark.parametrize("model,dtype,accept_reject", [pytest.param("svm", "f64", True, id="svm-f64"),
+                                                       pytest.param("garch", "f64", True, id="garch-f64"),
+                                                       pytest.param("lgssm", "f32", True, id="lgssm-f32"),
+                                                       pytest.param("svm", "f64", False, id="svm-f64-exact")])
+def test_one_step_equals_run_batch(model, dtype, accept_reject):
     """Every chain's out record after one step is what ctx.run_batch computes for the same descriptors (device
-    generator, the ensemble's seed, stream = global chain id, step 0), bit for bit."""
+    generator, the ensemble's seed, stream = global chain id, step 0), bit for bit.  accept_reject=False: no
+    accept-reject round, every backward draw of every child is the device's exact categorical draw
+    (max_accept_reject = 0; what that draw returns is checked in tests/test_gpu_paris_device_replay.py)."""
     from sgmcmc_ssm_amd import _capi
     from sgmcmc_ssm_amd.ensemble import ChainEnsemble
     from sgmcmc_ssm_amd.particle_filters import make_problem
     T, C, N = 50, 96, 100
     y = _series(model, T)
     p = default_params(model)
-    ens = ChainEnsemble(model, y, p, num_chains=C, N=N, pf="paris", epsilon=1e-4, dtype=dtype, seed=21, chain_offset=7)
+    ens = ChainEnsemble(model, y, p, num_chains=C, N=N, pf="paris", epsilon=1e-4, dtype=dtype, seed=21, chain_offset=7,
+                        accept_reject=accept_reject)
     ens.step(1)
     ens.synchronize()
     assert ens.ctx.last_variant() == "paris64x2"
     g, ll = ens.last_gradient_statistics()
     d = ens._desc[0]
     assert int(d["smoother"]) == _capi.SMOOTHER["paris"] and d["lambduh"] == 1.0
-    assert int(d["Ntilde"]) == 2 and int(d["max_accept_reject"]) == 64
+    assert int(d["Ntilde"]) == 2 and int(d["max_accept_reject"]) == (64 if accept_reject else 0)
     probs = [make_problem(model, ens.kernel, "paris", y.reshape(-1), p.theta(), N, prior_mean=float(d["prior_mean"]),
                           prior_var=float(d["prior_var"]), flags=int(d["flags"]), dtype=dtype, seed=21, stream=7 + c,
-                          rng="device")
+                          rng="device", accept_reject=accept_reject)
              for c in range(C)]
+    assert probs[0]["max_accept_reject"] == (64 if accept_reject else 0) and int(probs[0].get("flags", 0)) == int(d["flags"])
     outs = ens.ctx.run_batch(probs)
     assert ens.ctx.last_variant() == "paris64x2"
     np.testing.assert_array_equal(g, np.array([o["mean_stat"] for o in outs]))

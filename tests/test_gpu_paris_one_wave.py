@@ -59,6 +59,8 @@ def test_one_wave_pool_parity(ctx, force_one_wave, model, kernel, N, Ntilde, R):
     assert ctx.last_variant() == "paris64x2"
     np.testing.assert_allclose(o["all_x_t"], ref["all_x_t"], rtol=RTOL, atol=ATOL)
     np.testing.assert_allclose(o["all_log_weights"], ref["all_log_weights"], rtol=RTOL, atol=ATOL)
+    # the traced backward parents (REPLAY hands them back too): the oracle's, draw for draw
+    assert np.array_equal(np.transpose(o["all_paris_J"], (0, 2, 1)), ref["all_paris_J"])
     np.testing.assert_allclose(o["all_statistics"], ref["all_statistics"], rtol=RTOL, atol=1e-8)
     np.testing.assert_allclose(o["mean_stat"], ref["mean_statistic"], rtol=RTOL, atol=1e-8)
     assert abs(o["loglik"] - ref["loglikelihood_estimate"]) <= ATOL + RTOL * abs(ref["loglikelihood_estimate"])

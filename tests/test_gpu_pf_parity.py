@@ -335,6 +335,13 @@ _REFUSALS = [
     ("svm", 1, dict(rec_u=16), _INV, "problem 1: rec_u / rec_z / rec_z0 record the DEVICE generator's draws and need trace_x"),
     ("device", 1, dict(rec_z0=8), _INV, "problem 1: rec_u / rec_z / rec_z0 record the DEVICE generator's draws and need trace_x"),
     ("svm", 1, dict(trace_anc=16), _INV, "problem 1: trace_anc needs trace_x"),
+    # the traced backward parents [T][Ntilde][N]: with trace_x, of a PaRIS window, and not beside the elementwise pass
+    # (which owns the buffer as a work piece)
+    ("paris_device", 1, dict(trace_paris_J=32), _INV, "problem 1: trace_paris_J needs trace_x and pf = 'paris'"),
+    ("svm", 1, dict(trace_x=24, trace_logw=24, trace_paris_J=32), _INV, "problem 1: trace_paris_J needs trace_x and pf = 'paris'"),
+    ("paris_device", 1, dict(elementwise=1, ew_mean=6, trace_paris_J=32), _INV,
+     "problem 1: elementwise statistics cannot be combined with trace outputs"),
+    ("kalman", 1, dict(trace_paris_J=32), _INV, "problem 1: the exact Kalman score has no particles"),
     ("svm", 1, dict(stats_T=24), _INV, "problem 1: logw_T/stats_T need x_T"),
     ("svm", 1, dict(trace_x=24), _INV, "problem 1: trace_x and trace_logw go together"),
     ("svm", 1, dict(trace_stats=72), _INV, "problem 1: trace_stats needs trace_x"),
