@@ -2,6 +2,7 @@
 // (pfg_inst_*.hip), each of which instantiates launch_mkr for one (model, proposal kernel, generator).
 // They map a LaunchPlan (make_plan in pfg_plan.hip) onto an instantiation and choose nothing themselves.
 #pragma once
+#include <mutex>
 #include "pfg_host.hpp"
 #include "pfg_device.hpp"
 
@@ -84,11 +85,38 @@ inline int launch_kernel(pfg_ctx *ctx, pf_kernel_t kern, int nt, const LaunchPla
 // (The launchers below reference their kernels in a fixed order, which is the order the kernels take in the code
 // object; the compiler's register allocation has been seen to depend on it.)
 
+// The exp table in device memory (pfg::ExpTabMem<TAG>, read by the RegTraits::TABMEM kernels of this unit) is filled ONCE per
+// device and process, by the first launch that needs it: the fill kernel goes onto that launch's stream and the host waits
+// for it there before it marks the device, so the table is complete before any reader is enqueued on any stream -- and, as
+// nothing writes it again, it never changes under a running kernel.  A stream that is being captured cannot be waited on:
+// the first TABMEM launch of a device must be an eager one (ChainEnsemble runs an eager step before it captures).
+template <int TAG>
+int ensure_exp_tab_mem(pfg_ctx *ctx, hipStream_t st) {
+    static std::mutex mu;
+    static std::vector<char> filled;
+    std::lock_guard<std::mutex> lock(mu);
+    if ((size_t)ctx->device < filled.size() && filled[(size_t)ctx->device]) return PFG_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    PFG_HIP(ctx, hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(ctx, PFG_ERR_INVALID, "the first launch of this kernel on a device fills its exp table and cannot be captured: run one eager launch first");
+    hipLaunchKernelGGL(pfg::exp_tab_mem_fill_kernel<TAG>, dim3(1), dim3(pfg::TAB_E2_ACC), 0, st);
+    PFG_HIP(ctx, hipGetLastError());
+    PFG_HIP(ctx, hipStreamSynchronize(st));
+    if (filled.size() <= (size_t)ctx->device) filled.resize((size_t)ctx->device + 1, 0);
+    filled[(size_t)ctx->device] = 1;
+    return PFG_OK;
+}
+
 // an LDS-resident kernel; traced = the descriptors may carry trace_* / rec_* buffers: the TRACE = true instantiation,
 // otherwise the twin with the trace instrumentation compiled out (device generator: what bench.py times; REPLAY: the
 // drop-in Sampler's launch)
 template <int MODEL, int KERNEL, typename REAL, int NT, int PPT, int RNG, bool PP, int MODE, bool TRACE = true, bool SCORE1 = false>
 int launch_one_t(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
+    using TR = pfg::RegTraits<MODEL, KERNEL, REAL, NT, PPT, RNG, PP, MODE>;
+    if constexpr (TR::TABMEM) {
+        if (const int rc = ensure_exp_tab_mem<TR::EXPTAB_TAG>(ctx, st)) return rc;
+    }
     return launch_kernel(ctx, pfg::pf_reg_kernel<MODEL, KERNEL, REAL, NT, PPT, RNG, PP, MODE, TRACE, SCORE1>, NT, p, B, dp, st);
 }
 template <int MODEL, int KERNEL, typename REAL, int NT, int PPT, int RNG, bool PP>

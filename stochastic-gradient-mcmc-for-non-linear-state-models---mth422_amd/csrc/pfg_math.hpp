@@ -230,7 +230,20 @@ struct TabF64 {
     const double *e2;
     const double2 *lg;
     const double2 *sc;
+    gptr<const double> e2g;     // a copy of e2[0 .. 128) in global memory (ExpTabMem); set by the kernels that read it, see exp_tab_hot
 };
+
+// The 128 doubles 2^(j/128) once more, in device memory: 1 KB that every CU keeps in its vector L1.  A kernel whose LDS
+// pipe is the busy one reads its hot table entries from here (global_load_dwordx2, scalar base + 32-bit lane offset) and
+// leaves LDS and the lgkmcnt queue to the CDF and the particle records (RegTraits::TABMEM).  A static member of a
+// template: only a unit that instantiates such a kernel carries the array (TAG = the unit's model and proposal kernel),
+// and that unit fills it (pfg_launch.hpp, ensure_exp_tab_mem) with tab_fill's own expression before the first reader runs.
+template <int TAG> struct ExpTabMem { static __device__ double e2[TAB_E2_ACC]; };
+template <int TAG> __device__ double ExpTabMem<TAG>::e2[TAB_E2_ACC];
+template <int TAG> __global__ void exp_tab_mem_fill_kernel() {
+    const int j = (int)threadIdx.x;
+    if (j < TAB_E2_ACC) ExpTabMem<TAG>::e2[j] = exp2((double)j * (1.0 / TAB_E2_ACC));
+}
 
 __device__ inline void tab_fill(double *mem, bool with_rng, int tid, int nthreads) {
     double *lg = mem + TAB_E2, *sc = lg + 2 * TAB_LG;
@@ -290,6 +303,50 @@ __device__ __forceinline__ double exp_tab(double x, const double *__restrict__ e
     return ldexp(fma(t, p, t), k >> 7);
 #endif
 }
+
+#if defined(PFG_FAST_ALGEBRA) && PFG_TAB_E2_FAST == 128
+#define PFG_HAS_EXP_HOT 1
+// exp_tab's 128-entry cubic form for the hot lookups of pf_reg_kernel's STALE instantiations (phase B and the particle
+// step: eight per lane-timestep), by the bits of HOT (RegTraits::HOT_B / HOT_G):
+//   PFG_HOT_MEM    the table entry comes from t.e2g (ExpTabMem) instead of LDS: the same 128 doubles, so the value is bit for
+//                  bit exp_tab's;
+//   PFG_HOT_MAGIC  the reduction  kd = rint(x c), k = (int)kd  (three fp64-class instructions) as  s = fma(x, c, 1.5 * 2^52),
+//                  kd = s - 1.5 * 2^52, k = low word of s  (two).  |x c| < 2^31 is the caller's to guarantee (finite and
+//                  moderate, or clamped: the fmax of the non-FINITE form stays in front).  The fma rounds x c once, to an
+//                  integer; rint rounds the ROUNDED product: where that lands on a half-integer exactly the two can pick
+//                  neighbouring k -- both valid reductions (|r| <= ln2/256 + 1 ulp), the results then differ by the cubic's
+//                  error (tests/test_exp_magic_host.py);
+//   PFG_HOT_LANE   knock-out (timing / counters only, NOT a valid exp): the entry of the lane's own index -- a conflict-free
+//                  read -- while the real index is kept alive (PFG_EXP_TABLANE).
+enum { PFG_HOT_MEM = 1, PFG_HOT_MAGIC = 2, PFG_HOT_LANE = 4 };
+template <bool FINITE, int HOT>
+__device__ __forceinline__ double exp_tab_hot(double x, const TabF64 &t) {
+    if (!FINITE) x = fmax(x, -1000.0);
+    double kd;
+    int k;
+    if constexpr ((HOT & PFG_HOT_MAGIC) != 0) {
+        const double s = fma(x, 184.6649652337873, 0x1.8p52);        // 128/ln2
+        kd = s - 0x1.8p52;
+        k = __double2loint(s);
+    } else {
+        kd = rint(x * 184.6649652337873);
+        k = (int)kd;
+    }
+    const double r = fma(kd, -0.0054152123481245725, x);             // ln2/128
+    uint32_t j = (uint32_t)k & 127u;
+    if constexpr ((HOT & PFG_HOT_LANE) != 0) {
+        asm volatile("" :: "v"(j));
+        j = threadIdx.x & 127u;
+    }
+    double tv;
+    if constexpr ((HOT & PFG_HOT_MEM) != 0) tv = t.e2g[j];
+    else tv = t.e2[j];
+    double p = fma(r, 0.16666666666666666, 0.5);
+    p = fma(p, r, 1.0);
+    p = p * r;
+    return ldexp(fma(tv, p, tv), k >> 7);
+}
+#endif
 
 // the <= 2 ulp form whatever the unit's flags (the whole-GPU window builds its resampling CDF with it also in the
 // device-generator units: at N = 10^5 .. 10^6 the 3e-12 of the cubic form above would flip ancestors between the kernel
@@ -351,6 +408,15 @@ template <> struct Math<double, true> {
     __device__ __forceinline__ double exp_acc(double x) const { return exp_tab_acc(x, t.e2); }
 #ifdef PFG_FAST_ALGEBRA
     __device__ __forceinline__ double exp_finite(double x) const { return exp_tab<true>(x, t.e2); }
+#ifdef PFG_HAS_EXP_HOT
+    // the hot lookups of the STALE kernels (HOT = 0: exp / exp_finite themselves), see exp_tab_hot
+    template <int HOT> __device__ __forceinline__ double exp_hot(double x) const {
+        if constexpr (HOT == 0) return exp_tab(x, t.e2); else return exp_tab_hot<false, HOT>(x, t);
+    }
+    template <int HOT> __device__ __forceinline__ double exp_finite_hot(double x) const {
+        if constexpr (HOT == 0) return exp_tab<true>(x, t.e2); else return exp_tab_hot<true, HOT>(x, t);
+    }
+#endif
 #else
     __device__ __forceinline__ double exp_finite(double x) const { return exp_tab(x, t.e2); }
 #endif

@@ -229,7 +229,9 @@ __device__ __forceinline__ void particle_step(const Consts<REAL> &c, const MATH 
 //   PFG_STEP_RAWSCORE   (STAT = score) add[] comes out as the RAW factors {e, z, xp} of the three sums r0 += (w y^2) e, r1 += (w z) z,
 //                       r2 += (w z) xp (RegTraits::RAWSCORE; raw_score_in / raw_score_out map them from / to the score's scale).
 //                       pf_reg_kernel sets the bit for the children block of a raw window's statistic steps alone.
-enum { PFG_STEP_SHIFTFOLD = 1, PFG_STEP_SCOREDZ = 2, PFG_STEP_RAWSCORE = 4 };
+//   PFG_STEP_HOT        (three bits from PFG_STEP_HOT_SHIFT on) how exp(-x1) reads its table entry and reduces its argument: the
+//                       PFG_HOT_* bits of exp_tab_hot (RegTraits::HOT_G).
+enum { PFG_STEP_SHIFTFOLD = 1, PFG_STEP_SCOREDZ = 2, PFG_STEP_RAWSCORE = 4, PFG_STEP_HOT_SHIFT = 4, PFG_STEP_HOT = 7 << PFG_STEP_HOT_SHIFT };
 // the SVM score from the raw sums (r[0..2], Cw = the sum of the window weights added so far) and back (Cw = 0)
 template <typename REAL>
 __device__ __forceinline__ void raw_score_out(const Consts<REAL> &c, REAL Cw, const REAL *r, REAL *s) {
@@ -250,7 +252,12 @@ __device__ __forceinline__ void particle_step_svm_tuned(const Consts<REAL> &c, c
     const REAL half = (REAL)0.5;
     const REAL dz = c.iLQinv * z;
     const REAL x1 = (TUNE & PFG_STEP_SCOREDZ) ? fma(c.A, xp[0], dz) : c.iLQinv * z + xp[0] * c.A;
+#ifdef PFG_HAS_EXP_HOT
+    constexpr int HOT = (TUNE & PFG_STEP_HOT) >> PFG_STEP_HOT_SHIFT;
+    const REAL e = mth.template exp_finite_hot<HOT>(-x1);          // x1 is finite
+#else
     const REAL e = mth.exp_finite(-x1);          // x1 is finite
+#endif
     const REAL y2 = y * y;
     if (TUNE & PFG_STEP_SHIFTFOLD) {
         const REAL ke = (-half * y2) * c.Rinv;

@@ -101,6 +101,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
     mth.t.e2 = tabmem;
     mth.t.lg = reinterpret_cast<const double2 *>(tabmem + TAB_E2);
     mth.t.sc = reinterpret_cast<const double2 *>(tabmem + TAB_E2 + 2 * TAB_LG);
+    if constexpr (TR::TABMEM) mth.t.e2g = (gptr<const double>)ExpTabMem<TR::EXPTAB_TAG>::e2;
     if (tab_bytes<REAL, RNG, TR::TAB>() > 0) tab_fill(tabmem, RNG == PFG_RNG_DEVICE, tid, NT);
     if (TR::FAST && !TR::BLK) {
 #pragma unroll
@@ -362,7 +363,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
         const bool needS = needS_every || (t == T);
         double cs[PPT];
 #pragma unroll
-        for (int k = 0; k < PPT; ++k) cs[k] = (double)mth.exp(TR::SHIFTFOLD ? lw[k] : (REAL)(lw[k] - (REAL)m));   // exp(-inf) = 0
+        for (int k = 0; k < PPT; ++k) {
+            const REAL a = TR::SHIFTFOLD ? lw[k] : (REAL)(lw[k] - (REAL)m);
+            if constexpr (TR::HOT_B != 0) cs[k] = (double)mth.template exp_hot<TR::HOT_B>(a);      // (STALE: REAL is double)
+            else cs[k] = (double)mth.exp(a);                                                        // exp(-inf) = 0
+        }
         if (needS) {
             PFG_MARK("cold needS")
 #pragma unroll

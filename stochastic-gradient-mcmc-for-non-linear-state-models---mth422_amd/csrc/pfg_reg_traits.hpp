@@ -138,6 +138,23 @@ namespace pfg {
 #ifndef PFG_OPT_RAWSCORE
 #define PFG_OPT_RAWSCORE 1
 #endif
+//  The eight hot exp of a lane-timestep (the same two STALE instantiations: four in phase B, four in the particle step of phase G), each
+//  one ds_read_b64 of e2[k & 127] at a per-lane random index -- 128 entries fold onto 32 bank pairs, so the 32 lanes the LDS serves at
+//  a time collide like 32 balls in 32 bins.  What they cost is measured with PFG_EXP_TABLANE (profiles/r08_lds_table_split.txt).
+//  PFG_OPT_EXPTABMEM   (TABMEM_B = bit 0, TABMEM_G = bit 1; 3 = both) those lookups read a copy of the table in global memory
+//                  (pfg::ExpTabMem: 1 KB that lives in the CU's vector L1) with global_load_dwordx2, scalar base + 32-bit lane offset:
+//                  they leave the LDS array and the lgkmcnt queue for the idle vector-memory pipe and wait on vmcnt.  The same 128
+//                  doubles and the same instructions on them: outputs are bitwise the LDS form's.  The LDS copy stays for the cold
+//                  paths (prologue, stale-shift retry, log-likelihood flush).
+//  PFG_OPT_EXPMAGIC    (EXPMAGIC) the same lookups reduce their argument with the magic-number form (exp_tab_hot, PFG_HOT_MAGIC): two
+//                  fp64-class instructions instead of three per exp, and the table address one instruction earlier.
+//  A/B, gates and verdicts: profiles/r08_ab_exp_table.txt.
+#ifndef PFG_OPT_EXPTABMEM
+#define PFG_OPT_EXPTABMEM 0
+#endif
+#ifndef PFG_OPT_EXPMAGIC
+#define PFG_OPT_EXPMAGIC 1
+#endif
 // PFG_OPT_N2SKIP (the O(N^2) instantiations, MODE_N2): the backward sweep over all parents is skipped on the steps before t1 of a
 // window that starts without init_stats -- its result there is +0.0 exactly, see n2_slots.  -DPFG_OPT_N2SKIP=0 runs every sweep (A/B).
 #ifndef PFG_OPT_N2SKIP
@@ -154,8 +171,15 @@ namespace pfg {
 // A/B experiment switches (diagnostic builds only; default = production):
 //  PFG_EXP_PLAIN      compile the filter / lambda != 1 / no-statistic cases out (Poyiadjis O(N) score only)
 //  PFG_EXP_OWNGATHER  knock-out: every child gathers its own slot (pf_reg_kernel, phase E); no GADDR then
+//  PFG_EXP_TABLANE    knock-out: the eight hot exp of the STALE kernels read table entry (tid & 127) -- conflict-free -- instead of
+//                     (k & 127); the real index is kept alive, the VALU work is unchanged (NOT a valid sampler; PFG_BENCH_KNOCKOUT)
 #ifndef PFG_EXP_PLAIN
 #define PFG_EXP_PLAIN 0
+#endif
+#ifdef PFG_EXP_TABLANE
+#define PFG_TABLANE_ON 1
+#else
+#define PFG_TABLANE_ON 0
 #endif
 #ifdef PFG_EXP_OWNGATHER
 #define PFG_GATHERADDR_ON 0
@@ -255,7 +279,19 @@ struct RegTraits {
     static constexpr bool SUMSHIFT = PFG_OPT_SUMSHIFT && STALE, SHIFTFOLD = PFG_OPT_SHIFTFOLD && STALE, SCOREDZ = PFG_OPT_SCOREDZ && STALE;
     // RAWSCORE: the score of a raw window as raw sums, see PFG_OPT_RAWSCORE
     static constexpr bool RAWSCORE = PFG_OPT_RAWSCORE && STALE;
-    static constexpr int STEP_TUNE = (SHIFTFOLD ? PFG_STEP_SHIFTFOLD : 0) | (SCOREDZ ? PFG_STEP_SCOREDZ : 0) | (RAWSCORE ? PFG_STEP_RAWSCORE : 0);
+    // the hot table lookups of phase B / of the particle step (phase G), see PFG_OPT_EXPTABMEM, PFG_OPT_EXPMAGIC, PFG_EXP_TABLANE: HOT_x = exp_tab_hot's bits
+#ifdef PFG_HAS_EXP_HOT
+    static constexpr bool TABMEM_B = (PFG_OPT_EXPTABMEM & 1) && STALE, TABMEM_G = (PFG_OPT_EXPTABMEM & 2) && STALE, EXPMAGIC = PFG_OPT_EXPMAGIC && STALE;
+    static constexpr int HOT_COMMON = (EXPMAGIC ? PFG_HOT_MAGIC : 0) | ((PFG_TABLANE_ON && STALE) ? PFG_HOT_LANE : 0);
+    static constexpr int HOT_B = HOT_COMMON | (TABMEM_B ? PFG_HOT_MEM : 0), HOT_G = HOT_COMMON | (TABMEM_G ? PFG_HOT_MEM : 0);
+#else
+    static constexpr bool TABMEM_B = false, TABMEM_G = false, EXPMAGIC = false;
+    static constexpr int HOT_B = 0, HOT_G = 0;
+#endif
+    static constexpr bool TABMEM = TABMEM_B || TABMEM_G;        // the instantiation reads pfg::ExpTabMem<EXPTAB_TAG>: its launcher fills it first
+    static constexpr int EXPTAB_TAG = MODEL * 16 + KERNEL;
+    static constexpr int STEP_TUNE = (SHIFTFOLD ? PFG_STEP_SHIFTFOLD : 0) | (SCOREDZ ? PFG_STEP_SCOREDZ : 0) | (RAWSCORE ? PFG_STEP_RAWSCORE : 0) |
+                                     (HOT_G << PFG_STEP_HOT_SHIFT);
     // GADDR (256 x 4): search offset -> gather byte address..  rel = 4 x physical CDF position (one pad slot per 32 entries), p4 =
     // rel - 4 (rel * 993 >> 17) = 4 x CDF position p (exact: rel * 993 < 2^23), and (p4 * 1025) & 0x3ff0 = 16 x the particle index
     // ((p & 3) << 8) | (p >> 2): p4 < 2^12, so the copies p4 << 10 and p4 do not overlap -- bits 4..11 of p4 are p >> 2 and bits
