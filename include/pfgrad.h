@@ -57,8 +57,10 @@ enum pfg_kernel { PFG_KERNEL_PRIOR = 0, PFG_KERNEL_OPTIMAL = 1 };
 enum pfg_smoother { PFG_SMOOTHER_NEMETH = 0, PFG_SMOOTHER_FILTER = 1, PFG_SMOOTHER_PARIS = 2,
                     /* EXTENSION (not in the reference, which resamples multinomially every step,
                      * pf.py:26-30): NEMETH with systematic resampling, u_i = (i + u0)/N with ONE
-                     * uniform u0 per timestep.  DEVICE rng, N <= 1024; parity-unpinned, checked
-                     * statistically.  Its own kernel instantiation (keeps the hot path untouched). */
+                     * uniform u0 per timestep (the next word of lane 0's keyed generator).  DEVICE rng, N <= 1024.
+                     * No REPLAY stream (the reference has no such resampler); a traced launch records the uniform of
+                     * every child in rec_ud, from which the oracle replays the search and the whole recursion.
+                     * Its own kernel instantiation (keeps the hot path untouched). */
                     PFG_SMOOTHER_NEMETH_SYSTEMATIC = 3,
                     /* poyiadjis_smoother, the O(N^2) algorithm (pf.py:84-136): every child averages
                      * stats_j + w_t h(x_j, child) over ALL parents j with the backward weights
@@ -271,7 +273,8 @@ typedef struct pfg_result {
     double *rec_z, *rec_z0;
     double *rec_ud;     /* [T*N]: large-N device kernel (pf_big_kernel), whose resampling uniforms are not raw
                            generator words but SORTED uniforms built from exponential spacings: the uniform in
-                           (0,1) child i searched the CDF with at step t (rec_u stays 0 there) */
+                           (0,1) child i searched the CDF with at step t (rec_u stays 0 there); the stratified,
+                           adaptive and systematic instantiations record the uniform of child i the same way */
     /* pfg_problem.elementwise: ew_mean [3 (tL-t1)] = average_statistic of the elementwise run (required);
      * ew_stats [N * 3 (tL-t1)] = its per-particle statistics, row-major (optional) */
     double *ew_mean, *ew_stats;

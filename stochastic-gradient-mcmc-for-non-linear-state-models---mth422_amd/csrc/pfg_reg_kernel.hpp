@@ -634,8 +634,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 ll_W = mine ? W : ll_W;
                 ll_w = mine ? (counts ? wt_prev : 0.0) : ll_w;
                 ll_m = mine ? (float)m : ll_m;          // m is an f32 value
-                // (STRATIFIED, N2: one instantiation serves traced and production launches, so a traced running value must not
-                // move the flushes -- the parked terms are summed for the trace alone and `ll` is bitwise the production one)
+                // (TWINLESS_LL -- STRATIFIED, SYSTEMATIC, N2, ...: one instantiation serves traced and production launches, so a
+                // traced running value must not move the flushes -- the parked terms are summed for the trace alone and `ll` is
+                // bitwise the production one)
                 const bool due = (t & (WAVE - 1)) == WAVE - 1 || t == T;
                 if (due || (!TR::TWINLESS_LL && PFG_TR(P.trace_ll))) {
                     PFG_MARK("cold loglik-flush")
@@ -698,6 +699,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(RegTraits<MO
                 const double u0 = red_W0[0];
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) uu[k] = ((double)(k * NT + tid) + u0) * invN;
+                if (PFG_TR(P.trace_x) && P.rec_ud) {          // test instrumentation, as for STRATIFIED
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k)
+                        if (valid[k]) P.rec_ud[(size_t)t * N + k * NT + tid] = uu[k];
+                }
             } else if (TR::STRATIFIED) {
                 // extension: child r = k NT + tid searches with (r + U_r) / N, U_r from the lane that owns it
 #pragma unroll

@@ -301,8 +301,9 @@ struct RegTraits {
     static constexpr bool GADDR = PFG_GATHERADDR_ON && BLK && PAIRED && NT == 256 && PPT == 4 && MODEL == PFG_MODEL_SVM && !PP;
     static_assert(!GADDR || 4 * (SLOTS + SLOTS / 32) * 993 < (1 << 23), "GADDR: rel * 993 must fit the 24-bit multiply");
     static constexpr bool LAZYLL = PFG_OPT_LAZYLL && TAB && sizeof(REAL) == 8;
-    // LAZYLL in an instantiation without a production twin: tracing the running log-likelihood must not move the flushes
-    static constexpr bool TWINLESS_LL = STRATIFIED || N2 || ADAPTIVE || PARIS;
+    // LAZYLL in an instantiation without a production twin (systematic included: its one TRACE = true instantiation serves
+    // production launches too): tracing the running log-likelihood must not move the flushes
+    static constexpr bool TWINLESS_LL = STRATIFIED || N2 || ADAPTIVE || PARIS || SYSTEMATIC;
     static constexpr bool PIVOTS = PFG_OPT_PIVOTS && SLOTS == 1024;
     static constexpr bool RAWCAP = MODE == MODE_PARIS && RNG == PFG_RNG_REPLAY;     // PaRIS on the window's raw np.random stream
 

@@ -80,7 +80,8 @@ class ChainEnsemble(object):
       subsequence_length S / buffer_length B: -1 = full sequence (no window sampling)
       dtype: 'f64' | 'f32' particle-state arithmetic;  seed: Philox key
       chain_offset: global index of this rank's first chain (keeps streams distinct across GPUs)
-      resampling: 'multinomial' (the reference's) | 'systematic' (extension, parity-unpinned, N <= 1024) |
+      resampling: 'multinomial' (the reference's) | 'systematic' (extension, N <= 1024: no REPLAY stream -- the reference has no
+               such resampler --, the kernel is replayed on the CPU from the draws a traced launch records) |
                'stratified' (extension: child r of a step resamples with (r + U_r) / N, one uniform per child -- the
                score's variance falls to 0.2-0.5 of the multinomial one at the same N; pf 'poyiadjis_N' | 'nemeth',
                kind 'pf', N <= 16384, every path those serve: single- and multi-window, host and device windows, graphs)

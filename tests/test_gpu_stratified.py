@@ -128,6 +128,7 @@ def test_replay_parity_at_the_maximum(ctx):
 # 4. recorded-draw replay of the DEVICE instantiations
 # ---------------------------------------------------------------------------------------------------------------------
 DRTOL, DATOL = 1e-8, 1e-8       # test_gpu_device_replay.py
+DSTAT_ATOL = 1e-7               # per-particle statistics and their weighted mean, same test
 
 DEVICE_CASES = [
     # model, kernel, lambduh, N, T, window, variant
@@ -181,8 +182,8 @@ def test_device_kernel_replayed_by_oracle(ctx, case):
     np.testing.assert_allclose(o["all_x_t"], ref["all_x_t"], rtol=DRTOL, atol=DATOL)
     np.testing.assert_allclose(o["all_log_weights"], ref["all_log_weights"], rtol=DRTOL, atol=DATOL)
     np.testing.assert_allclose(o["all_loglikelihood_estimate"], ref["all_loglikelihood_estimate"], rtol=DRTOL, atol=DATOL)
-    np.testing.assert_allclose(o["all_statistics"], ref["all_statistics"], rtol=DRTOL, atol=1e-7)
-    np.testing.assert_allclose(o["mean_stat"], ref["mean_statistic"], rtol=DRTOL, atol=1e-7)
+    np.testing.assert_allclose(o["all_statistics"], ref["all_statistics"], rtol=DRTOL, atol=DSTAT_ATOL)
+    np.testing.assert_allclose(o["mean_stat"], ref["mean_statistic"], rtol=DRTOL, atol=DSTAT_ATOL)
     np.testing.assert_allclose(o["loglik"], ref["loglikelihood_estimate"], rtol=DRTOL, atol=DATOL)
 
 
@@ -295,9 +296,10 @@ def _ensemble_series(model, T, seed=5):
     return GEN[model](T=T, parameters=default_params(model))["observations"].reshape(-1)
 
 
-def _hand_built(ens, y_host, theta_rows, step, pf, lam):
+def _hand_built(ens, y_host, theta_rows, step, pf, lam, resampling="stratified", smoother=SM):
     """ctx.run_batch of the descriptors the ensemble's latest step ran: the windows the device wrote, the chains'
-    parameters before the step, (seed, stream, step) as the resident launch keys its generator."""
+    parameters before the step, (seed, stream, step) as the resident launch keys its generator.  `resampling` / `smoother`:
+    what make_problem is asked for and the smoother it and the descriptors must then name."""
     d, yoff, woff, seq_len = device_windows.ensemble_windows(ens) if ens._multi else \
         device_windows.decode(ens.desc_dev, ens.y_dev.data_ptr(), ens.weights_dev.data_ptr()) + (None,)
     wtab = ens.weights_dev.cpu().numpy().reshape(-1)
@@ -310,8 +312,8 @@ def _hand_built(ens, y_host, theta_rows, step, pf, lam):
         q = particle_filters.make_problem(ens.model, ens.kernel, pf, y_host[yoff[i]:yoff[i] + T], theta_rows[i // per], ens.N,
                                           t1=t1, tL=tL, weights=w, prior_mean=float(d["prior_mean"][i]),
                                           prior_var=float(d["prior_var"][i]), flags=int(d["flags"][i]), dtype=ens.dtype,
-                                          rng="device", seed=ens.seed, stream=int(d["stream"][i]), resampling="stratified", **kw)
-        assert q["smoother"] == SM and int(d["smoother"][i]) == 8
+                                          rng="device", seed=ens.seed, stream=int(d["stream"][i]), resampling=resampling, **kw)
+        assert q["smoother"] == smoother and int(d["smoother"][i]) == _capi.SMOOTHER[smoother]
         q["step"] = step
         probs.append(q)
     outs = ens.ctx.run_batch(probs)
@@ -322,7 +324,7 @@ def _hand_built(ens, y_host, theta_rows, step, pf, lam):
     return recs, seq_len
 
 
-def _three_steps_equal_hand_built(ens, y_host, pf, lam, variant):
+def _three_steps_equal_hand_built(ens, y_host, pf, lam, variant, resampling="stratified", smoother=SM):
     h = _capi.STAT_DIM[ens.model]
     for step in range(3):
         before = ens.theta()
@@ -330,7 +332,7 @@ def _three_steps_equal_hand_built(ens, y_host, pf, lam, variant):
         ens.synchronize()
         assert ens.ctx.last_variant() == variant
         g, ll = ens.last_gradient_statistics()
-        recs, seq_len = _hand_built(ens, y_host, before, step, pf, lam)
+        recs, seq_len = _hand_built(ens, y_host, before, step, pf, lam, resampling, smoother)
         assert ens.ctx.last_variant() == variant
         if ens._multi:
             win, _ = ens.window_statistics()
