@@ -108,12 +108,10 @@ enum class Family {
     None,
     Reg,           // LDS-resident kernel, entry (nt, ppt, pp)
     Paris, N2,     // its PaRIS / O(N^2) Poyiadjis instantiations, 256 x ppt or one wave (64 x 2); nt = MEM_NT: the large-N kernel's PaRIS one
-    Systematic,    // its systematic-resampling instantiation (device generator), 256 x 4
-    Stratified,    // stratified resampling (PFG_SMOOTHER_NEMETH_STRATIFIED), three size classes: the LDS-resident 256 x 4
-                   // instantiation (n_max <= 1024; np2 = 0), above it the large-N kernel's twin (REPLAY; lw4: N <= 4096) or
-                   // the fast large-N kernel's twin (device generator, np2 slots)
-    Adaptive,      // ESS-triggered resampling (PFG_FLAG_ADAPTIVE_RESAMPLING), the same three size classes as Stratified: the
-                   // 256 x 4 LDS-resident instantiation, the large-N kernel's twin (REPLAY) or the fast large-N kernel's (device)
+    Systematic, Stratified, Adaptive,  // the twins of a resampling scheme other than multinomial (Scheme below, one row of
+                   // kSchemes in pfg_plan.hip each), in up to three size classes: the LDS-resident 256 x 4 instantiation
+                   // (n_max <= 1024; np2 = 0), above it the large-N kernel's twin (REPLAY; lw4: N <= 4096) or the fast
+                   // large-N kernel's twin (device generator, np2 slots)
     Mem,           // large-N kernel (state in an HBM scratch); lw4: N <= 4096, log-weights in registers
     Big,           // large-N kernel, device-generator fast path for np2 particle slots
     Grid,          // whole-GPU window above the one-workgroup kernels' maximum (pfg_grid_kernel.hpp), tile class (ppt, kmax)
@@ -175,11 +173,51 @@ int launch_ffbs(pfg_ctx *ctx, const LaunchPlan &p, int rng, int B, const pfg_dev
 // (N above the one-workgroup kernels, or PFGRAD_VARIANT=grid, runs as whole-GPU windows), pfg_launch_device* (one-workgroup
 // kernels only) and pfg_launch_device_grid* (whole-GPU windows).
 enum class Caller { Query, Batch, Device, Grid };
-// make_plan's `smoother` for a batch of adaptive windows (PFG_FLAG_ADAPTIVE_RESAMPLING): a planner-level id like
-// PFG_SMOOTHER_POYIADJIS_N is a launch-level one, outside the ABI's enum -- the descriptors say NEMETH and carry the flag
-constexpr int kPlanAdaptive = 1000;
-LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B, bool traced,
-                     bool predictive = false, int t_max = 0, int phase = -1, bool elementwise = false);
+// How the windows of a batch resample, as their descriptors (or the launch) state it: a smoother id of its own
+// (systematic, stratified) or NEMETH windows that carry PFG_FLAG_ADAPTIVE_RESAMPLING.  A scheme fills a batch.
+enum class Resampling { Multinomial, Systematic, Stratified, Adaptive };
+inline Resampling resampling_of(int smoother, uint32_t flags) {
+    if (flags & PFG_FLAG_ADAPTIVE_RESAMPLING) return Resampling::Adaptive;
+    return smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC ? Resampling::Systematic
+           : smoother == PFG_SMOOTHER_NEMETH_STRATIFIED ? Resampling::Stratified : Resampling::Multinomial;
+}
+// What is built for a scheme other than multinomial: one row of kSchemes (pfg_plan.hip), read by make_plan and by
+// pfg_run_batch's check_window.  Every scheme is a twin of the NEMETH kernels; a scheme whose n_limit is 1024 has the
+// 256 x 4 unit alone.
+struct Scheme {
+    Family family;
+    const char *what;                   // its name in messages
+    int mode;                           // pfg::MODE_*
+    int n_limit;                        // its largest N
+    const char *limit_note;             // ... and what the refusal above it adds
+    bool device_only;                   // no REPLAY stream to run it from
+    bool no_predictive, no_elementwise; // refuses the predictive statistic / elementwise statistics
+    const char *unit, *big4096, *big16384, *mem;                    // the variant names of its size classes
+    size_t (*unit_lds)(int model, int dtype, int rng, int N);       // 256 x 4: single buffer in fp64, ping-pong in f32
+    size_t (*big_lds)(int model, int dtype, int rng, int np2);
+};
+const Scheme &scheme_of(Resampling r);  // r != Multinomial
+// a smoother id that a launch may state: those of the particle filters, and (kalman) PFG_SMOOTHER_KALMAN / KALMAN_FFBS
+constexpr bool launch_smoother_id(int smoother, bool kalman) {
+    return smoother >= PFG_SMOOTHER_NEMETH && (smoother <= (kalman ? PFG_SMOOTHER_KALMAN_FFBS : PFG_SMOOTHER_POYIADJIS_N) ||
+                                               smoother == PFG_SMOOTHER_NEMETH_STRATIFIED);
+}
+
+// What make_plan is asked: smoother as the dispatcher receives it (PFG_SMOOTHER_POYIADJIS_N states that every window is
+// (NEMETH, lambduh = 1, score)), the scheme beside it; B windows of up to n_max particles.
+struct PlanRequest {
+    Caller caller = Caller::Query;
+    int model = 0, dtype = PFG_F64, rng = PFG_RNG_REPLAY;
+    int smoother = PFG_SMOOTHER_NEMETH;
+    Resampling resampling = Resampling::Multinomial;
+    int n_max = 0;
+    int B = 1 << 30;            // (a query: a large batch, never the latency variant)
+    bool traced = false;        // the descriptors may carry trace_* / rec_* buffers
+    bool predictive = false;    // the windows ask for the predictive statistic
+    int t_max = 0, phase = -1;  // KalmanFfbs: the longest buffer; Grid: the longest window and the phase to launch
+    bool elementwise = false;   // a window of the batch asks for elementwise statistics
+};
+LaunchPlan make_plan(const PlanRequest &r);
 int check_ids(pfg_ctx *ctx, int smoother, int model, int kernel, int dtype, int rng);
 int launch(pfg_ctx *ctx, const LaunchPlan &p, int model, int kernel, int rng, int B, const pfg_dev_problem *dp, hipStream_t st);
 // pfg_run_batch, Family::Grid: what every window of a whole-GPU batch must satisfy; plan.t_max becomes the longest T

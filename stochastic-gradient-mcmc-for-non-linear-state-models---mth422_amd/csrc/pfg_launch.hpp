@@ -171,34 +171,23 @@ int launch_big(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *
     return launch_big_one<MODEL, KERNEL, REAL, 16384>(ctx, p, B, dp, st);
 }
 
-// stratified resampling: the 256 x 4 LDS-resident instantiation (single buffer in fp64, ping-pong in f32, as systematic;
-// one instantiation that honours trace buffers serves traced and production launches), the large-N kernel's twin (REPLAY)
-// or the fast large-N kernel's twin (device generator)
-template <int MODEL, int KERNEL, typename REAL, int RNG>
-int launch_stratified(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
+// a resampling scheme other than multinomial (MODE_SYSTEMATIC / MODE_STRATIFIED / MODE_ADAPTIVE; Scheme in pfg_host.hpp):
+// the 256 x 4 LDS-resident instantiation (single buffer in fp64, ping-pong in f32; one instantiation that honours trace
+// buffers serves traced and production launches) and, where the scheme has them, the twins of the kernels that serve
+// multinomial windows above N = 1024: the large-N kernel's (REPLAY) or the fast large-N kernel's (device generator)
+template <int MODEL, int KERNEL, typename REAL, int RNG, int MODE>
+int launch_scheme(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
+    constexpr bool STRAT = MODE == pfg::MODE_STRATIFIED, ADAPT = MODE == pfg::MODE_ADAPTIVE;
     if (p.np2 == 0 && p.nt == 256)
-        return launch_one_t<MODEL, KERNEL, REAL, 256, 4, RNG, sizeof(REAL) == 4, pfg::MODE_STRATIFIED>(ctx, p, B, dp, st);
-    if constexpr (RNG == PFG_RNG_REPLAY) {
-        if (p.lw4) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, true, false, true>, pfg::MEM_NT, p, B, dp, st);
-        return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, false, false, true>, pfg::MEM_NT, p, B, dp, st);
+        return launch_one_t<MODEL, KERNEL, REAL, 256, 4, RNG, sizeof(REAL) == 4, MODE>(ctx, p, B, dp, st);
+    if constexpr (!STRAT && !ADAPT) {
+        return fail(ctx, PFG_ERR_INVALID, "the launch plan names no kernel of this unit");
+    } else if constexpr (RNG == PFG_RNG_REPLAY) {
+        if (p.lw4) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, /*PARIS*/ false, /*LW4*/ true, /*SCORE1*/ false, STRAT, ADAPT>, pfg::MEM_NT, p, B, dp, st);
+        return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, /*PARIS*/ false, /*LW4*/ false, /*SCORE1*/ false, STRAT, ADAPT>, pfg::MEM_NT, p, B, dp, st);
     } else {
-        if (p.np2 == 4096) return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 4096, true>, pfg::MEM_NT, p, B, dp, st);
-        return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 16384, true>, pfg::MEM_NT, p, B, dp, st);
-    }
-}
-
-// adaptive (ESS-triggered) resampling: the same three size classes, each a twin of the kernel that serves multinomial
-// windows of that size
-template <int MODEL, int KERNEL, typename REAL, int RNG>
-int launch_adaptive(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
-    if (p.np2 == 0 && p.nt == 256)
-        return launch_one_t<MODEL, KERNEL, REAL, 256, 4, RNG, sizeof(REAL) == 4, pfg::MODE_ADAPTIVE>(ctx, p, B, dp, st);
-    if constexpr (RNG == PFG_RNG_REPLAY) {
-        if (p.lw4) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, true, false, false, true>, pfg::MEM_NT, p, B, dp, st);
-        return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, false, false, false, false, true>, pfg::MEM_NT, p, B, dp, st);
-    } else {
-        if (p.np2 == 4096) return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 4096, false, true>, pfg::MEM_NT, p, B, dp, st);
-        return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 16384, false, true>, pfg::MEM_NT, p, B, dp, st);
+        if (p.np2 == 4096) return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 4096, STRAT, ADAPT>, pfg::MEM_NT, p, B, dp, st);
+        return launch_kernel(ctx, pfg::pf_big_kernel<MODEL, KERNEL, REAL, 16384, STRAT, ADAPT>, pfg::MEM_NT, p, B, dp, st);
     }
 }
 
@@ -212,8 +201,8 @@ int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *
     switch (p.family) {
         case Family::Systematic:    // built for the device generator: single buffer in fp64, ping-pong in f32
             if constexpr (dev) {
-                if (p.f64) return launch_one_t<MODEL, KERNEL, double, 256, 4, RNG, false, pfg::MODE_SYSTEMATIC>(ctx, p, B, dp, st);
-                return launch_one_t<MODEL, KERNEL, float, 256, 4, RNG, true, pfg::MODE_SYSTEMATIC>(ctx, p, B, dp, st);
+                if (p.f64) return launch_scheme<MODEL, KERNEL, double, RNG, pfg::MODE_SYSTEMATIC>(ctx, p, B, dp, st);
+                return launch_scheme<MODEL, KERNEL, float, RNG, pfg::MODE_SYSTEMATIC>(ctx, p, B, dp, st);
             }
             break;
         case Family::Big:
@@ -240,9 +229,11 @@ int launch_mkr(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *
             return PFG_GRID_CASE(float);
 #undef PFG_GRID_CASE
         case Family::Stratified:    // (last: the kernels above keep their places in the code object)
-            return p.f64 ? launch_stratified<MODEL, KERNEL, double, RNG>(ctx, p, B, dp, st) : launch_stratified<MODEL, KERNEL, float, RNG>(ctx, p, B, dp, st);
+            return p.f64 ? launch_scheme<MODEL, KERNEL, double, RNG, pfg::MODE_STRATIFIED>(ctx, p, B, dp, st)
+                         : launch_scheme<MODEL, KERNEL, float, RNG, pfg::MODE_STRATIFIED>(ctx, p, B, dp, st);
         case Family::Adaptive:      // (behind Stratified, for the same reason)
-            return p.f64 ? launch_adaptive<MODEL, KERNEL, double, RNG>(ctx, p, B, dp, st) : launch_adaptive<MODEL, KERNEL, float, RNG>(ctx, p, B, dp, st);
+            return p.f64 ? launch_scheme<MODEL, KERNEL, double, RNG, pfg::MODE_ADAPTIVE>(ctx, p, B, dp, st)
+                         : launch_scheme<MODEL, KERNEL, float, RNG, pfg::MODE_ADAPTIVE>(ctx, p, B, dp, st);
         case Family::None:
             break;
     }

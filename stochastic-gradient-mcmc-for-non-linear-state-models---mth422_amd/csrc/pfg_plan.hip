@@ -138,9 +138,32 @@ LaunchPlan refuse(LaunchPlan &p, int rc, std::string msg) {
     return std::move(p);
 }
 
+template <int MODE>
+size_t scheme_big_lds(int model, int dtype, int rng, int np2) {
+    return with_types(model, dtype, rng, [&](auto, auto, auto real, auto) {
+        return pfg::big_kernel_lds_bytes<decltype(real), MODE == pfg::MODE_STRATIFIED, MODE == pfg::MODE_ADAPTIVE>(np2);
+    });
+}
+template <int MODE>
+size_t scheme_unit_lds(int model, int dtype, int rng, int N) {
+    return (dtype == PFG_F64 ? reg_lds<256, 4, false, MODE> : reg_lds<256, 4, true, MODE>)(model, dtype, rng, N);
+}
+const Scheme kSchemes[] = {
+    // the resampling schemes other than multinomial, in the order of Resampling: the fields of Scheme (pfg_host.hpp).
+    // (Systematic windows never ask for the predictive or elementwise statistics: check_window refuses both for the id.)
+    {Family::Systematic, "systematic", pfg::MODE_SYSTEMATIC, 1024, "", true, false, false,
+     "systematic256x4", nullptr, nullptr, nullptr, scheme_unit_lds<pfg::MODE_SYSTEMATIC>, scheme_big_lds<pfg::MODE_SYSTEMATIC>},
+    {Family::Stratified, "stratified", pfg::MODE_STRATIFIED, pfg::MEM_MAX_N, "", false, true, false, "stratified256x4",
+     "big4096_stratified", "big16384_stratified", "mem1024_stratified", scheme_unit_lds<pfg::MODE_STRATIFIED>, scheme_big_lds<pfg::MODE_STRATIFIED>},
+    {Family::Adaptive, "adaptive", pfg::MODE_ADAPTIVE, pfg::MEM_MAX_N, " (no whole-GPU windows)", false, true, true, "adaptive256x4",
+     "big4096_adaptive", "big16384_adaptive", "mem1024_adaptive", scheme_unit_lds<pfg::MODE_ADAPTIVE>, scheme_big_lds<pfg::MODE_ADAPTIVE>},
+};
+
 }  // namespace
 
 namespace pfg_host {
+
+const Scheme &scheme_of(Resampling r) { return kSchemes[(int)r - 1]; }
 
 // Which kernel runs a batch of B windows of up to n_max particles, with what LDS and scratch, under which name.  smoother
 // as the dispatcher receives it: PFG_SMOOTHER_POYIADJIS_N states that every window is (NEMETH, lambduh = 1, score) -- the
@@ -150,8 +173,10 @@ namespace pfg_host {
 // which only the general large-N kernel computes.  elementwise: a window of the batch asks for elementwise statistics (the
 // one-wave O(N^2) variant is not picked for those).  The environment variables PFGRAD_VARIANT, PFGRAD_NO_SCORE1 and
 // PFGRAD_CDF_SINGLE are read here and nowhere else.
-LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B, bool traced,
-                     bool predictive, int t_max, int phase, bool elementwise) {
+LaunchPlan make_plan(const PlanRequest &r) {
+    const Caller caller = r.caller;
+    const int model = r.model, dtype = r.dtype, rng = r.rng, smoother = r.smoother, n_max = r.n_max, B = r.B, t_max = r.t_max, phase = r.phase;
+    const bool traced = r.traced, predictive = r.predictive, elementwise = r.elementwise;
     LaunchPlan p;
     p.f64 = dtype == PFG_F64;
     p.n_max = n_max; p.t_max = t_max; p.phase = phase;
@@ -172,9 +197,7 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
     else if (smoother == PFG_SMOOTHER_KALMAN) p.family = Family::Kalman;
     else if (smoother == PFG_SMOOTHER_KALMAN_FFBS) p.family = Family::KalmanFfbs;
     else if (smoother == PFG_SMOOTHER_PARIS) p.family = Family::Paris;
-    else if (smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC) p.family = Family::Systematic;
-    else if (smoother == PFG_SMOOTHER_NEMETH_STRATIFIED) p.family = Family::Stratified;
-    else if (smoother == kPlanAdaptive) p.family = Family::Adaptive;
+    else if (r.resampling != Resampling::Multinomial) p.family = scheme_of(r.resampling).family;
     else if (smoother == PFG_SMOOTHER_POYIADJIS_N2) p.family = Family::N2;
     else if (predictive && n_max <= pfg::MEM_MAX_N) p.family = Family::Mem;
     else {
@@ -246,62 +269,41 @@ LaunchPlan make_plan(Caller caller, int model, int dtype, int rng, int smoother,
             p.lds = mem_lds();
             break;
         }
-        case Family::Systematic:        // the 256 x 4 default variants of fp64 / f32
-            p.name = "systematic256x4";
-            p.nt = 256; p.ppt = 4; p.pp = !p.f64;
-            if (rng != PFG_RNG_DEVICE) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling needs the DEVICE rng");
-            if (n_max > 1024) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling is built for N <= 1024");
-            p.lds = (p.f64 ? reg_lds<256, 4, false, pfg::MODE_SYSTEMATIC> : reg_lds<256, 4, true, pfg::MODE_SYSTEMATIC>)(model, dtype, rng, n_max);
-            if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, "systematic resampling: state does not fit LDS");
-            break;
+        case Family::Systematic:
         case Family::Stratified:
-            // three size classes, each a twin of the kernel that serves multinomial windows of that size (256 x 4 as
-            // systematic: single buffer in fp64, ping-pong in f32)
-            if (predictive) return refuse(p, PFG_ERR_UNSUPPORTED, "stratified resampling is not built for the predictive statistic");
-            if (n_max > pfg::MEM_MAX_N) return refuse(p, PFG_ERR_UNSUPPORTED, "stratified resampling is built for N <= 16384");
-            if (n_max <= 1024) {
-                p.name = "stratified256x4";
+        case Family::Adaptive: {
+            // a row of kSchemes: up to three size classes, each a twin of the kernel that serves multinomial windows of
+            // that size (256 x 4: single buffer in fp64, ping-pong in f32)
+            const Scheme &s = scheme_of(r.resampling);
+            const std::string what = std::string(s.what) + " resampling";
+            if (predictive && s.no_predictive) return refuse(p, PFG_ERR_UNSUPPORTED, what + " is not built for the predictive statistic");
+            if (elementwise && s.no_elementwise) return refuse(p, PFG_ERR_UNSUPPORTED, what + " is not built for elementwise statistics");
+            // (a scheme that ends with the 256 x 4 unit names it in its refusals too: pfg_last_variant of a refused launch)
+            const bool unit = n_max <= 1024 || s.n_limit <= 1024;
+            if (unit) {
+                p.name = s.unit;
                 p.nt = 256; p.ppt = 4; p.pp = !p.f64;
-                p.lds = (p.f64 ? reg_lds<256, 4, false, pfg::MODE_STRATIFIED> : reg_lds<256, 4, true, pfg::MODE_STRATIFIED>)(model, dtype, rng, n_max);
-                if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, "stratified resampling: state does not fit LDS");
-            } else if (rng == PFG_RNG_DEVICE) {
+            }
+            if (s.device_only && rng != PFG_RNG_DEVICE) return refuse(p, PFG_ERR_UNSUPPORTED, what + " needs the DEVICE rng");
+            if (n_max > s.n_limit) return refuse(p, PFG_ERR_UNSUPPORTED, what + " is built for N <= " + std::to_string(s.n_limit) + s.limit_note);
+            if (unit) {
+                p.lds = s.unit_lds(model, dtype, rng, n_max);
+                if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, what + ": state does not fit LDS");
+                break;
+            }
+            p.nt = pfg::MEM_NT;
+            p.scratch = mem_scratch(false);
+            if (rng == PFG_RNG_DEVICE) {
                 p.np2 = n_max <= 4096 ? 4096 : 16384;
-                p.name = p.np2 == 4096 ? "big4096_stratified" : "big16384_stratified";
-                p.nt = pfg::MEM_NT;
-                p.lds = with_types(model, dtype, rng, [&](auto, auto, auto real, auto) { return pfg::big_kernel_lds_bytes<decltype(real), true>(p.np2); });
-                p.scratch = mem_scratch(false);
+                p.name = p.np2 == 4096 ? s.big4096 : s.big16384;
+                p.lds = s.big_lds(model, dtype, rng, p.np2);
             } else {
                 p.lw4 = n_max <= 4096;
-                p.name = "mem1024_stratified";
-                p.nt = pfg::MEM_NT;
+                p.name = s.mem;
                 p.lds = mem_lds();
-                p.scratch = mem_scratch(false);
             }
             break;
-        case Family::Adaptive:
-            // as Stratified: three size classes, each a twin of the kernel that serves multinomial windows of that size
-            if (predictive) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for the predictive statistic");
-            if (elementwise) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for elementwise statistics");
-            if (n_max > pfg::MEM_MAX_N) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling is built for N <= 16384 (no whole-GPU windows)");
-            if (n_max <= 1024) {
-                p.name = "adaptive256x4";
-                p.nt = 256; p.ppt = 4; p.pp = !p.f64;
-                p.lds = (p.f64 ? reg_lds<256, 4, false, pfg::MODE_ADAPTIVE> : reg_lds<256, 4, true, pfg::MODE_ADAPTIVE>)(model, dtype, rng, n_max);
-                if (p.lds > kLdsLimit) return refuse(p, PFG_ERR_UNSUPPORTED, "adaptive resampling: state does not fit LDS");
-            } else if (rng == PFG_RNG_DEVICE) {
-                p.np2 = n_max <= 4096 ? 4096 : 16384;
-                p.name = p.np2 == 4096 ? "big4096_adaptive" : "big16384_adaptive";
-                p.nt = pfg::MEM_NT;
-                p.lds = with_types(model, dtype, rng, [&](auto, auto, auto real, auto) { return pfg::big_kernel_lds_bytes<decltype(real), false, true>(p.np2); });
-                p.scratch = mem_scratch(false);
-            } else {
-                p.lw4 = n_max <= 4096;
-                p.name = "mem1024_adaptive";
-                p.nt = pfg::MEM_NT;
-                p.lds = mem_lds();
-                p.scratch = mem_scratch(false);
-            }
-            break;
+        }
         case Family::Grid: {
             // every window of the batch must fall into the same tile class; NEMETH / FILTER with the score, sufficient or
             // no statistic
@@ -419,16 +421,24 @@ int check_entry(pfg_ctx *ctx, const char *fn, int B, const pfg_dev_problem *dev_
     return PFG_OK;
 }
 
+// the request of a query (B: a large batch) or entry point that states `smoother` (no flag: see pfg_launch_device_adaptive);
+// what else differs from a query's request is set by name
+PlanRequest request(Caller caller, int model, int dtype, int rng, int smoother, int n_max, int B = 1 << 30) {
+    PlanRequest r;
+    r.caller = caller; r.model = model; r.dtype = dtype; r.rng = rng; r.n_max = n_max; r.B = B;
+    r.smoother = smoother; r.resampling = resampling_of(smoother, 0);
+    return r;
+}
+
 // ... and does once its own arguments are checked
-int dispatch(pfg_ctx *ctx, Caller caller, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
-             const pfg_dev_problem *dp, hipStream_t st, bool traced = false, int t_max = 0, int phase = -1) {
+int dispatch(pfg_ctx *ctx, const PlanRequest &r, int kernel, const pfg_dev_problem *dp, hipStream_t st) {
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = check_ids(ctx, smoother, model, kernel, dtype, rng);
+    const int rc = check_ids(ctx, r.smoother, r.model, kernel, r.dtype, r.rng);
     if (rc) return rc;
-    if (B <= 0) return PFG_OK;
-    if (n_max < 1 && smoother != PFG_SMOOTHER_KALMAN) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
-    if (caller == Caller::Grid && t_max < 0) return fail(ctx, PFG_ERR_INVALID, "T_max must be >= 0");
-    return launch(ctx, make_plan(caller, model, dtype, rng, smoother, n_max, B, traced, false, t_max, phase), model, kernel, rng, B, dp, st);
+    if (r.B <= 0) return PFG_OK;
+    if (r.n_max < 1 && r.smoother != PFG_SMOOTHER_KALMAN) return fail(ctx, PFG_ERR_INVALID, "N must be >= 1");
+    if (r.caller == Caller::Grid && r.t_max < 0) return fail(ctx, PFG_ERR_INVALID, "T_max must be >= 0");
+    return launch(ctx, make_plan(r), r.model, kernel, r.rng, r.B, dp, st);
 }
 
 }  // namespace
@@ -438,56 +448,59 @@ extern "C" {
 // both for a large batch of plain windows: never the latency variant or a twin
 int64_t pfg_scratch_bytes(int model, int dtype, int rng, int N) {
     if (model < 0 || model > 2 || N < 1) return -1;
-    const LaunchPlan p = make_plan(Caller::Query, model, dtype, rng, PFG_SMOOTHER_NEMETH, N, 1 << 30, false);
+    const LaunchPlan p = make_plan(request(Caller::Query, model, dtype, rng, PFG_SMOOTHER_NEMETH, N));
     return p.name ? (int64_t)p.scratch : -1;
 }
 
 int64_t pfg_scratch_bytes_smoother(int model, int dtype, int rng, int smoother, int N) {
-    if (model < 0 || model > 2 || N < 1 || smoother < PFG_SMOOTHER_NEMETH ||
-        (smoother > PFG_SMOOTHER_POYIADJIS_N && smoother != PFG_SMOOTHER_NEMETH_STRATIFIED))
-        return -1;
-    const LaunchPlan p = make_plan(Caller::Device, model, dtype, rng, smoother, N, 1 << 30, false);
+    if (model < 0 || model > 2 || N < 1 || !launch_smoother_id(smoother, false)) return -1;
+    const LaunchPlan p = make_plan(request(Caller::Device, model, dtype, rng, smoother, N));
     return p.rc || !p.name ? -1 : (int64_t)p.scratch;
 }
 
 const char *pfg_variant_name(int model, int kernel, int dtype, int rng, int n_max) {
     (void)kernel;
-    const LaunchPlan p = make_plan(Caller::Query, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, 1 << 30, false);
+    const LaunchPlan p = make_plan(request(Caller::Query, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max));
     return p.name ? p.name : "none";
 }
 
 int pfg_launch_device(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int B,
                       const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
-    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B, dev_probs, (hipStream_t)hip_stream);
+    return dispatch(ctx, request(Caller::Device, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B), kernel, dev_probs, (hipStream_t)hip_stream);
 }
 
 int pfg_launch_device_traced(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max, int B,
                              const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
-    if (smoother < PFG_SMOOTHER_NEMETH || (smoother > PFG_SMOOTHER_POYIADJIS_N && smoother != PFG_SMOOTHER_NEMETH_STRATIFIED))
-        return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
-    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream, true);
+    if (!launch_smoother_id(smoother, false)) return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
+    PlanRequest r = request(Caller::Device, model, dtype, rng, smoother, n_max, B);
+    r.traced = true;
+    return dispatch(ctx, r, kernel, dev_probs, (hipStream_t)hip_stream);
 }
 
 int pfg_launch_device_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max,
                                int B, const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
-    if (smoother < PFG_SMOOTHER_NEMETH || smoother > PFG_SMOOTHER_NEMETH_STRATIFIED)
-        return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
-    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream);
+    if (!launch_smoother_id(smoother, true)) return fail(ctx, PFG_ERR_INVALID, "Unrecognized pf (smoother id)");
+    return dispatch(ctx, request(Caller::Device, model, dtype, rng, smoother, n_max, B), kernel, dev_probs, (hipStream_t)hip_stream);
 }
 
+// NEMETH windows whose descriptors carry PFG_FLAG_ADAPTIVE_RESAMPLING: the launch states the scheme
 int pfg_launch_device_adaptive(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int B,
                                const pfg_dev_problem *dev_probs, void *hip_stream, int traced) {
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
-    return dispatch(ctx, Caller::Device, model, kernel, dtype, rng, kPlanAdaptive, n_max, B, dev_probs, (hipStream_t)hip_stream, traced != 0);
+    PlanRequest r = request(Caller::Device, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B);
+    r.resampling = Resampling::Adaptive; r.traced = traced != 0;
+    return dispatch(ctx, r, kernel, dev_probs, (hipStream_t)hip_stream);
 }
 
 int pfg_launch_device_grid(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int T_max, int B,
                            const pfg_dev_problem *dev_probs, void *hip_stream) {
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
-    return dispatch(ctx, Caller::Grid, model, kernel, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B, dev_probs, (hipStream_t)hip_stream, true, T_max);
+    PlanRequest r = request(Caller::Grid, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B);
+    r.traced = true; r.t_max = T_max;
+    return dispatch(ctx, r, kernel, dev_probs, (hipStream_t)hip_stream);
 }
 
 int pfg_launch_device_grid_smoother(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int smoother, int n_max, int T_max,
@@ -496,8 +509,9 @@ int pfg_launch_device_grid_smoother(pfg_ctx *ctx, int model, int kernel, int dty
     if (smoother != PFG_SMOOTHER_NEMETH && smoother != PFG_SMOOTHER_FILTER && smoother != PFG_SMOOTHER_POYIADJIS_N)
         return fail(ctx, PFG_ERR_UNSUPPORTED, "whole-GPU windows are built for NEMETH / FILTER / POYIADJIS_N");
     if (phase < PFG_GRID_PHASE_FINISH) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_grid_smoother: phase must be PFG_GRID_PHASE_ALL, a timestep >= 0, PFG_GRID_PHASE_INIT or PFG_GRID_PHASE_FINISH");
-    return dispatch(ctx, Caller::Grid, model, kernel, dtype, rng, smoother, n_max, B, dev_probs, (hipStream_t)hip_stream, true,
-                    phase == PFG_GRID_PHASE_ALL ? T_max : 0, phase);
+    PlanRequest r = request(Caller::Grid, model, dtype, rng, smoother, n_max, B);
+    r.traced = true; r.t_max = phase == PFG_GRID_PHASE_ALL ? T_max : 0; r.phase = phase;
+    return dispatch(ctx, r, kernel, dev_probs, (hipStream_t)hip_stream);
 }
 
 int pfg_launch_device_grid_phase(pfg_ctx *ctx, int model, int kernel, int dtype, int rng, int n_max, int phase, int B,
@@ -505,7 +519,9 @@ int pfg_launch_device_grid_phase(pfg_ctx *ctx, int model, int kernel, int dtype,
     if (const int rc = check_entry(ctx, __func__, B, dev_probs)) return rc;
     if (phase < PFG_GRID_PHASE_FINISH) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_grid_phase: phase must be a timestep >= 0, PFG_GRID_PHASE_INIT or PFG_GRID_PHASE_FINISH");
     if (phase == -1) return fail(ctx, PFG_ERR_INVALID, "pfg_launch_device_grid_phase: use pfg_launch_device_grid for the whole window");
-    return dispatch(ctx, Caller::Grid, model, kernel, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B, dev_probs, (hipStream_t)hip_stream, true, 0, phase);
+    PlanRequest r = request(Caller::Grid, model, dtype, rng, PFG_SMOOTHER_NEMETH, n_max, B);
+    r.traced = true; r.phase = phase;
+    return dispatch(ctx, r, kernel, dev_probs, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

@@ -33,6 +33,16 @@ bool host_registered(const void *p, size_t bytes) {
 int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const pfg_problem &first, int b) {
     const std::string id = "problem " + std::to_string(b) + ": ";
     auto bad = [&](int code, const char *msg) { return fail(ctx, code, id + msg); };
+    // what a resampling scheme refuses, from its row of kSchemes (pfg_plan.hip); the recursions a scheme has no kernel for
+    // are named (its id or flag says NEMETH)
+    const Scheme &systematic = scheme_of(Resampling::Systematic), &stratified = scheme_of(Resampling::Stratified);
+    auto unbuilt = [&](const Scheme &s, const std::string &rest) { return fail(ctx, PFG_ERR_UNSUPPORTED, id + s.what + " resampling " + rest); };
+    auto above = [](const Scheme &s) { return "is built for N <= " + std::to_string(s.n_limit) + s.limit_note; };
+    auto not_nemeth = [&](const Scheme &s, int smoother) -> int {
+        const char *pf = smoother == PFG_SMOOTHER_FILTER ? "filter" : smoother == PFG_SMOOTHER_PARIS ? "paris"
+                         : smoother == PFG_SMOOTHER_POYIADJIS_N2 ? "poyiadjis_N2" : nullptr;
+        return pf ? unbuilt(s, std::string("is built for the NEMETH recursion, not pf = '") + pf + "'") : PFG_OK;
+    };
     const int model = first.model, dtype = first.dtype, rng = first.rng;
     const bool kalman = first.smoother == PFG_SMOOTHER_KALMAN;     // the exact score: no particles, no streams
     const bool ffbs = first.smoother == PFG_SMOOTHER_KALMAN_FFBS;  // FFBS paths: N paths, REPLAY normals in z only
@@ -68,24 +78,20 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
     if (adaptive != ((first.flags & PFG_FLAG_ADAPTIVE_RESAMPLING) != 0))
         return bad(PFG_ERR_INVALID, "adaptive resampling (PFG_FLAG_ADAPTIVE_RESAMPLING) cannot share a batch with windows that resample at every step");
     if (adaptive) {
-        if (q.smoother == PFG_SMOOTHER_FILTER) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for the NEMETH recursion, not pf = 'filter'");
-        if (q.smoother == PFG_SMOOTHER_PARIS) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for the NEMETH recursion, not pf = 'paris'");
-        if (q.smoother == PFG_SMOOTHER_POYIADJIS_N2) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for the NEMETH recursion, not pf = 'poyiadjis_N2'");
+        const Scheme &s = scheme_of(Resampling::Adaptive);
+        if (const int rc = not_nemeth(s, q.smoother)) return rc;
         if (q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC || q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED)
             return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for multinomial draws, not systematic or stratified ones");
         if (q.smoother != PFG_SMOOTHER_NEMETH) return bad(PFG_ERR_INVALID, "adaptive resampling needs a particle filter (smoother NEMETH)");
-        if (q.stat == PFG_STAT_PREDICTIVE) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for the predictive statistic");
-        if (q.elementwise) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is not built for elementwise statistics");
-        if (q.N > pfg::MEM_MAX_N) return bad(PFG_ERR_UNSUPPORTED, "adaptive resampling is built for N <= 16384 (no whole-GPU windows)");
+        if (s.no_predictive && q.stat == PFG_STAT_PREDICTIVE) return unbuilt(s, "is not built for the predictive statistic");
+        if (s.no_elementwise && q.elementwise) return unbuilt(s, "is not built for elementwise statistics");
+        if (q.N > s.n_limit) return unbuilt(s, above(s));
         const float tau = pfg::ess_threshold_of(q.reserved);
         if (!(tau > 0.0f && tau <= 1.0f)) return bad(PFG_ERR_INVALID, "ess_threshold must be in (0, 1]");
     }
     if (mixed(PFG_SMOOTHER_NEMETH_STRATIFIED)) {
         // the id says NEMETH: the recursions it has no kernel for are named, any other mix is a caller's error
-        const int other = q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED ? first.smoother : q.smoother;
-        if (other == PFG_SMOOTHER_FILTER) return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for the NEMETH recursion, not pf = 'filter'");
-        if (other == PFG_SMOOTHER_PARIS) return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for the NEMETH recursion, not pf = 'paris'");
-        if (other == PFG_SMOOTHER_POYIADJIS_N2) return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for the NEMETH recursion, not pf = 'poyiadjis_N2'");
+        if (const int rc = not_nemeth(stratified, q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED ? first.smoother : q.smoother)) return rc;
         return bad(PFG_ERR_INVALID, "stratified resampling cannot share a batch with other smoothers");
     }
     if (mixed(PFG_SMOOTHER_POYIADJIS_N2)) return bad(PFG_ERR_INVALID, "pf = 'poyiadjis_N2' cannot share a batch with other smoothers");
@@ -126,8 +132,8 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
     }
     if ((q.stat < PFG_STAT_SCORE || q.stat > PFG_STAT_PREDICTIVE) && !(ffbs && q.stat == PFG_STAT_GIBBS))
         return bad(PFG_ERR_INVALID, "bad stat id");
-    if (q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED && q.stat == PFG_STAT_PREDICTIVE)
-        return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is not built for the predictive statistic");
+    if (q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED && stratified.no_predictive && q.stat == PFG_STAT_PREDICTIVE)
+        return unbuilt(stratified, "is not built for the predictive statistic");
     if ((q.stat == PFG_STAT_PREDICTIVE) != (first.stat == PFG_STAT_PREDICTIVE))
         return bad(PFG_ERR_INVALID, "the predictive statistic cannot share a batch with others");
     if (q.stat == PFG_STAT_PREDICTIVE) {
@@ -147,10 +153,9 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
     if (q.init_x && !q.init_logw) return bad(PFG_ERR_INVALID, "init_x needs init_logw");
     if (mixed(PFG_SMOOTHER_NEMETH_SYSTEMATIC))
         return bad(PFG_ERR_INVALID, "systematic resampling cannot share a batch with other smoothers");
-    if (q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC && (rng != PFG_RNG_DEVICE || q.N > 1024))
-        return bad(PFG_ERR_UNSUPPORTED, "systematic resampling needs the DEVICE rng and N <= 1024");
-    if (q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED && q.N > pfg::MEM_MAX_N)
-        return bad(PFG_ERR_UNSUPPORTED, "stratified resampling is built for N <= 16384");
+    if (q.smoother == PFG_SMOOTHER_NEMETH_SYSTEMATIC && (rng != PFG_RNG_DEVICE || q.N > systematic.n_limit))
+        return unbuilt(systematic, "needs the DEVICE rng and N <= " + std::to_string(systematic.n_limit));
+    if (q.smoother == PFG_SMOOTHER_NEMETH_STRATIFIED && q.N > stratified.n_limit) return unbuilt(stratified, above(stratified));
     if (!(q.prior_var >= 0.0) && !(q.flags & PFG_FLAG_GARCH_STATIONARY_PRIOR) && !q.init_x)
         return bad(PFG_ERR_INVALID, "prior_var must be >= 0");
     if (model == PFG_MODEL_SVM && std::fabs(q.theta[0]) > 1.0) {
@@ -181,10 +186,12 @@ int check_window(pfg_ctx *ctx, const pfg_problem &q, const pfg_result &r, const 
 }
 
 // What the plan needs of a valid batch: the longest window (Kalman: of steps [t1, tL), else of particles), the longest
-// FFBS buffer, whether any window records a trajectory or asks for elementwise statistics, and the smoother to plan for.
-struct BatchSummary { int n_max = 0, t_max = 0; bool traced = false, elementwise = false; int smoother = PFG_SMOOTHER_NEMETH; };
-BatchSummary summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
-    BatchSummary s;
+// FFBS buffer, whether any window records a trajectory or asks for elementwise statistics, and the smoother and
+// resampling scheme to plan for.
+PlanRequest summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
+    PlanRequest s;
+    s.caller = Caller::Batch; s.model = ps[0].model; s.dtype = ps[0].dtype; s.rng = ps[0].rng; s.B = B;
+    s.predictive = ps[0].stat == PFG_STAT_PREDICTIVE;   // large-N kernel only (any N)
     bool score1 = true;         // every window the Poyiadjis O(N) score: units with a twin specialised to it run that
     for (int b = 0; b < B; ++b) {
         const pfg_problem &q = ps[b];
@@ -198,10 +205,9 @@ BatchSummary summarize(int B, const pfg_problem *ps, const pfg_result *rs) {
     }
     // the smoothers with kernels of their own fill whole batches; the rest run the plain kernels
     const int s0 = ps[0].smoother;
-    if (ps[0].flags & PFG_FLAG_ADAPTIVE_RESAMPLING)        // (NEMETH windows, checked: their own kernels)
-        s.smoother = kPlanAdaptive;
-    else if (s0 == PFG_SMOOTHER_PARIS || s0 == PFG_SMOOTHER_NEMETH_SYSTEMATIC || s0 == PFG_SMOOTHER_POYIADJIS_N2 ||
-        s0 == PFG_SMOOTHER_KALMAN || s0 == PFG_SMOOTHER_KALMAN_FFBS || s0 == PFG_SMOOTHER_NEMETH_STRATIFIED)
+    s.resampling = resampling_of(s0, ps[0].flags);
+    if (s.resampling != Resampling::Multinomial || s0 == PFG_SMOOTHER_PARIS || s0 == PFG_SMOOTHER_POYIADJIS_N2 ||
+        s0 == PFG_SMOOTHER_KALMAN || s0 == PFG_SMOOTHER_KALMAN_FFBS)     // (adaptive: NEMETH windows, checked)
         s.smoother = s0;
     else if (score1 && !s.traced)
         s.smoother = PFG_SMOOTHER_POYIADJIS_N;
@@ -441,9 +447,9 @@ int pfg_run_batch(pfg_ctx *ctx, int B, const pfg_problem *ps, pfg_result *rs) {
     if (rc) return rc;
 
     // ---- plan ---------------------------------------------------------------------------
-    const BatchSummary sum = summarize(B, ps, rs);
-    const bool predictive = ps[0].stat == PFG_STAT_PREDICTIVE;   // large-N kernel only (any N)
-    LaunchPlan plan = make_plan(Caller::Batch, model, dtype, rng, sum.smoother, sum.n_max, B, sum.traced, predictive, sum.t_max, -1, sum.elementwise);
+    const PlanRequest sum = summarize(B, ps, rs);
+    const bool predictive = sum.predictive;
+    LaunchPlan plan = make_plan(sum);
     if (plan.rc && !plan.name) return fail(ctx, plan.rc, plan.err);
     if (plan.family == Family::Grid && (rc = check_grid_batch(ctx, plan, B, ps))) return rc;
     // every window of the batch gets n_max-sized state (the predictive statistic's buffers after it)

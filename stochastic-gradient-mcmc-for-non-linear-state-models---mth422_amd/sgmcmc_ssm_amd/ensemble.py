@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from .particle_filters import resolve_resampling
 from .sgmcmc_sampler import random_subsequence_and_weights
 
 _MODELS = {}
@@ -289,22 +290,9 @@ class ChainEnsemble(object):
         ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
         'pmmh')."""
         tau = None
-        if ess_threshold is not None and ess_threshold != 0:
-            # adaptive resampling (extension, include/pfgrad.h): what it is not built for is refused by name
-            tau = float(ess_threshold)
-            if not 0.0 < tau <= 1.0:
-                raise ValueError("ess_threshold must be in (0, 1] (None or 0: resample at every step), got {0}".format(ess_threshold))
-            if kind != "pf" or sampler == "gibbs":
-                raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
-            if pf not in ("poyiadjis_N", "nemeth"):
-                raise NotImplementedError("adaptive resampling (ess_threshold) is built for pf = 'poyiadjis_N' | 'nemeth', "
-                                          "got pf = '{0}'".format(pf))
-            if resampling != "multinomial":
-                raise NotImplementedError("adaptive resampling (ess_threshold) is built for resampling='multinomial', "
-                                          "got '{0}'".format(resampling))
-            if int(N) > 16384:
-                raise NotImplementedError("adaptive resampling (ess_threshold) is built for N <= 16384 "
-                                          "(no whole-GPU windows), got N = {0}".format(int(N)))
+        if ess_threshold is not None and ess_threshold != 0 and (kind != "pf" or sampler == "gibbs"):
+            # (what else adaptive resampling is not built for: resolve_resampling, below)
+            raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
         if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh"):
             raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'gibbs' or 'pmmh'")
         scale = None
@@ -372,6 +360,12 @@ class ChainEnsemble(object):
         max_accept_reject = 0 if not accept_reject else (64 if max_accept_reject is None else max(0, int(max_accept_reject)))
         # which smoother runs: the one decision the descriptors, the launch and the scratch sizing follow
         lam, paris = 1.0, {}
+        if kind == "pf":
+            # the resampling scheme of a NEMETH window (particle_filters.SCHEMES); the other smoothers say below what they
+            # make of `resampling`, and only the threshold is judged for them
+            own = pf in ("poyiadjis_N", "nemeth")
+            nemeth, _, tau = resolve_resampling("nemeth" if own else pf, pf, resampling if own else "multinomial",
+                                                ess_threshold, N)
         if kind != "pf":
             if pf == "paris":
                 raise ValueError("pf='paris' needs kind='pf'")
@@ -405,17 +399,7 @@ class ChainEnsemble(object):
         elif pf in ("poyiadjis_N", "nemeth"):
             if pf == "nemeth":
                 lam = 0.95 if lambduh is None else float(lambduh)
-            smoother = "nemeth"
-            if resampling == "systematic":       # extension, see include/pfgrad.h
-                if N > 1024:
-                    raise NotImplementedError("systematic resampling is built for N <= 1024")
-                smoother = "nemeth_systematic"
-            elif resampling == "stratified":     # extension, see include/pfgrad.h
-                if N > 16384:
-                    raise NotImplementedError("stratified resampling is built for N <= 16384")
-                smoother = "nemeth_stratified"
-            elif resampling != "multinomial":
-                raise ValueError("Unrecognized resampling = {0}".format(resampling))
+            smoother = nemeth           # 'nemeth', or what its resampling scheme makes of it
         else:
             raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2', got {0}".format(pf))
         # every chain the Poyiadjis O(N) score (NEMETH, lambduh = 1, score): units with a twin specialised to it run that
@@ -513,19 +497,16 @@ class ChainEnsemble(object):
         if self._smoother == "kalman_ffbs":
             # the forward messages of the longest buffer: a window and its two buffers, or the whole series
             return _capi.kalman_scratch_bytes(min(self.T, self.S + 2 * self.B) if self.S > 0 else self.T)
-        if self.ess_threshold:
-            # adaptive windows: 0 for N <= 1024, the large-N twins' slab up to 16384 (also where plain device-generator
-            # windows would run LDS-resident, 1024 < N <= 4096)
-            sb = self.ctx.scratch_bytes_adaptive(self.model, self.dtype, self.N)
-            if sb < 0:
-                raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(self.N))
-            return sb
-        if self._multi or self._smoother in ("paris", "poyiadjis_n2", "nemeth_stratified"):
+        if self.ess_threshold or self._multi or self._smoother in ("paris", "poyiadjis_n2", "nemeth_stratified"):
             # PaRIS, N <= 1024: 0, the LDS-resident variants keep their state in LDS; above: paris_mem1024's slab.  The
             # single-window PaRIS path (N <= 1024 only) relies on that answer of 0 where it once wrote the literal.
             # The O(N^2) smoother likewise: 0 for N <= 1024, n2_mem1024's slab above it (multi-window path only).
-            # Stratified windows: 0 for N <= 1024, the large-N twin's slab up to 16384
-            sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", self._smoother, self.N)
+            # Stratified and adaptive windows: 0 for N <= 1024, the large-N twins' slab up to 16384 (adaptive: also where
+            # plain device-generator windows would run LDS-resident, 1024 < N <= 4096)
+            if self.ess_threshold:
+                sb = self.ctx.scratch_bytes_adaptive(self.model, self.dtype, self.N)
+            else:
+                sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", self._smoother, self.N)
             if sb < 0:
                 raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(self.N))
             return sb

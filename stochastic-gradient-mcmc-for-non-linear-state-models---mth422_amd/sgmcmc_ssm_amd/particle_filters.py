@@ -16,6 +16,7 @@ RNG modes
 
 There is no NumPy fallback: without libpfgrad.so and an MI355X every entry point raises.
 """
+import collections
 import os
 
 import numpy as np
@@ -42,6 +43,48 @@ def _smoother_of(pf, kwargs):
         kwargs.pop("lambduh", None)
         return "poyiadjis_n2", 1.0
     raise ValueError("Unrecognized pf = {0}".format(pf))
+
+
+# The resampling schemes beside the reference's multinomial one (extensions, include/pfgrad.h), one row each: the mirror
+# of kSchemes in csrc/pfg_plan.hip.  what: the name in messages; smoother, flags: what the descriptors of a NEMETH window
+# say; n_max (+ n_note): the largest N with a kernel; device_only: no REPLAY stream exists; no_predictive: refuses that statistic
+_Scheme = collections.namedtuple("_Scheme", "what smoother flags n_max n_note device_only no_predictive")
+SCHEMES = {
+    # one uniform per timestep
+    "systematic": _Scheme("systematic resampling", "nemeth_systematic", 0, 1024, "", True, False),
+    # child r searches with (r + U_r) / N.  rng='replay': U_r is the stream's u[t][r], drawn exactly as for multinomial
+    # resampling (np.random ends where the multinomial call leaves it); rng='device': the lane's
+    "stratified": _Scheme("stratified resampling", "nemeth_stratified", 0, 16384, "", False, True),
+    # PFG_FLAG_ADAPTIVE_RESAMPLING: resample only when ESS < ess_threshold * N.  rng='replay' draws the streams of a
+    # multinomial window (u[t] of a step that does not resample is ignored), so np.random ends where that call leaves it
+    "adaptive": _Scheme("adaptive resampling (ess_threshold)", "nemeth", _capi.FLAG_ADAPTIVE_RESAMPLING, 16384,
+                        " (no whole-GPU windows)", False, True),
+}
+
+
+def resolve_resampling(smoother, pf, resampling, ess_threshold, N, stat=None, rng=None):
+    """The scheme `resampling` and `ess_threshold` (None or 0: off) ask for on top of the base smoother of `pf` -> (the
+    smoother the descriptors state, their flag bits, the validated threshold or None), or the refusal SCHEMES states."""
+    if resampling not in ("multinomial", "systematic", "stratified"):
+        raise ValueError("Unrecognized resampling = {0}".format(resampling))
+    if rng == "replay" and resampling != "multinomial" and SCHEMES[resampling].device_only:
+        raise ValueError("resampling='{0}' needs rng='device' (no reference stream to replay)".format(resampling))
+    tau = float(ess_threshold) if ess_threshold is not None and ess_threshold != 0 else None
+    if tau is not None and not 0.0 < tau <= 1.0:
+        raise ValueError("ess_threshold must be in (0, 1] (None or 0: resample at every step), got {0}".format(ess_threshold))
+    name = resampling if tau is None else "adaptive"
+    if name == "multinomial":
+        return smoother, 0, None
+    s = SCHEMES[name]
+    if smoother != "nemeth":
+        raise NotImplementedError("{0} is built for pf = 'poyiadjis_N' | 'nemeth', got pf = '{1}'".format(s.what, pf))
+    if name == "adaptive" and resampling != "multinomial":
+        raise NotImplementedError("{0} is built for resampling='multinomial', got '{1}'".format(s.what, resampling))
+    if s.no_predictive and stat == "predictive":
+        raise NotImplementedError("{0} is not built for the predictive statistic".format(s.what))
+    if int(N) > s.n_max:
+        raise NotImplementedError("{0} is built for N <= {1}{2}, got N = {3}".format(s.what, s.n_max, s.n_note, int(N)))
+    return s.smoother, s.flags, tau
 
 
 # Stream buffers are recycled between calls: a fresh 16 MB ndarray costs ~45 ms of first-touch
@@ -235,49 +278,11 @@ def make_problem(model, kernel, pf, observations, theta, N, t1=0, tL=None, weigh
     kwargs = dict(kwargs)
     kwargs.pop("tqdm", None)
     kwargs.pop("tqdm_name", None)
-    resampling = kwargs.pop("resampling", "multinomial")
-    if resampling == "systematic":
-        # extension (the reference only resamples multinomially): one uniform per timestep
-        if rng == "replay":
-            raise ValueError("resampling='systematic' needs rng='device' (no reference stream to replay)")
-    elif resampling not in ("multinomial", "stratified"):
-        raise ValueError("Unrecognized resampling = {0}".format(resampling))
     smoother, lambduh = _smoother_of(pf, kwargs)
-    # extension (include/pfgrad.h, PFG_FLAG_ADAPTIVE_RESAMPLING): resample only when ESS < ess_threshold * N.  None or 0: off,
-    # this function returns what it always has.  rng='replay' draws the streams of a multinomial window below (u[t] of a
-    # step that does not resample is ignored), so np.random ends where the multinomial call leaves it
-    ess_threshold = kwargs.pop("ess_threshold", None)
-    if ess_threshold is not None and ess_threshold != 0:
-        ess_threshold = float(ess_threshold)
-        if not 0.0 < ess_threshold <= 1.0:
-            raise ValueError("ess_threshold must be in (0, 1] (None or 0: resample at every step), got {0}".format(ess_threshold))
-        if smoother != "nemeth":
-            raise NotImplementedError("adaptive resampling (ess_threshold) is built for pf = 'poyiadjis_N' | 'nemeth', "
-                                      "got pf = '{0}'".format(pf))
-        if resampling != "multinomial":
-            raise NotImplementedError("adaptive resampling (ess_threshold) is built for resampling='multinomial', "
-                                      "got '{0}'".format(resampling))
-        if stat == "predictive":
-            raise NotImplementedError("adaptive resampling (ess_threshold) is not built for the predictive statistic")
-        if int(N) > 16384:
-            raise NotImplementedError("adaptive resampling (ess_threshold) is built for N <= 16384 (no whole-GPU windows)")
-        flags = int(flags) | _capi.FLAG_ADAPTIVE_RESAMPLING
-    else:
-        ess_threshold = None
-    if resampling == "systematic":
-        if smoother != "nemeth":
-            raise NotImplementedError("systematic resampling is built for pf = 'poyiadjis_N' | 'nemeth'")
-        smoother = "nemeth_systematic"
-    elif resampling == "stratified":
-        # extension: child r searches with (r + U_r) / N.  rng='replay': U_r is the stream's u[t][r], drawn below exactly
-        # as for multinomial resampling (np.random ends where the multinomial call leaves it); rng='device': the lane's
-        if smoother != "nemeth":
-            raise NotImplementedError("stratified resampling is built for pf = 'poyiadjis_N' | 'nemeth'")
-        if stat == "predictive":
-            raise NotImplementedError("stratified resampling is not built for the predictive statistic")
-        if int(N) > 16384:
-            raise NotImplementedError("stratified resampling is built for N <= 16384")
-        smoother = "nemeth_stratified"
+    # the resampling scheme (SCHEMES; multinomial, ess_threshold None or 0: this function returns what it always has)
+    smoother, scheme_flags, ess_threshold = resolve_resampling(smoother, pf, kwargs.pop("resampling", "multinomial"),
+                                                               kwargs.pop("ess_threshold", None), N, stat=stat, rng=rng)
+    flags = int(flags) | scheme_flags if scheme_flags else flags
     y = np.ascontiguousarray(observations, dtype=float)
     if y.ndim == 2:
         if y.shape[1] != 1:
