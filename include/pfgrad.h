@@ -568,6 +568,41 @@ int pfg_pmmh_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const 
                            const pfg_prior_hyper *hyper, int init, uint64_t seed, uint64_t chain_offset,
                            uint64_t *step_ctr, void *hip_stream);
 
+/* EXTENSION (not in the reference): the particle Metropolis-adjusted Langevin algorithm (Nemeth, Sherlock and Fearnhead
+ * 2016) for B resident chains -- PMMH with a Langevin proposal driven by the filter's own score estimate.  The launch
+ * between the two calls is the SCORE launch on theta_prop: it leaves the score in out[0..3] (score-column order: SVM
+ * [LRinv, LQinv, A], LGSSM [LRinv, LQinv, C, A], GARCH [LRinv, log_mu, logit_phi, logit_lambduh]) and the
+ * log-likelihood estimate of the WHOLE data set in out[4].  Coordinates, support, arrays and the keying of the draws
+ * are those of the PMMH calls above (tags of their own, csrc/pfg_chains.hip).  With s = scale [PFG_MAX_THETA] and
+ *   d_j(theta, g) = grad_logprior_j(theta) + g_j      (the prior gradient pfg_sgld_update_device adds, g mapped from
+ *                                                      score columns to theta coordinates as that call maps it)
+ *
+ * pfg_pmala_propose_device: theta_prop[b]_j = theta[b]_j + (s_j^2 / 2) d_j(theta[b], grad_cur[b]) + s_j z_j, grad_cur
+ * [B][PFG_MAX_THETA] the score the chain's current state was accepted with (LGSSM: C stays 1 and takes no normal).
+ * With s_j^2 / 2 = epsilon / Tscale for every j this is the law of pfg_sgld_update_device's step before
+ * project_parameters.  valid and the treatment of a proposal outside the support: as pfg_pmmh_propose_device.
+ * *step_ctr is read, not incremented.
+ *
+ * pfg_pmala_accept_device: init != 0: ll_cur[b] = out[4], grad_cur[b] = out[0..3], nothing else changes, *step_ctr is
+ * left as it is.  Otherwise, with log q(b | a, g) = -sum_j (b_j - a_j - (s_j^2 / 2) d_j(a, g))^2 / (2 s_j^2) over the
+ * coordinates that move,
+ *   log alpha = (out[4] + logprior(theta_prop)) - (ll_cur + logprior(theta))
+ *               + log q(theta | theta_prop, out[0..3]) - log q(theta_prop | theta, grad_cur),
+ * and chain b accepts iff valid[b], out[4] and every score component the drift uses are finite and log(u) < log alpha
+ * (a NaN rejects): theta[b] = theta_prop[b], ll_cur[b] = out[4], grad_cur[b] = out[0..3] verbatim, n_accept[b] += 1.
+ * A chain that rejects keeps theta, ll_cur AND grad_cur: neither estimate is ever refreshed, which is what makes the
+ * chain exact for every N.  The target is PMMH's, exp(logprior(theta)) p(y | theta) on the raw row: the drift uses
+ * grad_logprior, which is not the gradient of logprior in every coordinate, and need not be -- q is evaluated with the
+ * same drift in both directions.  *step_ctr is incremented afterwards.
+ * A bad model id, B < 0 or a NULL array: PFG_ERR_INVALID (step_ctr may be NULL: counter 0, no increment). */
+int pfg_pmala_propose_device(pfg_ctx *ctx, int model, int B, const double *theta, const double *grad_cur,
+                             double *theta_prop, int32_t *valid, const double *scale, const pfg_prior_hyper *hyper,
+                             uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream);
+int pfg_pmala_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const double *theta_prop,
+                            const int32_t *valid, const double *outs, double *ll_cur, double *grad_cur,
+                            uint64_t *n_accept, const pfg_prior_hyper *hyper, const double *scale, int init,
+                            uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream);
+
 /* Inverse-multiquadric kernel Stein discrepancy of K points x[K][d] with score estimates
  * g[K][d] (HOST pointers, d <= 8): sqrt(sum_{i,j} k0(x_i,x_j)) / K for
  * k(x,y) = (c^2 + |x-y|^2)^(-beta) -- IMQ_KSD of sgmcmc_ssm/trace_metric_functions.py:20-81

@@ -36,6 +36,29 @@
 //            0x504D0003  uniform53(r.x, r.y)   -> u, the accept uniform in (0, 1)
 //          (SVM: z0, z1, z2 for A, LQinv, LRinv; LGSSM: z0, z2, z3 for A, LQinv, LRinv; GARCH: z0..z3 in theta order).
 //          Disjoint from 0x5A11 / 0x5A12, the Gibbs tags 0x61B5vvaa and the window tags 0x53...... / 0x57.......
+//   pmala  particle Metropolis-adjusted Langevin (Nemeth, Sherlock and Fearnhead 2016), two kernels around the SCORE
+//          launch, which leaves the score estimate in out[0..3] and the log-likelihood estimate in out[4].  In PMMH's
+//          coordinates and support, with s_j = scale[j] and the drift of coordinate j
+//            d_j(theta, g) = grad_logprior_j(theta) + g_j       (the prior gradient and the score columns of
+//                                                                sgld_update_kernel: SVM [LR, LQ, A], LGSSM [LR, LQ, C, A],
+//                                                                GARCH [LR, log_mu, logit_phi, logit_lambduh])
+//            propose  theta'_j = (theta_j + (0.5 (s_j s_j)) d_j(theta, grad_cur)) + s_j z_j; LGSSM's C stays 1 (no normal,
+//                     no density term).  Outside the support valid = 0 and theta' = theta, as for pmmh.
+//            accept   log q(b | a, g) = -sum_j (b_j - (a_j + (0.5 (s_j s_j)) d_j(a, g)))^2 / (2 (s_j s_j)) over the free
+//                     coordinates, and
+//                       log alpha = (((out[4] + logprior(theta')) - (ll_cur + logprior(theta)))
+//                                    + log q(theta | theta', out[0..3])) - log q(theta' | theta, grad_cur);
+//                     accepted iff valid, out[4] and every score component the drift uses are finite, and
+//                     log(u) < log alpha (a NaN rejects).  On accept theta = theta', ll_cur = out[4], grad_cur =
+//                     out[0..3] verbatim (score-column order); a chain that rejects keeps theta, ll_cur AND grad_cur:
+//                     neither estimate is ever refreshed, which is what makes the chain exact for every N (the pair
+//                     (ll, g) is the auxiliary variable of the pseudo-marginal argument; the drift may be any function
+//                     of (theta, g) as long as q is evaluated with the same one in both directions).
+//          With (s_j s_j) / 2 = eps / T for every j the proposal is the law of sgld_update_kernel's step before
+//          project_parameters.  Draws: the counter layout of pmmh under tags of their own,
+//            0x4D4C0001  normal_pair(r.x, r.y) -> z0, z1      0x4D4C0002  normal_pair(r.x, r.y) -> z2, z3
+//            0x4D4C0003  uniform53(r.x, r.y)   -> u
+//          with pmmh's slot assignment (SVM z0, z1, z2; LGSSM z0, z2, z3; GARCH z0..z3).  Disjoint from every tag above.
 // Built with -ffp-contract=off; IEEE division and ::sqrt / ::log throughout.
 #include "pfg_host.hpp"
 #include "pfg_math.hpp"
@@ -345,6 +368,126 @@ __global__ void pmmh_accept_kernel(int model, int B, double *__restrict__ theta,
     }
 }
 
+// ---- pMALA: the drift, the proposal's log-density, propose, accept ----
+// d_j(theta, g) = grad_logprior_j(theta) + g_j in theta order, the prior gradient and the score columns as sgld_update_kernel
+// states them (spelled out here: that kernel stays as it is); 0 for the slot that does not move (LGSSM's C, SVM's fourth)
+__device__ void pmala_drift(int model, const double *th, const double *g, const pfg_prior_hyper &hy, double *d) {
+    if (model == PFG_MODEL_SVM || model == PFG_MODEL_LGSSM) {
+        const bool lg = model == PFG_MODEL_LGSSM;
+        const double A = th[0], LQ = th[lg ? 2 : 1], LR = th[lg ? 3 : 2];
+        const double Qinv = LQ * LQ + 1e-16;
+        // score columns: SVM [LR, LQ, A]; LGSSM [LR, LQ, C, A]
+        d[0] = coef_prior_grad(Qinv, A, hy.mean_A, hy.var_col_A) + g[lg ? 3 : 2];
+        d[lg ? 1 : 3] = 0.0;
+        d[lg ? 2 : 1] = chol_prior_grad(LQ, hy.df_Qinv, hy.scale_Qinv) + g[1];
+        d[lg ? 3 : 2] = chol_prior_grad(LR, hy.df_Rinv, hy.scale_Rinv) + g[0];
+    } else {
+        const double mu = exp(th[0]), phi = 1.0 / (1.0 + exp(-th[1])), lam = 1.0 / (1.0 + exp(-th[2]));
+        // garch_var.py:152-165; score columns [LR, log_mu, logit_phi, logit_lambduh]
+        d[0] = (-hy.shape_mu - 1.0 + hy.scale_mu / mu) + g[1];
+        d[1] = ((hy.alpha_phi - 1.0) / (1.0 + phi) - (hy.beta_phi - 1.0) / (1.0 - phi)) * phi * (1.0 - phi) + g[2];
+        d[2] = ((hy.alpha_lambduh - 1.0) / (1.0 + lam) - (hy.beta_lambduh - 1.0) / (1.0 - lam)) * lam * (1.0 - lam) + g[3];
+        d[3] = chol_prior_grad(th[3], hy.df_Rinv, hy.scale_Rinv) + g[0];
+    }
+}
+// the coordinates a proposal moves: SVM 0..2, LGSSM 0, 2, 3, GARCH 0..3
+__device__ __forceinline__ bool pmala_free(int model, int j) { return model == PFG_MODEL_SVM ? j < 3 : (model == PFG_MODEL_LGSSM ? j != 1 : true); }
+// the mean of the proposal from a with drift d: a_j + (s_j^2 / 2) d_j
+__device__ __forceinline__ double pmala_mean(double a, double s, double d) { return a + (0.5 * (s * s)) * d; }
+// log q(b | a, g), d = d(a, g), less the constant of the scales
+__device__ double pmala_log_q(int model, const double *b, const double *a, const double *d, const double *s) {
+    double q = 0.0;
+    for (int j = 0; j < PFG_MAX_THETA; ++j) {
+        if (!pmala_free(model, j)) continue;
+        const double r = b[j] - pmala_mean(a[j], s[j], d[j]);
+        q = q + (r * r) / (2.0 * (s[j] * s[j]));
+    }
+    return -q;
+}
+
+__global__ void pmala_propose_kernel(int model, int B, const double *__restrict__ theta, const double *__restrict__ grad_cur,
+                                     double *__restrict__ theta_prop, int32_t *__restrict__ valid,
+                                     const double *__restrict__ scale, pfg_prior_hyper hy, uint64_t seed, uint64_t chain_offset,
+                                     const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double *th = theta + (size_t)b * PFG_MAX_THETA;
+    double *tp = theta_prop + (size_t)b * PFG_MAX_THETA;
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const uint32_t c1 = (uint32_t)step, c2 = (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32);
+    const pfg::u32x4 r0 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x4D4C0001u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const pfg::u32x4 r1 = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x4D4C0002u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    double z[4];
+    const pfg::Math<double, false> mth = {};
+    mth.normal_pair(r0.x, r0.y, z[0], z[1]);
+    mth.normal_pair(r1.x, r1.y, z[2], z[3]);
+    double a[PFG_MAX_THETA], d[PFG_MAX_THETA], p[PFG_MAX_THETA];
+    for (int j = 0; j < PFG_MAX_THETA; ++j) a[j] = th[j];
+    pmala_drift(model, a, grad_cur + (size_t)b * PFG_MAX_THETA, hy, d);
+    bool ok;
+    if (model == PFG_MODEL_SVM) {
+        for (int j = 0; j < 3; ++j) p[j] = pmala_mean(a[j], scale[j], d[j]) + scale[j] * z[j];
+        p[3] = a[3];
+        ok = fabs(p[0]) <= 0.9999 && p[1] > 0.0 && p[1] < INFINITY && p[2] > 0.0 && p[2] < INFINITY;
+    } else if (model == PFG_MODEL_LGSSM) {
+        p[0] = pmala_mean(a[0], scale[0], d[0]) + scale[0] * z[0];
+        p[1] = 1.0;
+        p[2] = pmala_mean(a[2], scale[2], d[2]) + scale[2] * z[2];
+        p[3] = pmala_mean(a[3], scale[3], d[3]) + scale[3] * z[3];
+        ok = fabs(p[0]) <= 0.9999 && p[2] > 0.0 && p[2] < INFINITY && p[3] > 0.0 && p[3] < INFINITY;
+    } else {
+        for (int j = 0; j < 4; ++j) p[j] = pmala_mean(a[j], scale[j], d[j]) + scale[j] * z[j];
+        ok = fabs(p[0]) < INFINITY && fabs(p[1]) < INFINITY && fabs(p[2]) < INFINITY && p[3] > 0.0 && p[3] < INFINITY;
+    }
+    valid[b] = ok ? 1 : 0;
+    for (int j = 0; j < PFG_MAX_THETA; ++j) tp[j] = ok ? p[j] : a[j];
+}
+
+// init != 0: ll_cur = out[4] and grad_cur = out[0..3], nothing else.  Otherwise the accept / reject step; a chain that
+// rejects keeps theta, ll_cur AND grad_cur, the estimates it was accepted with (never fresh ones: see the header)
+__global__ void pmala_accept_kernel(int model, int B, double *__restrict__ theta, const double *__restrict__ theta_prop,
+                                    const int32_t *__restrict__ valid, const double *__restrict__ outs,
+                                    double *__restrict__ ll_cur, double *__restrict__ grad_cur, uint64_t *__restrict__ n_accept,
+                                    pfg_prior_hyper hy, const double *__restrict__ scale, int init, uint64_t seed,
+                                    uint64_t chain_offset, const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double *o = outs + (size_t)b * PFG_OUT_DOUBLES;
+    double *gc = grad_cur + (size_t)b * PFG_MAX_THETA;
+    const double ll_prop = o[4];
+    double gp[PFG_MAX_THETA];
+    for (int j = 0; j < PFG_MAX_THETA; ++j) gp[j] = o[j];
+    if (init) {
+        ll_cur[b] = ll_prop;
+        for (int j = 0; j < PFG_MAX_THETA; ++j) gc[j] = gp[j];
+        return;
+    }
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    double a[PFG_MAX_THETA], p[PFG_MAX_THETA], g[PFG_MAX_THETA], s[PFG_MAX_THETA], da[PFG_MAX_THETA], dp[PFG_MAX_THETA];
+    for (int j = 0; j < PFG_MAX_THETA; ++j) {
+        a[j] = th[j]; p[j] = theta_prop[(size_t)b * PFG_MAX_THETA + j]; g[j] = gc[j]; s[j] = scale[j];
+    }
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const uint32_t c1 = (uint32_t)step, c2 = (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32);
+    const pfg::u32x4 r = pfg::philox4x32_10({(uint32_t)gid, c1, c2, 0x4D4C0003u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u = uniform53(r.x, r.y);
+    pmala_drift(model, a, g, hy, da);
+    pmala_drift(model, p, gp, hy, dp);
+    const double q_fwd = pmala_log_q(model, p, a, da, s), q_rev = pmala_log_q(model, a, p, dp, s);
+    const double log_alpha = (((ll_prop + logprior_value(model, p, hy)) - (ll_cur[b] + logprior_value(model, a, hy))) + q_rev) - q_fwd;
+    // the score components the drift uses (LGSSM: not C's column 2; SVM: columns 0..2); false for a NaN as well
+    bool finite = fabs(ll_prop) < INFINITY;
+    for (int j = 0; j < PFG_MAX_THETA; ++j)
+        if (model == PFG_MODEL_SVM ? j < 3 : (model == PFG_MODEL_LGSSM ? j != 2 : true)) finite = finite && fabs(gp[j]) < INFINITY;
+    if (valid[b] != 0 && finite && ::log(u) < log_alpha) {
+        for (int j = 0; j < PFG_MAX_THETA; ++j) { th[j] = p[j]; gc[j] = gp[j]; }
+        ll_cur[b] = ll_prop;
+        n_accept[b] += 1;
+    }
+}
+
 // ---- the entry points: one prologue, one epilogue ----
 // What every rule checks of its arguments (`what` names the entry point).  lgssm_only: how SGRLD and Gibbs refuse other
 // models' chains (the reference's one preconditioner and conjugate prior).  Gibbs has no step size: the defaults pass.
@@ -436,4 +579,30 @@ int pfg_pmmh_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const 
     if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
     return run_update(ctx, B, init ? nullptr : step_ctr, hip_stream, pmmh_accept_kernel, model, B, theta, theta_prop, valid,
                       outs, ll_cur, n_accept, *hyper, init, seed, chain_offset, (const uint64_t *)step_ctr);
+}
+
+int pfg_pmala_propose_device(pfg_ctx *ctx, int model, int B, const double *theta, const double *grad_cur, double *theta_prop,
+                             int32_t *valid, const double *scale, const pfg_prior_hyper *hyper, uint64_t seed,
+                             uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (!theta || !grad_cur || !theta_prop || !valid || !scale || !hyper)
+        return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+    if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
+    // (no bump: the accept step that closes the pMALA step advances the counter)
+    return run_update(ctx, B, nullptr, hip_stream, pmala_propose_kernel, model, B, theta, grad_cur, theta_prop, valid, scale,
+                      *hyper, seed, chain_offset, step_ctr);
+}
+
+int pfg_pmala_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const double *theta_prop, const int32_t *valid,
+                            const double *outs, double *ll_cur, double *grad_cur, uint64_t *n_accept,
+                            const pfg_prior_hyper *hyper, const double *scale, int init, uint64_t seed, uint64_t chain_offset,
+                            uint64_t *step_ctr, void *hip_stream) {
+    if (!ctx) return PFG_ERR_INVALID;
+    if (!theta || !theta_prop || !valid || !outs || !ll_cur || !grad_cur || !n_accept || !hyper || !scale)
+        return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
+    if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
+    return run_update(ctx, B, init ? nullptr : step_ctr, hip_stream, pmala_accept_kernel, model, B, theta, theta_prop, valid,
+                      outs, ll_cur, grad_cur, n_accept, *hyper, scale, init, seed, chain_offset, (const uint64_t *)step_ctr);
 }

@@ -181,7 +181,8 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_launch_device_traced", "pfg_last_traced", "pfg_launch_device_grid", "pfg_launch_device_grid_phase",
            "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device",
            "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
-           "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device")
+           "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device",
+           "pfg_pmala_propose_device", "pfg_pmala_accept_device")
 
 _lib = None
 
@@ -292,6 +293,13 @@ def load_library():
                                            C.c_void_p, C.c_void_p, C.POINTER(PriorHyper), C.c_int, C.c_uint64, C.c_uint64,
                                            C.c_void_p, C.c_void_p]
     lib.pfg_pmmh_accept_device.restype = C.c_int
+    lib.pfg_pmala_propose_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(PriorHyper), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pfg_pmala_propose_device.restype = C.c_int
+    lib.pfg_pmala_accept_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PriorHyper), C.c_void_p, C.c_int,
+                                            C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pfg_pmala_accept_device.restype = C.c_int
     lib.pfg_imq_ksd.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp]
     lib.pfg_imq_ksd.restype = C.c_int
     lib.pfg_sample_windows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -753,6 +761,29 @@ class Context:
             C.c_void_p(outs_ptr or 0), C.c_void_p(ll_ptr or 0), C.c_void_p(n_accept_ptr or 0),
             C.byref(hyper) if hyper is not None else None, int(bool(init)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
             C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def pmala_propose_device(self, model, B, theta_ptr, grad_ptr, theta_prop_ptr, valid_ptr, scale_ptr, hyper, seed,
+                             chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
+        """pfg_pmala_propose_device: theta_prop = theta + scale^2 / 2 (.) (grad_logprior + grad) + scale (.) z, or theta and
+        valid = 0 outside the support."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_pmala_propose_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(grad_ptr or 0), C.c_void_p(theta_prop_ptr or 0),
+            C.c_void_p(valid_ptr or 0), C.c_void_p(scale_ptr or 0), C.byref(hyper) if hyper is not None else None,
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def pmala_accept_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, grad_ptr, n_accept_ptr,
+                            hyper, scale_ptr, init, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
+        """pfg_pmala_accept_device: the accept / reject step on out[4], out[0..3] and the two proposal densities (init:
+        ll = out[4], grad = out[0..3] only); bumps *step_ctr unless init."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_pmala_accept_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
+            C.c_void_p(outs_ptr or 0), C.c_void_p(ll_ptr or 0), C.c_void_p(grad_ptr or 0), C.c_void_p(n_accept_ptr or 0),
+            C.byref(hyper) if hyper is not None else None, C.c_void_p(scale_ptr or 0), int(bool(init)),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
 
     def scratch_bytes(self, model, dtype, rng, N):
         return int(self.lib.pfg_scratch_bytes(MODEL[model], DTYPE[dtype], RNG[rng], int(N)))

@@ -1,4 +1,4 @@
-"""ChainEnsemble: many independent SGLD / SGHMC / SGRLD / Gibbs / PMMH chains resident on one MI355X.
+"""ChainEnsemble: many independent SGLD / SGHMC / SGRLD / Gibbs / PMMH / pMALA chains resident on one MI355X.
 
 The reference runs one chain in one Python thread; its experiment grid fans chains / settings
 out over processes (driver_utils.py:69-111).  On an MI355X one chain keeps one workgroup (one
@@ -28,6 +28,8 @@ from .particle_filters import resolve_resampling
 from .sgmcmc_sampler import random_subsequence_and_weights
 
 _MODELS = {}
+# the score columns pMALA's drift reads (LGSSM: not C's, column 2: C stays 1)
+_PMALA_SCORE_COLUMNS = {"svm": (0, 1, 2), "lgssm": (0, 1, 3), "garch": (0, 1, 2, 3)}
 
 
 def _model_info(model):
@@ -113,9 +115,29 @@ class ChainEnsemble(object):
                WITHOUT Jacobian terms -- the density whose gradient SGLD uses.  epsilon, friction and lambduh are
                ignored; loglik() and acceptance_rate() read the chains' estimates and acceptance; the constructor runs
                one launch at the initial parameters (the init pass: it consumes counter value 0, step s draws with
-               counter s + 1) and refuses a chain whose initial log-likelihood is not finite)
-      proposal_scale: sampler='pmmh' (required there, refused elsewhere): the random walk's standard deviations in raw-theta
-               units, a positive scalar or a length-P vector (LGSSM: C stays 1 whatever its entry)
+               counter s + 1) and refuses a chain whose initial log-likelihood is not finite) |
+               'pmala' (extension: the particle Metropolis-adjusted Langevin algorithm, Nemeth, Sherlock and Fearnhead
+               2016 -- PMMH whose proposal drifts along the filter's own score estimate.  With s = proposal_scale, g the
+               score and ll the log-likelihood estimate the chain's current state was accepted with, and
+               d(theta, g) = grad_logprior(theta) + g (the drift of the SGLD update, score columns mapped as there), a step
+               proposes theta'_j = theta_j + (s_j^2 / 2) d_j(theta, g) + s_j z_j (pfg_pmala_propose_device; LGSSM's C
+               stays 1; PMMH's support), runs the SCORE launch of the resolved kind on theta' -- the launch of a
+               full-series SGLD step -- and accepts on (pfg_pmala_accept_device)
+                   log alpha = (ll' + logprior(theta')) - (ll + logprior(theta)) + log q(theta | theta', g') - log q(theta' | theta, g),
+                   log q(b | a, g) = -sum_j (b_j - a_j - (s_j^2 / 2) d_j(a, g))^2 / (2 s_j^2).
+               With s_j^2 / 2 = epsilon / T for every j the proposal is the law of the SGLD step before
+               project_parameters, so this is SGLD with the Metropolis correction it lacks.  A chain that rejects keeps
+               theta, ll AND g -- neither estimate is refreshed -- so it samples PMMH's target exactly for every N: exp(
+               prior.logprior(theta)) p(y | theta) on the raw row.  (grad_logprior is not the gradient of logprior on
+               every coordinate; exactness does not need it to be, q uses the same drift both ways.)
+               Settings as 'pmmh' -- the whole data set in every step, kind 'pf' with pf 'poyiadjis_N' | 'nemeth', any
+               resampling and ess_threshold, N <= 16384, or kind 'marginal' (LGSSM, f64: the Kalman score and likelihood
+               are exact, plain MALA); pmmh_stat is refused.  loglik(), score() and acceptance_rate() read the chains'
+               estimates and acceptance, last_gradient_statistics() the estimates at the latest proposals; the init
+               pass is PMMH's and refuses a chain whose initial log-likelihood or score is not finite)
+      proposal_scale: sampler='pmmh' | 'pmala' (required there, refused elsewhere): the random walk's (the Langevin
+               proposal's) standard deviations in raw-theta units, a positive scalar or a length-P vector (LGSSM: C stays 1
+               whatever its entry)
       pmmh_stat: sampler='pmmh', kind='pf': None | 'none' (the launch computes no statistic, the default) | 'score' (the
                score launch of the same shape, its score ignored: tools/pmmh_time.py measures one against the other)
       kind: 'pf' (the particle-filter score) | 'marginal' (LGSSM, dtype 'f64': the exact Kalman score of
@@ -162,8 +184,8 @@ class ChainEnsemble(object):
                null weights pointer, a whole short sequence of a list points at its row of T_total / T_k.
       _scratch_bytes: the scratch per descriptor of the resolved smoother.
       launch_windows / launch_pf / launch_reduce / launch_update: the launches of a step on one stream (_stream);
-               _enqueue_step orders them, step / run / _graph drive them.  sampler='pmmh': launch_propose before
-               launch_pf, launch_accept as the update; _pmmh_init is the init pass.
+               _enqueue_step orders them, step / run / _graph drive them.  sampler='pmmh' | 'pmala': launch_propose
+               before launch_pf, launch_accept as the update; _pmmh_init / _pmala_init is the init pass.
     """
 
     def __init__(self, model, observations, parameters, num_chains=None, N=1000, pf="poyiadjis_N",
@@ -223,13 +245,16 @@ class ChainEnsemble(object):
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         self.momentum_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
         self.proposal_scale = s.proposal_scale
-        if sampler == "pmmh":
+        self._mh = sampler in ("pmmh", "pmala")         # a proposal, a launch on it, an accept step
+        if self._mh:
             # the proposal the launch reads, its validity, each chain's current estimate and acceptance count
             self.theta_prop_dev = self.theta_dev.clone()
             self.valid_dev = torch.ones(C, dtype=torch.int32, device=dev)
             self.ll_dev = torch.zeros(C, dtype=torch.float64, device=dev)
             self.accept_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
             self.scale_dev = torch.from_numpy(s.proposal_scale).to(dev)
+        if sampler == "pmala":      # the score estimate each chain's current state was accepted with: out[0..3], verbatim
+            self.grad_cur_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
         # one weights row per window start of every sequence longer than S.  Single-window lists: every row times
         # T_total / T_sequence, the Seq sampler's rescaling of a one-sequence gradient, whole short sequences a row of it;
         # the multi-window path leaves that rescaling to the reduction
@@ -262,7 +287,7 @@ class ChainEnsemble(object):
             self.scratch_dev = torch.empty(self._nd * sb, dtype=torch.uint8, device=dev)
         garch_stationary = model == "garch" and self.helper.default_forward_message is None
         self._desc = _capi.device_descriptors(
-            self._nd, theta=self.theta_prop_dev if sampler == "pmmh" else self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
+            self._nd, theta=self.theta_prop_dev if self._mh else self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
             scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv, lambduh=self.lambduh, seed=self.seed, N=self.N,
             smoother=s.smoother, stat=s.stat, flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0,
             ess_threshold=s.ess_threshold, **s.paris)
@@ -273,6 +298,8 @@ class ChainEnsemble(object):
             self.launch_windows()           # static windows: written once, no draw
         if sampler == "pmmh":
             self._pmmh_init()
+        if sampler == "pmala":
+            self._pmala_init()
 
     @staticmethod
     def _resolve_settings(model, observations, parameters=None, num_chains=None, N=1000, pf="poyiadjis_N", lambduh=None,
@@ -288,23 +315,27 @@ class ChainEnsemble(object):
         Ntilde, max_accept_reject; M, K, W, multi; S, B, strict; y (the concatenated series), T, segments ([K+1] offsets
         into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto;
         ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
-        'pmmh')."""
+        'pmmh' | 'pmala')."""
         tau = None
         if ess_threshold is not None and ess_threshold != 0 and (kind != "pf" or sampler == "gibbs"):
             # (what else adaptive resampling is not built for: resolve_resampling, below)
             raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
-        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh"):
-            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'gibbs' or 'pmmh'")
+        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala"):
+            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'pmala', 'gibbs' or 'pmmh'")
         scale = None
-        if sampler != "pmmh":
+        if sampler not in ("pmmh", "pmala"):
             if proposal_scale is not None:
                 raise ValueError("proposal_scale is the random walk of sampler='pmmh', got sampler = '{0}'".format(sampler))
             if pmmh_stat is not None:
                 raise ValueError("pmmh_stat belongs to sampler='pmmh', got sampler = '{0}'".format(sampler))
         else:
-            # particle marginal Metropolis-Hastings (extension): what it is not built for is refused by name
+            # particle marginal Metropolis-Hastings and particle MALA (extensions): what they are not built for is refused
+            # by name
+            if sampler == "pmala" and pmmh_stat is not None:
+                raise ValueError("pmmh_stat belongs to sampler='pmmh' (sampler='pmala' needs the score launch), got sampler = 'pmala'")
             if proposal_scale is None:
-                raise ValueError("sampler='pmmh' needs proposal_scale: a positive scalar or a length-P vector in raw-theta units")
+                raise ValueError("sampler='{0}' needs proposal_scale: a positive scalar or a length-P vector in raw-theta "
+                                 "units".format(sampler))
             P = _capi.THETA_DIM[model]
             ps = np.asarray(proposal_scale, dtype=np.float64).reshape(-1)
             if ps.size not in (1, P) or not np.all(np.isfinite(ps)) or not np.all(ps > 0.0):
@@ -313,13 +344,17 @@ class ChainEnsemble(object):
             scale = np.zeros(_capi.MAX_THETA)
             scale[:P] = ps
             if kind == "complete":
-                raise NotImplementedError("sampler='pmmh' accepts on a log-likelihood estimate: kind='pf' or kind='marginal' "
-                                          "(kind='complete' samples paths and has none)")
+                raise NotImplementedError("sampler='{0}' accepts on a log-likelihood estimate: kind='pf' or kind='marginal' "
+                                          "(kind='complete' samples paths and has none)".format(sampler))
             if kind == "pf" and pf not in ("poyiadjis_N", "nemeth"):
-                raise NotImplementedError("sampler='pmmh' reads the filter's log-likelihood only: pf = 'poyiadjis_N' | 'nemeth' "
-                                          "(the smoothing of pf = '{0}' would be thrown away)".format(pf))
+                if sampler == "pmmh":
+                    raise NotImplementedError("sampler='pmmh' reads the filter's log-likelihood only: pf = 'poyiadjis_N' | "
+                                              "'nemeth' (the smoothing of pf = '{0}' would be thrown away)".format(pf))
+                raise NotImplementedError("sampler='pmala' drifts along the O(N) filter's score: pf = 'poyiadjis_N' | 'nemeth' "
+                                          "(the score of pf = '{0}' as the drift is not built)".format(pf))
             if kind == "pf" and int(N) > 16384:
-                raise NotImplementedError("sampler='pmmh' is built for N <= 16384 (no whole-GPU windows), got N = {0}".format(int(N)))
+                raise NotImplementedError("sampler='{0}' is built for N <= 16384 (no whole-GPU windows), got N = {1}".format(
+                    sampler, int(N)))
             if pmmh_stat not in (None, "none", "score"):
                 raise ValueError("pmmh_stat must be None, 'none' or 'score'")
         M, K, W = ChainEnsemble._window_counts(observations, minibatch_size, num_sequences)
@@ -454,15 +489,16 @@ class ChainEnsemble(object):
             if N > 16384:
                 raise NotImplementedError("the multi-window path is built for N <= 16384 (one workgroup per window), "
                                           "got N = {0}".format(N))
-        if sampler == "pmmh":
+        if sampler in ("pmmh", "pmala"):
             # every step needs the likelihood of the whole data set: no window is drawn, nothing is rescaled
-            whole = "pmmh needs the whole series in every step: "
+            whole = sampler + " needs the whole series in every step: "
             if segments is None and (S != -1 or int(buffer_length) != -1):
                 raise NotImplementedError(whole + "subsequence_length = buffer_length = -1, got {0} / {1}".format(
                     int(subsequence_length), int(buffer_length)))
             if segments is not None and (not multi or K != -1 or int(subsequence_length) != -1 or M != 1 or draws or rescale):
                 raise NotImplementedError(whole + "a list of sequences takes num_sequences = -1, subsequence_length = -1, "
-                                          "buffer_length = 0 and minibatch_size 1 (every sequence whole, out[4] summed)")
+                                          "buffer_length = 0 and minibatch_size 1 (every sequence whole, out[4] summed{0})".format(
+                                              ", the score columns too" if sampler == "pmala" else ""))
             if multi and (M != 1 or draws or rescale):
                 raise NotImplementedError(whole + "minibatch_size = 1 (an average of log-likelihoods is no estimate of one)")
         return types.SimpleNamespace(
@@ -640,7 +676,7 @@ class ChainEnsemble(object):
     def launch_update(self, stream=None):
         theta, out = (self.model, self.C, self.theta_dev.data_ptr()), (self.out_dev.data_ptr(), self.hyper)
         key = (self.seed ^ 0x5DEECE66D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
-        if self.sampler == "pmmh":
+        if self._mh:
             self.launch_accept(stream)
         elif self.sampler == "sgrld":
             self.ctx.sgrld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
@@ -656,12 +692,23 @@ class ChainEnsemble(object):
         return (self.seed ^ 0x5DEECE66D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
 
     def launch_propose(self, stream=None):
-        """sampler='pmmh': theta_prop_dev = theta_dev + proposal_scale (.) z, valid_dev (pfg_pmmh_propose_device)."""
+        """sampler='pmmh': theta_prop_dev = theta_dev + proposal_scale (.) z, valid_dev (pfg_pmmh_propose_device).
+        sampler='pmala': the Langevin proposal along grad_cur_dev (pfg_pmala_propose_device)."""
+        if self.sampler == "pmala":
+            return self.ctx.pmala_propose_device(
+                self.model, self.C, self.theta_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
+                self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), self.hyper, *self._pmmh_key(stream))
         self.ctx.pmmh_propose_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
                                      self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), *self._pmmh_key(stream))
 
     def launch_accept(self, stream=None, init=False):
-        """sampler='pmmh': accept / reject on out_dev[:, 4] and the log-prior; bumps the counter (pfg_pmmh_accept_device)."""
+        """sampler='pmmh': accept / reject on out_dev[:, 4] and the log-prior; bumps the counter (pfg_pmmh_accept_device).
+        sampler='pmala': the same with the two proposal densities, on out_dev[:, :5] (pfg_pmala_accept_device)."""
+        if self.sampler == "pmala":
+            return self.ctx.pmala_accept_device(
+                self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(), self.valid_dev.data_ptr(),
+                self.out_dev.data_ptr(), self.ll_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.accept_dev.data_ptr(),
+                self.hyper, self.scale_dev.data_ptr(), init, *self._pmmh_key(stream))
         self.ctx.pmmh_accept_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
                                     self.valid_dev.data_ptr(), self.out_dev.data_ptr(), self.ll_dev.data_ptr(),
                                     self.accept_dev.data_ptr(), self.hyper, init, *self._pmmh_key(stream))
@@ -680,6 +727,22 @@ class ChainEnsemble(object):
         bad = np.flatnonzero(~np.isfinite(self.ll_dev.cpu().numpy()))
         if bad.size:
             raise ValueError("pmmh: the initial log-likelihood of chain {0} is not finite".format(int(bad[0]) + self.chain_offset))
+
+    def _pmala_init(self):
+        """The init pass of sampler='pmala', as _pmmh_init: the score launch at the initial parameters, ll_dev = its out[4],
+        grad_cur_dev = its out[0..3]; it consumes counter value 0."""
+        self.theta_prop_dev.copy_(self.theta_dev)
+        self.launch_pf()
+        if self._multi:
+            self.launch_reduce()
+        self.launch_accept(init=True)
+        self.step_ctr.fill_(1)
+        self.synchronize()
+        used = self.grad_cur_dev.cpu().numpy()[:, list(_PMALA_SCORE_COLUMNS[self.model])]
+        bad = np.flatnonzero(~(np.isfinite(self.ll_dev.cpu().numpy()) & np.all(np.isfinite(used), axis=1)))
+        if bad.size:
+            raise ValueError("pmala: the initial log-likelihood or score of chain {0} is not finite".format(
+                int(bad[0]) + self.chain_offset))
 
     def launch_windows(self, stream=None):
         """Device-side window sampling (window_sampling='device'): rewrite y / T / t1 / tL / weights of
@@ -703,7 +766,7 @@ class ChainEnsemble(object):
                                        self._rescale, float(self.T), self.out_dev.data_ptr(), self._stream(stream))
 
     def _enqueue_step(self):
-        pmmh = self.sampler == "pmmh"       # (its windows are static: nothing to draw on either path)
+        pmmh = self._mh       # 'pmmh' | 'pmala' (their windows are static: nothing to draw on either path)
         if self._multi:
             if self._draws:
                 self.launch_windows()
@@ -742,8 +805,10 @@ class ChainEnsemble(object):
             # one eager step first (code-object load, LDS-size attributes), undone afterwards so
             # that building the graph does not advance the chains
             state = (self.theta_dev, self.momentum_dev, self.step_ctr, self.desc_dev)
-            if self.sampler == "pmmh":
+            if self._mh:
                 state += (self.theta_prop_dev, self.valid_dev, self.ll_dev, self.accept_dev)
+            if self.sampler == "pmala":
+                state += (self.grad_cur_dev,)
             snap = [t.clone() for t in state]
             self._enqueue_step()
             self.synchronize()
@@ -792,6 +857,9 @@ class ChainEnsemble(object):
                      model=self.model, N=self.N, C=self.C, ess_threshold=self.ess_threshold)
         if self.sampler == "pmmh":      # the estimate a chain was accepted with is part of its state
             state.update(ll=self.ll_dev.cpu().numpy(), n_accept=self.accept_dev.cpu().numpy())
+        if self.sampler == "pmala":     # ... and so is the score estimate the proposals drift along
+            state.update(ll=self.ll_dev.cpu().numpy(), grad=self.grad_cur_dev.cpu().numpy(),
+                         n_accept=self.accept_dev.cpu().numpy())
         return state
 
     def load_state_dict(self, state):
@@ -805,9 +873,11 @@ class ChainEnsemble(object):
         self.theta_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["theta"])))
         self.momentum_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["momentum"])))
         self.step_ctr.fill_(int(state["step_ctr"]))
-        if self.sampler == "pmmh":
+        if self._mh:
             self.ll_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["ll"], dtype=np.float64)))
             self.accept_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["n_accept"], dtype=np.int64)))
+        if self.sampler == "pmala":
+            self.grad_cur_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["grad"], dtype=np.float64)))
         self.steps_done = int(state["steps_done"])       # host window draws are keyed by (seed, chain, steps_done)
         self.synchronize()
 
@@ -854,22 +924,30 @@ class ChainEnsemble(object):
             return out[:, :7], None
         if self.sampler == "pmmh":      # no score is computed: (None, the log-likelihood estimates at the latest PROPOSALS)
             return None, out[:, 4]
-        return out[:, :_capi.STAT_DIM[self.model]], out[:, 4]
+        return out[:, :_capi.STAT_DIM[self.model]], out[:, 4]       # (sampler='pmala': at the latest PROPOSALS)
 
     def loglik(self):
-        """sampler='pmmh': [C] log-likelihood estimates the chains hold, each the one its current state was accepted with."""
+        """sampler='pmmh' | 'pmala': [C] log-likelihood estimates the chains hold, each the one its current state was
+        accepted with."""
         self._need_pmmh("loglik")
         return self.ll_dev.cpu().numpy()
 
+    def score(self):
+        """sampler='pmala': [C, h] score estimates the chains hold (score-column order, as last_gradient_statistics), each
+        the one its current state was accepted with and its next proposal drifts along."""
+        if self.sampler != "pmala":
+            raise ValueError("score() belongs to sampler='pmala', this ensemble runs '{0}'".format(self.sampler))
+        return self.grad_cur_dev[:, :_capi.STAT_DIM[self.model]].cpu().numpy()
+
     def acceptance_rate(self):
-        """sampler='pmmh': [C] accepted proposals / steps done (nan before the first step)."""
+        """sampler='pmmh' | 'pmala': [C] accepted proposals / steps done (nan before the first step)."""
         self._need_pmmh("acceptance_rate")
         n = self.accept_dev.cpu().numpy().astype(np.float64)
         return n / self.steps_done if self.steps_done else np.full(self.C, np.nan)
 
     def _need_pmmh(self, what):
-        if self.sampler != "pmmh":
-            raise ValueError("{0}() belongs to sampler='pmmh', this ensemble runs '{1}'".format(what, self.sampler))
+        if not self._mh:
+            raise ValueError("{0}() belongs to sampler='pmmh' (and 'pmala'), this ensemble runs '{1}'".format(what, self.sampler))
 
     def window_statistics(self):
         """Multi-window path: the latest launch's [C, W, 8] window records and [C, W] sequence lengths."""
