@@ -330,7 +330,7 @@ typedef struct pfg_dev_problem {
 } pfg_dev_problem;
 
 int pfg_version(void);
-/* sizeof() of an ABI struct: 0 pfg_problem, 1 pfg_result, 2 pfg_dev_problem, 3 pfg_prior_hyper
+/* sizeof() of an ABI struct: 0 pfg_problem, 1 pfg_result, 2 pfg_dev_problem, 3 pfg_prior_hyper, 4 pfg_csmc_problem
  * (bindings assert their mirror has the same size) */
 int pfg_struct_size(int which);
 int pfg_create(pfg_ctx **out, int device_id);
@@ -602,6 +602,58 @@ int pfg_pmala_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const
                             const int32_t *valid, const double *outs, double *ll_cur, double *grad_cur,
                             uint64_t *n_accept, const pfg_prior_hyper *hyper, const double *scale, int init,
                             uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream);
+
+/* EXTENSION (not in the reference, whose SVM sample_x / sample_gibbs raise): particle Gibbs (Andrieu, Doucet and Holenstein
+ * 2010) for B resident SVM or LGSSM chains -- a conditional SMC sweep with ancestor sampling (Lindsten, Jordan and Schon
+ * 2014) that moves each chain's latent path, then the conjugate parameter draw from that path's statistics.
+ *
+ * pfg_csmc_problem: one chain's sweep.  Every pointer is DEVICE memory.  theta: the raw row (PFG_MAX_THETA doubles); y [T];
+ * path [T]: the reference path x*, replaced by the new path (has_ref = 0: written only -- all N particles are free, a
+ * bootstrap filter with stored genealogy); scratch: pfg_csmc_scratch_bytes(T, N) bytes, 256-byte aligned -- the states
+ * [T][N] f64, then the parents [T][N] uint16 (row 0 unused); out: PFG_OUT_DOUBLES doubles, the statistics of the NEW path
+ * -- LGSSM the PFG_STAT_GIBBS record, SVM [sum_{t>=1} x_{t-1}^2, sum_{t>=1} x_t x_{t-1}, sum_{t>=1} x_t^2,
+ * sum_t y_t^2 exp(-x_t), 0, 0, T, 0]; n_degenerate: one counter.  The target is the law the filters and FFBS target:
+ * x_{-1} ~ N(prior_mean, prior_var), x_t | x_{t-1} ~ f_theta, weights g_theta(y_t | x_t), prior proposal, multinomial
+ * resampling at every step; particle N-1 carries the reference path and draws its parent from W_{t-1}^i f(x*_t | x_{t-1}^i).
+ * A chain whose weight sum or ancestor-weight sum is zero or not finite at some step keeps its path, gets the statistics
+ * of that path and *n_degenerate += 1 (has_ref = 0: a NaN record); NaN is never written to a path.  A descriptor with a
+ * NULL array, T < 1, N < 2 or above the launch's n_max, or a prior variance that is not positive: a NaN record and the
+ * count.  The trace pointers are read by a traced launch only and may be NULL: trace_anc [T][N] every particle's parent
+ * (row 0 not written), trace_ref_anc [T] the reference particle's sampled ancestor (entry 0 not written), trace_w [T][N]
+ * the normalised weights, trace_k [1] the final index.
+ *
+ * pfg_csmc_device: one workgroup per problem, 64 x 2 (one wave) for n_max <= 128, 256 x 4 up to 1024; `problems` is a
+ * DEVICE array of B records, n_max >= every record's N.  Draws: Philox4x32-10 keyed by (seed, chain_offset + b,
+ * *step_ctr, t, particle) under tags of their own (csrc/pfg_csmc.hip); *step_ctr is read, not incremented.  traced != 0
+ * runs the twin that honours the trace pointers; both write the same path, bit for bit.  PFG_ERR_UNSUPPORTED: GARCH, a
+ * dtype other than PFG_F64, n_max > 1024 or < 2; PFG_ERR_INVALID: a bad model id, B < 0, problems == NULL.
+ *
+ * pfg_pgibbs_update_device: the parameter draw from `outs` [B][PFG_OUT_DOUBLES], one lane per chain, keyed as
+ * pfg_gibbs_update_device.  LGSSM: that call's arithmetic, expression for expression.  SVM: Qinv and A | Q from
+ * out[0..2] as there (T - 1 transitions), Rinv = scale chi2(df) with df = df_Rinv + T, scale = 1 / (1 / scale_Rinv +
+ * out[3]) -- the emission law is y_t ~ N(0, R exp(x_t)) --, then project_parameters.  The transition sums run over
+ * t >= 1: the dependence of x_0's law on theta is left out of the conditional, as in the reference's LGSSM Gibbs.
+ * *step_ctr is incremented afterwards.  GARCH: PFG_ERR_UNSUPPORTED (its prior has no conjugate draw). */
+typedef struct pfg_csmc_problem {
+    const double *theta;
+    const double *y;
+    double *path;
+    void *scratch;
+    double *out;
+    uint64_t *n_degenerate;
+    int32_t *trace_anc;
+    int32_t *trace_ref_anc;
+    double *trace_w;
+    int32_t *trace_k;
+    double prior_mean, prior_var;
+    int32_t T, N, has_ref, reserved;
+} pfg_csmc_problem;
+int64_t pfg_csmc_scratch_bytes(int T, int N);   /* -1: T < 1, N < 2 or N > 1024 */
+int pfg_csmc_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_csmc_problem *problems, uint64_t seed,
+                    uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced);
+int pfg_pgibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                             const pfg_prior_hyper *hyper, uint64_t seed, uint64_t chain_offset,
+                             uint64_t *step_ctr, void *hip_stream);
 
 /* Inverse-multiquadric kernel Stein discrepancy of K points x[K][d] with score estimates
  * g[K][d] (HOST pointers, d <= 8): sqrt(sum_{i,j} k0(x_i,x_j)) / K for

@@ -59,6 +59,16 @@
 //            0x4D4C0001  normal_pair(r.x, r.y) -> z0, z1      0x4D4C0002  normal_pair(r.x, r.y) -> z2, z3
 //            0x4D4C0003  uniform53(r.x, r.y)   -> u
 //          with pmmh's slot assignment (SVM z0, z1, z2; LGSSM z0, z2, z3; GARCH z0..z3).  Disjoint from every tag above.
+//   pgibbs particle Gibbs (Andrieu, Doucet and Holenstein 2010): the parameter draw from the statistics the conditional SMC
+//          sweep of pfg_csmc.hip left in out[0..7], keyed by ChainKey exactly as gibbs is (same tags: a chain runs one of
+//          the two).  LGSSM: gibbs, expression for expression, in a kernel of its own (gibbs_update_kernel stays as it is).
+//          SVM: (Qinv, A) from out[0..2] with conjugate(df_Qinv, scale_Qinv, mean_A, var_col_A, ..., T - 1) and A | Q as
+//          gibbs; Rinv = scale chi2(df), df = df_Rinv + T, scale = 1 / (1 / scale_Rinv + out[3]), out[3] = sum_t y_t^2
+//          exp(-x_t) -- the emission law is y_t ~ N(0, R exp(x_t)) (svm/kernels.py:56-62, svm_logw) --, then SVM's
+//          project_parameters.  The transition sums run over t >= 1: the theta-dependence of x_0's law is left out of the
+//          conditional, as in the reference's LGSSM Gibbs.
+//          The sweep's own draws: tags 0x43530000 | particle, 0x43531000, 0x43532000 with the time step in the counter's
+//          third word (pfg_csmc.hip).  Disjoint from every tag above.
 // Built with -ffp-contract=off; IEEE division and ::sqrt / ::log throughout.
 #include "pfg_host.hpp"
 #include "pfg_math.hpp"
@@ -488,6 +498,46 @@ __global__ void pmala_accept_kernel(int model, int B, double *__restrict__ theta
     }
 }
 
+// ---- particle Gibbs: the parameter draw from the statistics of a conditional SMC path (pfg_csmc.hip) ----
+// LGSSM: gibbs_update_kernel's arithmetic, spelled out again (that kernel stays as it is).  SVM: see the header
+__global__ void pgibbs_update_kernel(int model, int B, double *__restrict__ theta, const double *__restrict__ outs,
+                                     pfg_prior_hyper hy, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    const double *s = outs + (size_t)b * PFG_OUT_DOUBLES;
+    const uint64_t step = step_ctr ? *step_ctr : 0ull;
+    const uint64_t gid = chain_offset + (uint64_t)b;
+    const ChainKey key{(uint32_t)gid, (uint32_t)step, (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32), (uint32_t)seed,
+                       (uint32_t)(seed >> 32)};
+    const double T = s[6];
+    // transitions (t >= 1): T - 1 of them; emissions: T
+    const Conj q = conjugate(hy.df_Qinv, hy.scale_Qinv, hy.mean_A, hy.var_col_A, s[0], s[1], s[2], T - 1.0);
+    double r_df, r_scale;
+    if (model == PFG_MODEL_LGSSM) {
+        const Conj r = conjugate(hy.df_Rinv, hy.scale_Rinv, hy.mean_C, hy.var_col_C, s[3], s[4], s[5], T);
+        r_df = r.df; r_scale = r.scale;
+    } else {
+        r_df = hy.df_Rinv + T;
+        r_scale = 1.0 / (1.0 / hy.scale_Rinv + s[3]);
+    }
+    const double Qinv = q.scale * (2.0 * gamma_draw(key, 0, 0.5 * q.df));
+    const double Rinv = r_scale * (2.0 * gamma_draw(key, 1, 0.5 * r_df));
+    const double LQ = ::sqrt(Qinv), LR = ::sqrt(Rinv);
+    // A | Q ~ N(Scp / Spp, 1 / ((LQinv^2 + 1e-9) Spp)) (matrices.py:556-580)
+    const pfg::u32x4 ra = key.draw(2, 0);
+    double zA, unused;
+    const pfg::Math<double, false> mth = {};
+    mth.normal_pair(ra.x, ra.y, zA, unused);
+    const double P = LQ * LQ + 1e-9;
+    const double A = q.Scp / q.Spp + ::sqrt((1.0 / P) * (1.0 / q.Spp)) * zA;
+    if (model == PFG_MODEL_LGSSM) {
+        lgssm_project_store(th, A, LQ, LR);
+    } else {
+        th[0] = clip_ar(A); th[1] = reflect_chol(LQ); th[2] = reflect_chol(LR);
+    }
+}
+
 // ---- the entry points: one prologue, one epilogue ----
 // What every rule checks of its arguments (`what` names the entry point).  lgssm_only: how SGRLD and Gibbs refuse other
 // models' chains (the reference's one preconditioner and conjugate prior).  Gibbs has no step size: the defaults pass.
@@ -605,4 +655,14 @@ int pfg_pmala_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const
     if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
     return run_update(ctx, B, init ? nullptr : step_ctr, hip_stream, pmala_accept_kernel, model, B, theta, theta_prop, valid,
                       outs, ll_cur, grad_cur, n_accept, *hyper, scale, init, seed, chain_offset, (const uint64_t *)step_ctr);
+}
+
+int pfg_pgibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
+                             const pfg_prior_hyper *hyper, uint64_t seed, uint64_t chain_offset,
+                             uint64_t *step_ctr, void *hip_stream) {
+    if (const int rc = check_update(ctx, __func__, model, theta, outs, hyper)) return rc;
+    if (model == PFG_MODEL_GARCH)
+        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(__func__) + ": no conjugate Gibbs draw for GARCHSampler");
+    return run_update(ctx, B, step_ctr, hip_stream, pgibbs_update_kernel, model, B, theta, outs, *hyper, seed, chain_offset,
+                      (const uint64_t *)step_ctr);
 }

@@ -151,6 +151,22 @@ DEV_PROBLEM_DTYPE = np.dtype([
 ], align=True)
 
 
+# numpy mirror of pfg_csmc_problem (one conditional SMC sweep; every pointer a device address)
+CSMC_PROBLEM_DTYPE = np.dtype([
+    ("theta", "u8"), ("y", "u8"), ("path", "u8"), ("scratch", "u8"), ("out", "u8"), ("n_degenerate", "u8"),
+    ("trace_anc", "u8"), ("trace_ref_anc", "u8"), ("trace_w", "u8"), ("trace_k", "u8"),
+    ("prior_mean", "f8"), ("prior_var", "f8"),
+    ("T", "i4"), ("N", "i4"), ("has_ref", "i4"), ("reserved", "i4"),
+], align=True)
+CSMC_MAX_N = 1024
+
+
+def csmc_scratch_bytes(T, N):
+    """pfg_csmc_scratch_bytes: the states [T][N] f64 and the parents [T][N] uint16 of one chain, rounded up to 256 bytes
+    (-1: T < 1, N < 2 or N > 1024).  The library's own answer: the formula is stated once, in pfg_csmc.hip."""
+    return int(load_library().pfg_csmc_scratch_bytes(int(T), int(N)))
+
+
 def device_descriptors(n, *, theta, row, out, step_ctr, scratch, scratch_bytes, stream, prior_mean, prior_var, lambduh, seed,
                        N, smoother, stat="score", flags=0, Ntilde=0, max_accept_reject=0, ess_threshold=None):
     """The static fields of n pfg_dev_problem records (the windows -- y, T, t1, tL, weights -- are the caller's):
@@ -182,7 +198,8 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device",
            "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
            "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device",
-           "pfg_pmala_propose_device", "pfg_pmala_accept_device")
+           "pfg_pmala_propose_device", "pfg_pmala_accept_device", "pfg_csmc_scratch_bytes", "pfg_csmc_device",
+           "pfg_pgibbs_update_device")
 
 _lib = None
 
@@ -222,7 +239,7 @@ def load_library():
     lib.pfg_version.restype = C.c_int
     lib.pfg_struct_size.argtypes = [C.c_int]
     lib.pfg_struct_size.restype = C.c_int
-    sizes = (C.sizeof(Problem), C.sizeof(Result), DEV_PROBLEM_DTYPE.itemsize, C.sizeof(PriorHyper))
+    sizes = (C.sizeof(Problem), C.sizeof(Result), DEV_PROBLEM_DTYPE.itemsize, C.sizeof(PriorHyper), CSMC_PROBLEM_DTYPE.itemsize)
     for which, mine in enumerate(sizes):
         if lib.pfg_struct_size(which) != mine:
             raise RuntimeError("ABI mismatch: struct {0} is {1} bytes in libpfgrad.so, {2} in the binding"
@@ -284,6 +301,13 @@ def load_library():
     lib.pfg_gibbs_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                             C.POINTER(PriorHyper), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.pfg_gibbs_update_device.restype = C.c_int
+    lib.pfg_pgibbs_update_device.argtypes = lib.pfg_gibbs_update_device.argtypes
+    lib.pfg_pgibbs_update_device.restype = C.c_int
+    lib.pfg_csmc_scratch_bytes.argtypes = [C.c_int, C.c_int]
+    lib.pfg_csmc_scratch_bytes.restype = C.c_int64
+    lib.pfg_csmc_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_int]
+    lib.pfg_csmc_device.restype = C.c_int
     lib.pfg_logprior_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(PriorHyper), C.c_void_p, C.c_void_p]
     lib.pfg_logprior_device.restype = C.c_int
     lib.pfg_pmmh_propose_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -735,6 +759,26 @@ class Context:
             self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper),
             C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
             C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def pgibbs_update_device(self, model, B, theta_ptr, outs_ptr, hyper, seed, chain_offset=0, step_ctr_ptr=None,
+                             stream_ptr=0):
+        """pfg_pgibbs_update_device: the conjugate draw from the statistics of a conditional SMC path (SVM, LGSSM)."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_pgibbs_update_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(outs_ptr or 0),
+            C.byref(hyper) if hyper is not None else None,
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def csmc_device(self, model, dtype, n_max, B, problems_ptr, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0,
+                    traced=False):
+        """pfg_csmc_device: one conditional SMC sweep with ancestor sampling per pfg_csmc_problem record (a device array)."""
+        m = model if isinstance(model, int) else MODEL[model]
+        d = dtype if isinstance(dtype, int) else DTYPE[dtype]
+        self._check(self.lib.pfg_csmc_device(
+            self.handle, m, d, int(n_max), int(B), C.c_void_p(problems_ptr or 0),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr)), int(bool(traced))))
 
     def logprior_device(self, model, B, theta_ptr, hyper, logprior_ptr, stream_ptr=0):
         """pfg_logprior_device: logprior[b] = Prior.logprior of the raw row theta[b], up to a constant of the hyper-parameters."""

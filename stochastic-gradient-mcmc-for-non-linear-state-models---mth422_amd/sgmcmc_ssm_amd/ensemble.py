@@ -1,4 +1,4 @@
-"""ChainEnsemble: many independent SGLD / SGHMC / SGRLD / Gibbs / PMMH / pMALA chains resident on one MI355X.
+"""ChainEnsemble: many independent SGLD / SGHMC / SGRLD / Gibbs / PMMH / pMALA / particle Gibbs chains resident on one MI355X.
 
 The reference runs one chain in one Python thread; its experiment grid fans chains / settings
 out over processes (driver_utils.py:69-111).  On an MI355X one chain keeps one workgroup (one
@@ -135,6 +135,17 @@ class ChainEnsemble(object):
                are exact, plain MALA); pmmh_stat is refused.  loglik(), score() and acceptance_rate() read the chains'
                estimates and acceptance, last_gradient_statistics() the estimates at the latest proposals; the init
                pass is PMMH's and refuses a chain whose initial log-likelihood or score is not finite)
+               'pgibbs' (extension: particle Gibbs, Andrieu, Doucet and Holenstein 2010, model 'svm' | 'lgssm', dtype 'f64',
+               2 <= N <= 1024, the whole series: a step is one conditional SMC sweep with ancestor sampling (Lindsten,
+               Jordan and Schon 2014; pfg_csmc_device) that replaces each chain's latent path [T] -- the path is part of
+               the chain's state --, then the conjugate draw of the parameters from that path's statistics
+               (pfg_pgibbs_update_device).  The only sampler here that gives latent paths for the nonlinear model.
+               Prior proposal, multinomial resampling at every step; pf, resampling, ess_threshold, kernel='optimal',
+               windows, sequence lists and W > 1 are refused by name, epsilon is ignored.  The constructor runs one
+               unconditional sweep at the initial parameters for the first path (the init pass: counter value 0, step s
+               draws with s + 1).  path(), suff_stats() and n_degenerate() read the chains' paths, the statistics of the
+               latest paths and how often a chain's sweep kept its path because its weights degenerated.  The scratch is
+               C * pfg_csmc_scratch_bytes(T, N) bytes: 10 T N per chain)
       proposal_scale: sampler='pmmh' | 'pmala' (required there, refused elsewhere): the random walk's (the Langevin
                proposal's) standard deviations in raw-theta units, a positive scalar or a length-P vector (LGSSM: C stays 1
                whatever its entry)
@@ -185,7 +196,9 @@ class ChainEnsemble(object):
       _scratch_bytes: the scratch per descriptor of the resolved smoother.
       launch_windows / launch_pf / launch_reduce / launch_update: the launches of a step on one stream (_stream);
                _enqueue_step orders them, step / run / _graph drive them.  sampler='pmmh' | 'pmala': launch_propose
-               before launch_pf, launch_accept as the update; _pmmh_init / _pmala_init is the init pass.
+               before launch_pf, launch_accept as the update; _pmmh_init / _pmala_init is the init pass.  sampler='pgibbs':
+               launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev, static), launch_update the conjugate
+               draw; _pgibbs_init allocates path_dev, the counters and the scratch and runs the init pass.
     """
 
     def __init__(self, model, observations, parameters, num_chains=None, N=1000, pf="poyiadjis_N",
@@ -200,7 +213,8 @@ class ChainEnsemble(object):
             subsequence_length=subsequence_length, buffer_length=buffer_length, dtype=dtype, partition_style=partition_style,
             resampling=resampling, sampler=sampler, window_sampling=window_sampling, kind=kind, num_samples=num_samples,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, accept_reject=accept_reject, minibatch_size=minibatch_size,
-            num_sequences=num_sequences, ess_threshold=ess_threshold, proposal_scale=proposal_scale, pmmh_stat=pmmh_stat)
+            num_sequences=num_sequences, ess_threshold=ess_threshold, proposal_scale=proposal_scale, pmmh_stat=pmmh_stat,
+            kernel=kernel)
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         Parameters, Prior, Helper = _model_info(model)
@@ -286,6 +300,9 @@ class ChainEnsemble(object):
         if sb > 0:       # state in HBM (L2-resident), one slab per descriptor: the large-N kernel, paris_mem1024, Kalman messages
             self.scratch_dev = torch.empty(self._nd * sb, dtype=torch.uint8, device=dev)
         garch_stationary = model == "garch" and self.helper.default_forward_message is None
+        # sampler='pgibbs' launches none of these records (its sweep reads csmc_desc_dev) and N <= 1024 gives them no scratch;
+        # they are kept, C * 376 bytes, because the step, the graph snapshot and enable_stamps address _desc / desc_dev
+        # without asking the sampler
         self._desc = _capi.device_descriptors(
             self._nd, theta=self.theta_prop_dev if self._mh else self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
             scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv, lambduh=self.lambduh, seed=self.seed, N=self.N,
@@ -300,13 +317,15 @@ class ChainEnsemble(object):
             self._pmmh_init()
         if sampler == "pmala":
             self._pmala_init()
+        if sampler == "pgibbs":
+            self._pgibbs_init(pm, pv)
 
     @staticmethod
     def _resolve_settings(model, observations, parameters=None, num_chains=None, N=1000, pf="poyiadjis_N", lambduh=None,
                           subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
                           resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
                           Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                          ess_threshold=None, proposal_scale=None, pmmh_stat=None):
+                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None):
         """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
         device is made here and nowhere else, so it runs (and is tested) without a GPU.
 
@@ -317,11 +336,14 @@ class ChainEnsemble(object):
         ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
         'pmmh' | 'pmala')."""
         tau = None
+        if sampler == "pgibbs":
+            ChainEnsemble._refuse_pgibbs(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind,
+                                         minibatch_size, num_sequences, ess_threshold, kernel)
         if ess_threshold is not None and ess_threshold != 0 and (kind != "pf" or sampler == "gibbs"):
             # (what else adaptive resampling is not built for: resolve_resampling, below)
             raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
-        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala"):
-            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'pmala', 'gibbs' or 'pmmh'")
+        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala", "pgibbs"):
+            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'pgibbs', 'pmala', 'gibbs' or 'pmmh'")
         scale = None
         if sampler not in ("pmmh", "pmala"):
             if proposal_scale is not None:
@@ -365,7 +387,7 @@ class ChainEnsemble(object):
             raise NotImplementedError("kind='{0}' with W = {1} windows per chain and step is not built: "
                                       "the multi-window path is kind='pf' only".format(kind, W))
         explicit = minibatch_size is not None or num_sequences is not None
-        multi = W > 1 or (explicit and kind == "pf" and sampler != "gibbs")
+        multi = W > 1 or (explicit and kind == "pf" and sampler not in ("gibbs", "pgibbs"))
         if sampler == "sgrld" and model != "lgssm":           # sgmcmc_sampler.py:643-646: LGSSM alone has one
             raise NotImplementedError("No Default Preconditioner for {0}: sampler='sgrld' is built for model 'lgssm'".format(
                 dict(svm="SVMSampler", garch="GARCHSampler").get(model, model)))
@@ -505,6 +527,42 @@ class ChainEnsemble(object):
             proposal_scale=scale, kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, M=M, K=K, W=W, multi=multi, S=S, B=B, strict=strict, y=y, T=T,
             segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau)
+
+    @staticmethod
+    def _refuse_pgibbs(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind, minibatch_size,
+                       num_sequences, ess_threshold, kernel):
+        """What sampler='pgibbs' is not built for, each refusal naming its reason (the conditional sweep is one kernel family:
+        SVM and LGSSM, f64, the prior proposal, multinomial resampling at every step, the whole series, N <= 1024)."""
+        what = "sampler='pgibbs' (conditional SMC with ancestor sampling, then the conjugate draw) "
+        if model == "garch":
+            raise NotImplementedError(what + "is built for model 'svm' | 'lgssm': GARCH's prior has no conjugate draw")
+        if dtype != "f64":
+            raise NotImplementedError(what + "is built for dtype 'f64', got '{0}'".format(dtype))
+        if isinstance(observations, (list, tuple)):
+            raise NotImplementedError(what + "samples the path of one series: lists of sequences are not built")
+        if int(subsequence_length) != -1 or int(buffer_length) != -1:
+            raise NotImplementedError(what + "samples the path of the whole series: subsequence_length = buffer_length = -1, "
+                                      "got {0} / {1}".format(int(subsequence_length), int(buffer_length)))
+        M = 1 if minibatch_size is None else int(minibatch_size)
+        K = 1 if num_sequences is None else int(num_sequences)
+        if M != 1 or K != 1:
+            raise NotImplementedError(what + "draws one path per chain and step: W = 1 window (minibatch_size = num_sequences "
+                                      "= 1), got minibatch_size = {0}, num_sequences = {1}".format(M, K))
+        if kind != "pf":
+            raise NotImplementedError(what + "is a particle method: kind='pf', got kind = '{0}'".format(kind))
+        if pf != "poyiadjis_N":
+            raise NotImplementedError(what + "runs its own sweep, no smoother: pf stays at its default, got pf = '{0}'".format(pf))
+        if resampling != "multinomial":
+            raise NotImplementedError(what + "resamples multinomially inside the conditional sweep, got resampling = "
+                                      "'{0}'".format(resampling))
+        if ess_threshold is not None and ess_threshold != 0:
+            raise NotImplementedError(what + "resamples at every step: adaptive resampling (ess_threshold) is not built "
+                                      "inside the conditional sweep")
+        if kernel not in (None, "prior"):
+            raise NotImplementedError(what + "proposes from the prior kernel, got kernel = '{0}'".format(kernel))
+        if not 2 <= int(N) <= _capi.CSMC_MAX_N:
+            raise NotImplementedError(what + "keeps one chain's particles in one workgroup and needs a free particle beside "
+                                      "the reference: 2 <= N <= {0}, got N = {1}".format(_capi.CSMC_MAX_N, int(N)))
 
     @staticmethod
     def _window_counts(observations, minibatch_size, num_sequences):
@@ -664,6 +722,8 @@ class ChainEnsemble(object):
         none: 1) in each of _nd descriptors."""
         if traced and self.kind != "pf":
             raise ValueError("kind='{0}' has no particles to trace".format(self.kind))
+        if self.sampler == "pgibbs":    # the conditional sweep: its own descriptors (traced: the twin that fills their trace_*)
+            return self.launch_csmc(stream, traced=traced)
         if self.ess_threshold:      # adaptive resampling: its own kernels, the family stated at launch level
             return self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.N, self._nd,
                                                    self.desc_dev.data_ptr(), self._stream(stream), traced=traced)
@@ -682,6 +742,8 @@ class ChainEnsemble(object):
             self.ctx.sgrld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
         elif self.sampler == "gibbs":
             self.ctx.gibbs_update_device(*theta, *out, *key)
+        elif self.sampler == "pgibbs":
+            self.ctx.pgibbs_update_device(*theta, *out, *key)
         elif self.sampler == "sghmc":
             self.ctx.sghmc_update_device(*theta, self.momentum_dev.data_ptr(), *out, self.epsilon, self.friction,
                                          float(self.T), *key)
@@ -742,6 +804,49 @@ class ChainEnsemble(object):
         bad = np.flatnonzero(~(np.isfinite(self.ll_dev.cpu().numpy()) & np.all(np.isfinite(used), axis=1)))
         if bad.size:
             raise ValueError("pmala: the initial log-likelihood or score of chain {0} is not finite".format(
+                int(bad[0]) + self.chain_offset))
+
+    def launch_csmc(self, stream=None, traced=False, init=False):
+        """sampler='pgibbs': one conditional SMC sweep with ancestor sampling per chain (pfg_csmc_device): path_dev is replaced,
+        the new paths' statistics land in out_dev.  init: the descriptors with has_ref = 0, an unconditional sweep."""
+        desc = self._csmc_init_desc_dev if init else self.csmc_desc_dev
+        self.ctx.csmc_device(self.model, self.dtype, self.N, self.C, desc.data_ptr(), self.seed ^ 0x43534D43, self.chain_offset,
+                             self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
+
+    def _pgibbs_init(self, prior_mean, prior_var):
+        """The state and the init pass of sampler='pgibbs', the constructor's last act: path_dev [C, T], the counters, the
+        scratch and the pfg_csmc_problem records (static: the step replays in hipGraphs), then one sweep with has_ref = 0 at
+        the initial parameters for the first paths.  It consumes counter value 0: the counter is 1 afterwards."""
+        C, T, N, dev = self.C, self.T, self.N, self.device
+        self.path_dev = torch.zeros((C, T), dtype=torch.float64, device=dev)
+        self.ndeg_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
+        sb = _capi.csmc_scratch_bytes(T, N)
+        try:
+            self.csmc_scratch_dev = torch.empty(C * sb, dtype=torch.uint8, device=dev)
+        except RuntimeError as e:       # (torch.cuda.OutOfMemoryError is one)
+            raise MemoryError("sampler='pgibbs' keeps every chain's particle history in HBM: C * pfg_csmc_scratch_bytes(T, N) = "
+                              "{0} * {1} = {2} bytes ({3:.2f} GB) could not be allocated ({4})".format(
+                                  C, sb, C * sb, C * sb / 1e9, str(e).splitlines()[0])) from e
+        idx = np.arange(C, dtype=np.uint64)
+        d = np.zeros(C, dtype=_capi.CSMC_PROBLEM_DTYPE)
+        d["theta"] = self.theta_dev.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
+        d["y"] = self.y_dev.data_ptr()
+        d["path"] = self.path_dev.data_ptr() + idx * np.uint64(8 * T)
+        d["scratch"] = self.csmc_scratch_dev.data_ptr() + idx * np.uint64(sb)
+        d["out"] = self.out_dev.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
+        d["n_degenerate"] = self.ndeg_dev.data_ptr() + idx * np.uint64(8)
+        d["prior_mean"], d["prior_var"], d["T"], d["N"], d["has_ref"] = prior_mean, prior_var, T, N, 1
+        self._csmc_desc = d
+        self.csmc_desc_dev = torch.from_numpy(d.view(np.uint8).reshape(C, -1)).to(dev)
+        d0 = d.copy()
+        d0["has_ref"] = 0
+        self._csmc_init_desc_dev = torch.from_numpy(d0.view(np.uint8).reshape(C, -1)).to(dev)
+        self.launch_csmc(init=True)
+        self.step_ctr.fill_(1)
+        self.synchronize()
+        bad = np.flatnonzero(self.ndeg_dev.cpu().numpy() != 0)
+        if bad.size:
+            raise ValueError("pgibbs: the particle weights of chain {0} degenerated in the init pass (no first path)".format(
                 int(bad[0]) + self.chain_offset))
 
     def launch_windows(self, stream=None):
@@ -809,6 +914,8 @@ class ChainEnsemble(object):
                 state += (self.theta_prop_dev, self.valid_dev, self.ll_dev, self.accept_dev)
             if self.sampler == "pmala":
                 state += (self.grad_cur_dev,)
+            if self.sampler == "pgibbs":
+                state += (self.path_dev, self.ndeg_dev)
             snap = [t.clone() for t in state]
             self._enqueue_step()
             self.synchronize()
@@ -860,9 +967,18 @@ class ChainEnsemble(object):
         if self.sampler == "pmala":     # ... and so is the score estimate the proposals drift along
             state.update(ll=self.ll_dev.cpu().numpy(), grad=self.grad_cur_dev.cpu().numpy(),
                          n_accept=self.accept_dev.cpu().numpy())
+        if self.sampler == "pgibbs":    # the path is part of a chain's state
+            state.update(sampler="pgibbs", T=self.T, path=self.path_dev.cpu().numpy(), n_degenerate=self.ndeg_dev.cpu().numpy())
         return state
 
     def load_state_dict(self, state):
+        # only 'pgibbs' checkpoints name their sampler and T: a 'pgibbs' ensemble wants both, and no other sampler takes one
+        # (it would drop the path silently)
+        keys = ("sampler", "T") if self.sampler == "pgibbs" else ("sampler",) if state.get("sampler", None) is not None else ()
+        for key in keys:
+            if state.get(key, None) != getattr(self, key):
+                raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(
+                    key, state.get(key, None), getattr(self, key)))
         for key in ("model", "N", "C", "seed", "chain_offset"):
             if state[key] != getattr(self, key):
                 raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(
@@ -878,6 +994,9 @@ class ChainEnsemble(object):
             self.accept_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["n_accept"], dtype=np.int64)))
         if self.sampler == "pmala":
             self.grad_cur_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["grad"], dtype=np.float64)))
+        if self.sampler == "pgibbs":
+            self.path_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["path"], dtype=np.float64)))
+            self.ndeg_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["n_degenerate"], dtype=np.int64)))
         self.steps_done = int(state["steps_done"])       # host window draws are keyed by (seed, chain, steps_done)
         self.synchronize()
 
@@ -920,7 +1039,7 @@ class ChainEnsemble(object):
         T) and None: a sampled path has no log-likelihood estimate.  Multi-window path: the REDUCED records
         (pfg_reduce_windows_device); window_statistics() has the windows'."""
         out = self.out_dev.cpu().numpy()
-        if self.sampler == "gibbs":
+        if self.sampler in ("gibbs", "pgibbs"):     # (pgibbs: the statistics of the latest conditional SMC paths)
             return out[:, :7], None
         if self.sampler == "pmmh":      # no score is computed: (None, the log-likelihood estimates at the latest PROPOSALS)
             return None, out[:, 4]
@@ -938,6 +1057,26 @@ class ChainEnsemble(object):
         if self.sampler != "pmala":
             raise ValueError("score() belongs to sampler='pmala', this ensemble runs '{0}'".format(self.sampler))
         return self.grad_cur_dev[:, :_capi.STAT_DIM[self.model]].cpu().numpy()
+
+    def path(self):
+        """sampler='pgibbs': [C, T] latent paths the chains hold."""
+        self._need_pgibbs("path")
+        return self.path_dev.cpu().numpy()
+
+    def suff_stats(self):
+        """sampler='pgibbs': [C, 7] statistics of the latest paths, as last_gradient_statistics()[0] (SVM: the three transition
+        sums, sum_t y_t^2 exp(-x_t), 0, 0, T)."""
+        self._need_pgibbs("suff_stats")
+        return self.out_dev[:, :7].cpu().numpy()
+
+    def n_degenerate(self):
+        """sampler='pgibbs': [C] sweeps in which a chain kept its path because its weights degenerated."""
+        self._need_pgibbs("n_degenerate")
+        return self.ndeg_dev.cpu().numpy()
+
+    def _need_pgibbs(self, what):
+        if self.sampler != "pgibbs":
+            raise ValueError("{0}() belongs to sampler='pgibbs', this ensemble runs '{1}'".format(what, self.sampler))
 
     def acceptance_rate(self):
         """sampler='pmmh' | 'pmala': [C] accepted proposals / steps done (nan before the first step)."""
