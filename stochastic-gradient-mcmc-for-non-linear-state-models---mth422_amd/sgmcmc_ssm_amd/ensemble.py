@@ -195,10 +195,14 @@ class ChainEnsemble(object):
                null weights pointer, a whole short sequence of a list points at its row of T_total / T_k.
       _scratch_bytes: the scratch per descriptor of the resolved smoother.
       launch_windows / launch_pf / launch_reduce / launch_update: the launches of a step on one stream (_stream);
-               _enqueue_step orders them, step / run / _graph drive them.  sampler='pmmh' | 'pmala': launch_propose
-               before launch_pf, launch_accept as the update; _pmmh_init / _pmala_init is the init pass.  sampler='pgibbs':
-               launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev, static), launch_update the conjugate
-               draw; _pgibbs_init allocates path_dev, the counters and the scratch and runs the init pass.
+               _enqueue_step is the one sequence of them (windows, proposal, filter, reduction, update, each where the
+               sampler and the path have one), step / run / _graph drive it; _update_key keys every update rule.
+               sampler='pmmh' | 'pmala': launch_propose before launch_pf, launch_accept as the update; _mh_init is the init
+               pass of both.  sampler='pgibbs': launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev,
+               static), launch_update the conjugate draw; _pgibbs_init allocates path_dev, the counters and the scratch
+               and runs the init pass.
+      _chain_state: what a chain of the sampler carries beyond theta, the momentum and the counter, and the scratch of a
+               step: the one list state_dict, load_state_dict and _graph's snapshot follow.
     """
 
     def __init__(self, model, observations, parameters, num_chains=None, N=1000, pf="poyiadjis_N",
@@ -313,10 +317,8 @@ class ChainEnsemble(object):
         self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)).to(dev)
         if self._multi and not self._draws:
             self.launch_windows()           # static windows: written once, no draw
-        if sampler == "pmmh":
-            self._pmmh_init()
-        if sampler == "pmala":
-            self._pmala_init()
+        if self._mh:
+            self._mh_init()
         if sampler == "pgibbs":
             self._pgibbs_init(pm, pv)
 
@@ -735,7 +737,7 @@ class ChainEnsemble(object):
 
     def launch_update(self, stream=None):
         theta, out = (self.model, self.C, self.theta_dev.data_ptr()), (self.out_dev.data_ptr(), self.hyper)
-        key = (self.seed ^ 0x5DEECE66D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
+        key = self._update_key(stream)
         if self._mh:
             self.launch_accept(stream)
         elif self.sampler == "sgrld":
@@ -750,7 +752,8 @@ class ChainEnsemble(object):
         else:
             self.ctx.sgld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
 
-    def _pmmh_key(self, stream):
+    def _update_key(self, stream):
+        """What keys the draws of every update rule and says where it runs: seed, first chain id, the counter, the stream."""
         return (self.seed ^ 0x5DEECE66D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
 
     def launch_propose(self, stream=None):
@@ -759,9 +762,9 @@ class ChainEnsemble(object):
         if self.sampler == "pmala":
             return self.ctx.pmala_propose_device(
                 self.model, self.C, self.theta_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
-                self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), self.hyper, *self._pmmh_key(stream))
+                self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), self.hyper, *self._update_key(stream))
         self.ctx.pmmh_propose_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
-                                     self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), *self._pmmh_key(stream))
+                                     self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), *self._update_key(stream))
 
     def launch_accept(self, stream=None, init=False):
         """sampler='pmmh': accept / reject on out_dev[:, 4] and the log-prior; bumps the counter (pfg_pmmh_accept_device).
@@ -770,15 +773,16 @@ class ChainEnsemble(object):
             return self.ctx.pmala_accept_device(
                 self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(), self.valid_dev.data_ptr(),
                 self.out_dev.data_ptr(), self.ll_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.accept_dev.data_ptr(),
-                self.hyper, self.scale_dev.data_ptr(), init, *self._pmmh_key(stream))
+                self.hyper, self.scale_dev.data_ptr(), init, *self._update_key(stream))
         self.ctx.pmmh_accept_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
                                     self.valid_dev.data_ptr(), self.out_dev.data_ptr(), self.ll_dev.data_ptr(),
-                                    self.accept_dev.data_ptr(), self.hyper, init, *self._pmmh_key(stream))
+                                    self.accept_dev.data_ptr(), self.hyper, init, *self._update_key(stream))
 
-    def _pmmh_init(self):
-        """The init pass, the constructor's last act: the launch at the initial parameters, ll_dev = its out[4].  It
-        consumes counter value 0 -- the counter is 1 afterwards, step s (from 0) draws with s + 1 -- so that no step's
-        particle filter repeats the draws the initial estimate was made with."""
+    def _mh_init(self):
+        """The init pass of sampler='pmmh' | 'pmala', the constructor's last act: the launch at the initial parameters, ll_dev =
+        its out[4] (pmala: grad_cur_dev = its out[0..3] as well).  It consumes counter value 0 -- the counter is 1 afterwards,
+        step s (from 0) draws with s + 1 -- so that no step's particle filter repeats the draws the initial estimate was
+        made with."""
         self.theta_prop_dev.copy_(self.theta_dev)
         self.launch_pf()
         if self._multi:
@@ -786,25 +790,14 @@ class ChainEnsemble(object):
         self.launch_accept(init=True)
         self.step_ctr.fill_(1)
         self.synchronize()
-        bad = np.flatnonzero(~np.isfinite(self.ll_dev.cpu().numpy()))
+        finite, what = np.isfinite(self.ll_dev.cpu().numpy()), "log-likelihood"
+        if self.sampler == "pmala":     # ... and the score columns the drift reads
+            used = self.grad_cur_dev.cpu().numpy()[:, list(_PMALA_SCORE_COLUMNS[self.model])]
+            finite, what = finite & np.all(np.isfinite(used), axis=1), "log-likelihood or score"
+        bad = np.flatnonzero(~finite)
         if bad.size:
-            raise ValueError("pmmh: the initial log-likelihood of chain {0} is not finite".format(int(bad[0]) + self.chain_offset))
-
-    def _pmala_init(self):
-        """The init pass of sampler='pmala', as _pmmh_init: the score launch at the initial parameters, ll_dev = its out[4],
-        grad_cur_dev = its out[0..3]; it consumes counter value 0."""
-        self.theta_prop_dev.copy_(self.theta_dev)
-        self.launch_pf()
-        if self._multi:
-            self.launch_reduce()
-        self.launch_accept(init=True)
-        self.step_ctr.fill_(1)
-        self.synchronize()
-        used = self.grad_cur_dev.cpu().numpy()[:, list(_PMALA_SCORE_COLUMNS[self.model])]
-        bad = np.flatnonzero(~(np.isfinite(self.ll_dev.cpu().numpy()) & np.all(np.isfinite(used), axis=1)))
-        if bad.size:
-            raise ValueError("pmala: the initial log-likelihood or score of chain {0} is not finite".format(
-                int(bad[0]) + self.chain_offset))
+            raise ValueError("{0}: the initial {1} of chain {2} is not finite".format(self.sampler, what,
+                                                                                   int(bad[0]) + self.chain_offset))
 
     def launch_csmc(self, stream=None, traced=False, init=False):
         """sampler='pgibbs': one conditional SMC sweep with ancestor sampling per chain (pfg_csmc_device): path_dev is replaced,
@@ -871,24 +864,23 @@ class ChainEnsemble(object):
                                        self._rescale, float(self.T), self.out_dev.data_ptr(), self._stream(stream))
 
     def _enqueue_step(self):
-        pmmh = self._mh       # 'pmmh' | 'pmala' (their windows are static: nothing to draw on either path)
+        """One step: the windows if there are any to draw, the proposal if the sampler has one, the filter, the reduction
+        on the multi-window path, the update."""
+        # who draws them: nobody when they are static ('pmmh' | 'pmala' read the whole data set on either path)
         if self._multi:
-            if self._draws:
-                self.launch_windows()
-            if pmmh:
-                self.launch_propose()
-            self.launch_pf()
-            self.launch_reduce()
-            self.launch_update()
-            return
-        if pmmh:
-            self.launch_propose()
-        elif self.window_sampling == "device":
+            draws = "device" if self._draws else None
+        else:
+            draws = None if self._mh else self.window_sampling
+        if draws == "device":
             self.launch_windows()
-        elif self.steps_done > 0 and self._set_windows():
+        elif draws == "host" and self.steps_done > 0 and self._set_windows():
             self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self.C, -1)),
                                 non_blocking=True)
+        if self._mh:
+            self.launch_propose()
         self.launch_pf()
+        if self._multi:
+            self.launch_reduce()
         self.launch_update()
 
     def step(self, num_steps=1):
@@ -909,13 +901,8 @@ class ChainEnsemble(object):
         if g is None:
             # one eager step first (code-object load, LDS-size attributes), undone afterwards so
             # that building the graph does not advance the chains
-            state = (self.theta_dev, self.momentum_dev, self.step_ctr, self.desc_dev)
-            if self._mh:
-                state += (self.theta_prop_dev, self.valid_dev, self.ll_dev, self.accept_dev)
-            if self.sampler == "pmala":
-                state += (self.grad_cur_dev,)
-            if self.sampler == "pgibbs":
-                state += (self.path_dev, self.ndeg_dev)
+            carried, scratch = self._chain_state()
+            state = [self.theta_dev, self.momentum_dev, self.step_ctr] + scratch + [t for _, t in carried]
             snap = [t.clone() for t in state]
             self._enqueue_step()
             self.synchronize()
@@ -962,14 +949,24 @@ class ChainEnsemble(object):
                      step_ctr=int(self.step_ctr.item()), steps_done=int(self.steps_done),
                      seed=self.seed, chain_offset=self.chain_offset,
                      model=self.model, N=self.N, C=self.C, ess_threshold=self.ess_threshold)
-        if self.sampler == "pmmh":      # the estimate a chain was accepted with is part of its state
-            state.update(ll=self.ll_dev.cpu().numpy(), n_accept=self.accept_dev.cpu().numpy())
-        if self.sampler == "pmala":     # ... and so is the score estimate the proposals drift along
-            state.update(ll=self.ll_dev.cpu().numpy(), grad=self.grad_cur_dev.cpu().numpy(),
-                         n_accept=self.accept_dev.cpu().numpy())
-        if self.sampler == "pgibbs":    # the path is part of a chain's state
-            state.update(sampler="pgibbs", T=self.T, path=self.path_dev.cpu().numpy(), n_degenerate=self.ndeg_dev.cpu().numpy())
+        if self.sampler == "pgibbs":    # (the only checkpoints that name their sampler and T: load_state_dict)
+            state.update(sampler="pgibbs", T=self.T)
+        state.update((key, t.cpu().numpy()) for key, t in self._chain_state()[0])
         return state
+
+    def _chain_state(self):
+        """(carried, scratch).  carried: what a chain of this sampler carries beyond theta, the momentum and the counter, as
+        ordered (checkpoint key, tensor) pairs -- the estimates a 'pmmh' | 'pmala' chain was accepted with and its
+        acceptance count, the path of a 'pgibbs' chain and how often its sweep degenerated.  state_dict and load_state_dict
+        follow it.  scratch: what a step overwrites besides; _graph restores both after its eager step."""
+        carried, scratch = [], [self.desc_dev]
+        if self._mh:
+            grad = [("grad", self.grad_cur_dev)] if self.sampler == "pmala" else []
+            carried = [("ll", self.ll_dev)] + grad + [("n_accept", self.accept_dev)]
+            scratch += [self.theta_prop_dev, self.valid_dev]
+        if self.sampler == "pgibbs":
+            carried = [("path", self.path_dev), ("n_degenerate", self.ndeg_dev)]
+        return carried, scratch
 
     def load_state_dict(self, state):
         # only 'pgibbs' checkpoints name their sampler and T: a 'pgibbs' ensemble wants both, and no other sampler takes one
@@ -989,14 +986,9 @@ class ChainEnsemble(object):
         self.theta_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["theta"])))
         self.momentum_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["momentum"])))
         self.step_ctr.fill_(int(state["step_ctr"]))
-        if self._mh:
-            self.ll_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["ll"], dtype=np.float64)))
-            self.accept_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["n_accept"], dtype=np.int64)))
-        if self.sampler == "pmala":
-            self.grad_cur_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["grad"], dtype=np.float64)))
-        if self.sampler == "pgibbs":
-            self.path_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["path"], dtype=np.float64)))
-            self.ndeg_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["n_degenerate"], dtype=np.int64)))
+        for key, t in self._chain_state()[0]:
+            dtype = np.int64 if t.dtype == torch.int64 else np.float64
+            t.copy_(torch.from_numpy(np.ascontiguousarray(state[key], dtype=dtype)))
         self.steps_done = int(state["steps_done"])       # host window draws are keyed by (seed, chain, steps_done)
         self.synchronize()
 
