@@ -330,8 +330,8 @@ typedef struct pfg_dev_problem {
 } pfg_dev_problem;
 
 int pfg_version(void);
-/* sizeof() of an ABI struct: 0 pfg_problem, 1 pfg_result, 2 pfg_dev_problem, 3 pfg_prior_hyper, 4 pfg_csmc_problem
- * (bindings assert their mirror has the same size) */
+/* sizeof() of an ABI struct: 0 pfg_problem, 1 pfg_result, 2 pfg_dev_problem, 3 pfg_prior_hyper, 4 pfg_csmc_problem,
+ * 5 pfg_cpm_problem (bindings assert their mirror has the same size) */
 int pfg_struct_size(int which);
 int pfg_create(pfg_ctx **out, int device_id);
 void pfg_destroy(pfg_ctx *ctx);
@@ -654,6 +654,52 @@ int pfg_csmc_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const 
 int pfg_pgibbs_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,
                              const pfg_prior_hyper *hyper, uint64_t seed, uint64_t chain_offset,
                              uint64_t *step_ctr, void *hip_stream);
+
+/* EXTENSION (not in the reference): the filter of correlated pseudo-marginal PMMH (Deligiannidis, Doucet and Pitt 2018) for
+ * B resident SVM or LGSSM chains.  The log-likelihood estimate out[4] is a deterministic function of theta and of an array
+ * U [T+1][N+1] of standard normals that the chain carries; a step proposes U' = rho U + sqrt(1 - rho^2) eps beside theta'
+ * and accepts both with pfg_pmmh_accept_device, unchanged.  Particles are sorted by state before each resampling and
+ * resampled systematically on one uniform taken from U', which makes the estimate a smooth function of U; the chain is
+ * exact for every N and every rho in [0, 1).
+ *
+ * pfg_cpm_problem: one chain's filter.  Every pointer is DEVICE memory.  theta: the raw row (PFG_MAX_THETA doubles); y [T];
+ * u0, u1: the chain's two buffers, pfg_cpm_aux_bytes(T, N) bytes each -- row 0, columns 0 .. N-1: the normals of x_{-1};
+ * row t+1, columns 0 .. N-1: the state normals of step t, column N: its resampling normal (column N of rows 0 and 1 is
+ * carried and not read); which: the selector, the kernel reads u[*which & 1], writes U' to the other buffer and filters
+ * on U' (rho == 0 reads no buffer: the init pass); out: PFG_OUT_DOUBLES doubles, out[4] = sum_t log((1 / N) sum_i w_t^i)
+ * with the Gaussian constants of the emission density, every other slot 0.  The target is the law the filters target:
+ * x_{-1} ~ N(prior_mean, prior_var), x_t | x_{t-1} ~ f_theta, weights g_theta(y_t | x_t), prior proposal, resampling at
+ * every step t >= 1.  A weight sum that is zero or not finite: out[4] = -inf (pfg_pmmh_accept_device rejects it), U' is
+ * written in full and stays finite.  A descriptor with a NULL array (the trace pointers may be NULL), T < 1, N < 2 or above
+ * the launch's n_max, or a prior variance that is not positive: a NaN record and no other store.  The trace pointers are
+ * read by a traced launch only: trace_anc [T][N] each child's parent in sorted coordinates (row 0 not written),
+ * trace_ll [T] the per-step increments of out[4].
+ *
+ * pfg_cpm_device: one workgroup per problem, 64 x 2 (one wave) for n_max <= 128, 256 x 4 up to 1024; `problems` is a DEVICE
+ * array of B records, n_max >= every record's N.  eps: Philox4x32-10 keyed by (seed, chain_offset + b, *step_ctr, row,
+ * column) under tags of their own (csrc/pfg_cpm.hip); *step_ctr is read, not incremented.  traced != 0 runs the twin that
+ * honours the trace pointers; both write the same out[4] and the same U', bit for bit.  PFG_ERR_UNSUPPORTED: GARCH, a dtype
+ * other than PFG_F64, n_max > 1024 or < 2; PFG_ERR_INVALID: a bad model id, B < 0, problems == NULL, rho outside [0, 1).
+ *
+ * pfg_cpm_commit_device: one lane per chain, after pfg_pmmh_accept_device: if (init || n_accept[b] != seen[b])
+ * { which[b] ^= 1; seen[b] = n_accept[b]; } -- a chain that accepted now reads the buffer the filter wrote. */
+typedef struct pfg_cpm_problem {
+    const double *theta;
+    const double *y;
+    double *u0;
+    double *u1;
+    const int32_t *which;
+    double *out;
+    int32_t *trace_anc;
+    double *trace_ll;
+    double prior_mean, prior_var;
+    int32_t T, N;
+} pfg_cpm_problem;
+int64_t pfg_cpm_aux_bytes(int T, int N);        /* one buffer, rounded up to 256; -1: T < 1, N < 2 or N > 1024 */
+int pfg_cpm_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_cpm_problem *problems, double rho,
+                   uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced);
+int pfg_cpm_commit_device(pfg_ctx *ctx, int B, const uint64_t *n_accept, uint64_t *seen, int32_t *which, int init,
+                          void *hip_stream);
 
 /* Inverse-multiquadric kernel Stein discrepancy of K points x[K][d] with score estimates
  * g[K][d] (HOST pointers, d <= 8): sqrt(sum_{i,j} k0(x_i,x_j)) / K for

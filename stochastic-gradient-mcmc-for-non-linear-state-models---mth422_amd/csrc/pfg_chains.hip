@@ -9,7 +9,8 @@
 //              0x4D4C0001, 0x4D4C0002    pmala: z0, z1 and z2, z3         0x4D4C0003  uniform53(r.x, r.y) -> u
 //            z_j belongs to theta slot j (SVM A, LQinv, LRinv: z0, z1, z2; LGSSM A, C, LQinv, LRinv: C's z1 is not used by
 //            sgrld, pmmh and pmala; GARCH log_mu, logit_phi, logit_lambduh, LRinv: z0..z3).  All disjoint from one another,
-//            from the window tags 0x53...... / 0x57...... and from the sweep's 0x4353.... (pfg_csmc.hip).
+//            from the window tags 0x53...... / 0x57......, from the sweep's 0x4353.... (pfg_csmc.hip) and from the correlated
+//            filter's 0x43500000 | column >> 2, at most 0x43500100 (pfg_cpm.hip).
 //   drift    d_j(theta, g) = grad_logprior_j(theta) + g_j in theta order, g the score columns of a launch (SVM [LR, LQ,
 //            A], LGSSM [LR, LQ, C, A], GARCH [LR, log_mu, logit_phi, logit_lambduh]).  sgld, sgrld and pmala use it.
 //   project  project_parameters: |A| <= 0.9999, a negative Cholesky factor reflected, LGSSM's C = 1.

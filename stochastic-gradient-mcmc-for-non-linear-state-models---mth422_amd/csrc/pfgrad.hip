@@ -389,6 +389,7 @@ int pfg_struct_size(int which) {
         case 2: return (int)sizeof(pfg_dev_problem);
         case 3: return (int)sizeof(pfg_prior_hyper);
         case 4: return (int)sizeof(pfg_csmc_problem);
+        case 5: return (int)sizeof(pfg_cpm_problem);
     }
     return -1;
 }

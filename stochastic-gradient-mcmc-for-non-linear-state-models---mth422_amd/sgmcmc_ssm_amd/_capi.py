@@ -160,11 +160,26 @@ CSMC_PROBLEM_DTYPE = np.dtype([
 ], align=True)
 CSMC_MAX_N = 1024
 
+# numpy mirror of pfg_cpm_problem (one correlated pseudo-marginal filter; every pointer a device address)
+CPM_PROBLEM_DTYPE = np.dtype([
+    ("theta", "u8"), ("y", "u8"), ("u0", "u8"), ("u1", "u8"), ("which", "u8"), ("out", "u8"),
+    ("trace_anc", "u8"), ("trace_ll", "u8"),
+    ("prior_mean", "f8"), ("prior_var", "f8"),
+    ("T", "i4"), ("N", "i4"),
+], align=True)
+CPM_MAX_N = 1024
+
 
 def csmc_scratch_bytes(T, N):
     """pfg_csmc_scratch_bytes: the states [T][N] f64 and the parents [T][N] uint16 of one chain, rounded up to 256 bytes
     (-1: T < 1, N < 2 or N > 1024).  The library's own answer: the formula is stated once, in pfg_csmc.hip."""
     return int(load_library().pfg_csmc_scratch_bytes(int(T), int(N)))
+
+
+def cpm_aux_bytes(T, N):
+    """pfg_cpm_aux_bytes: one buffer U [T+1][N+1] f64 of one chain, rounded up to 256 bytes (-1: T < 1, N < 2 or N > 1024).
+    The library's own answer: the formula is stated once, in pfg_cpm.hip."""
+    return int(load_library().pfg_cpm_aux_bytes(int(T), int(N)))
 
 
 def device_descriptors(n, *, theta, row, out, step_ctr, scratch, scratch_bytes, stream, prior_mean, prior_var, lambduh, seed,
@@ -199,7 +214,7 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
            "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device",
            "pfg_pmala_propose_device", "pfg_pmala_accept_device", "pfg_csmc_scratch_bytes", "pfg_csmc_device",
-           "pfg_pgibbs_update_device")
+           "pfg_pgibbs_update_device", "pfg_cpm_aux_bytes", "pfg_cpm_device", "pfg_cpm_commit_device")
 
 _lib = None
 
@@ -239,7 +254,8 @@ def load_library():
     lib.pfg_version.restype = C.c_int
     lib.pfg_struct_size.argtypes = [C.c_int]
     lib.pfg_struct_size.restype = C.c_int
-    sizes = (C.sizeof(Problem), C.sizeof(Result), DEV_PROBLEM_DTYPE.itemsize, C.sizeof(PriorHyper), CSMC_PROBLEM_DTYPE.itemsize)
+    sizes = (C.sizeof(Problem), C.sizeof(Result), DEV_PROBLEM_DTYPE.itemsize, C.sizeof(PriorHyper), CSMC_PROBLEM_DTYPE.itemsize,
+             CPM_PROBLEM_DTYPE.itemsize)
     for which, mine in enumerate(sizes):
         if lib.pfg_struct_size(which) != mine:
             raise RuntimeError("ABI mismatch: struct {0} is {1} bytes in libpfgrad.so, {2} in the binding"
@@ -308,6 +324,13 @@ def load_library():
     lib.pfg_csmc_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64,
                                     C.c_void_p, C.c_void_p, C.c_int]
     lib.pfg_csmc_device.restype = C.c_int
+    lib.pfg_cpm_aux_bytes.argtypes = [C.c_int, C.c_int]
+    lib.pfg_cpm_aux_bytes.restype = C.c_int64
+    lib.pfg_cpm_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_uint64,
+                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pfg_cpm_device.restype = C.c_int
+    lib.pfg_cpm_commit_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.pfg_cpm_commit_device.restype = C.c_int
     lib.pfg_logprior_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(PriorHyper), C.c_void_p, C.c_void_p]
     lib.pfg_logprior_device.restype = C.c_int
     lib.pfg_pmmh_propose_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -779,6 +802,23 @@ class Context:
             self.handle, m, d, int(n_max), int(B), C.c_void_p(problems_ptr or 0),
             C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
             C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr)), int(bool(traced))))
+
+    def cpm_device(self, model, dtype, n_max, B, problems_ptr, rho, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0,
+                   traced=False):
+        """pfg_cpm_device: one sorted, correlated filter per pfg_cpm_problem record (a device array): U' = rho U + sqrt(1 -
+        rho^2) eps into the chain's other buffer, out[4] the log-likelihood estimate on U'."""
+        m = model if isinstance(model, int) else MODEL[model]
+        d = dtype if isinstance(dtype, int) else DTYPE[dtype]
+        self._check(self.lib.pfg_cpm_device(
+            self.handle, m, d, int(n_max), int(B), C.c_void_p(problems_ptr or 0), C.c_double(float(rho)),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr)), int(bool(traced))))
+
+    def cpm_commit_device(self, B, n_accept_ptr, seen_ptr, which_ptr, init, stream_ptr=0):
+        """pfg_cpm_commit_device: a chain whose acceptance count moved (init: every chain) flips its buffer selector."""
+        self._check(self.lib.pfg_cpm_commit_device(
+            self.handle, int(B), C.c_void_p(n_accept_ptr or 0), C.c_void_p(seen_ptr or 0), C.c_void_p(which_ptr or 0),
+            int(bool(init)), C.c_void_p(int(stream_ptr))))
 
     def logprior_device(self, model, B, theta_ptr, hyper, logprior_ptr, stream_ptr=0):
         """pfg_logprior_device: logprior[b] = Prior.logprior of the raw row theta[b], up to a constant of the hyper-parameters."""

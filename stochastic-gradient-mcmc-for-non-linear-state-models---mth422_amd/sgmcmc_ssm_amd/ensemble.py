@@ -151,6 +151,20 @@ class ChainEnsemble(object):
                whatever its entry)
       pmmh_stat: sampler='pmmh', kind='pf': None | 'none' (the launch computes no statistic, the default) | 'score' (the
                score launch of the same shape, its score ignored: tools/pmmh_time.py measures one against the other)
+      correlation: sampler='pmmh': None (the default: plain PMMH, today's launches, numbers and state_dict keys) | rho in [0, 1)
+               (extension: the correlated pseudo-marginal method, Deligiannidis, Doucet and Pitt 2018.  The chain keeps the
+               standard normals U [T+1, N+1] its estimate was computed from as part of its state; a step proposes
+               U' = rho U + sqrt(1 - rho^2) eps beside theta' and runs pfg_cpm_device, a filter that is a smooth function of
+               U' -- the particles are sorted by state before each resampling, and resampling is systematic on one uniform
+               taken from U' -- so the two estimates in the accept ratio share most of their noise: at T = 1000, N = 100 the
+               acceptance rises from 0.06 to 0.51 at rho = 0.99.  The accept step is PMMH's, unchanged; a chain that rejects
+               keeps theta, its estimate AND its normals.  U -> U' is reversible with respect to N(0, I) and the estimate is
+               unbiased under it, so the chain is exact for every N and rho; rho = 0 draws fresh normals at every step.
+               Model 'svm' | 'lgssm', dtype 'f64', 2 <= N <= 1024, the whole series, kind 'pf'; pf, resampling,
+               ess_threshold, kernel='optimal', pmmh_stat, windows, sequence lists, W > 1 and every other sampler are
+               refused by name.  aux() reads the normals the chains hold; state_dict carries them ('aux', the current
+               buffer only) with 'correlation' and 'T', and load_state_dict refuses another rho, T or N.  The ensemble keeps
+               two buffers per chain: 2 * C * pfg_cpm_aux_bytes(T, N) bytes, 19.9 GB at T = 1000, N = 100, 12288 chains)
       kind: 'pf' (the particle-filter score) | 'marginal' (LGSSM, dtype 'f64': the exact Kalman score of
                every window, PFG_SMOOTHER_KALMAN -- the reference's kind='marginal', the KF baseline of its
                LGSSM experiment; N, pf and resampling are ignored) | 'complete' (LGSSM, dtype 'f64': the
@@ -198,7 +212,9 @@ class ChainEnsemble(object):
                _enqueue_step is the one sequence of them (windows, proposal, filter, reduction, update, each where the
                sampler and the path have one), step / run / _graph drive it; _update_key keys every update rule.
                sampler='pmmh' | 'pmala': launch_propose before launch_pf, launch_accept as the update; _mh_init is the init
-               pass of both.  sampler='pgibbs': launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev,
+               pass of both.  With correlation set launch_pf is launch_cpm on the pfg_cpm_problem records (cpm_desc_dev, static:
+               _cpm_alloc), launch_accept ends in the commit that flips the selector of a chain that accepted, and _mh_init
+               runs the rho = 0 launch.  sampler='pgibbs': launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev,
                static), launch_update the conjugate draw; _pgibbs_init allocates path_dev, the counters and the scratch
                and runs the init pass.
       _chain_state: what a chain of the sampler carries beyond theta, the momentum and the counter, and the scratch of a
@@ -211,14 +227,14 @@ class ChainEnsemble(object):
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
                  Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                 ess_threshold=None, proposal_scale=None, pmmh_stat=None):
+                 ess_threshold=None, proposal_scale=None, pmmh_stat=None, correlation=None):
         s = self._resolve_settings(
             model, observations, parameters, num_chains=num_chains, N=N, pf=pf, lambduh=lambduh,
             subsequence_length=subsequence_length, buffer_length=buffer_length, dtype=dtype, partition_style=partition_style,
             resampling=resampling, sampler=sampler, window_sampling=window_sampling, kind=kind, num_samples=num_samples,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, accept_reject=accept_reject, minibatch_size=minibatch_size,
             num_sequences=num_sequences, ess_threshold=ess_threshold, proposal_scale=proposal_scale, pmmh_stat=pmmh_stat,
-            kernel=kernel)
+            kernel=kernel, correlation=correlation)
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         Parameters, Prior, Helper = _model_info(model)
@@ -228,6 +244,7 @@ class ChainEnsemble(object):
         self.Ntilde, self.max_accept_reject = s.Ntilde, s.max_accept_reject
         self.resampling, self.sampler, self.friction = resampling, sampler, float(friction)
         self.ess_threshold = s.ess_threshold        # None: resample at every step
+        self.correlation = s.correlation            # None: plain PMMH, a fresh estimate per proposal
         self.window_sampling, self.partition_style, self.strict = window_sampling, partition_style, s.strict
         self._multi, self.W, self.segments, self.T, self.S, self.B = s.multi, s.W, s.segments, s.T, s.S, s.B
         self.P, self.C = s.theta0.shape[1], s.theta0.shape[0]
@@ -317,6 +334,8 @@ class ChainEnsemble(object):
         self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)).to(dev)
         if self._multi and not self._draws:
             self.launch_windows()           # static windows: written once, no draw
+        if self.correlation is not None:
+            self._cpm_alloc(pm, pv)
         if self._mh:
             self._mh_init()
         if sampler == "pgibbs":
@@ -327,7 +346,7 @@ class ChainEnsemble(object):
                           subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
                           resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
                           Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None):
+                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None, correlation=None):
         """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
         device is made here and nowhere else, so it runs (and is tested) without a GPU.
 
@@ -336,8 +355,13 @@ class ChainEnsemble(object):
         Ntilde, max_accept_reject; M, K, W, multi; S, B, strict; y (the concatenated series), T, segments ([K+1] offsets
         into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto;
         ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
-        'pmmh' | 'pmala')."""
+        'pmmh' | 'pmala'); correlation (rho as a float, None unless the correlated pseudo-marginal filter is on)."""
         tau = None
+        if correlation is not None:
+            ChainEnsemble._refuse_correlated(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling,
+                                             sampler, kind, minibatch_size, num_sequences, ess_threshold, kernel, pmmh_stat,
+                                             correlation)
+            correlation = float(correlation)
         if sampler == "pgibbs":
             ChainEnsemble._refuse_pgibbs(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind,
                                          minibatch_size, num_sequences, ess_threshold, kernel)
@@ -528,7 +552,8 @@ class ChainEnsemble(object):
         return types.SimpleNamespace(
             proposal_scale=scale, kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, M=M, K=K, W=W, multi=multi, S=S, B=B, strict=strict, y=y, T=T,
-            segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau)
+            segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau,
+            correlation=correlation)
 
     @staticmethod
     def _refuse_pgibbs(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind, minibatch_size,
@@ -565,6 +590,56 @@ class ChainEnsemble(object):
         if not 2 <= int(N) <= _capi.CSMC_MAX_N:
             raise NotImplementedError(what + "keeps one chain's particles in one workgroup and needs a free particle beside "
                                       "the reference: 2 <= N <= {0}, got N = {1}".format(_capi.CSMC_MAX_N, int(N)))
+
+    @staticmethod
+    def _refuse_correlated(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, sampler, kind,
+                           minibatch_size, num_sequences, ess_threshold, kernel, pmmh_stat, correlation):
+        """What `correlation` is not built for, each refusal naming its reason (the correlated filter is one kernel family: PMMH
+        on SVM and LGSSM, f64, the prior proposal, sorted systematic resampling at every step, the whole series, N <= 1024)."""
+        what = "correlation (correlated pseudo-marginal PMMH: the sorted filter on normals the chain carries) "
+        if sampler != "pmmh":
+            raise NotImplementedError(what + "belongs to sampler='pmmh', got sampler = '{0}'{1}".format(
+                sampler, " (pMALA would need a score that is smooth in the normals as well)" if sampler == "pmala" else ""))
+        if model == "garch":
+            raise NotImplementedError(what + "is built for model 'svm' | 'lgssm': the sort orders a scalar state, GARCH's has two "
+                                      "components")
+        if dtype != "f64":
+            raise NotImplementedError(what + "is built for dtype 'f64', got '{0}'".format(dtype))
+        if isinstance(observations, (list, tuple)):
+            raise NotImplementedError(what + "carries the normals of one series: lists of sequences are not built")
+        if int(subsequence_length) != -1 or int(buffer_length) != -1:
+            raise NotImplementedError(what + "filters the whole series: subsequence_length = buffer_length = -1, got {0} / "
+                                      "{1}".format(int(subsequence_length), int(buffer_length)))
+        M = 1 if minibatch_size is None else int(minibatch_size)
+        K = 1 if num_sequences is None else int(num_sequences)
+        if M != 1 or K != 1:
+            raise NotImplementedError(what + "runs one filter per chain and step: W = 1 window (minibatch_size = num_sequences "
+                                      "= 1), got minibatch_size = {0}, num_sequences = {1}".format(M, K))
+        if kind != "pf":
+            raise NotImplementedError(what + "is a particle method: kind='pf', got kind = '{0}'".format(kind))
+        if pf != "poyiadjis_N":
+            raise NotImplementedError(what + "runs its own filter, no smoother: pf stays at its default, got pf = '{0}'".format(pf))
+        if resampling != "multinomial":
+            raise NotImplementedError(what + "resamples systematically in the order of the states, on a uniform it carries: "
+                                      "resampling stays at its default, got resampling = '{0}'".format(resampling))
+        if ess_threshold is not None and ess_threshold != 0:
+            raise NotImplementedError(what + "resamples at every step: adaptive resampling (ess_threshold) is not built inside "
+                                      "the sorted filter")
+        if kernel not in (None, "prior"):
+            raise NotImplementedError(what + "proposes from the prior kernel, got kernel = '{0}'".format(kernel))
+        if pmmh_stat not in (None, "none"):
+            raise NotImplementedError(what + "computes the log-likelihood estimate alone: pmmh_stat stays at its default, got "
+                                      "pmmh_stat = '{0}'".format(pmmh_stat))
+        if not 2 <= int(N) <= _capi.CPM_MAX_N:
+            raise NotImplementedError(what + "keeps one chain's particles in one workgroup: 2 <= N <= {0}, got N = {1}".format(
+                _capi.CPM_MAX_N, int(N)))
+        try:
+            rho = float(correlation)
+        except (TypeError, ValueError):
+            rho = float("nan")
+        if not 0.0 <= rho < 1.0:        # (false for a NaN as well)
+            raise ValueError("correlation must lie in [0, 1) (rho of U' = rho U + sqrt(1 - rho^2) eps; 0: fresh normals at every "
+                             "step), got {0}".format(correlation))
 
     @staticmethod
     def _window_counts(observations, minibatch_size, num_sequences):
@@ -726,6 +801,8 @@ class ChainEnsemble(object):
             raise ValueError("kind='{0}' has no particles to trace".format(self.kind))
         if self.sampler == "pgibbs":    # the conditional sweep: its own descriptors (traced: the twin that fills their trace_*)
             return self.launch_csmc(stream, traced=traced)
+        if self.correlation is not None:    # the sorted, correlated filter: its own descriptors as well
+            return self.launch_cpm(stream, traced=traced)
         if self.ess_threshold:      # adaptive resampling: its own kernels, the family stated at launch level
             return self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.N, self._nd,
                                                    self.desc_dev.data_ptr(), self._stream(stream), traced=traced)
@@ -777,6 +854,9 @@ class ChainEnsemble(object):
         self.ctx.pmmh_accept_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
                                     self.valid_dev.data_ptr(), self.out_dev.data_ptr(), self.ll_dev.data_ptr(),
                                     self.accept_dev.data_ptr(), self.hyper, init, *self._update_key(stream))
+        if self.correlation is not None:    # a chain that accepted (init: every chain) now reads the buffer the filter wrote
+            self.ctx.cpm_commit_device(self.C, self.accept_dev.data_ptr(), self.seen_dev.data_ptr(), self.which_dev.data_ptr(),
+                                       init, self._stream(stream))
 
     def _mh_init(self):
         """The init pass of sampler='pmmh' | 'pmala', the constructor's last act: the launch at the initial parameters, ll_dev =
@@ -784,7 +864,10 @@ class ChainEnsemble(object):
         step s (from 0) draws with s + 1 -- so that no step's particle filter repeats the draws the initial estimate was
         made with."""
         self.theta_prop_dev.copy_(self.theta_dev)
-        self.launch_pf()
+        if self.correlation is not None:    # fresh normals: rho = 0 reads no buffer
+            self.launch_cpm(init=True)
+        else:
+            self.launch_pf()
         if self._multi:
             self.launch_reduce()
         self.launch_accept(init=True)
@@ -798,6 +881,53 @@ class ChainEnsemble(object):
         if bad.size:
             raise ValueError("{0}: the initial {1} of chain {2} is not finite".format(self.sampler, what,
                                                                                    int(bad[0]) + self.chain_offset))
+
+    def launch_cpm(self, stream=None, traced=False, init=False):
+        """sampler='pmmh' with correlation: one sorted, correlated filter per chain on theta_prop_dev (pfg_cpm_device): U' = rho U +
+        sqrt(1 - rho^2) eps goes to the chain's other buffer, the estimate on U' to out_dev[:, 4].  init: rho = 0."""
+        self.ctx.cpm_device(self.model, self.dtype, self.N, self.C, self.cpm_desc_dev.data_ptr(),
+                            0.0 if init else self.correlation, self.seed ^ 0x43504D4D, self.chain_offset,
+                            self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
+
+    def _cpm_alloc(self, prior_mean, prior_var):
+        """The state of a correlated chain beyond PMMH's: two buffers of normals per chain (aux_dev, [2][C] slabs of
+        pfg_cpm_aux_bytes(T, N) bytes), the selector which_dev, the acceptance count seen_dev the selector was last moved at, and
+        the pfg_cpm_problem records (static: the step replays in hipGraphs).  _mh_init fills the first buffer."""
+        C, T, N, dev = self.C, self.T, self.N, self.device
+        sb = self._aux_bytes = _capi.cpm_aux_bytes(T, N)
+        try:
+            self.aux_dev = torch.zeros(2 * C * sb, dtype=torch.uint8, device=dev)
+        except RuntimeError as e:       # (torch.cuda.OutOfMemoryError is one)
+            raise MemoryError("correlation keeps two buffers of normals per chain in HBM: 2 * C * pfg_cpm_aux_bytes(T, N) = "
+                              "2 * {0} * {1} = {2} bytes ({3:.2f} GB) could not be allocated ({4})".format(
+                                  C, sb, 2 * C * sb, 2 * C * sb / 1e9, str(e).splitlines()[0])) from e
+        self.which_dev = torch.zeros(C, dtype=torch.int32, device=dev)
+        self.which_dev.fill_(1)          # the init pass writes buffer 0 and commits: every chain then reads buffer 0
+        self.seen_dev = torch.zeros(C, dtype=torch.int64, device=dev)        # (the library's uint64 counts)
+        idx = np.arange(C, dtype=np.uint64)
+        d = np.zeros(C, dtype=_capi.CPM_PROBLEM_DTYPE)
+        d["theta"] = self.theta_prop_dev.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
+        d["y"] = self.y_dev.data_ptr()
+        d["u0"] = self.aux_dev.data_ptr() + idx * np.uint64(sb)
+        d["u1"] = self.aux_dev.data_ptr() + (idx + np.uint64(C)) * np.uint64(sb)
+        d["which"] = self.which_dev.data_ptr() + idx * np.uint64(4)
+        d["out"] = self.out_dev.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
+        d["prior_mean"], d["prior_var"], d["T"], d["N"] = prior_mean, prior_var, T, N
+        self._cpm_desc = d
+        self.cpm_desc_dev = torch.from_numpy(d.view(np.uint8).reshape(C, -1)).to(dev)
+
+    def _aux_view(self):
+        """aux_dev as [2, C, doubles per slab]."""
+        return self.aux_dev.view(torch.float64).view(2, self.C, self._aux_bytes // 8)
+
+    def aux(self):
+        """sampler='pmmh' with correlation: [C, T+1, N+1] the normals each chain holds, those its estimate loglik() was
+        computed from."""
+        if self.correlation is None:
+            raise ValueError("aux() belongs to sampler='pmmh' with correlation set")
+        rows = torch.arange(self.C, device=self.device)
+        cur = self._aux_view()[self.which_dev.long() & 1, rows]
+        return cur[:, :(self.T + 1) * (self.N + 1)].reshape(self.C, self.T + 1, self.N + 1).cpu().numpy()
 
     def launch_csmc(self, stream=None, traced=False, init=False):
         """sampler='pgibbs': one conditional SMC sweep with ancestor sampling per chain (pfg_csmc_device): path_dev is replaced,
@@ -952,18 +1082,25 @@ class ChainEnsemble(object):
         if self.sampler == "pgibbs":    # (the only checkpoints that name their sampler and T: load_state_dict)
             state.update(sampler="pgibbs", T=self.T)
         state.update((key, t.cpu().numpy()) for key, t in self._chain_state()[0])
+        if self.correlation is not None:    # the current buffer only (the other one is a step's scratch), and what it belongs to
+            state.update(aux=self.aux(), correlation=self.correlation, T=self.T)
         return state
 
     def _chain_state(self):
         """(carried, scratch).  carried: what a chain of this sampler carries beyond theta, the momentum and the counter, as
         ordered (checkpoint key, tensor) pairs -- the estimates a 'pmmh' | 'pmala' chain was accepted with and its
-        acceptance count, the path of a 'pgibbs' chain and how often its sweep degenerated.  state_dict and load_state_dict
+        acceptance count, the buffer selector of a correlated 'pmmh' chain and the count it was last moved at (its normals
+        travel as 'aux'), the path of a 'pgibbs' chain and how often its sweep degenerated.  state_dict and load_state_dict
         follow it.  scratch: what a step overwrites besides; _graph restores both after its eager step."""
         carried, scratch = [], [self.desc_dev]
         if self._mh:
             grad = [("grad", self.grad_cur_dev)] if self.sampler == "pmala" else []
             carried = [("ll", self.ll_dev)] + grad + [("n_accept", self.accept_dev)]
             scratch += [self.theta_prop_dev, self.valid_dev]
+        if self.correlation is not None:
+            # the selector names the chain's current buffer and a step writes the other one only, so restoring the selector
+            # restores the buffer: _graph copies these two, state_dict and load_state_dict move the current buffer as 'aux'
+            carried += [("which", self.which_dev), ("seen", self.seen_dev)]
         if self.sampler == "pgibbs":
             carried = [("path", self.path_dev), ("n_degenerate", self.ndeg_dev)]
         return carried, scratch
@@ -980,6 +1117,14 @@ class ChainEnsemble(object):
             if state[key] != getattr(self, key):
                 raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(
                     key, state[key], getattr(self, key)))
+        if state.get("correlation", None) != self.correlation:          # (either side may be a plain PMMH chain: None)
+            raise ValueError("checkpoint correlation = {0} does not match the ensemble ({1})".format(
+                state.get("correlation", None), self.correlation))
+        if self.correlation is not None:
+            shape = (self.C, self.T + 1, self.N + 1)
+            if state.get("T", None) != self.T or tuple(np.shape(state["aux"])) != shape:
+                raise ValueError("checkpoint T = {0}, aux {1} does not match the ensemble (T = {2}, aux {3})".format(
+                    state.get("T", None), tuple(np.shape(state["aux"])), self.T, shape))
         if state.get("ess_threshold", None) != self.ess_threshold:      # (checkpoints from before the option: None)
             raise ValueError("checkpoint ess_threshold = {0} does not match the ensemble ({1})".format(
                 state.get("ess_threshold", None), self.ess_threshold))
@@ -987,8 +1132,12 @@ class ChainEnsemble(object):
         self.momentum_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["momentum"])))
         self.step_ctr.fill_(int(state["step_ctr"]))
         for key, t in self._chain_state()[0]:
-            dtype = np.int64 if t.dtype == torch.int64 else np.float64
+            dtype = {torch.int64: np.int64, torch.int32: np.int32}.get(t.dtype, np.float64)
             t.copy_(torch.from_numpy(np.ascontiguousarray(state[key], dtype=dtype)))
+        if self.correlation is not None:    # into the buffer each chain's selector (just loaded) names
+            flat = torch.from_numpy(np.ascontiguousarray(state["aux"], dtype=np.float64).reshape(self.C, -1)).to(self.device)
+            view, rows = self._aux_view(), torch.arange(self.C, device=self.device)
+            view[self.which_dev.long() & 1, rows, :flat.shape[1]] = flat
         self.steps_done = int(state["steps_done"])       # host window draws are keyed by (seed, chain, steps_done)
         self.synchronize()
 
