@@ -1,8 +1,9 @@
 // Every update rule of resident chains, kernels then entry points (pfg_*_update_device): one lane per chain, f64.
 // What the rules share is stated once, ahead of the kernels:
-//   key      make_key: the draws of chain b at one step are Philox4x32-10 of the counter {gid_lo, step_lo, step_hi ^ gid_hi,
-//            tag} under key (seed_lo, seed_hi), gid = chain_offset + b, step = *step_ctr (0 for a NULL counter), so a draw
-//            is a pure function of its key.  normals4 turns two tags into four normals, normal_pair(r.x, r.y) of each.
+//   key      make_key and uniform53 (pfg_chain_filter.hpp, shared with the filters that run one workgroup per chain): the
+//            draws of chain b at one step are Philox4x32-10 of the counter {gid_lo, step_lo, step_hi ^ gid_hi, tag} under
+//            key (seed_lo, seed_hi), gid = chain_offset + b, step = *step_ctr (0 for a NULL counter), so a draw is a pure
+//            function of its key.  normals4 turns two tags into four normals, normal_pair(r.x, r.y) of each.
 //              0x5A11, 0x5A12            sgld / sghmc / sgrld: z0, z1 and z2, z3, one per theta slot
 //              0x61B5vvaa                gibbs / pgibbs: attempt aa of variable vv (0 Qinv, 1 Rinv, 2 A; vv | 0x80 the boost)
 //              0x504D0001, 0x504D0002    pmmh:  z0, z1 and z2, z3         0x504D0003  uniform53(r.x, r.y) -> u in (0, 1)
@@ -70,8 +71,7 @@
 // Built with -ffp-contract=off; IEEE division and ::sqrt / ::log throughout.
 #include <initializer_list>
 
-#include "pfg_host.hpp"
-#include "pfg_math.hpp"
+#include "pfg_chain_filter.hpp"
 
 using namespace pfg_host;
 
@@ -84,24 +84,17 @@ constexpr uint32_t kTagPmmh = 0x504D0000u, kTagPmala = 0x4D4C0000u;        // | 
 constexpr uint32_t kNormals0 = 1u, kNormals1 = 2u, kUniform = 3u;
 
 // ---- the key ----
-struct ChainKey {
-    uint32_t gid, c1, c2, k0, k1;
-    __device__ __forceinline__ pfg::u32x4 draw_tag(uint32_t tag) const { return pfg::philox4x32_10({gid, c1, c2, tag}, k0, k1); }
-    __device__ __forceinline__ pfg::u32x4 draw(uint32_t var, uint32_t attempt) const { return draw_tag(kTagGibbs | (var << 8) | attempt); }
-};
-__device__ __forceinline__ ChainKey make_key(uint64_t seed, uint64_t chain_offset, int b, const uint64_t *step_ctr) {
-    const uint64_t step = step_ctr ? *step_ctr : 0ull;
-    const uint64_t gid = chain_offset + (uint64_t)b;
-    return {(uint32_t)gid, (uint32_t)step, (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)};
+using pfg::ChainKey;
+using pfg::make_key;
+using pfg::uniform53;
+__device__ __forceinline__ pfg::u32x4 gibbs_draw(const ChainKey &key, uint32_t var, uint32_t attempt) {
+    return key.draw_tag(kTagGibbs | (var << 8) | attempt);
 }
 __device__ __forceinline__ void normals4(const ChainKey &key, uint32_t tag0, uint32_t tag1, double *z) {
     const pfg::u32x4 r0 = key.draw_tag(tag0), r1 = key.draw_tag(tag1);
     const pfg::Math<double, false> mth = {};
     mth.normal_pair(r0.x, r0.y, z[0], z[1]);
     mth.normal_pair(r1.x, r1.y, z[2], z[3]);
-}
-__device__ __forceinline__ double uniform53(uint32_t a, uint32_t b) {      // (0, 1)
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6) + 0.5) * (1.0 / 9007199254740992.0);
 }
 
 // ---- the drift ----
@@ -247,7 +240,7 @@ __device__ double gamma_draw(const ChainKey &key, uint32_t var, double shape) {
     const double d = a - 1.0 / 3.0, c = 1.0 / ::sqrt(9.0 * d);
     const pfg::Math<double, false> mth = {};
     for (uint32_t k = 0; k < (uint32_t)kMaxRounds; ++k) {
-        const pfg::u32x4 r = key.draw(var, k);
+        const pfg::u32x4 r = gibbs_draw(key, var, k);
         double z, unused;
         mth.normal_pair(r.x, r.y, z, unused);
         const double t = 1.0 + c * z;
@@ -257,7 +250,7 @@ __device__ double gamma_draw(const ChainKey &key, uint32_t var, double shape) {
         if (::log(u) < 0.5 * z * z + d - d * v + d * ::log(v)) {
             double x = d * v;
             if (boost) {
-                const pfg::u32x4 s = key.draw(var | 0x80u, 0);
+                const pfg::u32x4 s = gibbs_draw(key, var | 0x80u, 0);
                 x *= ::exp(::log(uniform53(s.x, s.y)) / shape);
             }
             return x;
@@ -304,7 +297,7 @@ __global__ void pgibbs_update_kernel(int model, int B, double *__restrict__ thet
     const double Rinv = r_scale * (2.0 * gamma_draw(key, 1, 0.5 * r_df));
     const double LQ = ::sqrt(Qinv), LR = ::sqrt(Rinv);
     // A | Q ~ N(Scp / Spp, 1 / ((LQinv^2 + 1e-9) Spp)) (matrices.py:556-580)
-    const pfg::u32x4 ra = key.draw(2, 0);
+    const pfg::u32x4 ra = gibbs_draw(key, 2, 0);
     double zA, unused;
     const pfg::Math<double, false> mth = {};
     mth.normal_pair(ra.x, ra.y, zA, unused);

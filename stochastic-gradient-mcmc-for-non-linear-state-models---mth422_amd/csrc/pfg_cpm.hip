@@ -13,8 +13,8 @@
 //            never read by the filter.)  A chain owns two buffers u0, u1 and a selector *which: the kernel reads
 //            U = u[*which & 1], writes U' to the other one and filters on U'.  rho == 0 never reads U: the init pass.
 //   eps      entry (row, col): Philox4x32-10 under key (seed_lo, seed_hi), counter {gid_lo, step_lo, row ^ (step_hi ^
-//            gid_hi), 0x43500000 | (col >> 2)}, gid = chain_offset + b, step = *step_ctr -- the chain rules' folding of the
-//            high words (pfg_chains.hip).  One draw r serves four columns: normal_pair(r.x, r.y) -> columns 4q, 4q + 1,
+//            gid_hi), 0x43500000 | (col >> 2)}, gid = chain_offset + b, step = *step_ctr -- the chain key (pfg_chain_filter.hpp)
+//            drawn with the row XORed into the third word.  One draw r serves four columns: normal_pair(r.x, r.y) -> columns 4q, 4q + 1,
 //            normal_pair(r.z, r.w) -> columns 4q + 2, 4q + 3.  Tags 0x43500000 .. 0x43500100: disjoint from every tag
 //            pfg_chains.hip lists.  U' = rho * U + sqrt(1 - rho * rho) * eps (rho == 0: eps itself).
 //   t = 0    x_{-1}^i = prior_mean + sqrt(prior_var) U'[0][i], x_0^i = particle_step(x_{-1}^i, U'[1][i]), lw = log g(y_0 | x_0).
@@ -36,40 +36,13 @@
 // TRACED (the twin a traced launch runs) records, when the pointers are set, each child's parent in sorted coordinates and
 // the per-step increments of out[4]; the production instantiation does not read the trace pointers.  Both write the same
 // out[4] and the same U'.  Built with -ffp-contract=off; ocml exp / log / erfc (no LDS tables).
-#include "pfg_host.hpp"
-#include "pfg_models.hpp"
-#include "pfg_reg_kernel.hpp"
+#include "pfg_chain_filter.hpp"
 
 using namespace pfg_host;
 
 namespace {
 
 constexpr uint32_t kTagCpm = 0x43500000u;      // | column >> 2
-
-struct CpmKey {
-    uint32_t gid, c1, hi, k0, k1;
-    __device__ __forceinline__ pfg::u32x4 draw(int row, int col) const {
-        return pfg::philox4x32_10({gid, c1, (uint32_t)row ^ hi, kTagCpm | ((uint32_t)col >> 2)}, k0, k1);
-    }
-};
-
-// log g(y | x) of a given state: particle_step's expressions (svm/kernels.py:56-62, lgssm/kernels.py:58-62)
-template <int MODEL, typename MATH>
-__device__ __forceinline__ double emission_logw(const pfg::Consts<double> &c, const MATH &mth, double x, double y) {
-    if (MODEL == PFG_MODEL_SVM) return pfg::svm_logw(c, x, mth.exp_finite(-x), y * y);
-    const double diff = y - c.C * x;
-    return (c.c0 + (-0.5 * (diff * diff)) * c.Rinv) + c.logLRinv;
-}
-
-// smallest j in [from, N-1] with cdf[j] > target, N-1 when there is none
-__device__ __forceinline__ int cdf_search(const double *cdf, int N, double target, int from = 0) {
-    int lo = from, hi = N - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cdf[mid] > target) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
 
 // (xa, ia) before (xb, ib) in the order of the sort
 __device__ __forceinline__ bool key_less(double xa, int ia, double xb, int ib) { return xa < xb || (xa == xb && ia < ib); }
@@ -84,15 +57,13 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
     // sorted order; sorted position -> particle
     __shared__ double sx[NMAX], slw[NMAX], cdf[NMAX];
     __shared__ int si[NMAX];
-    __shared__ double red_max[NW], red_sum[NW], u_sh;
+    __shared__ double red_max[1][NW], red_sum[1][NW], u_sh;
 
     const pfg_cpm_problem &P = probs[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & (pfg::WAVE - 1), wave = tid / pfg::WAVE;
+    const int tid = threadIdx.x;
     const int T = P.T, N = P.N;
     const double prior_mean = P.prior_mean, prior_var = P.prior_var;
-    const bool ok = P.theta && P.y && P.u0 && P.u1 && P.which && P.out && T >= 1 && N >= 2 && N <= NMAX && prior_var > 0.0 &&
-                    prior_var < INFINITY && isfinite(prior_mean);
-    if (!ok) {
+    if (!(pfg::chain_filter_usable(P, NMAX) && P.u0 && P.u1 && P.which)) {
         if (tid < PFG_OUT_DOUBLES && P.out) P.out[tid] = NAN;
         return;
     }
@@ -102,10 +73,9 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
     const int cur = *P.which & 1;
     const auto uc = pfg::global_ptr(static_cast<const double *>(cur ? P.u1 : P.u0));
     const auto un = pfg::global_ptr(cur ? P.u0 : P.u1);
-    const uint64_t step = step_ctr ? *step_ctr : 0ull;
-    const uint64_t gid = chain_offset + (uint64_t)blockIdx.x;
-    const CpmKey key{(uint32_t)gid, (uint32_t)step, (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32), (uint32_t)seed,
-                     (uint32_t)(seed >> 32)};
+    const pfg::ChainKey key = pfg::make_key(seed, chain_offset, (int)blockIdx.x, step_ctr);
+    // the draw that holds eps (row, col)
+    auto draw = [&](int row, int col) { return key.draw_at((uint32_t)row, kTagCpm | ((uint32_t)col >> 2)); };
     const int i0 = tid * PPT, ld = N + 1;
     const double srho = ::sqrt(1.0 - rho * rho);
     const double sd0 = ::sqrt(prior_var);
@@ -130,7 +100,7 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
         const bool mine = spare && tid == owner;
         if (i0 < N || mine) {
             const int c0 = mine ? N : i0;
-            const pfg::u32x4 r = key.draw(row, c0);
+            const pfg::u32x4 r = draw(row, c0);
 #pragma unroll
             for (int k = 0; k < PPT; k += 2) {
                 const bool second = ((c0 + k) >> 1) & 1;
@@ -145,7 +115,7 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
             }
         }
         if (!spare && tid == 0) {
-            const pfg::u32x4 r = key.draw(row, N);
+            const pfg::u32x4 r = draw(row, N);
             const bool second = (N >> 1) & 1;
             double ea, eb;
             mth.normal_pair(second ? r.z : r.x, second ? r.w : r.y, ea, eb);
@@ -204,15 +174,8 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
                 sx[i] = INFINITY; slw[i] = -INFINITY; si[i] = i;
             }
         }
-        ma = pfg::wave_max(ma);
-        if (NW > 1) {
-            if (lane == 0) red_max[wave] = ma;
-        }
-        pfg::block_sync<NW>();
-        if (NW > 1) {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) ma = red_max[w] > ma ? red_max[w] : ma;
-        }
+        pfg::block_max(red_max, &ma);
+        if (ONE_WAVE) pfg::block_sync<NW>();      // the keys' stores before the sort's reads (256 x 4: block_max's barrier)
         // (S) the sort: the last step's weights need no order (their sum does not depend on it).  -DPFG_CPM_NO_SORT: a
         // diagnostic build that leaves it out, to time what it costs (tools/cpm_time.py); never the library's
 #ifndef PFG_CPM_NO_SORT
@@ -293,21 +256,8 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
             run += w;
             cs[k] = run;
         }
-        const double inc = pfg::wave_incl_scan(run);
-        double off = inc - run;
-        double W = pfg::bcast_lane63(inc);
-        if (NW > 1) {
-            if (lane == pfg::WAVE - 1) red_sum[wave] = inc;
-            pfg::block_sync<NW>();
-            W = 0.0;
-            double before = 0.0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                if (w == wave) before = W;
-                W += red_sum[w];
-            }
-            off += before;
-        }
+        double off, W;
+        pfg::block_cdf(red_sum, &run, &off, &W);
         // every thread holds the same W: the branch is uniform over the workgroup
         if (!(W > 0.0 && W < INFINITY)) { degenerate = true; break; }
         const double incr = (ma + ::log(W)) - logN;
@@ -329,11 +279,11 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
             if (r >= N) continue;
             const double target = (((double)r + u) / (double)N) * W;
             if (k == 0) {
-                j = cdf_search(cdf, N, target);
+                j = pfg::cdf_search(cdf, N, target);
             } else {
                 int probes = 0;
                 while (probes < 3 && j < N - 1 && !(cdf[j] > target)) { ++j; ++probes; }
-                if (j < N - 1 && !(cdf[j] > target)) j = cdf_search(cdf, N, target, j + 1);
+                if (j < N - 1 && !(cdf[j] > target)) j = pfg::cdf_search(cdf, N, target, j + 1);
             }
             const double xp = sx[j];
             double add[pfg::ModelDims<MODEL>::H];
@@ -348,15 +298,6 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
     if (tid < PFG_OUT_DOUBLES) P.out[tid] = tid == 4 ? (degenerate ? -INFINITY : ll) : 0.0;
 }
 
-template <int MODEL, bool TRACED>
-void launch_shape(int n_max, int B, const pfg_cpm_problem *dp, double rho, uint64_t seed, uint64_t chain_offset,
-                  const uint64_t *step_ctr, hipStream_t st) {
-    if (n_max <= 128)
-        hipLaunchKernelGGL((cpm_kernel<MODEL, 64, 2, TRACED>), dim3((unsigned)B), dim3(64), 0, st, dp, rho, seed, chain_offset, step_ctr);
-    else
-        hipLaunchKernelGGL((cpm_kernel<MODEL, 256, 4, TRACED>), dim3((unsigned)B), dim3(256), 0, st, dp, rho, seed, chain_offset, step_ctr);
-}
-
 // One lane per chain, after the accept step: a chain whose acceptance count moved (or every chain: init) now reads the
 // buffer the filter wrote
 __global__ void cpm_commit_kernel(int B, const uint64_t *__restrict__ n_accept, uint64_t *__restrict__ seen,
@@ -369,35 +310,23 @@ __global__ void cpm_commit_kernel(int B, const uint64_t *__restrict__ n_accept, 
 }  // namespace
 
 int64_t pfg_cpm_aux_bytes(int T, int N) {
-    if (T < 1 || N < 2 || N > 1024) return -1;
-    const int64_t bytes = ((int64_t)T + 1) * ((int64_t)N + 1) * 8;         // U [T+1][N+1] f64
-    return (bytes + 255) / 256 * 256;
+    if (!chain_filter_domain(T, N)) return -1;
+    return round_up_256(((int64_t)T + 1) * ((int64_t)N + 1) * 8);          // U [T+1][N+1] f64
 }
 
 int pfg_cpm_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_cpm_problem *problems, double rho,
                    uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
-    if (!ctx) return PFG_ERR_INVALID;
-    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
-    if (model == PFG_MODEL_GARCH)
-        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(__func__) + ": the correlated filter is built for SVM and LGSSM (the "
-                                              "sort orders a scalar state)");
-    if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(__func__) + ": f64 only");
-    if (n_max > 1024 || n_max < 2)
-        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(__func__) + ": 2 <= N <= 1024 particles (one workgroup per chain), got " +
-                                              std::to_string(n_max));
-    if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
-    if (!problems) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    const int rc = check_chain_filter_launch(ctx, __func__, "the correlated filter is built for SVM and LGSSM (the sort orders a "
+                                             "scalar state)", model, dtype, n_max, B, problems);
+    if (rc != PFG_OK) return rc;
     if (!(rho >= 0.0 && rho < 1.0)) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": rho must lie in [0, 1)");
     if (B == 0) return PFG_OK;
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (model == PFG_MODEL_SVM) {
-        if (traced) launch_shape<PFG_MODEL_SVM, true>(n_max, B, problems, rho, seed, chain_offset, step_ctr, st);
-        else launch_shape<PFG_MODEL_SVM, false>(n_max, B, problems, rho, seed, chain_offset, step_ctr, st);
-    } else {
-        if (traced) launch_shape<PFG_MODEL_LGSSM, true>(n_max, B, problems, rho, seed, chain_offset, step_ctr, st);
-        else launch_shape<PFG_MODEL_LGSSM, false>(n_max, B, problems, rho, seed, chain_offset, step_ctr, st);
-    }
+    dispatch_chain_filter(model, traced != 0, n_max, [&](auto m, auto nt, auto ppt, auto tr) {
+        hipLaunchKernelGGL((cpm_kernel<decltype(m)::value, decltype(nt)::value, decltype(ppt)::value, decltype(tr)::value>),
+                           dim3((unsigned)B), dim3(decltype(nt)::value), 0, (hipStream_t)hip_stream, problems, rho, seed,
+                           chain_offset, step_ctr);
+    });
     PFG_HIP(ctx, hipGetLastError());
     return PFG_OK;
 }

@@ -22,8 +22,8 @@
 //            has_ref = 0 there is no path to keep: the record is NaN.  A descriptor that is invalid (a NULL array, T < 1, N
 //            outside [2, the launch's shape], a prior variance that is not positive) gets a NaN record and the count too.
 // Draws: Philox4x32-10 under key (seed_lo, seed_hi), counter {gid_lo, step_lo, t ^ (step_hi ^ gid_hi), tag}, gid =
-// chain_offset + b, step = *step_ctr -- the chain rules' folding of the high words (pfg_chains.hip), with the time step in
-// the third word and the particle in the tag:
+// chain_offset + b, step = *step_ctr -- the chain key (pfg_chain_filter.hpp), drawn with the time step XORed into the third
+// word and the particle in the tag:
 //   0x43530000 | i  free particle i.  t = 0: normal_pair(r.x, r.y) -> the normals of x_{-1} and x_0;
 //                   t >= 1: uniform53(r.x, r.y) -> its resampling uniform, normal_pair(r.z, r.w) -> z, the first: its state normal
 //   0x43531000      uniform53(r.x, r.y) -> the ancestor-sampling uniform of step t
@@ -31,9 +31,7 @@
 // Disjoint from every tag pfg_chains.hip lists.  TRACED (the twin a traced launch runs) records, when the pointers are set,
 // every particle's parent, the reference particle's sampled ancestor, the normalised weights and k; the production
 // instantiation does not read the trace pointers.  Built with -ffp-contract=off; ocml exp / log (no LDS tables).
-#include "pfg_host.hpp"
-#include "pfg_models.hpp"
-#include "pfg_reg_kernel.hpp"
+#include "pfg_chain_filter.hpp"
 
 using namespace pfg_host;
 
@@ -41,35 +39,6 @@ namespace {
 
 constexpr uint32_t kTagParticle = 0x43530000u, kTagAncestor = 0x43531000u, kTagFinal = 0x43532000u;
 constexpr int kHistEntries = 8192;      // parents kept in LDS: 16 KB
-
-struct CsmcKey {
-    uint32_t gid, c1, hi, k0, k1;
-    __device__ __forceinline__ pfg::u32x4 draw(int t, uint32_t tag) const {
-        return pfg::philox4x32_10({gid, c1, (uint32_t)t ^ hi, tag}, k0, k1);
-    }
-};
-
-__device__ __forceinline__ double uniform53(uint32_t a, uint32_t b) {      // (0, 1), as the chain rules'
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-}
-
-// log g(y | x) of a given state: particle_step's expressions (svm/kernels.py:56-62, lgssm/kernels.py:58-62)
-template <int MODEL, typename MATH>
-__device__ __forceinline__ double emission_logw(const pfg::Consts<double> &c, const MATH &mth, double x, double y) {
-    if (MODEL == PFG_MODEL_SVM) return pfg::svm_logw(c, x, mth.exp_finite(-x), y * y);
-    const double diff = y - c.C * x;
-    return (c.c0 + (-0.5 * (diff * diff)) * c.Rinv) + c.logLRinv;
-}
-
-// smallest j in [0, N-1] with cdf[j] > target, N-1 when there is none
-__device__ __forceinline__ int cdf_search(const double *cdf, int N, double target) {
-    int lo = 0, hi = N - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cdf[mid] > target) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
 
 template <int MODEL, int NT, int PPT, bool TRACED>
 __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__restrict__ probs, uint64_t seed,
@@ -80,13 +49,11 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
     __shared__ uint16_t hist[kHistEntries];
 
     const pfg_csmc_problem &P = probs[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & (pfg::WAVE - 1), wave = tid / pfg::WAVE;
+    const int tid = threadIdx.x;
     const int T = P.T, N = P.N;
     const bool has_ref = P.has_ref != 0;
     const double prior_mean = P.prior_mean, prior_var = P.prior_var;
-    const bool ok = P.theta && P.y && P.scratch && P.out && P.n_degenerate && P.path && T >= 1 && N >= 2 &&
-                    N <= NMAX && prior_var > 0.0 && prior_var < INFINITY && isfinite(prior_mean);
-    if (!ok) {
+    if (!(pfg::chain_filter_usable(P, NMAX) && P.scratch && P.n_degenerate && P.path)) {
         if (tid < PFG_OUT_DOUBLES && P.out) P.out[tid] = NAN;
         if (tid == 0 && P.n_degenerate) *P.n_degenerate += 1;
         return;
@@ -98,10 +65,7 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
     const auto sx = pfg::global_ptr(static_cast<double *>(P.scratch));
     const auto sa = pfg::global_ptr(reinterpret_cast<uint16_t *>(static_cast<double *>(P.scratch) + (size_t)T * N));
     const bool hist_lds = (size_t)T * N <= (size_t)kHistEntries;
-    const uint64_t step = step_ctr ? *step_ctr : 0ull;
-    const uint64_t gid = chain_offset + (uint64_t)blockIdx.x;
-    const CsmcKey key{(uint32_t)gid, (uint32_t)step, (uint32_t)(step >> 32) ^ (uint32_t)(gid >> 32), (uint32_t)seed,
-                      (uint32_t)(seed >> 32)};
+    const pfg::ChainKey key = pfg::make_key(seed, chain_offset, (int)blockIdx.x, step_ctr);
     const int i0 = tid * PPT;
     const int ref_i = has_ref ? N - 1 : -1;      // the reference particle's index (none: every particle is free)
     const double sd0 = ::sqrt(prior_var);
@@ -117,9 +81,9 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
             if (i >= N) continue;
             if (i == ref_i) {
                 x[k] = ref[0];
-                lw[k] = emission_logw<MODEL>(c, mth, x[k], y0);
+                lw[k] = pfg::emission_logw<MODEL>(c, mth, x[k], y0);
             } else {
-                const pfg::u32x4 r = key.draw(0, kTagParticle | (uint32_t)i);
+                const pfg::u32x4 r = key.draw_at(0, kTagParticle | (uint32_t)i);
                 double za, zb, add[pfg::ModelDims<MODEL>::H];
                 mth.normal_pair(r.x, r.y, za, zb);
                 const double xm1 = prior_mean + sd0 * za;
@@ -136,54 +100,31 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
         const bool anc_step = has_ref && t < T;
         const double xstar = anc_step ? ref[t] : 0.0;
         // (A) the two maxima, one reduction
-        double l2[PPT], ma = -INFINITY, mb = -INFINITY;
+        double l2[PPT], m[2] = {-INFINITY, -INFINITY};
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             l2[k] = -INFINITY;
             if (i0 + k >= N) continue;
-            ma = lw[k] > ma ? lw[k] : ma;
+            m[0] = lw[k] > m[0] ? lw[k] : m[0];
             if (anc_step) {
                 l2[k] = lw[k] + pfg::backward_log_ratio<MODEL>(c, mth, &x[k], &xstar);
-                mb = l2[k] > mb ? l2[k] : mb;
+                m[1] = l2[k] > m[1] ? l2[k] : m[1];
             }
         }
-        ma = pfg::wave_max(ma);
-        if (anc_step) mb = pfg::wave_max(mb);
-        if (NW > 1) {
-            if (lane == 0) { red_max[0][wave] = ma; red_max[1][wave] = mb; }
-            pfg::block_sync<NW>();
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                ma = red_max[0][w] > ma ? red_max[0][w] : ma;
-                mb = red_max[1][w] > mb ? red_max[1][w] : mb;
-            }
-        }
+        pfg::block_max(red_max, m, anc_step);
         // (B) the two CDFs: a thread's running sums, one scan of the threads' totals
-        double wv[PPT], cs[PPT], cv[PPT], run = 0.0, runv = 0.0;
+        double wv[PPT], cs[PPT], cv[PPT], run[2] = {0.0, 0.0}, off[2], tot[2];
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const bool valid = i0 + k < N;
-            wv[k] = valid ? mth.exp(lw[k] - ma) : 0.0;
-            run += wv[k];
-            cs[k] = run;
-            if (anc_step) runv += valid ? mth.exp(l2[k] - mb) : 0.0;
-            cv[k] = runv;
+            wv[k] = valid ? mth.exp(lw[k] - m[0]) : 0.0;
+            run[0] += wv[k];
+            cs[k] = run[0];
+            if (anc_step) run[1] += valid ? mth.exp(l2[k] - m[1]) : 0.0;
+            cv[k] = run[1];
         }
-        const double inc = pfg::wave_incl_scan(run), incv = anc_step ? pfg::wave_incl_scan(runv) : 0.0;
-        double off = inc - run, offv = incv - runv;
-        double W = pfg::bcast_lane63(inc), V = pfg::bcast_lane63(incv);
-        if (NW > 1) {
-            if (lane == pfg::WAVE - 1) { red_sum[0][wave] = inc; red_sum[1][wave] = incv; }
-            pfg::block_sync<NW>();
-            W = 0.0; V = 0.0;
-            double before = 0.0, beforev = 0.0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                if (w == wave) { before = W; beforev = V; }
-                W += red_sum[0][w]; V += red_sum[1][w];
-            }
-            off += before; offv += beforev;
-        }
+        pfg::block_cdf(red_sum, run, off, tot, anc_step);
+        const double W = tot[0], V = tot[1];
         // every thread holds the same W and V: the branch is uniform over the workgroup
         if (!(W > 0.0 && W < INFINITY) || (anc_step && !(V > 0.0 && V < INFINITY))) { degenerate = true; break; }
 #pragma unroll
@@ -191,8 +132,8 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
             const int i = i0 + k;
             if (i >= N) continue;
             xs[i] = x[k];
-            cdf[i] = cs[k] + off;
-            if (anc_step) cdf2[i] = cv[k] + offv;
+            cdf[i] = cs[k] + off[0];
+            if (anc_step) cdf2[i] = cv[k] + off[1];
             if (TRACED && P.trace_w) P.trace_w[(size_t)(t - 1) * N + i] = wv[k] / W;
         }
         pfg::block_sync<NW>();
@@ -206,14 +147,14 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
             int j;
             double xn, lwn;
             if (i == ref_i) {
-                const pfg::u32x4 r = key.draw(t, kTagAncestor);
-                j = cdf_search(cdf2, N, uniform53(r.x, r.y) * V);
+                const pfg::u32x4 r = key.draw_at(t, kTagAncestor);
+                j = pfg::cdf_search(cdf2, N, pfg::uniform53(r.x, r.y) * V);
                 xn = xstar;
-                lwn = emission_logw<MODEL>(c, mth, xn, yt);
+                lwn = pfg::emission_logw<MODEL>(c, mth, xn, yt);
                 if (TRACED && P.trace_ref_anc) P.trace_ref_anc[t] = j;
             } else {
-                const pfg::u32x4 r = key.draw(t, kTagParticle | (uint32_t)i);
-                j = cdf_search(cdf, N, uniform53(r.x, r.y) * W);
+                const pfg::u32x4 r = key.draw_at(t, kTagParticle | (uint32_t)i);
+                j = pfg::cdf_search(cdf, N, pfg::uniform53(r.x, r.y) * W);
                 const double xp = xs[j];
                 double z, unused, add[pfg::ModelDims<MODEL>::H];
                 mth.normal_pair(r.z, r.w, z, unused);
@@ -242,8 +183,8 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
     }
     int kk = 0;
     if (!degenerate) {
-        const pfg::u32x4 r = key.draw(T, kTagFinal);
-        kk = cdf_search(cdf, N, uniform53(r.x, r.y) * Wlast);
+        const pfg::u32x4 r = key.draw_at(T, kTagFinal);
+        kk = pfg::cdf_search(cdf, N, pfg::uniform53(r.x, r.y) * Wlast);
         if (TRACED && P.trace_k) P.trace_k[0] = kk;
     }
     // x'_t, t descending: the recorded lineage (written over the path), or the path the chain keeps
@@ -280,46 +221,24 @@ __global__ __launch_bounds__(NT) void csmc_kernel(const pfg_csmc_problem *__rest
     out[7] = 0.0;
 }
 
-template <int MODEL, bool TRACED>
-void launch_shape(int n_max, int B, const pfg_csmc_problem *dp, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr,
-                  hipStream_t st) {
-    if (n_max <= 128)
-        hipLaunchKernelGGL((csmc_kernel<MODEL, 64, 2, TRACED>), dim3((unsigned)B), dim3(64), 0, st, dp, seed, chain_offset, step_ctr);
-    else
-        hipLaunchKernelGGL((csmc_kernel<MODEL, 256, 4, TRACED>), dim3((unsigned)B), dim3(256), 0, st, dp, seed, chain_offset, step_ctr);
-}
-
 }  // namespace
 
 int64_t pfg_csmc_scratch_bytes(int T, int N) {
-    if (T < 1 || N < 2 || N > 1024) return -1;
-    const int64_t bytes = (int64_t)T * (int64_t)N * 10;         // states f64 [T][N], then parents u16 [T][N]
-    return (bytes + 255) / 256 * 256;
+    if (!chain_filter_domain(T, N)) return -1;
+    return round_up_256((int64_t)T * (int64_t)N * 10);          // states f64 [T][N], then parents u16 [T][N]
 }
 
 int pfg_csmc_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_csmc_problem *problems, uint64_t seed,
                     uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
-    if (!ctx) return PFG_ERR_INVALID;
-    if (model < 0 || model > 2) return fail(ctx, PFG_ERR_INVALID, "Unrecognized model id");
-    if (model == PFG_MODEL_GARCH)
-        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(__func__) + ": the conditional sweep is built for SVM and LGSSM (GARCH's "
-                                              "prior has no conjugate draw to pair it with)");
-    if (dtype != PFG_F64) return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(__func__) + ": f64 only");
-    if (n_max > 1024 || n_max < 2)
-        return fail(ctx, PFG_ERR_UNSUPPORTED, std::string(__func__) + ": 2 <= N <= 1024 particles (one workgroup per chain), got " +
-                                              std::to_string(n_max));
-    if (B < 0) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": B must be >= 0");
-    if (!problems) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
-    if (B == 0) return PFG_OK;
+    const int rc = check_chain_filter_launch(ctx, __func__, "the conditional sweep is built for SVM and LGSSM (GARCH's prior has "
+                                             "no conjugate draw to pair it with)", model, dtype, n_max, B, problems);
+    if (rc != PFG_OK || B == 0) return rc;
     PFG_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (model == PFG_MODEL_SVM) {
-        if (traced) launch_shape<PFG_MODEL_SVM, true>(n_max, B, problems, seed, chain_offset, step_ctr, st);
-        else launch_shape<PFG_MODEL_SVM, false>(n_max, B, problems, seed, chain_offset, step_ctr, st);
-    } else {
-        if (traced) launch_shape<PFG_MODEL_LGSSM, true>(n_max, B, problems, seed, chain_offset, step_ctr, st);
-        else launch_shape<PFG_MODEL_LGSSM, false>(n_max, B, problems, seed, chain_offset, step_ctr, st);
-    }
+    dispatch_chain_filter(model, traced != 0, n_max, [&](auto m, auto nt, auto ppt, auto tr) {
+        hipLaunchKernelGGL((csmc_kernel<decltype(m)::value, decltype(nt)::value, decltype(ppt)::value, decltype(tr)::value>),
+                           dim3((unsigned)B), dim3(decltype(nt)::value), 0, (hipStream_t)hip_stream, problems, seed, chain_offset,
+                           step_ctr);
+    });
     PFG_HIP(ctx, hipGetLastError());
     return PFG_OK;
 }

@@ -358,13 +358,13 @@ class ChainEnsemble(object):
         'pmmh' | 'pmala'); correlation (rho as a float, None unless the correlated pseudo-marginal filter is on)."""
         tau = None
         if correlation is not None:
-            ChainEnsemble._refuse_correlated(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling,
-                                             sampler, kind, minibatch_size, num_sequences, ess_threshold, kernel, pmmh_stat,
-                                             correlation)
+            ChainEnsemble._refuse_correlated(sampler, pmmh_stat, correlation, model, observations, N, pf, subsequence_length,
+                                             buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
+                                             kernel)
             correlation = float(correlation)
         if sampler == "pgibbs":
-            ChainEnsemble._refuse_pgibbs(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind,
-                                         minibatch_size, num_sequences, ess_threshold, kernel)
+            ChainEnsemble._refuse_chain_filter("pgibbs", model, observations, N, pf, subsequence_length, buffer_length, dtype,
+                                               resampling, kind, minibatch_size, num_sequences, ess_threshold, kernel)
         if ess_threshold is not None and ess_threshold != 0 and (kind != "pf" or sampler == "gibbs"):
             # (what else adaptive resampling is not built for: resolve_resampling, below)
             raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
@@ -555,84 +555,75 @@ class ChainEnsemble(object):
             segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau,
             correlation=correlation)
 
-    @staticmethod
-    def _refuse_pgibbs(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind, minibatch_size,
-                       num_sequences, ess_threshold, kernel):
-        """What sampler='pgibbs' is not built for, each refusal naming its reason (the conditional sweep is one kernel family:
-        SVM and LGSSM, f64, the prior proposal, multinomial resampling at every step, the whole series, N <= 1024)."""
-        what = "sampler='pgibbs' (conditional SMC with ancestor sampling, then the conjugate draw) "
-        if model == "garch":
-            raise NotImplementedError(what + "is built for model 'svm' | 'lgssm': GARCH's prior has no conjugate draw")
-        if dtype != "f64":
-            raise NotImplementedError(what + "is built for dtype 'f64', got '{0}'".format(dtype))
-        if isinstance(observations, (list, tuple)):
-            raise NotImplementedError(what + "samples the path of one series: lists of sequences are not built")
-        if int(subsequence_length) != -1 or int(buffer_length) != -1:
-            raise NotImplementedError(what + "samples the path of the whole series: subsequence_length = buffer_length = -1, "
-                                      "got {0} / {1}".format(int(subsequence_length), int(buffer_length)))
-        M = 1 if minibatch_size is None else int(minibatch_size)
-        K = 1 if num_sequences is None else int(num_sequences)
-        if M != 1 or K != 1:
-            raise NotImplementedError(what + "draws one path per chain and step: W = 1 window (minibatch_size = num_sequences "
-                                      "= 1), got minibatch_size = {0}, num_sequences = {1}".format(M, K))
-        if kind != "pf":
-            raise NotImplementedError(what + "is a particle method: kind='pf', got kind = '{0}'".format(kind))
-        if pf != "poyiadjis_N":
-            raise NotImplementedError(what + "runs its own sweep, no smoother: pf stays at its default, got pf = '{0}'".format(pf))
-        if resampling != "multinomial":
-            raise NotImplementedError(what + "resamples multinomially inside the conditional sweep, got resampling = "
-                                      "'{0}'".format(resampling))
-        if ess_threshold is not None and ess_threshold != 0:
-            raise NotImplementedError(what + "resamples at every step: adaptive resampling (ess_threshold) is not built "
-                                      "inside the conditional sweep")
-        if kernel not in (None, "prior"):
-            raise NotImplementedError(what + "proposes from the prior kernel, got kernel = '{0}'".format(kernel))
-        if not 2 <= int(N) <= _capi.CSMC_MAX_N:
-            raise NotImplementedError(what + "keeps one chain's particles in one workgroup and needs a free particle beside "
-                                      "the reference: 2 <= N <= {0}, got N = {1}".format(_capi.CSMC_MAX_N, int(N)))
+    # What differs between the refusals of the two kernel families that run one workgroup per chain (_refuse_chain_filter):
+    # the prefix, the reason clause of each shared check, the largest N.
+    _CHAIN_FILTERS = {
+        "pgibbs": dict(
+            what="sampler='pgibbs' (conditional SMC with ancestor sampling, then the conjugate draw) ",
+            garch="GARCH's prior has no conjugate draw", lists="samples the path of one series",
+            whole="samples the path of the whole series", window="draws one path per chain and step", own="sweep",
+            resampling="resamples multinomially inside the conditional sweep", inside="the conditional sweep",
+            particles=" and needs a free particle beside the reference", max_n=_capi.CSMC_MAX_N),
+        "correlation": dict(
+            what="correlation (correlated pseudo-marginal PMMH: the sorted filter on normals the chain carries) ",
+            garch="the sort orders a scalar state, GARCH's has two components", lists="carries the normals of one series",
+            whole="filters the whole series", window="runs one filter per chain and step", own="filter",
+            resampling="resamples systematically in the order of the states, on a uniform it carries: resampling stays at its "
+                       "default", inside="the sorted filter", particles="", max_n=_capi.CPM_MAX_N),
+    }
 
     @staticmethod
-    def _refuse_correlated(model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, sampler, kind,
-                           minibatch_size, num_sequences, ess_threshold, kernel, pmmh_stat, correlation):
-        """What `correlation` is not built for, each refusal naming its reason (the correlated filter is one kernel family: PMMH
-        on SVM and LGSSM, f64, the prior proposal, sorted systematic resampling at every step, the whole series, N <= 1024)."""
-        what = "correlation (correlated pseudo-marginal PMMH: the sorted filter on normals the chain carries) "
-        if sampler != "pmmh":
-            raise NotImplementedError(what + "belongs to sampler='pmmh', got sampler = '{0}'{1}".format(
-                sampler, " (pMALA would need a score that is smooth in the normals as well)" if sampler == "pmala" else ""))
+    def _refuse_chain_filter(family, model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind,
+                             minibatch_size, num_sequences, ess_threshold, kernel, also=()):
+        """What sampler='pgibbs' and `correlation` are not built for, each refusal naming its reason: either is one kernel
+        family with one workgroup per chain -- SVM and LGSSM, f64, the prior proposal, its own resampling at every step, the
+        whole series, N <= 1024.  family: a key of _CHAIN_FILTERS.  also: (refused, reason) pairs of the family's own, checked
+        ahead of N."""
+        f = ChainEnsemble._CHAIN_FILTERS[family]
+        what = f["what"]
         if model == "garch":
-            raise NotImplementedError(what + "is built for model 'svm' | 'lgssm': the sort orders a scalar state, GARCH's has two "
-                                      "components")
+            raise NotImplementedError(what + "is built for model 'svm' | 'lgssm': " + f["garch"])
         if dtype != "f64":
             raise NotImplementedError(what + "is built for dtype 'f64', got '{0}'".format(dtype))
         if isinstance(observations, (list, tuple)):
-            raise NotImplementedError(what + "carries the normals of one series: lists of sequences are not built")
+            raise NotImplementedError(what + f["lists"] + ": lists of sequences are not built")
         if int(subsequence_length) != -1 or int(buffer_length) != -1:
-            raise NotImplementedError(what + "filters the whole series: subsequence_length = buffer_length = -1, got {0} / "
-                                      "{1}".format(int(subsequence_length), int(buffer_length)))
+            raise NotImplementedError(what + f["whole"] + ": subsequence_length = buffer_length = -1, got {0} / {1}".format(
+                int(subsequence_length), int(buffer_length)))
         M = 1 if minibatch_size is None else int(minibatch_size)
         K = 1 if num_sequences is None else int(num_sequences)
         if M != 1 or K != 1:
-            raise NotImplementedError(what + "runs one filter per chain and step: W = 1 window (minibatch_size = num_sequences "
-                                      "= 1), got minibatch_size = {0}, num_sequences = {1}".format(M, K))
+            raise NotImplementedError(what + f["window"] + ": W = 1 window (minibatch_size = num_sequences = 1), got "
+                                      "minibatch_size = {0}, num_sequences = {1}".format(M, K))
         if kind != "pf":
             raise NotImplementedError(what + "is a particle method: kind='pf', got kind = '{0}'".format(kind))
         if pf != "poyiadjis_N":
-            raise NotImplementedError(what + "runs its own filter, no smoother: pf stays at its default, got pf = '{0}'".format(pf))
+            raise NotImplementedError(what + "runs its own {0}, no smoother: pf stays at its default, got pf = '{1}'".format(
+                f["own"], pf))
         if resampling != "multinomial":
-            raise NotImplementedError(what + "resamples systematically in the order of the states, on a uniform it carries: "
-                                      "resampling stays at its default, got resampling = '{0}'".format(resampling))
+            raise NotImplementedError(what + f["resampling"] + ", got resampling = '{0}'".format(resampling))
         if ess_threshold is not None and ess_threshold != 0:
-            raise NotImplementedError(what + "resamples at every step: adaptive resampling (ess_threshold) is not built inside "
-                                      "the sorted filter")
+            raise NotImplementedError(what + "resamples at every step: adaptive resampling (ess_threshold) is not built inside " +
+                                      f["inside"])
         if kernel not in (None, "prior"):
             raise NotImplementedError(what + "proposes from the prior kernel, got kernel = '{0}'".format(kernel))
-        if pmmh_stat not in (None, "none"):
-            raise NotImplementedError(what + "computes the log-likelihood estimate alone: pmmh_stat stays at its default, got "
-                                      "pmmh_stat = '{0}'".format(pmmh_stat))
-        if not 2 <= int(N) <= _capi.CPM_MAX_N:
-            raise NotImplementedError(what + "keeps one chain's particles in one workgroup: 2 <= N <= {0}, got N = {1}".format(
-                _capi.CPM_MAX_N, int(N)))
+        for refused, reason in also:
+            if refused:
+                raise NotImplementedError(what + reason)
+        if not 2 <= int(N) <= f["max_n"]:
+            raise NotImplementedError(what + "keeps one chain's particles in one workgroup{0}: 2 <= N <= {1}, got N = {2}".format(
+                f["particles"], f["max_n"], int(N)))
+
+    @staticmethod
+    def _refuse_correlated(sampler, pmmh_stat, correlation, *shared):
+        """`correlation`: the sampler it belongs to, then the shared refusals (with pmmh_stat's ahead of N), then rho's range."""
+        if sampler != "pmmh":
+            raise NotImplementedError(ChainEnsemble._CHAIN_FILTERS["correlation"]["what"] + "belongs to sampler='pmmh', got "
+                                      "sampler = '{0}'{1}".format(sampler, " (pMALA would need a score that is smooth in the "
+                                                                  "normals as well)" if sampler == "pmala" else ""))
+        ChainEnsemble._refuse_chain_filter("correlation", *shared, also=[(
+            pmmh_stat not in (None, "none"), "computes the log-likelihood estimate alone: pmmh_stat stays at its default, got "
+                                             "pmmh_stat = '{0}'".format(pmmh_stat))])
         try:
             rho = float(correlation)
         except (TypeError, ValueError):
@@ -889,32 +880,48 @@ class ChainEnsemble(object):
                             0.0 if init else self.correlation, self.seed ^ 0x43504D4D, self.chain_offset,
                             self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
 
+    def _alloc_per_chain(self, make, kept, per_chain, sb, copies=1):
+        """`copies` * C slabs of sb bytes in one uint8 tensor (make: torch.zeros | torch.empty); a refusal names what is kept,
+        the size formula and the byte count."""
+        n = copies * self.C * sb
+        try:
+            return make(n, dtype=torch.uint8, device=self.device)
+        except RuntimeError as e:       # (torch.cuda.OutOfMemoryError is one)
+            times = "{0} * ".format(copies) if copies != 1 else ""
+            raise MemoryError("{0}: {1}C * {2} = {1}{3} * {4} = {5} bytes ({6:.2f} GB) could not be allocated ({7})".format(
+                kept, times, per_chain, self.C, sb, n, n / 1e9, str(e).splitlines()[0])) from e
+
+    def _chain_filter_records(self, dtype, theta, prior_mean, prior_var):
+        """(d, idx): C records of a chain-filter descriptor (pfg_csmc_problem | pfg_cpm_problem) with what both have filled in
+        -- chain b reads row b of `theta` and the whole series, writes row b of out_dev -- and the chain indices as uint64."""
+        idx = np.arange(self.C, dtype=np.uint64)
+        d = np.zeros(self.C, dtype=dtype)
+        d["theta"] = theta.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
+        d["y"] = self.y_dev.data_ptr()
+        d["out"] = self.out_dev.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
+        d["prior_mean"], d["prior_var"], d["T"], d["N"] = prior_mean, prior_var, self.T, self.N
+        return d, idx
+
+    def _upload_records(self, d):
+        return torch.from_numpy(d.view(np.uint8).reshape(len(d), -1)).to(self.device)
+
     def _cpm_alloc(self, prior_mean, prior_var):
         """The state of a correlated chain beyond PMMH's: two buffers of normals per chain (aux_dev, [2][C] slabs of
         pfg_cpm_aux_bytes(T, N) bytes), the selector which_dev, the acceptance count seen_dev the selector was last moved at, and
         the pfg_cpm_problem records (static: the step replays in hipGraphs).  _mh_init fills the first buffer."""
         C, T, N, dev = self.C, self.T, self.N, self.device
         sb = self._aux_bytes = _capi.cpm_aux_bytes(T, N)
-        try:
-            self.aux_dev = torch.zeros(2 * C * sb, dtype=torch.uint8, device=dev)
-        except RuntimeError as e:       # (torch.cuda.OutOfMemoryError is one)
-            raise MemoryError("correlation keeps two buffers of normals per chain in HBM: 2 * C * pfg_cpm_aux_bytes(T, N) = "
-                              "2 * {0} * {1} = {2} bytes ({3:.2f} GB) could not be allocated ({4})".format(
-                                  C, sb, 2 * C * sb, 2 * C * sb / 1e9, str(e).splitlines()[0])) from e
+        self.aux_dev = self._alloc_per_chain(torch.zeros, "correlation keeps two buffers of normals per chain in HBM",
+                                             "pfg_cpm_aux_bytes(T, N)", sb, 2)
         self.which_dev = torch.zeros(C, dtype=torch.int32, device=dev)
         self.which_dev.fill_(1)          # the init pass writes buffer 0 and commits: every chain then reads buffer 0
         self.seen_dev = torch.zeros(C, dtype=torch.int64, device=dev)        # (the library's uint64 counts)
-        idx = np.arange(C, dtype=np.uint64)
-        d = np.zeros(C, dtype=_capi.CPM_PROBLEM_DTYPE)
-        d["theta"] = self.theta_prop_dev.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
-        d["y"] = self.y_dev.data_ptr()
+        d, idx = self._chain_filter_records(_capi.CPM_PROBLEM_DTYPE, self.theta_prop_dev, prior_mean, prior_var)
         d["u0"] = self.aux_dev.data_ptr() + idx * np.uint64(sb)
         d["u1"] = self.aux_dev.data_ptr() + (idx + np.uint64(C)) * np.uint64(sb)
         d["which"] = self.which_dev.data_ptr() + idx * np.uint64(4)
-        d["out"] = self.out_dev.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
-        d["prior_mean"], d["prior_var"], d["T"], d["N"] = prior_mean, prior_var, T, N
         self._cpm_desc = d
-        self.cpm_desc_dev = torch.from_numpy(d.view(np.uint8).reshape(C, -1)).to(dev)
+        self.cpm_desc_dev = self._upload_records(d)
 
     def _aux_view(self):
         """aux_dev as [2, C, doubles per slab]."""
@@ -944,26 +951,18 @@ class ChainEnsemble(object):
         self.path_dev = torch.zeros((C, T), dtype=torch.float64, device=dev)
         self.ndeg_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
         sb = _capi.csmc_scratch_bytes(T, N)
-        try:
-            self.csmc_scratch_dev = torch.empty(C * sb, dtype=torch.uint8, device=dev)
-        except RuntimeError as e:       # (torch.cuda.OutOfMemoryError is one)
-            raise MemoryError("sampler='pgibbs' keeps every chain's particle history in HBM: C * pfg_csmc_scratch_bytes(T, N) = "
-                              "{0} * {1} = {2} bytes ({3:.2f} GB) could not be allocated ({4})".format(
-                                  C, sb, C * sb, C * sb / 1e9, str(e).splitlines()[0])) from e
-        idx = np.arange(C, dtype=np.uint64)
-        d = np.zeros(C, dtype=_capi.CSMC_PROBLEM_DTYPE)
-        d["theta"] = self.theta_dev.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
-        d["y"] = self.y_dev.data_ptr()
+        self.csmc_scratch_dev = self._alloc_per_chain(torch.empty, "sampler='pgibbs' keeps every chain's particle history in HBM",
+                                                      "pfg_csmc_scratch_bytes(T, N)", sb)
+        d, idx = self._chain_filter_records(_capi.CSMC_PROBLEM_DTYPE, self.theta_dev, prior_mean, prior_var)
         d["path"] = self.path_dev.data_ptr() + idx * np.uint64(8 * T)
         d["scratch"] = self.csmc_scratch_dev.data_ptr() + idx * np.uint64(sb)
-        d["out"] = self.out_dev.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
         d["n_degenerate"] = self.ndeg_dev.data_ptr() + idx * np.uint64(8)
-        d["prior_mean"], d["prior_var"], d["T"], d["N"], d["has_ref"] = prior_mean, prior_var, T, N, 1
+        d["has_ref"] = 1
         self._csmc_desc = d
-        self.csmc_desc_dev = torch.from_numpy(d.view(np.uint8).reshape(C, -1)).to(dev)
+        self.csmc_desc_dev = self._upload_records(d)
         d0 = d.copy()
         d0["has_ref"] = 0
-        self._csmc_init_desc_dev = torch.from_numpy(d0.view(np.uint8).reshape(C, -1)).to(dev)
+        self._csmc_init_desc_dev = self._upload_records(d0)
         self.launch_csmc(init=True)
         self.step_ctr.fill_(1)
         self.synchronize()

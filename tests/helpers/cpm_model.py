@@ -24,12 +24,10 @@ import numpy as np
 
 import keyed_draws as kd
 import pmmh_model as pm
-from csmc_model import _consts, _logw, _search
+from chain_filter_model import EDGE_REL, LD, PM, PV, SEED, THETA, Key, case_theta_y, consts, logw, search  # noqa: F401
 
-LD = np.longdouble
 TAG_CPM = 0x43500000
 CPM_SEED_XOR = 0x43504D4D           # ChainEnsemble keys the filter's eps with seed ^ this (ensemble.py, launch_cpm)
-EDGE_REL = 1e-12                    # a search whose target lies this close to a CDF entry may be left out
 U_MAX = 1.0 - 2.0 ** -53
 
 _erfc = np.vectorize(math.erfc, otypes=[np.float64])
@@ -41,13 +39,11 @@ def filter_seed(seed):
 
 def eps(T, N, seed, gids, step):
     """[C, T+1, N+1] long double: every eps of the launch at counter `step` of the chains with global ids `gids`."""
-    s = int(step or 0)
-    gid = kd._lo(gids)[:, None]
-    hi = (kd._hi([s]) ^ kd._hi(gids))[:, None]
-    q = np.arange((N >> 2) + 1, dtype=np.uint64)[None, :]
-    out = np.zeros((len(gids), T + 1, 4 * q.shape[1]), dtype=LD)
+    key = Key(gids, seed, step)
+    q = np.arange((N >> 2) + 1, dtype=np.uint64)
+    out = np.zeros((len(gids), T + 1, 4 * len(q)), dtype=LD)
     for row in range(T + 1):
-        r = kd.philox4x32_10((gid, s & kd.MASK32, np.uint64(row) ^ hi, np.uint64(TAG_CPM) | q), kd.split_seed(seed))
+        r = key.draw(row, np.uint64(TAG_CPM) | q)
         a, b = kd.normal_pair(r[0], r[1])
         c, d = kd.normal_pair(r[2], r[3])
         out[:, row] = np.stack([a, b, c, d], axis=-1).reshape(len(gids), -1)
@@ -77,11 +73,11 @@ def loglik(model, theta, y, U, prior_mean, prior_var, sort=True, F=np.float64, f
     U = np.asarray(U, dtype=np.float64)
     C, T, N = th.shape[0], U.shape[1] - 1, U.shape[2] - 1
     y = np.broadcast_to(np.asarray(y, dtype=np.float64), (C, T)).astype(F)
-    c = _consts(model, th, F)
+    c = consts(model, th, F)
     logN = np.log(F(N))
     xm1 = F(prior_mean) + np.sqrt(F(prior_var)) * U[:, 0, :N].astype(F)
     x = c["iLQ"] * U[:, 1, :N].astype(F) + xm1 * c["A"]
-    lw = _logw(model, c, x, y[:, 0:1], F)
+    lw = logw(model, c, x, y[:, 0:1], F)
     ll = np.zeros(C, dtype=F)
     inc = np.full((C, T), np.nan, dtype=F)
     anc = np.full((C, T, N), -1, dtype=np.int64)
@@ -107,12 +103,12 @@ def loglik(model, theta, y, U, prior_mean, prior_var, sort=True, F=np.float64, f
         cdf = np.where(good[:, None], cdf, np.arange(1, N + 1, dtype=F)[None, :])
         W = np.where(good, W, N)
         u = resampling_uniform(U[:, t + 1, N]).astype(F)[:, None]
-        j, g = _search(cdf, ((r + u) / F(N)) * W[:, None])
+        j, g = search(cdf, ((r + u) / F(N)) * W[:, None])
         own[:, t], gap[:, t] = j, g
         anc[:, t] = j if forced is None else np.asarray(forced)[:, t]
         xp = np.take_along_axis(x, anc[:, t], axis=1)
         x = c["iLQ"] * U[:, t + 1, :N].astype(F) + xp * c["A"]
-        lw = _logw(model, c, x, y[:, t:t + 1], F)
+        lw = logw(model, c, x, y[:, t:t + 1], F)
     ll = np.where(alive, ll, -np.inf)
     return dict(ll=ll, inc=inc, anc=anc, own=own, gap=gap, degenerate=~alive)
 
@@ -154,28 +150,16 @@ def chain_init(model, theta, y, T, N, prior_mean, prior_var, seed, chain_offset)
 
 
 # ---- the cases the CPU and the device tests share ---------------------------------------------------------------------------
-THETA = {"svm": [0.9, 2.0, 1.2], "lgssm": [0.9, 1.0, 2.0, 1.2]}
-PM, PV = 0.0, 10.0
 # (N, T, B, rho) of the device replay (tests/test_gpu_cpm.py): N on both sides of the one-wave switch (128 | 129), powers of
 # two and not (the padding), the ends 2 and 1024; T = 1 (no resampling at all), 2, 7, 24; B from 1 to 70; rho 0 (reads no U),
 # 0.5 and 0.99
 CASES = [(2, 1, 1, 0.0), (2, 24, 3, 0.5), (3, 7, 70, 0.99), (5, 2, 70, 0.5), (64, 7, 3, 0.0), (100, 24, 5, 0.99),
          (128, 24, 70, 0.5), (129, 2, 3, 0.99), (200, 7, 2, 0.5), (256, 24, 3, 0.0), (1000, 7, 70, 0.99), (1024, 24, 1, 0.5),
          (1024, 1, 3, 0.0)]
-SEED = 20261019
 
 
 def case_inputs(model, N, T, B, seed=SEED):
     """theta [B, P], y [T], the current U [B, T+1, N+1] of a case: deterministic, moderate."""
-    rs = np.random.RandomState(seed % (2 ** 31) + 7 * N + 131 * T + B)
-    th = np.tile(THETA[model], (B, 1)) * rs.uniform(0.95, 1.05, size=(B, len(THETA[model])))
-    if model == "lgssm":
-        th[:, 1] = 1.0
-    x = rs.standard_normal() * np.sqrt(PV)
-    xs = np.zeros(T)
-    for t in range(T):
-        x = THETA[model][0] * x + rs.standard_normal() / (THETA[model][2] if model == "lgssm" else THETA[model][1])
-        xs[t] = x
-    y = np.exp(xs / 2) * rs.standard_normal(T) / THETA[model][-1] if model == "svm" else xs + rs.standard_normal(T) / THETA[model][-1]
+    th, y, rs = case_theta_y(model, N, T, B, seed)
     U = rs.standard_normal((B, T + 1, N + 1))
     return th, y, U

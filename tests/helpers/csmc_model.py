@@ -1,8 +1,7 @@
 """Host restatement of particle Gibbs for SVM and LGSSM (NumPy, test-only): the conditional SMC sweep with ancestor sampling
 of csrc/pfg_csmc.hip and the parameter draw of pgibbs_update_kernel (csrc/pfg_chains.hip), written from the equations.
 
-  model    x_{-1} ~ N(prior_mean, prior_var);  x_t = A x_{t-1} + z / LQinv;  SVM: y_t ~ N(0, R exp(x_t));  LGSSM: y_t ~ N(C x_t, R);
-           Qinv = LQinv^2 + 1e-16, Rinv = LRinv^2 + 1e-16, R = 1 / Rinv
+  model    chain_filter_model.py states it, with the key and the search
   sweep    t = 0: particles 0 .. N-2 draw x_{-1} and x_0, particle N-1 is x*_0.  t >= 1: a free particle draws its parent from
            the weights of step t-1 (cumsum; the smallest j with cdf[j] > u W, at most N-1), moves and is weighted with
            log g(y_t | x_t); particle N-1 is x*_t and draws its parent from w_i f(x*_t | x_{t-1}^i).  Then k ~ W_{T-1} and the
@@ -22,68 +21,15 @@ search would have chosen and `gap_*` how far, relative to the weight sum, its ta
 import numpy as np
 
 import keyed_draws as kd
+from chain_filter_model import EDGE_REL, LD, PM, PV, SEED, THETA, Key, case_theta_y, consts, logw, search  # noqa: F401
 
-LD = np.longdouble
 TAG_PARTICLE, TAG_ANCESTOR, TAG_FINAL = 0x43530000, 0x43531000, 0x43532000
 CSMC_SEED_XOR = 0x43534D43          # ChainEnsemble keys the sweep with seed ^ this (ensemble.py, launch_csmc)
-LOG_2PI = LD("1.8378770664093454835606594728112353")
-EDGE_REL = 1e-12                    # a recorded index may be the neighbour when the uniform lies this close to a CDF edge
-EDGE_SHARE = 0.01                   # ... for at most this share of a case's indices
+EDGE_SHARE = 0.01                   # a recorded index may be the neighbour on a CDF edge (EDGE_REL): at most this share of a case
 
 
 def sweep_seed(seed):
     return (int(seed) ^ CSMC_SEED_XOR) & 0xFFFFFFFFFFFFFFFF
-
-
-class _Key(object):
-    def __init__(self, gids, seed, step):
-        s = int(step or 0)
-        self.gid = kd._lo(gids)[:, None]
-        self.c1 = s & kd.MASK32
-        self.hi = (kd._hi([s]) ^ kd._hi(gids))[:, None]
-        self.k = kd.split_seed(seed)
-
-    def draw(self, t, tags):
-        tags = np.atleast_1d(np.asarray(tags, dtype=np.uint64))[None, :]
-        return kd.philox4x32_10((self.gid, self.c1, np.uint64(int(t)) ^ self.hi, tags), self.k)
-
-
-def _consts(model, th, F):
-    th = np.asarray(th, dtype=F)
-    if model == "svm":
-        A, Cc, LQ, LR = th[:, 0], np.ones(len(th), dtype=F), th[:, 1], th[:, 2]
-    else:
-        A, Cc, LQ, LR = th[:, 0], th[:, 1], th[:, 2], th[:, 3]
-    one = F(1)
-    return dict(A=A[:, None], C=Cc[:, None], iLQ=(one / LQ)[:, None], Qinv=(LQ * LQ + F(1e-16))[:, None],
-                Rinv=(LR * LR + F(1e-16))[:, None], logLR=np.log(LR)[:, None], c0=F(-0.5) * F(LOG_2PI))
-
-
-def _logw(model, c, x, y, F):
-    """log g(y | x): svm/kernels.py:56-62, lgssm/kernels.py:58-62 in the kernel's order of operations."""
-    half = F(0.5)
-    with np.errstate(over="ignore", invalid="ignore"):
-        if model == "svm":
-            return ((c["c0"] + ((-half * (y * y)) * np.exp(-x)) * c["Rinv"]) + c["logLR"]) + (-half * x)
-        d = y - c["C"] * x
-        return (c["c0"] + (-half * (d * d)) * c["Rinv"]) + c["logLR"]
-
-
-def _search(cdf, target):
-    """smallest j with cdf[j] > target, at most N-1, per row; and the relative distance of target to the nearest edge.
-    cdf [C, N]; target [C] or [C, M]."""
-    N = cdf.shape[-1]
-    one = target.ndim == 1
-    tg = target[:, None] if one else target
-    if N <= 32:
-        j = (cdf[:, None, :] <= tg[:, :, None]).sum(axis=-1)
-    else:
-        j = np.stack([np.searchsorted(cdf[c], tg[c], side="right") for c in range(cdf.shape[0])])
-    below = np.take_along_axis(cdf, np.clip(j - 1, 0, N - 1), axis=1)
-    above = np.take_along_axis(cdf, np.clip(j, 0, N - 1), axis=1)
-    gap = np.minimum(np.abs(tg - below), np.abs(above - tg)) / cdf[:, -1:]
-    j = np.minimum(j, N - 1)
-    return (j[:, 0], gap[:, 0]) if one else (j, gap)
 
 
 def record(model, path, y, F=np.float64):
@@ -122,8 +68,8 @@ def sweep(model, theta, y, path, N, seed, gids, step, prior_mean, prior_var, has
     T = y.shape[-1]
     y = np.broadcast_to(y, (C, T)).astype(F)
     ref = None if not has_ref else np.asarray(path, dtype=np.float64).astype(F)
-    c = _consts(model, th, F)
-    key = _Key(gids, seed, step)
+    c = consts(model, th, F)
+    key = Key(gids, seed, step)
     n_free = N - 1 if has_ref else N
     free = np.arange(n_free)
     x = np.zeros((C, T, N), dtype=F)
@@ -141,7 +87,7 @@ def sweep(model, theta, y, path, N, seed, gids, step, prior_mean, prior_var, has
     x[:, 0, :n_free] = c["iLQ"] * zb.astype(F) + xm1 * c["A"]
     if has_ref:
         x[:, 0, N - 1] = ref[:, 0]
-    lw[:] = _logw(model, c, x[:, 0], y[:, 0:1], F)
+    lw[:] = logw(model, c, x[:, 0], y[:, 0:1], F)
 
     def weights(lw_, extra=None):
         l = lw_ if extra is None else lw_ + extra
@@ -167,17 +113,17 @@ def sweep(model, theta, y, path, N, seed, gids, step, prior_mean, prior_var, has
         W = np.where(good, W, N)
         if t == T:
             r = key.draw(T, TAG_FINAL)
-            own_k, gap_k = _search(cdf, kd.uniform53(r[0], r[1])[:, 0].astype(F) * W)
+            own_k, gap_k = search(cdf, kd.uniform53(r[0], r[1])[:, 0].astype(F) * W)
             break
         r = key.draw(t, TAG_PARTICLE | free)
         u = kd.uniform53(r[0], r[1]).astype(F)
-        j, g = _search(cdf, u * W[:, None])
+        j, g = search(cdf, u * W[:, None])
         own[:, t, :n_free], gap[:, t, :n_free] = j, g
         if has_ref:
             cdf2 = np.where(good[:, None], cdf2, np.arange(1, N + 1, dtype=F)[None, :])
             V = np.where(good, V, N)
             ra = key.draw(t, TAG_ANCESTOR)
-            ja, ga = _search(cdf2, kd.uniform53(ra[0], ra[1])[:, 0].astype(F) * V)
+            ja, ga = search(cdf2, kd.uniform53(ra[0], ra[1])[:, 0].astype(F) * V)
             own[:, t, N - 1], gap[:, t, N - 1] = ja, ga
         anc[:, t] = own[:, t] if forced is None else np.asarray(forced["anc"])[:, t]
         z, _ = kd.normal_pair(r[2], r[3])
@@ -186,7 +132,7 @@ def sweep(model, theta, y, path, N, seed, gids, step, prior_mean, prior_var, has
         if has_ref:
             x[:, t, N - 1] = ref[:, t]
             ref_anc[:, t] = anc[:, t, N - 1]
-        lw = _logw(model, c, x[:, t], y[:, t:t + 1], F)
+        lw = logw(model, c, x[:, t], y[:, t:t + 1], F)
 
     k = own_k if forced is None else np.asarray(forced["k"], dtype=np.int64)
     new = np.zeros((C, T), dtype=F)
@@ -313,23 +259,14 @@ def sample_prior_paths(theta, T, n, prior_mean, prior_var, rs):
 
 
 # ---- the cases the CPU and the device tests share ---------------------------------------------------------------------------
-THETA = {"svm": [0.9, 2.0, 1.2], "lgssm": [0.9, 1.0, 2.0, 1.2]}
-PM, PV = 0.0, 10.0
 # the (N, T, B) cases of the device replay (tests/test_gpu_csmc.py): a partial wave, both sides of the one-wave switch, a ragged
 # last slot and the maximum; T = 1 (no resampling at all), 2, 3 and 37, where the parents stay in LDS up to N = 128 (T N <=
 # 8192) and are read back from the scratch above it
 CASES = [(2, 1, 1), (2, 37, 3), (5, 2, 70), (64, 3, 3), (65, 37, 1), (128, 37, 70), (129, 2, 3), (257, 37, 3), (1000, 3, 70),
          (1024, 37, 1), (1024, 1, 3)]
-SEED = 20261019
 
 
 def case_inputs(model, N, T, B, seed=SEED):
     """theta [B, P], y [T], reference paths [B, T] of a case: deterministic, moderate."""
-    rs = np.random.RandomState(seed % (2 ** 31) + 7 * N + 131 * T + B)
-    th = np.tile(THETA[model], (B, 1)) * rs.uniform(0.95, 1.05, size=(B, len(THETA[model])))
-    if model == "lgssm":
-        th[:, 1] = 1.0
-    x = sample_prior_paths(THETA[model], T, 1, PM, PV, rs)[0]
-    y = np.exp(x / 2) * rs.standard_normal(T) / THETA[model][-1] if model == "svm" else x + rs.standard_normal(T) / THETA[model][-1]
-    path = sample_prior_paths(THETA[model], T, B, PM, PV, rs)
-    return th, y, path
+    th, y, rs = case_theta_y(model, N, T, B, seed)
+    return th, y, sample_prior_paths(THETA[model], T, B, PM, PV, rs)
