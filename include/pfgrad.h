@@ -701,6 +701,57 @@ int pfg_cpm_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const p
 int pfg_cpm_commit_device(pfg_ctx *ctx, int B, const uint64_t *n_accept, uint64_t *seen, int32_t *which, int init,
                           void *hip_stream);
 
+/* EXTENSION (not in the reference): density-tempered SMC over B resident PMMH chains (Del Moral, Doucet and Jasra 2006; Duan
+ * and Fulop 2015).  The chains are one interacting population that is carried from a Gaussian q0 -- the product over the
+ * slots a PMMH proposal moves of N(q0_mean[j], q0_sd[j]^2), two DEVICE arrays of PFG_MAX_THETA doubles -- to the posterior
+ * through temperatures phi in [0, 1], the target at phi being q0(theta)^(1 - phi) (exp(logprior(theta)) p-hat(y | theta))^phi on
+ * PMMH's support.  A stage is: pfg_smc_logtarget_device, pfg_smc_temper_device, pfg_smc_gather_device,
+ * pfg_smc_scale_device, then PMMH steps (pfg_pmmh_propose_device, the launch, pfg_smc_accept_device).  Everything is f64 and
+ * a pure function of the inputs and (seed, stage); all arrays are DEVICE memory.
+ *
+ * pfg_smc_logtarget_device: h[b] = (ll_cur[b] + logprior(theta[b])) - log q0(theta[b]), log q0(theta) = sum over the slots
+ * that move of -(theta_j - m_j)^2 / (2 s_j^2) - log(s_j sqrt(2 pi)).
+ *
+ * pfg_smc_temper_device: one workgroup of 1024 threads over h [B], 2 <= B <= 2^20 (anything else: PFG_ERR_INVALID, no
+ * launch).  With w_i(d) = exp(d (h_i - h_max)) (0 for h_i = -inf) and ESS(d) = (sum w_i)^2 / sum w_i^2: delta = 1 - *phi if
+ * ESS(1 - *phi) >= ess_target B, otherwise the lower end of 60 rounds of bisection on [0, 1 - *phi].  result
+ * [PFG_SMC_RESULT_DOUBLES] = {phi' = *phi + delta (1 exactly in the first case), delta, the evidence increment
+ * delta h_max + log(W / B), ESS(delta), the uniform u, W = cdf[B - 1], h_max, 0}; *phi = phi'; cdf (scratch,
+ * pfg_smc_scratch_bytes(B) bytes) the running sum of w(delta) in chain order; parent[r] the smallest j with
+ * cdf[j] > ((r + u) / B) W, B - 1 when there is none: systematic resampling of the chains on one uniform per stage,
+ * u = uniform53 of Philox4x32-10 with counter {stage_lo, stage_hi, 0, 0x534D0001} under seed ^ 0x534D4353.  *status = 0, or
+ * 1: no h is finite, 2: some h is NaN or +inf, 4: delta ended at exactly 0, 8: *phi is not in [0, 1) -- and then NOTHING
+ * but *status is stored.
+ *
+ * pfg_smc_gather_device: theta[b] = theta[parent[b]], ll[b] = ll[parent[b]] through theta_tmp [B][PFG_MAX_THETA] and ll_tmp
+ * [B] (out of place, then copied back: two launches).  A parent outside [0, B) leaves the chain as it is.
+ *
+ * pfg_smc_scale_device: one workgroup of 1024 threads; for every slot j whose bit is set in `slots`, scale[j] = factor sd_j,
+ * sd_j = sqrt(sum_b (theta[b][j] - mean_j)^2 / B) by two passes summed in a fixed order, unless sd_j is 0 or not finite:
+ * then, as for every other slot, scale[j] stays.
+ *
+ * pfg_smc_accept_device: pfg_pmmh_accept_device's step (never init) at the temperature *phi,
+ *   log alpha = *phi ((out[4] + logprior(theta_prop)) - (ll_cur + logprior(theta)))
+ *               + (1 - *phi) (log q0(theta_prop) - log q0(theta)),
+ * on PMMH's uniform and with PMMH's commit; log_alpha (may be NULL) receives every chain's log alpha.  At *phi = 1 the
+ * decision, theta, ll_cur and n_accept are pfg_pmmh_accept_device's bit for bit.  *step_ctr is incremented afterwards. */
+#define PFG_SMC_RESULT_DOUBLES 8
+int64_t pfg_smc_scratch_bytes(int B);           /* the CDF, rounded up to 256; -1: B < 2 or B > 2^20 */
+int pfg_smc_logtarget_device(pfg_ctx *ctx, int model, int B, const double *theta, const double *ll_cur,
+                             const pfg_prior_hyper *hyper, const double *q0_mean, const double *q0_sd, double *h,
+                             void *hip_stream);
+int pfg_smc_temper_device(pfg_ctx *ctx, int B, const double *h, double *phi, double ess_target, uint64_t seed,
+                          uint64_t stage, double *result, int32_t *status, int32_t *parent, void *scratch,
+                          void *hip_stream);
+int pfg_smc_gather_device(pfg_ctx *ctx, int B, const int32_t *parent, double *theta, double *ll, double *theta_tmp,
+                          double *ll_tmp, void *hip_stream);
+int pfg_smc_scale_device(pfg_ctx *ctx, int B, const double *theta, uint32_t slots, double factor, double *scale,
+                         void *hip_stream);
+int pfg_smc_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const double *theta_prop, const int32_t *valid,
+                          const double *outs, double *ll_cur, uint64_t *n_accept, const pfg_prior_hyper *hyper,
+                          const double *q0_mean, const double *q0_sd, const double *phi, double *log_alpha, uint64_t seed,
+                          uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream);
+
 /* Inverse-multiquadric kernel Stein discrepancy of K points x[K][d] with score estimates
  * g[K][d] (HOST pointers, d <= 8): sqrt(sum_{i,j} k0(x_i,x_j)) / K for
  * k(x,y) = (c^2 + |x-y|^2)^(-beta) -- IMQ_KSD of sgmcmc_ssm/trace_metric_functions.py:20-81

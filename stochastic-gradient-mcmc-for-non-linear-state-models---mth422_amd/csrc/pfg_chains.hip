@@ -12,6 +12,9 @@
 //            sgrld, pmmh and pmala; GARCH log_mu, logit_phi, logit_lambduh, LRinv: z0..z3).  All disjoint from one another,
 //            from the window tags 0x53...... / 0x57......, from the sweep's 0x4353.... (pfg_csmc.hip) and from the correlated
 //            filter's 0x43500000 | column >> 2, at most 0x43500100 (pfg_cpm.hip).
+//              0x534D0001                smc: the resampling uniform of a tempering stage (pfg_smc.hip), keyed by the stage and
+//                                        not by a chain: counter {stage_lo, stage_hi, 0, tag}.  The window tag 0x53000000 | j
+//                                        stops at j < PFG_MAX_DRAWN_SEQUENCES = 1024, far below 0x4D0001.
 //   drift    d_j(theta, g) = grad_logprior_j(theta) + g_j in theta order, g the score columns of a launch (SVM [LR, LQ,
 //            A], LGSSM [LR, LQ, C, A], GARCH [LR, log_mu, logit_phi, logit_lambduh]).  sgld, sgrld and pmala use it.
 //   project  project_parameters: |A| <= 0.9999, a negative Cholesky factor reflected, LGSSM's C = 1.
@@ -68,6 +71,15 @@
 //                     (the pair (ll, g) is the auxiliary variable of the pseudo-marginal argument; the drift may be any
 //                     function of (theta, g) as long as q is evaluated with the same one in both directions).
 //          With (s_j s_j) / 2 = eps / T for every j the proposal is the law of sgld's step before project.
+//   smc    the two chain-wise kernels of density-tempered SMC over PMMH chains (the population kernels: pfg_smc.hip).  With
+//          q0 the product over the slots that move of N(m_j, s_j^2), log q0(theta) = sum_j -(theta_j - m_j)^2 / (2 s_j^2) -
+//          log(s_j sqrt(2 pi)):
+//            logtarget  h = (ll_cur + logprior(theta)) - log q0(theta), what a stage's weights exp(delta h) are made of
+//            accept     pmmh's accept step on the target q0^(1 - phi) (exp(logprior) p-hat)^phi, phi read from device memory:
+//                         log alpha = phi ((out[4] + logprior(theta')) - (ll_cur + logprior(theta)))
+//                                     + (1 - phi) (log q0(theta') - log q0(theta))
+//                       on pmmh's own uniform tag, with pmmh's commit.  At phi = 1 this is pmmh's log alpha exactly (1 x + 0 y =
+//                       x for a finite y), so the decision is pmmh_accept_kernel's bit for bit.
 // Built with -ffp-contract=off; IEEE division and ::sqrt / ::log throughout.
 #include <initializer_list>
 
@@ -374,6 +386,48 @@ __global__ void pmmh_accept_kernel(int model, int B, double *__restrict__ theta,
                ll_cur + b, ll_prop, n_accept + b);
 }
 
+// ---- tempered SMC over PMMH chains: log q0, the log-target ratio, the tempered accept ----
+__device__ __forceinline__ double log_q0(int model, const double *th, const double *mean, const double *sd) {
+    double q = 0.0;
+    for (int j = 0; j < PFG_MAX_THETA; ++j) {
+        if (!moves(model, j)) continue;
+        const double r = th[j] - mean[j];
+        q = q + (-((r * r) / (2.0 * (sd[j] * sd[j]))) - ::log(sd[j] * 2.5066282746310002));      // sqrt(2 pi)
+    }
+    return q;
+}
+
+__global__ void smc_logtarget_kernel(int model, int B, const double *__restrict__ theta, const double *__restrict__ ll_cur,
+                                     pfg_prior_hyper hy, const double *__restrict__ q0_mean, const double *__restrict__ q0_sd,
+                                     double *__restrict__ h) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double *th = theta + (size_t)b * PFG_MAX_THETA;
+    h[b] = (ll_cur[b] + logprior_value(model, th, hy)) - log_q0(model, th, q0_mean, q0_sd);
+}
+
+// pmmh_accept_kernel's step (never init) at the temperature *phi; log_alpha_out (may be NULL): every chain's log alpha
+__global__ void smc_accept_kernel(int model, int B, double *__restrict__ theta, const double *__restrict__ theta_prop,
+                                  const int32_t *__restrict__ valid, const double *__restrict__ outs,
+                                  double *__restrict__ ll_cur, uint64_t *__restrict__ n_accept, pfg_prior_hyper hy,
+                                  const double *__restrict__ q0_mean, const double *__restrict__ q0_sd,
+                                  const double *__restrict__ phi, double *__restrict__ log_alpha_out, uint64_t seed,
+                                  uint64_t chain_offset, const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double ll_prop = outs[(size_t)b * PFG_OUT_DOUBLES + 4];
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    const double *tp = theta_prop + (size_t)b * PFG_MAX_THETA;
+    const double f = *phi;
+    const double d_post = (ll_prop + logprior_value(model, tp, hy)) - (ll_cur[b] + logprior_value(model, th, hy));
+    const double d_q0 = log_q0(model, tp, q0_mean, q0_sd) - log_q0(model, th, q0_mean, q0_sd);
+    const double log_alpha = f * d_post + (1.0 - f) * d_q0;
+    if (log_alpha_out) log_alpha_out[b] = log_alpha;
+    const bool finite = fabs(ll_prop) < INFINITY;        // false for a NaN as well
+    metropolis(make_key(seed, chain_offset, b, step_ctr), kTagPmmh | kUniform, valid[b] != 0 && finite, log_alpha, th, tp,
+               ll_cur + b, ll_prop, n_accept + b);
+}
+
 // ---- pMALA: the proposal's mean and log-density, propose, accept ----
 // the mean of the proposal from a with drift d: a_j + (s_j^2 / 2) d_j
 __device__ __forceinline__ double pmala_mean(double a, double s, double d) { return a + (0.5 * (s * s)) * d; }
@@ -538,6 +592,24 @@ int pfg_pmmh_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const 
     if (const int rc = check_args(ctx, __func__, model, B, {theta, theta_prop, valid, outs, ll_cur, n_accept, hyper})) return rc;
     return run_update(ctx, B, init ? nullptr : step_ctr, hip_stream, pmmh_accept_kernel, model, B, theta, theta_prop, valid,
                       outs, ll_cur, n_accept, *hyper, init, seed, chain_offset, (const uint64_t *)step_ctr);
+}
+
+int pfg_smc_logtarget_device(pfg_ctx *ctx, int model, int B, const double *theta, const double *ll_cur,
+                             const pfg_prior_hyper *hyper, const double *q0_mean, const double *q0_sd, double *h,
+                             void *hip_stream) {
+    if (const int rc = check_args(ctx, __func__, model, B, {theta, ll_cur, hyper, q0_mean, q0_sd, h})) return rc;
+    return run_update(ctx, B, nullptr, hip_stream, smc_logtarget_kernel, model, B, theta, ll_cur, *hyper, q0_mean, q0_sd, h);
+}
+
+int pfg_smc_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const double *theta_prop, const int32_t *valid,
+                          const double *outs, double *ll_cur, uint64_t *n_accept, const pfg_prior_hyper *hyper,
+                          const double *q0_mean, const double *q0_sd, const double *phi, double *log_alpha, uint64_t seed,
+                          uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream) {
+    if (const int rc = check_args(ctx, __func__, model, B, {theta, theta_prop, valid, outs, ll_cur, n_accept, hyper, q0_mean,
+                                                            q0_sd, phi}))
+        return rc;
+    return run_update(ctx, B, step_ctr, hip_stream, smc_accept_kernel, model, B, theta, theta_prop, valid, outs, ll_cur,
+                      n_accept, *hyper, q0_mean, q0_sd, phi, log_alpha, seed, chain_offset, (const uint64_t *)step_ctr);
 }
 
 int pfg_pmala_propose_device(pfg_ctx *ctx, int model, int B, const double *theta, const double *grad_cur, double *theta_prop,

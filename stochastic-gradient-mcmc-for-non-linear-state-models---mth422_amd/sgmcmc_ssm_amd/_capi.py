@@ -168,6 +168,10 @@ CPM_PROBLEM_DTYPE = np.dtype([
     ("T", "i4"), ("N", "i4"),
 ], align=True)
 CPM_MAX_N = 1024
+SMC_MIN_CHAINS, SMC_MAX_CHAINS = 2, 1 << 20        # a tempered population (pfg_smc_temper_device: one workgroup)
+SMC_RESULT_DOUBLES = 8                              # PFG_SMC_RESULT_DOUBLES
+# the theta slots a PMMH proposal moves (pfg_chains.hip: moves), as pfg_smc_scale_device's bit mask
+PMMH_MOVING_SLOTS = {"svm": 0b0111, "lgssm": 0b1101, "garch": 0b1111}
 
 
 def csmc_scratch_bytes(T, N):
@@ -180,6 +184,11 @@ def cpm_aux_bytes(T, N):
     """pfg_cpm_aux_bytes: one buffer U [T+1][N+1] f64 of one chain, rounded up to 256 bytes (-1: T < 1, N < 2 or N > 1024).
     The library's own answer: the formula is stated once, in pfg_cpm.hip."""
     return int(load_library().pfg_cpm_aux_bytes(int(T), int(N)))
+
+
+def smc_scratch_bytes(B):
+    """pfg_smc_scratch_bytes: the CDF [B] f64 of one tempering stage, rounded up to 256 bytes (-1: B < 2 or B > 2^20)."""
+    return int(load_library().pfg_smc_scratch_bytes(int(B)))
 
 
 def device_descriptors(n, *, theta, row, out, step_ctr, scratch, scratch_bytes, stream, prior_mean, prior_var, lambduh, seed,
@@ -214,7 +223,9 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
            "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device",
            "pfg_pmala_propose_device", "pfg_pmala_accept_device", "pfg_csmc_scratch_bytes", "pfg_csmc_device",
-           "pfg_pgibbs_update_device", "pfg_cpm_aux_bytes", "pfg_cpm_device", "pfg_cpm_commit_device")
+           "pfg_pgibbs_update_device", "pfg_cpm_aux_bytes", "pfg_cpm_device", "pfg_cpm_commit_device",
+           "pfg_smc_scratch_bytes", "pfg_smc_logtarget_device", "pfg_smc_temper_device", "pfg_smc_gather_device",
+           "pfg_smc_scale_device", "pfg_smc_accept_device")
 
 _lib = None
 
@@ -331,6 +342,21 @@ def load_library():
     lib.pfg_cpm_device.restype = C.c_int
     lib.pfg_cpm_commit_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.pfg_cpm_commit_device.restype = C.c_int
+    lib.pfg_smc_scratch_bytes.argtypes = [C.c_int]
+    lib.pfg_smc_scratch_bytes.restype = C.c_int64
+    lib.pfg_smc_logtarget_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PriorHyper),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pfg_smc_logtarget_device.restype = C.c_int
+    lib.pfg_smc_temper_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_uint64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pfg_smc_temper_device.restype = C.c_int
+    lib.pfg_smc_gather_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    lib.pfg_smc_gather_device.restype = C.c_int
+    lib.pfg_smc_scale_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p]
+    lib.pfg_smc_scale_device.restype = C.c_int
+    lib.pfg_smc_accept_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(PriorHyper)] + \
+                                         [C.c_void_p] * 4 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.pfg_smc_accept_device.restype = C.c_int
     lib.pfg_logprior_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(PriorHyper), C.c_void_p, C.c_void_p]
     lib.pfg_logprior_device.restype = C.c_int
     lib.pfg_pmmh_propose_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -868,6 +894,45 @@ class Context:
             C.byref(hyper) if hyper is not None else None, C.c_void_p(scale_ptr or 0), int(bool(init)),
             C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
             C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def smc_logtarget_device(self, model, B, theta_ptr, ll_ptr, hyper, q0_mean_ptr, q0_sd_ptr, h_ptr, stream_ptr=0):
+        """pfg_smc_logtarget_device: h[b] = (ll[b] + logprior(theta[b])) - log q0(theta[b])."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_smc_logtarget_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(ll_ptr or 0),
+            C.byref(hyper) if hyper is not None else None, C.c_void_p(q0_mean_ptr or 0), C.c_void_p(q0_sd_ptr or 0),
+            C.c_void_p(h_ptr or 0), C.c_void_p(int(stream_ptr))))
+
+    def smc_temper_device(self, B, h_ptr, phi_ptr, ess_target, seed, stage, result_ptr, status_ptr, parent_ptr, scratch_ptr,
+                          stream_ptr=0):
+        """pfg_smc_temper_device: the next temperature, the evidence increment and the chains' parents (one workgroup)."""
+        self._check(self.lib.pfg_smc_temper_device(
+            self.handle, int(B), C.c_void_p(h_ptr or 0), C.c_void_p(phi_ptr or 0), C.c_double(float(ess_target)),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(stage)), C.c_void_p(result_ptr or 0),
+            C.c_void_p(status_ptr or 0), C.c_void_p(parent_ptr or 0), C.c_void_p(scratch_ptr or 0), C.c_void_p(int(stream_ptr))))
+
+    def smc_gather_device(self, B, parent_ptr, theta_ptr, ll_ptr, theta_tmp_ptr, ll_tmp_ptr, stream_ptr=0):
+        """pfg_smc_gather_device: theta[b], ll[b] = theta[parent[b]], ll[parent[b]] through the two scratch arrays."""
+        self._check(self.lib.pfg_smc_gather_device(
+            self.handle, int(B), C.c_void_p(parent_ptr or 0), C.c_void_p(theta_ptr or 0), C.c_void_p(ll_ptr or 0),
+            C.c_void_p(theta_tmp_ptr or 0), C.c_void_p(ll_tmp_ptr or 0), C.c_void_p(int(stream_ptr))))
+
+    def smc_scale_device(self, B, theta_ptr, slots, factor, scale_ptr, stream_ptr=0):
+        """pfg_smc_scale_device: scale[j] = factor * sd_j of the population for every slot j in the bit mask `slots`."""
+        self._check(self.lib.pfg_smc_scale_device(
+            self.handle, int(B), C.c_void_p(theta_ptr or 0), C.c_uint32(int(slots)), C.c_double(float(factor)),
+            C.c_void_p(scale_ptr or 0), C.c_void_p(int(stream_ptr))))
+
+    def smc_accept_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, n_accept_ptr, hyper,
+                          q0_mean_ptr, q0_sd_ptr, phi_ptr, log_alpha_ptr, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
+        """pfg_smc_accept_device: pfg_pmmh_accept_device's step at the temperature *phi; bumps *step_ctr."""
+        m = model if isinstance(model, int) else MODEL[model]
+        self._check(self.lib.pfg_smc_accept_device(
+            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
+            C.c_void_p(outs_ptr or 0), C.c_void_p(ll_ptr or 0), C.c_void_p(n_accept_ptr or 0),
+            C.byref(hyper) if hyper is not None else None, C.c_void_p(q0_mean_ptr or 0), C.c_void_p(q0_sd_ptr or 0),
+            C.c_void_p(phi_ptr or 0), C.c_void_p(log_alpha_ptr or 0), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
 
     def scratch_bytes(self, model, dtype, rng, N):
         return int(self.lib.pfg_scratch_bytes(MODEL[model], DTYPE[dtype], RNG[rng], int(N)))
