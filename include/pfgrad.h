@@ -526,6 +526,38 @@ int pfg_sgrld_update_device(pfg_ctx *ctx, int model, int B, double *theta, const
                             const pfg_prior_hyper *hyper, double epsilon, double Tscale,
                             uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream);
 
+/* SGD and ADAGRAD steps for B resident chains (sgmcmc_sampler.py:467-484, 504-527), every model, on the `outs` and
+ * `hyper` of pfg_sgld_update_device, followed by project_parameters.  With g_v = (grad_logprior_v(theta) + ghat_v) / Tscale:
+ *   pfg_sgd_update_device      theta_v += eps g_v
+ *   pfg_adagrad_update_device  G_v += g_v g_v;  theta_v += eps g_v / sqrt(G_v + 1e-9)      (NOISE_NUGGET)
+ * moment [B][PFG_MAX_THETA] holds G and is updated in place; it covers every variable, LGSSM's C included although the
+ * projection pins C; SVM's fourth slot is untouched.  Neither draws anything.  *step_ctr (may be NULL) is incremented
+ * afterwards, so that the filters of the next step draw afresh. */
+int pfg_sgd_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs, const pfg_prior_hyper *hyper,
+                          double epsilon, double Tscale, uint64_t *step_ctr, void *hip_stream);
+int pfg_adagrad_update_device(pfg_ctx *ctx, int model, int B, double *theta, double *moment, const double *outs,
+                              const pfg_prior_hyper *hyper, double epsilon, double Tscale, uint64_t *step_ctr,
+                              void *hip_stream);
+
+/* EXTENSION: SGLD with control variates (Baker, Fearnhead, Fox and Nemeth 2019) for B resident chains.  outs and
+ * outs_centre [B][PFG_OUT_DOUBLES]: the records of the chain's window at theta and of the SAME window at the centre
+ * (ChainEnsemble runs both in one launch on the same draws); centre_grad [B][4]: the whole-data score at the centre in
+ * score-column order, raw and unscaled, without the prior.  The step is pfg_sgld_update_device's -- the same device code,
+ * normals and key -- on
+ *   ghat_k = centre_grad_k + (outs_k - outs_centre_k),   k = 0..3, in that operand order,
+ * so with outs == outs_centre it is pfg_sgld_update_device on a record holding centre_grad, and with centre_grad = 0,
+ * outs_centre = 0 it is pfg_sgld_update_device on outs, both bit for bit.  *step_ctr is incremented afterwards.
+ *
+ * pfg_cv_accumulate_device: the mean over num_repeats launches behind centre_grad.  Call `repeat` (0 .. num_repeats - 1, in
+ * order) adds columns 0..4 of outs [B][PFG_OUT_DOUBLES] into acc [B][PFG_OUT_DOUBLES] (repeat 0 stores), and the last one
+ * divides once by num_repeats: a fixed order of IEEE operations, no atomics.  Columns 5..7 of acc are not touched.
+ * *step_ctr (may be NULL: the counter of the centring launches) is incremented afterwards. */
+int pfg_sgld_cv_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs, const double *outs_centre,
+                              const double *centre_grad, const pfg_prior_hyper *hyper, double epsilon, double Tscale,
+                              uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream);
+int pfg_cv_accumulate_device(pfg_ctx *ctx, int B, const double *outs, double *acc, int repeat, int num_repeats,
+                             uint64_t *step_ctr, void *hip_stream);
+
 /* Gibbs parameter draw for B resident LGSSM chains: LGSSMPrior.sample_posterior (base_parameters.py:354-377,
  * 437-450) from the PFG_STAT_GIBBS statistics an FFBS launch with one path per chain left in `outs`
  * [B][PFG_OUT_DOUBLES] -- Qinv, Rinv from their 1 x 1 Wishart (scale * chi2(df)) posteriors, A given Q from its

@@ -26,6 +26,17 @@
 //   sgld   every model: theta += eps (d(theta, ghat) / T) + N(0, 2 eps / T), then project; sghmc: the same kernel with a
 //          momentum buffer and friction alpha.  LGSSM's C takes its increment before project pins it to 1: under sghmc it
 //          is part of the momentum.
+//   sgd    SGMCMCSampler.step_sgd (sgmcmc_sampler.py:467-484): theta += eps (d(theta, ghat) / T), then project.  No draws.
+//   adagrad  SGMCMCSampler.step_adagrad (sgmcmc_sampler.py:504-527) with a moment buffer G [B][4], one kernel with sgd:
+//          g = d(theta, ghat) / T, G += g g, theta += eps (g / sqrt(G + 1e-9)) (the reference's NOISE_NUGGET), then project.
+//          G covers every variable, LGSSM's C included although project pins C; SVM's fourth slot is untouched.  No draws.
+//   sgld_cv  SGLD with control variates (Baker, Fearnhead, Fox and Nemeth 2019): sgld's step -- its operations, its normals, its
+//          key -- on g_k = centre_grad_k + (out_k - out_centre_k), k the four score columns: `out` the record of the chain's
+//          window at theta, `out_centre` the record of the SAME window on the SAME draws at the centre, centre_grad the
+//          whole-data score at the centre (raw, unscaled, without the prior: d adds the prior's gradient at theta).  With
+//          out == out_centre it is sgld on centre_grad, with centre_grad = out_centre = 0 sgld on out, both bit for bit.
+//          cv_accumulate: the mean over R launches behind centre_grad -- repeat r adds columns 0..4 of a record to the
+//          accumulator (r = 0 stores), the last one divides once by R: a fixed order without atomics.
 //   sgrld  SGMCMCSampler.sample_sgrld with LGSSMPreconditioner (sgmcmc_sampler.py:631-641, base_parameters.py:588-661,
 //          models/lgssm.py:51-54), then project.  With theta = (A, C, LQinv, LRinv), Qinv = LQinv^2 + 1e-16,
 //          Q = 1 / Qinv, g_v = d_v(theta, ghat) and every preconditioner term at the pre-step theta:
@@ -214,6 +225,64 @@ __global__ void sgld_update_kernel(int model, int B, double *__restrict__ theta,
             mv[j] = v;
         }
         return th[j] + v;
+    };
+    const double p[PFG_MAX_THETA] = {step(0), step(1), step(2), model == PFG_MODEL_SVM ? 0.0 : step(3)};      // SVM has three
+    project_store(model, th, p);
+}
+
+// SGLD with control variates: g_k = centre_grad_k + (out_k - out_centre_k), in that operand order, then sgld_update_kernel's
+// step without a momentum, operation for operation (the tests hold the two to each other bitwise).  It is written out in
+// both: a shared helper changed sgld_update_kernel's instructions.
+__global__ void sgld_cv_update_kernel(int model, int B, double *__restrict__ theta, const double *__restrict__ outs,
+                                      const double *__restrict__ outs_centre, const double *__restrict__ centre_grad,
+                                      pfg_prior_hyper hy, double eps, double Tscale, uint64_t seed, uint64_t chain_offset,
+                                      const uint64_t *step_ctr) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    const double *o = outs + (size_t)b * PFG_OUT_DOUBLES, *oc = outs_centre + (size_t)b * PFG_OUT_DOUBLES;
+    const double *cg = centre_grad + (size_t)b * PFG_MAX_THETA;
+    double z[4], d[PFG_MAX_THETA], g[PFG_MAX_THETA];
+    for (int k = 0; k < PFG_MAX_THETA; ++k) g[k] = cg[k] + (o[k] - oc[k]);
+    normals4(make_key(seed, chain_offset, b, step_ctr), kTagNormals0, kTagNormals1, z);
+    drift(model, th, g, hy, d);
+    const double nsd = sqrt(1.0 / Tscale) * sqrt(2.0 * eps) * 1.0;
+    auto step = [&](int j) { return th[j] + (eps * (d[j] / Tscale) + nsd * z[j]); };
+    const double p[PFG_MAX_THETA] = {step(0), step(1), step(2), model == PFG_MODEL_SVM ? 0.0 : step(3)};      // SVM has three
+    project_store(model, th, p);
+}
+
+// repeat r of R of the centring pass: acc[0..4] = (r == 0 ? out : acc + out), the last repeat divided by R
+__global__ void cv_accumulate_kernel(int B, const double *__restrict__ outs, double *__restrict__ acc, int r, int R) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double *o = outs + (size_t)b * PFG_OUT_DOUBLES;
+    double *a = acc + (size_t)b * PFG_OUT_DOUBLES;
+    for (int j = 0; j < 5; ++j) {
+        double v = r == 0 ? o[j] : a[j] + o[j];
+        if (r == R - 1) v = v / (double)R;
+        a[j] = v;
+    }
+}
+
+// ---- SGD, ADAGRAD ----
+// moment == nullptr: SGD.  Otherwise ADAGRAD: G <- G + g g per slot, the increment g / sqrt(G + 1e-9).  No draws.
+__global__ void optim_update_kernel(int model, int B, double *__restrict__ theta, const double *__restrict__ outs,
+                                    pfg_prior_hyper hy, double eps, double Tscale, double *__restrict__ moment) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double *th = theta + (size_t)b * PFG_MAX_THETA;
+    double d[PFG_MAX_THETA];
+    drift(model, th, outs + (size_t)b * PFG_OUT_DOUBLES, hy, d);
+    double *G = moment ? moment + (size_t)b * PFG_MAX_THETA : nullptr;
+    auto step = [&](int j) {
+        double g = d[j] / Tscale;
+        if (G) {
+            const double Gj = G[j] + g * g;
+            G[j] = Gj;
+            g = g / sqrt(Gj + 1e-9);
+        }
+        return th[j] + eps * g;
     };
     const double p[PFG_MAX_THETA] = {step(0), step(1), step(2), model == PFG_MODEL_SVM ? 0.0 : step(3)};      // SVM has three
     project_store(model, th, p);
@@ -543,6 +612,38 @@ int pfg_sghmc_update_device(pfg_ctx *ctx, int model, int B, double *theta, doubl
     if (const int rc = check_update(ctx, "pfg_sgld_update_device", model, theta, outs, hyper, nullptr, epsilon, Tscale)) return rc;
     return run_update(ctx, B, step_ctr, hip_stream, sgld_update_kernel, model, B, theta, outs, *hyper, epsilon, Tscale, seed,
                       chain_offset, (const uint64_t *)step_ctr, momentum, alpha);
+}
+
+int pfg_sgd_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs, const pfg_prior_hyper *hyper,
+                          double epsilon, double Tscale, uint64_t *step_ctr, void *hip_stream) {
+    if (const int rc = check_update(ctx, __func__, model, theta, outs, hyper, nullptr, epsilon, Tscale)) return rc;
+    return run_update(ctx, B, step_ctr, hip_stream, optim_update_kernel, model, B, theta, outs, *hyper, epsilon, Tscale,
+                      (double *)nullptr);
+}
+
+int pfg_adagrad_update_device(pfg_ctx *ctx, int model, int B, double *theta, double *moment, const double *outs,
+                              const pfg_prior_hyper *hyper, double epsilon, double Tscale, uint64_t *step_ctr,
+                              void *hip_stream) {
+    if (const int rc = check_update(ctx, __func__, model, theta, outs, hyper, nullptr, epsilon, Tscale)) return rc;
+    if (!moment) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    return run_update(ctx, B, step_ctr, hip_stream, optim_update_kernel, model, B, theta, outs, *hyper, epsilon, Tscale, moment);
+}
+
+int pfg_sgld_cv_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs, const double *outs_centre,
+                              const double *centre_grad, const pfg_prior_hyper *hyper, double epsilon, double Tscale,
+                              uint64_t seed, uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream) {
+    if (const int rc = check_update(ctx, __func__, model, theta, outs, hyper, nullptr, epsilon, Tscale)) return rc;
+    if (!outs_centre || !centre_grad) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": NULL argument");
+    return run_update(ctx, B, step_ctr, hip_stream, sgld_cv_update_kernel, model, B, theta, outs, outs_centre, centre_grad,
+                      *hyper, epsilon, Tscale, seed, chain_offset, (const uint64_t *)step_ctr);
+}
+
+int pfg_cv_accumulate_device(pfg_ctx *ctx, int B, const double *outs, double *acc, int repeat, int num_repeats,
+                             uint64_t *step_ctr, void *hip_stream) {
+    if (const int rc = check_args(ctx, __func__, 0, B, {outs, acc})) return rc;
+    if (num_repeats < 1 || repeat < 0 || repeat >= num_repeats)
+        return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": need 0 <= repeat < num_repeats");
+    return run_update(ctx, B, step_ctr, hip_stream, cv_accumulate_kernel, B, outs, acc, repeat, num_repeats);
 }
 
 int pfg_sgrld_update_device(pfg_ctx *ctx, int model, int B, double *theta, const double *outs,

@@ -225,7 +225,8 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_pmala_propose_device", "pfg_pmala_accept_device", "pfg_csmc_scratch_bytes", "pfg_csmc_device",
            "pfg_pgibbs_update_device", "pfg_cpm_aux_bytes", "pfg_cpm_device", "pfg_cpm_commit_device",
            "pfg_smc_scratch_bytes", "pfg_smc_logtarget_device", "pfg_smc_temper_device", "pfg_smc_gather_device",
-           "pfg_smc_scale_device", "pfg_smc_accept_device")
+           "pfg_smc_scale_device", "pfg_smc_accept_device", "pfg_sgd_update_device", "pfg_adagrad_update_device",
+           "pfg_sgld_cv_update_device", "pfg_cv_accumulate_device")
 
 _lib = None
 
@@ -325,6 +326,19 @@ def load_library():
                                             C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_uint64,
                                             C.c_uint64, C.c_void_p, C.c_void_p]
     lib.pfg_sgrld_update_device.restype = C.c_int
+    lib.pfg_sgd_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PriorHyper),
+                                          C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    lib.pfg_sgd_update_device.restype = C.c_int
+    lib.pfg_adagrad_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    lib.pfg_adagrad_update_device.restype = C.c_int
+    lib.pfg_sgld_cv_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_uint64, C.c_uint64,
+                                              C.c_void_p, C.c_void_p]
+    lib.pfg_sgld_cv_update_device.restype = C.c_int
+    lib.pfg_cv_accumulate_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p]
+    lib.pfg_cv_accumulate_device.restype = C.c_int
     lib.pfg_gibbs_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                             C.POINTER(PriorHyper), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.pfg_gibbs_update_device.restype = C.c_int
@@ -801,6 +815,35 @@ class Context:
             float(epsilon), float(Tscale), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
             C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
             C.c_void_p(int(stream_ptr))))
+
+    def sgd_update_device(self, model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, step_ctr_ptr=None, stream_ptr=0):
+        """pfg_sgd_update_device: theta += eps (grad_logprior + ghat) / Tscale, then the projection; no draws."""
+        self._check(self.lib.pfg_sgd_update_device(
+            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper), float(epsilon),
+            float(Tscale), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def adagrad_update_device(self, model, B, theta_ptr, moment_ptr, outs_ptr, hyper, epsilon, Tscale, step_ctr_ptr=None,
+                              stream_ptr=0):
+        """pfg_adagrad_update_device: the SGD step on g / sqrt(G + 1e-9), G [B][MAX_THETA] += g g in place."""
+        self._check(self.lib.pfg_adagrad_update_device(
+            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(moment_ptr), C.c_void_p(outs_ptr),
+            C.byref(hyper), float(epsilon), float(Tscale), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
+            C.c_void_p(int(stream_ptr))))
+
+    def sgld_cv_update_device(self, model, B, theta_ptr, outs_ptr, outs_centre_ptr, centre_grad_ptr, hyper, epsilon, Tscale,
+                              seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
+        """pfg_sgld_cv_update_device: the SGLD step on centre_grad + (outs - outs_centre) (include/pfgrad.h)."""
+        self._check(self.lib.pfg_sgld_cv_update_device(
+            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.c_void_p(outs_centre_ptr),
+            C.c_void_p(centre_grad_ptr), C.byref(hyper), float(epsilon), float(Tscale),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+
+    def cv_accumulate_device(self, B, outs_ptr, acc_ptr, repeat, num_repeats, step_ctr_ptr=None, stream_ptr=0):
+        """pfg_cv_accumulate_device: repeat `repeat` of the mean over num_repeats records (include/pfgrad.h)."""
+        self._check(self.lib.pfg_cv_accumulate_device(
+            self.handle, int(B), C.c_void_p(outs_ptr), C.c_void_p(acc_ptr), int(repeat), int(num_repeats),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
 
     def gibbs_update_device(self, model, B, theta_ptr, outs_ptr, hyper, seed, chain_offset=0, step_ctr_ptr=None,
                             stream_ptr=0):

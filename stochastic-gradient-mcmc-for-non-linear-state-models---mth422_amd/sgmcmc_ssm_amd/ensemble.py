@@ -146,6 +146,33 @@ class ChainEnsemble(object):
                draws with s + 1).  path(), suff_stats() and n_degenerate() read the chains' paths, the statistics of the
                latest paths and how often a chain's sweep kept its path because its weights degenerated.  The scratch is
                C * pfg_csmc_scratch_bytes(T, N) bytes: 10 T N per chain)
+               'sgd' | 'adagrad' (step_sgd and step_adagrad + project_parameters, pfg_sgd_update_device /
+               pfg_adagrad_update_device: optimisers towards the MAP, another update on the launch of an 'sgld' step, so
+               they take whatever 'sgld' takes; they draw nothing; moment() reads ADAGRAD's G, which travels in state_dict)
+               'sgld_cv' (extension: SGLD with control variates, Baker, Fearnhead, Fox and Nemeth 2019 -- the step's gradient
+               is centre_gradient + (window score at theta - window score at the centre), pfg_sgld_cv_update_device.  Every
+               descriptor has a TWIN that differs in theta (the centre's row), out and scratch alone, launched with it in
+               ONE launch of 2 * _nd descriptors: same window, same seed, stream and counter, hence the same normals and
+               uniforms -- common random numbers -- and at theta = centre the two records are bitwise equal, the step a
+               Langevin step on centre_gradient.  On buffered windows the variance of a plain step's gradient is dominated
+               by which window was drawn; the control variate removes that term down to O(|theta - centre|^2).  With
+               kind='marginal' (LGSSM) the window scores are exact and the classic result holds without qualification;
+               with kind='pf' the particle noise cancels as far as resampling, which is discontinuous in theta, lets it
+               (measured, DESIGN section 7: a large gain in A at every N; in LQinv / LRinv a gain at N = 1000 that fades by
+               one posterior sd from the centre, and a LOSS at N = 100 from a quarter sd on -- re-centre, or use
+               minibatch_size = 2, which costs the same).
+               A single series; kind 'pf' with pf 'poyiadjis_N' | 'nemeth', every resampling, ess_threshold, both dtypes,
+               N <= 16384, single- and multi-window, host and device windows, graphs -- or kind 'marginal'.  Lists of
+               sequences, pf 'paris' | 'poyiadjis_N2', kind 'complete' and N > 16384 are refused by name.  centre(),
+               centre_gradient() and cv_statistics() read the centres, their gradients and the two records of the latest
+               step; set_centre() moves the centre, e.g. to the end of an 'adagrad' run, or re-centres mid-run.  A step
+               costs the launch of twice the descriptors.  NOT the drop-in sampler's sample_sgld_cv, by design: there both
+               filters run at the current parameters on independent draws)
+      centre, centre_repeats, centre_N: sampler='sgld_cv' (refused elsewhere): the constructor's last act is
+               set_centre(centre, centre_repeats) -- centre [P], [C, P], a Parameters object or None = the start parameters;
+               centre_repeats whole-series launches (default 1) with centre_N particles (default N, at most 16384; refused
+               with kind='marginal', which centres on one exact Kalman launch) are averaged into the centre gradient.  An
+               error in that gradient is a bias that does not average out over steps: see set_centre
       proposal_scale: sampler='pmmh' | 'pmala' (required there, refused elsewhere): the random walk's (the Langevin
                proposal's) standard deviations in raw-theta units, a positive scalar or a length-P vector (LGSSM: C stays 1
                whatever its entry)
@@ -217,6 +244,9 @@ class ChainEnsemble(object):
                runs the rho = 0 launch.  sampler='pgibbs': launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev,
                static), launch_update the conjugate draw; _pgibbs_init allocates path_dev, the counters and the scratch
                and runs the init pass.
+               sampler='sgld_cv': _desc / desc_dev hold _nl = 2 * _nd records, the chains' and behind them their twins'
+               (_cv_alloc); launch_windows and launch_reduce serve both halves, launch_pf launches them together, set_centre is
+               the centring pass on centre_desc_dev.
       _chain_state: what a chain of the sampler carries beyond theta, the momentum and the counter, and the scratch of a
                step: the one list state_dict, load_state_dict and _graph's snapshot follow.
     """
@@ -227,14 +257,15 @@ class ChainEnsemble(object):
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
                  Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                 ess_threshold=None, proposal_scale=None, pmmh_stat=None, correlation=None):
+                 ess_threshold=None, proposal_scale=None, pmmh_stat=None, correlation=None, centre=None, centre_repeats=1,
+                 centre_N=None):
         s = self._resolve_settings(
             model, observations, parameters, num_chains=num_chains, N=N, pf=pf, lambduh=lambduh,
             subsequence_length=subsequence_length, buffer_length=buffer_length, dtype=dtype, partition_style=partition_style,
             resampling=resampling, sampler=sampler, window_sampling=window_sampling, kind=kind, num_samples=num_samples,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, accept_reject=accept_reject, minibatch_size=minibatch_size,
             num_sequences=num_sequences, ess_threshold=ess_threshold, proposal_scale=proposal_scale, pmmh_stat=pmmh_stat,
-            kernel=kernel, correlation=correlation)
+            kernel=kernel, correlation=correlation, centre=centre, centre_repeats=centre_repeats, centre_N=centre_N)
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         Parameters, Prior, Helper = _model_info(model)
@@ -279,6 +310,9 @@ class ChainEnsemble(object):
         self.out_dev = torch.zeros((C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         self.momentum_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
+        if sampler == "adagrad":        # G, the running sum of squared scaled gradients, per variable
+            self.moment_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
+        self._cv = sampler == "sgld_cv"                 # every descriptor has a twin at the centre, in the same launch
         self.proposal_scale = s.proposal_scale
         self._mh = sampler in ("pmmh", "pmala")         # a proposal, a launch on it, an accept step
         if self._mh:
@@ -317,9 +351,11 @@ class ChainEnsemble(object):
         sb = self._scratch_bytes()
         if self._multi:
             self.scratch_bytes_per_window = sb
+        # the descriptors of one launch: the chains', and under 'sgld_cv' their twins' behind them
+        self._nl = 2 * self._nd if self._cv else self._nd
         self.scratch_dev = None
         if sb > 0:       # state in HBM (L2-resident), one slab per descriptor: the large-N kernel, paris_mem1024, Kalman messages
-            self.scratch_dev = torch.empty(self._nd * sb, dtype=torch.uint8, device=dev)
+            self.scratch_dev = torch.empty(self._nl * sb, dtype=torch.uint8, device=dev)
         garch_stationary = model == "garch" and self.helper.default_forward_message is None
         # sampler='pgibbs' launches none of these records (its sweep reads csmc_desc_dev) and N <= 1024 gives them no scratch;
         # they are kept, C * 376 bytes, because the step, the graph snapshot and enable_stamps address _desc / desc_dev
@@ -329,9 +365,11 @@ class ChainEnsemble(object):
             scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv, lambduh=self.lambduh, seed=self.seed, N=self.N,
             smoother=s.smoother, stat=s.stat, flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0,
             ess_threshold=s.ess_threshold, **s.paris)
+        if self._cv:
+            self._cv_alloc(s, records, sb)
         if not self._multi:
             self._set_windows(first=True)
-        self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)).to(dev)
+        self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nl, -1)).to(dev)
         if self._multi and not self._draws:
             self.launch_windows()           # static windows: written once, no draw
         if self.correlation is not None:
@@ -340,13 +378,152 @@ class ChainEnsemble(object):
             self._mh_init()
         if sampler == "pgibbs":
             self._pgibbs_init(pm, pv)
+        if self._cv:
+            self.set_centre(centre, s.centre_repeats)
+
+    # -- sampler='sgld_cv': the twins, the centre and its gradient -----------------------------------------------------
+    _CENTRE_SEED = 0x43454E5452453031       # "CENTRE01": the centring launches draw under seed ^ this
+
+    def _cv_alloc(self, s, records, sb):
+        """The state of a control-variate chain beyond SGLD's: the centre theta_centre_dev [C, MAX_THETA], its whole-series
+        score centre_grad_dev [C, 4] (score-column order, raw) and the counter of the centring launches centre_ctr_dev; the
+        twins' records (single-window: out_centre_dev [C, 8] itself; multi-window: twin_out_dev [C * W, 8] and their sequence
+        lengths, reduced into out_centre_dev); the twin descriptors, appended to _desc -- a twin is its chain's record but for
+        theta (the centre's row), out and scratch, so it filters the same window on the same draws; and the C descriptors of
+        the centring pass (centre_desc_dev: the whole series at the centre, centre_N particles, keys of their own)."""
+        C, dev, nd = self.C, self.device, self._nd
+        self.theta_centre_dev = self.theta_dev.clone()
+        self.centre_grad_dev = torch.zeros((C, 4), dtype=torch.float64, device=dev)
+        self.centre_ctr_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.centre_repeats, self.centre_N = s.centre_repeats, s.centre_N
+        self.out_centre_dev = torch.zeros((C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
+        twin_records = self.out_centre_dev
+        if self._multi:
+            twin_records = self.twin_out_dev = torch.zeros((nd, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
+            self.twin_seq_len_dev = torch.zeros(nd, dtype=torch.int32, device=dev)
+        idx = np.arange(nd, dtype=np.uint64)
+        chain = idx // np.uint64(self.W if self._multi else 1)
+        twins = self._desc.copy()
+        twins["theta"] = self.theta_centre_dev.data_ptr() + chain * np.uint64(8 * _capi.MAX_THETA)
+        twins["out"] = twin_records.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
+        if self.scratch_dev is not None:
+            twins["scratch"] = self.scratch_dev.data_ptr() + (idx + np.uint64(nd)) * np.uint64(sb)
+        self._desc = np.concatenate([self._desc, twins])
+        # the centring pass: one whole-series window per chain
+        self._centre_sb = csb = self._scratch_bytes(N=self.centre_N, whole=True)
+        self.centre_scratch_dev = torch.empty(C * csb, dtype=torch.uint8, device=dev) if csb > 0 else None
+        self.centre_out_dev = torch.zeros((C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
+        self.centre_acc_dev = torch.zeros((C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
+        c = np.arange(C, dtype=np.uint64)
+        d = self._desc[:nd:self.W if self._multi else 1].copy()       # chain c's static fields (its first window's)
+        d["theta"] = self.theta_centre_dev.data_ptr() + c * np.uint64(8 * _capi.MAX_THETA)
+        d["out"] = self.centre_out_dev.data_ptr() + c * np.uint64(8 * _capi.OUT_DOUBLES)
+        d["scratch"] = 0 if self.centre_scratch_dev is None else self.centre_scratch_dev.data_ptr() + c * np.uint64(csb)
+        d["step_ctr"] = self.centre_ctr_dev.data_ptr()
+        d["seed"] = np.uint64((self.seed ^ self._CENTRE_SEED) & 0xFFFFFFFFFFFFFFFF)
+        d["stream"] = c + np.uint64(self.chain_offset)
+        d["N"] = self.centre_N
+        d["y"], d["weights"], d["T"], d["t1"], d["tL"] = self.y_dev.data_ptr(), 0, self.T, 0, self.T
+        self._centre_desc = d
+        self.centre_desc_dev = self._upload_records(d)
+
+    def set_centre(self, theta=None, repeats=None):
+        """sampler='sgld_cv': move the centre and recompute its gradient.  theta: [P], [C, P], a Parameters object, or None =
+        each chain's current parameters (periodic re-centring).  theta_centre_dev takes the projection of it
+        (project_parameters).  Then `repeats` (default: the constructor's centre_repeats) whole-series launches at the centre --
+        y whole, t1 = 0, tL = T, no weights, the ensemble's filter settings with centre_N particles -- keyed by (seed ^ a
+        constant of its own, the global chain id, centre_ctr), centre_ctr advancing by one per launch in device memory: the
+        centre gradient depends on (seed, global chain id, the calls made so far) only, never on the rank partition.
+        pfg_cv_accumulate_device leaves their mean in centre_grad_dev [C, 4].  kind='marginal': one exact Kalman launch
+        whatever `repeats` says.  The launches are enqueued on torch's current stream; the call then waits for them, to
+        refuse a centre whose gradient is not finite.
+
+        An error in centre_gradient() enters every step of every chain with the same sign: a BIAS that does not average out
+        over steps, unlike the window noise the control variate removes.  repeats and centre_N are the knobs (the error's
+        variance falls as 1 / (repeats * centre_N)); with kind='marginal' there is no such error."""
+        if not self._cv:
+            raise ValueError("set_centre() belongs to sampler='sgld_cv', this ensemble runs '{0}'".format(self.sampler))
+        R = self.centre_repeats if repeats is None else int(repeats)
+        if self.kind == "marginal":
+            R = 1
+        if R < 1:
+            raise ValueError("set_centre needs repeats >= 1, got {0}".format(repeats))
+        if theta is None:
+            self.theta_centre_dev.copy_(self.theta_dev)
+        else:
+            th = np.asarray(theta.theta() if hasattr(theta, "theta") else theta, dtype=np.float64)
+            if th.shape not in ((self.P,), (self.C, self.P)):
+                raise ValueError("set_centre takes theta of shape [{0}] or [{1}, {0}], got {2}".format(self.P, self.C, th.shape))
+            rows = np.zeros((self.C, _capi.MAX_THETA))
+            rows[:, :self.P] = th
+            self.theta_centre_dev.copy_(torch.from_numpy(rows))
+        self._project_rows(self.theta_centre_dev)
+        stream = self._stream(None)
+        for r in range(R):
+            if self.ess_threshold:
+                self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.centre_N, self.C,
+                                                self.centre_desc_dev.data_ptr(), stream)
+            else:
+                self.ctx.launch_device_smoother(self.model, self.kernel, self.dtype, "device", self._launch_smoother,
+                                                1 if self._smoother == "kalman" else self.centre_N, self.C,
+                                                self.centre_desc_dev.data_ptr(), stream)
+            self.ctx.cv_accumulate_device(self.C, self.centre_out_dev.data_ptr(), self.centre_acc_dev.data_ptr(), r, R,
+                                          self.centre_ctr_dev.data_ptr(), stream)
+        self.centre_grad_dev.copy_(self.centre_acc_dev[:, :4])
+        self.synchronize()
+        used = self.centre_grad_dev.cpu().numpy()[:, list(_PMALA_SCORE_COLUMNS[self.model])]
+        bad = np.flatnonzero(~np.all(np.isfinite(used), axis=1))
+        if bad.size:
+            raise ValueError("sgld_cv: the centre gradient of chain {0} is not finite".format(int(bad[0]) + self.chain_offset))
+
+    def _project_rows(self, t):
+        """project_parameters on the rows of the device tensor t [*, MAX_THETA], in place (the rule of pfg_chains.hip's
+        project_store: |A| <= 0.9999, a negative Cholesky factor reflected, LGSSM's C = 1; GARCH: its LRinv alone)."""
+        def reflect(j):
+            L = t[:, j]
+            t[:, j] = torch.where(L < 0.0, torch.sqrt(L * L + 1e-16), L)
+        if self.model != "garch":
+            A = t[:, 0]
+            t[:, 0] = torch.where(A.abs() > 0.9999, A * (0.9999 / A.abs()), A)
+        if self.model == "lgssm":
+            t[:, 1] = 1.0
+        for j in ((3,) if self.model == "garch" else (self.P - 2, self.P - 1)):
+            reflect(j)
+
+    def centre(self):
+        """sampler='sgld_cv': [C, P] the centres the chains' control variates are taken at."""
+        self._need_cv("centre")
+        return self.theta_centre_dev[:, :self.P].cpu().numpy()
+
+    def centre_gradient(self):
+        """sampler='sgld_cv': [C, h] the whole-series score estimate at each chain's centre (score-column order, raw, without
+        the prior), as last_gradient_statistics()[0]."""
+        self._need_cv("centre_gradient")
+        return self.centre_grad_dev[:, :_capi.STAT_DIM[self.model]].cpu().numpy()
+
+    def cv_statistics(self):
+        """sampler='sgld_cv': (cur, centre), the [C, 8] records of the latest step's window at each chain's parameters and at
+        its centre (multi-window path: the reduced records).  The step's gradient is centre_gradient() + (cur - centre)."""
+        self._need_cv("cv_statistics")
+        return self.out_dev.cpu().numpy(), self.out_centre_dev.cpu().numpy()
+
+    def moment(self):
+        """sampler='adagrad': [C, P] the running sums of squared scaled gradients G."""
+        if self.sampler != "adagrad":
+            raise ValueError("moment() belongs to sampler='adagrad', this ensemble runs '{0}'".format(self.sampler))
+        return self.moment_dev[:, :self.P].cpu().numpy()
+
+    def _need_cv(self, what):
+        if not self._cv:
+            raise ValueError("{0}() belongs to sampler='sgld_cv', this ensemble runs '{1}'".format(what, self.sampler))
 
     @staticmethod
     def _resolve_settings(model, observations, parameters=None, num_chains=None, N=1000, pf="poyiadjis_N", lambduh=None,
                           subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
                           resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
                           Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None, correlation=None):
+                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None, correlation=None, centre=None,
+                          centre_repeats=1, centre_N=None):
         """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
         device is made here and nowhere else, so it runs (and is tested) without a GPU.
 
@@ -355,8 +532,14 @@ class ChainEnsemble(object):
         Ntilde, max_accept_reject; M, K, W, multi; S, B, strict; y (the concatenated series), T, segments ([K+1] offsets
         into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto;
         ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
-        'pmmh' | 'pmala'); correlation (rho as a float, None unless the correlated pseudo-marginal filter is on)."""
+        'pmmh' | 'pmala'); correlation (rho as a float, None unless the correlated pseudo-marginal filter is on); sampler =
+        'sgld_cv' alone: centre_repeats, centre_N (the particles of the centring launches: N unless given)."""
         tau = None
+        if sampler == "sgld_cv":
+            ChainEnsemble._refuse_cv(observations, N, pf, kind, centre_repeats, centre_N)
+        elif centre is not None or centre_N is not None or centre_repeats != 1:
+            raise ValueError("centre, centre_repeats and centre_N belong to sampler='sgld_cv' (SGLD with control variates), got "
+                             "sampler = '{0}'".format(sampler))
         if correlation is not None:
             ChainEnsemble._refuse_correlated(sampler, pmmh_stat, correlation, model, observations, N, pf, subsequence_length,
                                              buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
@@ -368,8 +551,9 @@ class ChainEnsemble(object):
         if ess_threshold is not None and ess_threshold != 0 and (kind != "pf" or sampler == "gibbs"):
             # (what else adaptive resampling is not built for: resolve_resampling, below)
             raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
-        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala", "pgibbs"):
-            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'pgibbs', 'pmala', 'gibbs' or 'pmmh'")
+        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala", "pgibbs", "sgd", "adagrad", "sgld_cv"):
+            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'sgd', 'adagrad', 'sgld_cv', 'pgibbs', 'pmala', 'gibbs' or "
+                             "'pmmh'")
         scale = None
         if sampler not in ("pmmh", "pmala"):
             if proposal_scale is not None:
@@ -549,11 +733,43 @@ class ChainEnsemble(object):
                                               ", the score columns too" if sampler == "pmala" else ""))
             if multi and (M != 1 or draws or rescale):
                 raise NotImplementedError(whole + "minibatch_size = 1 (an average of log-likelihoods is no estimate of one)")
-        return types.SimpleNamespace(
+        s = types.SimpleNamespace(
             proposal_scale=scale, kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, M=M, K=K, W=W, multi=multi, S=S, B=B, strict=strict, y=y, T=T,
             segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau,
             correlation=correlation)
+        if sampler == "sgld_cv":        # (the other samplers' namespaces keep their fields)
+            s.centre_repeats = 1 if kind == "marginal" else int(centre_repeats)
+            s.centre_N = N if centre_N is None else int(centre_N)
+        return s
+
+    @staticmethod
+    def _refuse_cv(observations, N, pf, kind, centre_repeats, centre_N):
+        """What sampler='sgld_cv' is not built for, each refusal naming its reason: the chain and its twin at the centre filter
+        one window of one series on the same draws, in one launch of one-workgroup kernels."""
+        what = "sampler='sgld_cv' (SGLD with control variates: every window is filtered at theta and at the centre) "
+        if isinstance(observations, (list, tuple)):
+            raise NotImplementedError(what + "centres on the whole-data gradient of one series: lists of sequences are not built")
+        if kind == "complete":
+            raise NotImplementedError(what + "needs a score that is a function of (theta, draws): kind='pf' or kind='marginal', "
+                                      "got kind = 'complete' (sampled FFBS paths as a control variate are not built)")
+        if kind == "pf" and pf in ("paris", "poyiadjis_N2"):
+            raise NotImplementedError(what + "runs the O(N) filters: pf = 'poyiadjis_N' | 'nemeth', got pf = '{0}' (a paired "
+                                      "PaRIS / O(N^2) launch is not built)".format(pf))
+        if kind == "pf" and int(N) > 16384:
+            raise NotImplementedError(what + "is built for N <= 16384 (no whole-GPU windows), got N = {0}".format(int(N)))
+        if kind == "marginal" and centre_N is not None:
+            raise ValueError(what + "with kind='marginal' centres on the exact Kalman gradient: centre_N has no particles to "
+                             "count, got centre_N = {0}".format(centre_N))
+        if centre_N is not None and not 1 <= int(centre_N) <= 16384:
+            raise NotImplementedError(what + "centres with one-workgroup launches: 1 <= centre_N <= 16384, got centre_N = {0}".format(
+                int(centre_N)))
+        try:
+            ok = int(centre_repeats) == centre_repeats and int(centre_repeats) >= 1
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(what + "needs centre_repeats >= 1 whole-series launches at the centre, got {0}".format(centre_repeats))
 
     # What differs between the refusals of the two kernel families that run one workgroup per chain (_refuse_chain_filter):
     # the prefix, the reason clause of each shared check, the largest N.
@@ -651,14 +867,16 @@ class ChainEnsemble(object):
                                       "(num_sequences = -1 takes them all)".format(K, _capi.MAX_DRAWN_SEQUENCES))
         return M, K, M * (n_seq if K == -1 else K)
 
-    def _scratch_bytes(self):
-        """pfg_dev_problem.scratch bytes per descriptor of the resolved smoother; refuses what the library refuses."""
+    def _scratch_bytes(self, N=None, whole=False):
+        """pfg_dev_problem.scratch bytes per descriptor of the resolved smoother; refuses what the library refuses.
+        N, whole: of a launch with another particle count on whole-series windows (the centring pass of 'sgld_cv')."""
+        N, S = self.N if N is None else int(N), -1 if whole else self.S
         if self._smoother == "kalman":
             # the backward messages of the longest window: S (segments: no window is longer), or the whole series
-            return _capi.kalman_scratch_bytes(self.S if self.S > 0 else self.T)
+            return _capi.kalman_scratch_bytes(S if S > 0 else self.T)
         if self._smoother == "kalman_ffbs":
             # the forward messages of the longest buffer: a window and its two buffers, or the whole series
-            return _capi.kalman_scratch_bytes(min(self.T, self.S + 2 * self.B) if self.S > 0 else self.T)
+            return _capi.kalman_scratch_bytes(min(self.T, S + 2 * self.B) if S > 0 else self.T)
         if self.ess_threshold or self._multi or self._smoother in ("paris", "poyiadjis_n2", "nemeth_stratified"):
             # PaRIS, N <= 1024: 0, the LDS-resident variants keep their state in LDS; above: paris_mem1024's slab.  The
             # single-window PaRIS path (N <= 1024 only) relies on that answer of 0 where it once wrote the literal.
@@ -666,17 +884,17 @@ class ChainEnsemble(object):
             # Stratified and adaptive windows: 0 for N <= 1024, the large-N twins' slab up to 16384 (adaptive: also where
             # plain device-generator windows would run LDS-resident, 1024 < N <= 4096)
             if self.ess_threshold:
-                sb = self.ctx.scratch_bytes_adaptive(self.model, self.dtype, self.N)
+                sb = self.ctx.scratch_bytes_adaptive(self.model, self.dtype, N)
             else:
-                sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", self._smoother, self.N)
+                sb = self.ctx.scratch_bytes_smoother(self.model, self.dtype, "device", self._smoother, N)
             if sb < 0:
-                raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(self.N))
+                raise NotImplementedError("N = {0} is above the one-workgroup kernels' maximum (16384)".format(N))
             return sb
         # pfg_scratch_bytes answers above N = 16384 too (the whole-GPU plan's slab) where pfg_scratch_bytes_smoother says -1,
         # and 'nemeth_systematic' says -1 above N = 1024; the single-window path keeps the query it has always made
-        sb = self.ctx.scratch_bytes(self.model, self.dtype, "device", self.N)
+        sb = self.ctx.scratch_bytes(self.model, self.dtype, "device", N)
         if sb < 0:
-            raise ValueError("N = {0} is above the supported maximum".format(self.N))
+            raise ValueError("N = {0} is above the supported maximum".format(N))
         return sb
 
     def _weights_blocks(self, bounds, S, scale=None):
@@ -747,8 +965,16 @@ class ChainEnsemble(object):
         np.random.choice(K, 1)) and a window start inside it on the host (sgmcmc_sampler.py:259-288).  Either way
         y / T / t1 / tL / weights follow from (sequence, start) below, a single series being a list of one sequence: the
         window is S long, or the whole sequence when that is no longer than S; weights is the start's row of the sequence's
-        block, null without a table (a full single series).  Returns whether the descriptors changed."""
-        d, S, B, C, bounds = self._desc, self.S, self.B, self.C, self._bounds
+        block, null without a table (a full single series).  Returns whether the descriptors changed.  sampler='sgld_cv': the
+        twins (the records behind the chains') take their chains' windows."""
+        changed = self._set_chain_windows(self._desc[:self.C], first)
+        if self._cv and (changed or first):
+            for f in ("y", "T", "t1", "tL", "weights"):
+                self._desc[f][self.C:] = self._desc[f][:self.C]
+        return changed
+
+    def _set_chain_windows(self, d, first):
+        S, B, C, bounds = self.S, self.B, self.C, self._bounds
         static = self.segments is None and S == -1
         if static and not first:
             return False
@@ -787,7 +1013,8 @@ class ChainEnsemble(object):
         traced=True runs the twin instantiation that honours trace_* / rec_* buffers a caller put into
         the descriptors (tests, diagnostics); the production launch ignores them.
         The launch is the resolved one: the launch smoother (_resolve_settings), at most N particles (the Kalman score has
-        none: 1) in each of _nd descriptors."""
+        none: 1) in each of _nl descriptors (_nd, and under 'sgld_cv' the twins behind them: ONE launch, so a chain and its
+        twin run the same kernel instantiation)."""
         if traced and self.kind != "pf":
             raise ValueError("kind='{0}' has no particles to trace".format(self.kind))
         if self.sampler == "pgibbs":    # the conditional sweep: its own descriptors (traced: the twin that fills their trace_*)
@@ -795,12 +1022,12 @@ class ChainEnsemble(object):
         if self.correlation is not None:    # the sorted, correlated filter: its own descriptors as well
             return self.launch_cpm(stream, traced=traced)
         if self.ess_threshold:      # adaptive resampling: its own kernels, the family stated at launch level
-            return self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.N, self._nd,
+            return self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.N, self._nl,
                                                    self.desc_dev.data_ptr(), self._stream(stream), traced=traced)
         launch, smoother = self.ctx.launch_device_smoother, self._launch_smoother
         if traced and self.pf != "paris":       # the PaRIS kernels always honour trace buffers: traced or not, the same launch
             launch, smoother = self.ctx.launch_device_traced, self._smoother
-        launch(self.model, self.kernel, self.dtype, "device", smoother, 1 if self._smoother == "kalman" else self.N, self._nd,
+        launch(self.model, self.kernel, self.dtype, "device", smoother, 1 if self._smoother == "kalman" else self.N, self._nl,
                self.desc_dev.data_ptr(), self._stream(stream))
 
     def launch_update(self, stream=None):
@@ -814,6 +1041,13 @@ class ChainEnsemble(object):
             self.ctx.gibbs_update_device(*theta, *out, *key)
         elif self.sampler == "pgibbs":
             self.ctx.pgibbs_update_device(*theta, *out, *key)
+        elif self.sampler == "sgd":
+            self.ctx.sgd_update_device(*theta, *out, self.epsilon, float(self.T), *key[2:])
+        elif self.sampler == "adagrad":
+            self.ctx.adagrad_update_device(*theta, self.moment_dev.data_ptr(), *out, self.epsilon, float(self.T), *key[2:])
+        elif self._cv:
+            self.ctx.sgld_cv_update_device(*theta, self.out_dev.data_ptr(), self.out_centre_dev.data_ptr(),
+                                           self.centre_grad_dev.data_ptr(), self.hyper, self.epsilon, float(self.T), *key)
         elif self.sampler == "sghmc":
             self.ctx.sghmc_update_device(*theta, self.momentum_dev.data_ptr(), *out, self.epsilon, self.friction,
                                          float(self.T), *key)
@@ -976,21 +1210,31 @@ class ChainEnsemble(object):
         every descriptor for the step *step_ctr is at.  No-op for full-sequence chains.  Multi-window path: all
         C * W descriptors and their sequence lengths (pfg_sample_windows_multi_device)."""
         weights = self.weights_dev.data_ptr() if self.weights_dev is not None else 0
-        if self._multi:
-            self.ctx.sample_windows_multi_device(
-                self.C, self.bounds_dev.numel() - 1, self.bounds_dev.data_ptr(), self.woffs_dev.data_ptr(),
-                self.num_sequences if self.segments is not None else -1, self.M, self.desc_dev.data_ptr(),
-                self.seq_len_dev.data_ptr(), self.y_dev.data_ptr(), weights, self.S, self.B, self.strict,
-                self.seed ^ 0x4D554C5449574E44, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
-        elif self.S != -1:
-            self.ctx.sample_windows_device(
-                self.C, self.desc_dev.data_ptr(), self.y_dev.data_ptr(), weights, self.T, self.S, self.B, self.strict,
-                self.seed ^ 0x2545F4914F6CDD1D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
+        # sampler='sgld_cv': the twins' records are sampled again under the chains' key, so they hold the chains' windows
+        halves = [(self.desc_dev.data_ptr(), self.seq_len_dev.data_ptr() if self._multi else 0)]
+        if self._cv:
+            halves.append((self.desc_dev.data_ptr() + self._nd * self.desc_dev.shape[1],
+                           self.twin_seq_len_dev.data_ptr() if self._multi else 0))
+        for desc, seq_len in halves:
+            if self._multi:
+                self.ctx.sample_windows_multi_device(
+                    self.C, self.bounds_dev.numel() - 1, self.bounds_dev.data_ptr(), self.woffs_dev.data_ptr(),
+                    self.num_sequences if self.segments is not None else -1, self.M, desc, seq_len, self.y_dev.data_ptr(),
+                    weights, self.S, self.B, self.strict, self.seed ^ 0x4D554C5449574E44, self.chain_offset,
+                    self.step_ctr.data_ptr(), self._stream(stream))
+            elif self.S != -1:
+                self.ctx.sample_windows_device(
+                    self.C, desc, self.y_dev.data_ptr(), weights, self.T, self.S, self.B, self.strict,
+                    self.seed ^ 0x2545F4914F6CDD1D, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
 
     def launch_reduce(self, stream=None):
         """Multi-window path: the C * W window records -> the C records the update reads (pfg_reduce_windows_device)."""
         self.ctx.reduce_windows_device(self.C, self.K_eff, self.M, self.win_out_dev.data_ptr(), self.seq_len_dev.data_ptr(),
                                        self._rescale, float(self.T), self.out_dev.data_ptr(), self._stream(stream))
+        if self._cv:        # the twins' window records -> out_centre_dev
+            self.ctx.reduce_windows_device(self.C, self.K_eff, self.M, self.twin_out_dev.data_ptr(),
+                                           self.twin_seq_len_dev.data_ptr(), self._rescale, float(self.T),
+                                           self.out_centre_dev.data_ptr(), self._stream(stream))
 
     def _enqueue_step(self):
         """One step: the windows if there are any to draw, the proposal if the sampler has one, the filter, the reduction
@@ -1003,7 +1247,7 @@ class ChainEnsemble(object):
         if draws == "device":
             self.launch_windows()
         elif draws == "host" and self.steps_done > 0 and self._set_windows():
-            self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self.C, -1)),
+            self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self._nl, -1)),
                                 non_blocking=True)
         if self._mh:
             self.launch_propose()
@@ -1089,7 +1333,8 @@ class ChainEnsemble(object):
         """(carried, scratch).  carried: what a chain of this sampler carries beyond theta, the momentum and the counter, as
         ordered (checkpoint key, tensor) pairs -- the estimates a 'pmmh' | 'pmala' chain was accepted with and its
         acceptance count, the buffer selector of a correlated 'pmmh' chain and the count it was last moved at (its normals
-        travel as 'aux'), the path of a 'pgibbs' chain and how often its sweep degenerated.  state_dict and load_state_dict
+        travel as 'aux'), the path of a 'pgibbs' chain and how often its sweep degenerated, the moment of an 'adagrad' chain,
+        the centre, its gradient and the counter of the centring launches of an 'sgld_cv' chain.  state_dict and load_state_dict
         follow it.  scratch: what a step overwrites besides; _graph restores both after its eager step."""
         carried, scratch = [], [self.desc_dev]
         if self._mh:
@@ -1102,6 +1347,11 @@ class ChainEnsemble(object):
             carried += [("which", self.which_dev), ("seen", self.seen_dev)]
         if self.sampler == "pgibbs":
             carried = [("path", self.path_dev), ("n_degenerate", self.ndeg_dev)]
+        if self.sampler == "adagrad":
+            carried = [("moment", self.moment_dev)]
+        if self._cv:    # (a step moves none of the three; they travel with the checkpoint)
+            carried = [("centre", self.theta_centre_dev), ("centre_gradient", self.centre_grad_dev),
+                       ("centre_ctr", self.centre_ctr_dev)]
         return carried, scratch
 
     def load_state_dict(self, state):
@@ -1150,9 +1400,9 @@ class ChainEnsemble(object):
         instructions outside the T-loop).  Multi-window path: one record per window, [C * W, 16]."""
         if self._multi:         # the device wrote the windows: start from its copy
             self._desc = self.desc_dev.cpu().numpy().reshape(-1).view(_capi.DEV_PROBLEM_DTYPE).copy()
-        self.stamps_dev = torch.zeros((self._nd, _capi.STAMP_WORDS), dtype=torch.int64, device=self.device)
-        self._desc["stamps"] = self.stamps_dev.data_ptr() + np.arange(self._nd, dtype=np.uint64) * np.uint64(8 * _capi.STAMP_WORDS)
-        self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self._nd, -1)))
+        self.stamps_dev = torch.zeros((self._nl, _capi.STAMP_WORDS), dtype=torch.int64, device=self.device)
+        self._desc["stamps"] = self.stamps_dev.data_ptr() + np.arange(self._nl, dtype=np.uint64) * np.uint64(8 * _capi.STAMP_WORDS)
+        self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self._nl, -1)))
         self.synchronize()
 
     def kernel_clock(self):
