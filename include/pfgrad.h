@@ -331,7 +331,7 @@ typedef struct pfg_dev_problem {
 
 int pfg_version(void);
 /* sizeof() of an ABI struct: 0 pfg_problem, 1 pfg_result, 2 pfg_dev_problem, 3 pfg_prior_hyper, 4 pfg_csmc_problem,
- * 5 pfg_cpm_problem (bindings assert their mirror has the same size) */
+ * 5 pfg_cpm_problem, 6 pfg_sqmc_problem (bindings assert their mirror has the same size) */
 int pfg_struct_size(int which);
 int pfg_create(pfg_ctx **out, int device_id);
 void pfg_destroy(pfg_ctx *ctx);
@@ -732,6 +732,45 @@ int pfg_cpm_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const p
                    uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced);
 int pfg_cpm_commit_device(pfg_ctx *ctx, int B, const uint64_t *n_accept, uint64_t *seen, int32_t *which, int init,
                           void *hip_stream);
+
+/* EXTENSION (not in the reference): the filter of sequential quasi-Monte Carlo (Gerber and Chopin 2015) for B resident SVM or
+ * LGSSM chains, as the estimate of PMMH.  The particles are sorted by state before each resampling, and the N (resampling,
+ * move) pairs of a timestep are one randomised Sobol' point set in [0, 1)^2: with a_i = bitreverse32(i) and b_i the second
+ * Sobol' coordinate of index i (the XOR over the set bits k of i of V_k, V_0 = 0x80000000, V_{k+1} = V_k ^ (V_k >> 1)), row
+ * r = 0 .. T (row 0 serves x_{-1}, row t+1 step t) draws four words (s_a, s_b, l_a, l_b) once and point i of the row is
+ * u = ((((a_i ^ s_a) << 20) | (l_a >> 12)) + 0.5) 2^-52, v likewise from b_i, s_b, l_b -- a random digital shift, which keeps
+ * the net and makes every point uniform, so the estimate is unbiased and PMMH on it exact for every N.  x_{-1}^i = prior_mean
+ * + sqrt(prior_var) Phi^-1(v_i) of row 0.  Step 0: the particles in ascending order of (x_{-1}, index), the child at position
+ * k moves from the parent at position k.  Step t >= 1: the particles in ascending order of (state, index), the CDF of their
+ * weights W in that order, and the child at position k takes the smallest j with cdf[j] > u_(k) W (at most N-1), u_(k) =
+ * (k + delta) / N the k-th smallest u of row t+1.  Every child moves by the prior kernel with z = Phi^-1(v) of the point whose
+ * u has rank k, i(k) = bitreverse_m(k ^ (s_a >> (32 - m))), N = 2^m.
+ *
+ * pfg_sqmc_problem: one chain's filter.  Every pointer is DEVICE memory.  theta: the raw row (PFG_MAX_THETA doubles); y [T];
+ * out: PFG_OUT_DOUBLES doubles, out[4] = sum_t log((1 / N) sum_i w_t^i) with the Gaussian constants of the emission density,
+ * every other slot 0.  A weight sum that is zero or not finite: out[4] = -inf (pfg_pmmh_accept_device rejects it).  A
+ * descriptor with a NULL array (the trace pointers may be NULL), T < 1, N not a power of two, N < 2 or above the launch's
+ * n_max, or a prior variance that is not positive: a NaN record and no other store.  The trace pointers are read by a
+ * traced launch only: trace_anc [T][N] each child's parent in sorted coordinates (row 0: -1), trace_ll [T] the per-step
+ * increments of out[4], trace_z [T+1][N] the normals as used (row 0 by particle, the later rows by child).
+ *
+ * pfg_sqmc_device: one workgroup per problem, 64 x 2 (one wave) for n_max <= 128, 256 x 4 up to 1024; `problems` is a DEVICE
+ * array of B records, n_max >= every record's N.  The shifts: Philox4x32-10 keyed by (seed, chain_offset + b, *step_ctr,
+ * row) under a tag of their own (csrc/pfg_sqmc.hip); *step_ctr is read, not incremented.  traced != 0 runs the twin that
+ * honours the trace pointers; both write the same out, bit for bit.  PFG_ERR_UNSUPPORTED: GARCH, a dtype other than PFG_F64,
+ * n_max > 1024 or < 2; PFG_ERR_INVALID: a bad model id, B < 0, problems == NULL. */
+typedef struct pfg_sqmc_problem {
+    const double *theta;
+    const double *y;
+    double *out;
+    int32_t *trace_anc;
+    double *trace_ll;
+    double *trace_z;
+    double prior_mean, prior_var;
+    int32_t T, N;
+} pfg_sqmc_problem;
+int pfg_sqmc_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_sqmc_problem *problems, uint64_t seed,
+                    uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced);
 
 /* EXTENSION (not in the reference): density-tempered SMC over B resident PMMH chains (Del Moral, Doucet and Jasra 2006; Duan
  * and Fulop 2015).  The chains are one interacting population that is carried from a Gaussian q0 -- the product over the

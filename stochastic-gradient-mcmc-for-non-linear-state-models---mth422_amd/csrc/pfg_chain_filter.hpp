@@ -1,6 +1,7 @@
 // What the kernels that run one chain per lane or per workgroup share: the chain key of every draw (pfg_chains.hip,
-// pfg_csmc.hip, pfg_cpm.hip) and, for the filters with one workgroup per chain, f64, N <= 1024 (pfg_csmc.hip, pfg_cpm.hip),
-// the device pieces -- emission_logw, cdf_search, the descriptor check, the workgroup maximum and CDF offsets -- and the host
+// pfg_csmc.hip, pfg_cpm.hip, pfg_sqmc.hip) and, for the filters with one workgroup per chain, f64, N <= 1024 (pfg_csmc.hip,
+// pfg_cpm.hip, pfg_sqmc.hip), the device pieces -- emission_logw, cdf_search, the descriptor check, the workgroup maximum and
+// CDF offsets, the sort by state of the two filters that resample in the order of the states -- and the host
 // pieces: the entry point's argument check, the (model, traced, n_max) -> instantiation dispatch and the sizing helpers.
 // Each file keeps its tags, its LDS, its phase structure and what it does with a descriptor it refuses.
 #pragma once
@@ -100,6 +101,73 @@ __device__ __forceinline__ void block_cdf(double (&red)[K][NW], const double *ru
             }
         }
         for (int k = 0; k < K; ++k) off[k] += before[k];
+    }
+}
+
+// ---- the sort of the filters that resample in the order of the states (pfg_cpm.hip, pfg_sqmc.hip)
+// (xa, ia) before (xb, ib) in the order of the sort
+__device__ __forceinline__ bool key_less(double xa, int ia, double xb, int ib) { return xa < xb || (xa == xb && ia < ib); }
+
+// The N (state, log-weight) pairs of a workgroup of NT threads x PPT particles, particle i = tid * PPT + k, ascending by
+// (state, particle index): a total order.  Afterwards sx holds the sorted states and si sorted position -> particle.
+//   one wave (NT == 64)  a rank sort: a particle's position is the number of keys before its own, N broadcast LDS reads per
+//                        thread and no barrier.  The caller has stored the keys in particle order in `keys` and synchronised;
+//                        x, lw: the thread's own particles.  Distinct states need one comparison per pair; equal ones collide
+//                        on a position, which the read-back sees, and the whole wave then ranks again with the index as the
+//                        tie-break.  slw: the log-weights by sorted position.
+//   otherwise            a bitonic network over npad, the next power of two, in LDS, a barrier per stage.  The caller has stored
+//                        sx[i], si[i] = i for i < npad (the padding: +inf keys) and synchronised; slw (the caller's, by
+//                        particle) is not touched.
+template <int NT, int PPT>
+__device__ __forceinline__ void sort_by_state(int N, int npad, const double *x, const double *lw, const double *keys, double *sx,
+                                              double *slw, int *si) {
+    constexpr int NW = NT / WAVE;
+    const int tid = threadIdx.x, i0 = tid * PPT;
+    if constexpr (NW == 1) {
+        auto scatter = [&](const int *rank) {
+#pragma unroll
+            for (int k = 0; k < PPT; ++k)
+                if (i0 + k < N) { sx[rank[k]] = x[k]; slw[rank[k]] = lw[k]; si[rank[k]] = i0 + k; }
+            block_sync<NW>();
+        };
+        int rank[PPT];
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) rank[k] = 0;
+        for (int j = 0; j < N; ++j) {
+            const double xj = keys[j];
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) rank[k] += xj < x[k] ? 1 : 0;
+        }
+        scatter(rank);
+        bool clash = false;
+#pragma unroll
+        for (int k = 0; k < PPT; ++k)
+            if (i0 + k < N) clash = clash || si[rank[k]] != i0 + k;
+        if (__any(clash)) {         // uniform over the wave
+            block_sync<NW>();
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) rank[k] = 0;
+            for (int j = 0; j < N; ++j) {
+                const double xj = keys[j];
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) rank[k] += key_less(xj, j, x[k], i0 + k) ? 1 : 0;
+            }
+            scatter(rank);
+        }
+    } else {
+        for (int kk = 2; kk <= npad; kk <<= 1) {
+            for (int j = kk >> 1; j > 0; j >>= 1) {
+                for (int q = tid; q < (npad >> 1); q += NT) {
+                    const int a = ((q & ~(j - 1)) << 1) | (q & (j - 1)), b = a | j;
+                    const bool up = (a & kk) == 0;
+                    const double xa = sx[a], xb = sx[b];
+                    const int ia = si[a], ib = si[b];
+                    const bool swap = up ? key_less(xb, ib, xa, ia) : key_less(xa, ia, xb, ib);
+                    if (swap) { sx[a] = xb; sx[b] = xa; si[a] = ib; si[b] = ia; }
+                }
+                block_sync<NW>();
+            }
+        }
     }
 }
 

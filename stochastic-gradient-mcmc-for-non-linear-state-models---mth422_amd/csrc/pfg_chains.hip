@@ -12,6 +12,8 @@
 //            sgrld, pmmh and pmala; GARCH log_mu, logit_phi, logit_lambduh, LRinv: z0..z3).  All disjoint from one another,
 //            from the window tags 0x53...... / 0x57......, from the sweep's 0x4353.... (pfg_csmc.hip) and from the correlated
 //            filter's 0x43500000 | column >> 2, at most 0x43500100 (pfg_cpm.hip).
+//              0x53510000                sqmc: the digital shift of a row of the point set (pfg_sqmc.hip), with the row XORed
+//                                        into the counter's third word
 //              0x534D0001                smc: the resampling uniform of a tempering stage (pfg_smc.hip), keyed by the stage and
 //                                        not by a chain: counter {stage_lo, stage_hi, 0, tag}.  The window tag 0x53000000 | j
 //                                        stops at j < PFG_MAX_DRAWN_SEQUENCES = 1024, far below 0x4D0001.

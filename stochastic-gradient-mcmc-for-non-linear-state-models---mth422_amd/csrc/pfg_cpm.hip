@@ -20,7 +20,8 @@
 //   t = 0    x_{-1}^i = prior_mean + sqrt(prior_var) U'[0][i], x_0^i = particle_step(x_{-1}^i, U'[1][i]), lw = log g(y_0 | x_0).
 //   t >= 1   the smoothness the correlation needs (a small move of U moves the estimate little) comes from resampling in
 //            the order of the states:
-//              sort     the N (state, log-weight) pairs ascending by (state, original index): a total order.  One wave: a
+//              sort     (pfg::sort_by_state, pfg_chain_filter.hpp: shared with pfg_sqmc.hip)
+//                       the N (state, log-weight) pairs ascending by (state, original index): a total order.  One wave: a
 //                       rank sort, a particle's position is the number of keys before its own (N broadcast LDS reads per
 //                       thread, no barrier; equal states are seen as a collision and ranked again with the index).  256 x 4: a
 //                       bitonic network over the next power of two in LDS, the padding carries +inf keys and zero weight.
@@ -43,9 +44,6 @@ using namespace pfg_host;
 namespace {
 
 constexpr uint32_t kTagCpm = 0x43500000u;      // | column >> 2
-
-// (xa, ia) before (xb, ib) in the order of the sort
-__device__ __forceinline__ bool key_less(double xa, int ia, double xb, int ib) { return xa < xb || (xa == xb && ia < ib); }
 
 template <int MODEL, int NT, int PPT, bool TRACED>
 __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restrict__ probs, double rho, uint64_t seed,
@@ -179,58 +177,8 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
         // (S) the sort: the last step's weights need no order (their sum does not depend on it).  -DPFG_CPM_NO_SORT: a
         // diagnostic build that leaves it out, to time what it costs (tools/cpm_time.py); never the library's
 #ifndef PFG_CPM_NO_SORT
-        if (t < T) {
-            if constexpr (ONE_WAVE) {
-                // rank sort: a particle's sorted position is the number of keys before its own, N broadcast reads per thread
-                // and no barrier.  Distinct states need one comparison per pair; equal ones collide on a position, which the
-                // read-back below sees, and the whole wave then ranks again with the index as the tie-break
-                auto scatter = [&](const int *rank) {
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k)
-                        if (i0 + k < N) { sx[rank[k]] = x[k]; slw[rank[k]] = lw[k]; si[rank[k]] = i0 + k; }
-                    pfg::block_sync<NW>();
-                };
-                int rank[PPT];
-#pragma unroll
-                for (int k = 0; k < PPT; ++k) rank[k] = 0;
-                for (int j = 0; j < N; ++j) {
-                    const double xj = cdf[j];
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k) rank[k] += xj < x[k] ? 1 : 0;
-                }
-                scatter(rank);
-                bool clash = false;
-#pragma unroll
-                for (int k = 0; k < PPT; ++k)
-                    if (i0 + k < N) clash = clash || si[rank[k]] != i0 + k;
-                if (__any(clash)) {         // uniform over the wave
-                    pfg::block_sync<NW>();
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k) rank[k] = 0;
-                    for (int j = 0; j < N; ++j) {
-                        const double xj = cdf[j];
-#pragma unroll
-                        for (int k = 0; k < PPT; ++k) rank[k] += key_less(xj, j, x[k], i0 + k) ? 1 : 0;
-                    }
-                    scatter(rank);
-                }
-            } else {
-                // bitonic network over the next power of two, a barrier per stage
-                for (int kk = 2; kk <= npad; kk <<= 1) {
-                    for (int j = kk >> 1; j > 0; j >>= 1) {
-                        for (int q = tid; q < (npad >> 1); q += NT) {
-                            const int a = ((q & ~(j - 1)) << 1) | (q & (j - 1)), b = a | j;
-                            const bool up = (a & kk) == 0;
-                            const double xa = sx[a], xb = sx[b];
-                            const int ia = si[a], ib = si[b];
-                            const bool swap = up ? key_less(xb, ib, xa, ia) : key_less(xa, ia, xb, ib);
-                            if (swap) { sx[a] = xb; sx[b] = xa; si[a] = ib; si[b] = ia; }
-                        }
-                        pfg::block_sync<NW>();
-                    }
-                }
-            }
-        }
+        // (pfg::sort_by_state: a rank sort in one wave, a bitonic network over the next power of two under 256 x 4)
+        if (t < T) pfg::sort_by_state<NT, PPT>(N, npad, x, lw, cdf, sx, slw, si);
 #else
         if (t < T && ONE_WAVE) {
 #pragma unroll

@@ -390,6 +390,7 @@ int pfg_struct_size(int which) {
         case 3: return (int)sizeof(pfg_prior_hyper);
         case 4: return (int)sizeof(pfg_csmc_problem);
         case 5: return (int)sizeof(pfg_cpm_problem);
+        case 6: return (int)sizeof(pfg_sqmc_problem);
     }
     return -1;
 }

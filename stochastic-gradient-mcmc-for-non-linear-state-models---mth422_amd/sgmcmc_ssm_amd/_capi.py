@@ -168,6 +168,14 @@ CPM_PROBLEM_DTYPE = np.dtype([
     ("T", "i4"), ("N", "i4"),
 ], align=True)
 CPM_MAX_N = 1024
+
+# numpy mirror of pfg_sqmc_problem (one sequential quasi-Monte Carlo filter; every pointer a device address)
+SQMC_PROBLEM_DTYPE = np.dtype([
+    ("theta", "u8"), ("y", "u8"), ("out", "u8"), ("trace_anc", "u8"), ("trace_ll", "u8"), ("trace_z", "u8"),
+    ("prior_mean", "f8"), ("prior_var", "f8"),
+    ("T", "i4"), ("N", "i4"),
+], align=True)
+SQMC_MAX_N = 1024                                   # and a power of two
 SMC_MIN_CHAINS, SMC_MAX_CHAINS = 2, 1 << 20        # a tempered population (pfg_smc_temper_device: one workgroup)
 SMC_RESULT_DOUBLES = 8                              # PFG_SMC_RESULT_DOUBLES
 # the theta slots a PMMH proposal moves (pfg_chains.hip: moves), as pfg_smc_scale_device's bit mask
@@ -223,7 +231,7 @@ EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_l
            "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
            "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device",
            "pfg_pmala_propose_device", "pfg_pmala_accept_device", "pfg_csmc_scratch_bytes", "pfg_csmc_device",
-           "pfg_pgibbs_update_device", "pfg_cpm_aux_bytes", "pfg_cpm_device", "pfg_cpm_commit_device",
+           "pfg_pgibbs_update_device", "pfg_cpm_aux_bytes", "pfg_cpm_device", "pfg_cpm_commit_device", "pfg_sqmc_device",
            "pfg_smc_scratch_bytes", "pfg_smc_logtarget_device", "pfg_smc_temper_device", "pfg_smc_gather_device",
            "pfg_smc_scale_device", "pfg_smc_accept_device", "pfg_sgd_update_device", "pfg_adagrad_update_device",
            "pfg_sgld_cv_update_device", "pfg_cv_accumulate_device")
@@ -267,7 +275,7 @@ def load_library():
     lib.pfg_struct_size.argtypes = [C.c_int]
     lib.pfg_struct_size.restype = C.c_int
     sizes = (C.sizeof(Problem), C.sizeof(Result), DEV_PROBLEM_DTYPE.itemsize, C.sizeof(PriorHyper), CSMC_PROBLEM_DTYPE.itemsize,
-             CPM_PROBLEM_DTYPE.itemsize)
+             CPM_PROBLEM_DTYPE.itemsize, SQMC_PROBLEM_DTYPE.itemsize)
     for which, mine in enumerate(sizes):
         if lib.pfg_struct_size(which) != mine:
             raise RuntimeError("ABI mismatch: struct {0} is {1} bytes in libpfgrad.so, {2} in the binding"
@@ -356,6 +364,8 @@ def load_library():
     lib.pfg_cpm_device.restype = C.c_int
     lib.pfg_cpm_commit_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.pfg_cpm_commit_device.restype = C.c_int
+    lib.pfg_sqmc_device.argtypes = lib.pfg_csmc_device.argtypes
+    lib.pfg_sqmc_device.restype = C.c_int
     lib.pfg_smc_scratch_bytes.argtypes = [C.c_int]
     lib.pfg_smc_scratch_bytes.restype = C.c_int64
     lib.pfg_smc_logtarget_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PriorHyper),
@@ -888,6 +898,17 @@ class Context:
         self._check(self.lib.pfg_cpm_commit_device(
             self.handle, int(B), C.c_void_p(n_accept_ptr or 0), C.c_void_p(seen_ptr or 0), C.c_void_p(which_ptr or 0),
             int(bool(init)), C.c_void_p(int(stream_ptr))))
+
+    def sqmc_device(self, model, dtype, n_max, B, problems_ptr, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0,
+                    traced=False):
+        """pfg_sqmc_device: one sequential quasi-Monte Carlo filter per pfg_sqmc_problem record (a device array): sorted
+        particles on one randomised Sobol' point set per timestep, out[4] the log-likelihood estimate."""
+        m = model if isinstance(model, int) else MODEL[model]
+        d = dtype if isinstance(dtype, int) else DTYPE[dtype]
+        self._check(self.lib.pfg_sqmc_device(
+            self.handle, m, d, int(n_max), int(B), C.c_void_p(problems_ptr or 0),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
+            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr)), int(bool(traced))))
 
     def logprior_device(self, model, B, theta_ptr, hyper, logprior_ptr, stream_ptr=0):
         """pfg_logprior_device: logprior[b] = Prior.logprior of the raw row theta[b], up to a constant of the hyper-parameters."""

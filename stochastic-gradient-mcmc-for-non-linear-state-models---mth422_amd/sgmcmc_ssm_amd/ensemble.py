@@ -192,6 +192,14 @@ class ChainEnsemble(object):
                refused by name.  aux() reads the normals the chains hold; state_dict carries them ('aux', the current
                buffer only) with 'correlation' and 'T', and load_state_dict refuses another rho, T or N.  The ensemble keeps
                two buffers per chain: 2 * C * pfg_cpm_aux_bytes(T, N) bytes, 19.9 GB at T = 1000, N = 100, 12288 chains)
+      sqmc: sampler='pmmh': False (the default: today's PMMH, bit for bit) | True (extension: sequential quasi-Monte Carlo,
+               Gerber and Chopin 2015.  launch_pf is pfg_sqmc_device: the particles are sorted by state before each resampling
+               and the N (resampling, move) pairs of a timestep are one Sobol' point set in [0, 1)^2 under a fresh random
+               digital shift, so the estimate itself is less noisy at a given N; it stays unbiased, so the chain is exact for
+               every N.  The chain carries nothing beyond PMMH's state; state_dict records 'sqmc' = True and load_state_dict
+               refuses a checkpoint of the other kind.  Model 'svm' | 'lgssm', dtype 'f64', N a power of two in 2 .. 1024,
+               the whole series, kind 'pf'; correlation, pf, resampling, ess_threshold, kernel='optimal', pmmh_stat, windows,
+               sequence lists, W > 1 and every other sampler are refused by name)
       kind: 'pf' (the particle-filter score) | 'marginal' (LGSSM, dtype 'f64': the exact Kalman score of
                every window, PFG_SMOOTHER_KALMAN -- the reference's kind='marginal', the KF baseline of its
                LGSSM experiment; N, pf and resampling are ignored) | 'complete' (LGSSM, dtype 'f64': the
@@ -241,7 +249,9 @@ class ChainEnsemble(object):
                sampler='pmmh' | 'pmala': launch_propose before launch_pf, launch_accept as the update; _mh_init is the init
                pass of both.  With correlation set launch_pf is launch_cpm on the pfg_cpm_problem records (cpm_desc_dev, static:
                _cpm_alloc), launch_accept ends in the commit that flips the selector of a chain that accepted, and _mh_init
-               runs the rho = 0 launch.  sampler='pgibbs': launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev,
+               runs the rho = 0 launch.  With sqmc set launch_pf is launch_sqmc on the pfg_sqmc_problem records (sqmc_desc_dev,
+               static: _sqmc_alloc), keyed seed ^ 0x53514D43; propose, accept and _mh_init are PMMH's.
+               sampler='pgibbs': launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev,
                static), launch_update the conjugate draw; _pgibbs_init allocates path_dev, the counters and the scratch
                and runs the init pass.
                sampler='sgld_cv': _desc / desc_dev hold _nl = 2 * _nd records, the chains' and behind them their twins'
@@ -257,15 +267,16 @@ class ChainEnsemble(object):
                  forward_message=None, partition_style=None, resampling="multinomial",
                  sampler="sgld", friction=0.1, window_sampling="host", kind="pf", num_samples=None,
                  Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                 ess_threshold=None, proposal_scale=None, pmmh_stat=None, correlation=None, centre=None, centre_repeats=1,
-                 centre_N=None):
+                 ess_threshold=None, proposal_scale=None, pmmh_stat=None, correlation=None, sqmc=False, centre=None,
+                 centre_repeats=1, centre_N=None):
         s = self._resolve_settings(
             model, observations, parameters, num_chains=num_chains, N=N, pf=pf, lambduh=lambduh,
             subsequence_length=subsequence_length, buffer_length=buffer_length, dtype=dtype, partition_style=partition_style,
             resampling=resampling, sampler=sampler, window_sampling=window_sampling, kind=kind, num_samples=num_samples,
             Ntilde=Ntilde, max_accept_reject=max_accept_reject, accept_reject=accept_reject, minibatch_size=minibatch_size,
             num_sequences=num_sequences, ess_threshold=ess_threshold, proposal_scale=proposal_scale, pmmh_stat=pmmh_stat,
-            kernel=kernel, correlation=correlation, centre=centre, centre_repeats=centre_repeats, centre_N=centre_N)
+            kernel=kernel, correlation=correlation, centre=centre, centre_repeats=centre_repeats, centre_N=centre_N,
+            sqmc=sqmc)
         if not torch.cuda.is_available():
             raise RuntimeError("ChainEnsemble needs an MI355X (no CPU fallback)")
         Parameters, Prior, Helper = _model_info(model)
@@ -276,6 +287,7 @@ class ChainEnsemble(object):
         self.resampling, self.sampler, self.friction = resampling, sampler, float(friction)
         self.ess_threshold = s.ess_threshold        # None: resample at every step
         self.correlation = s.correlation            # None: plain PMMH, a fresh estimate per proposal
+        self.sqmc = getattr(s, "sqmc", False)       # True: PMMH on the sequential quasi-Monte Carlo filter's estimate
         self.window_sampling, self.partition_style, self.strict = window_sampling, partition_style, s.strict
         self._multi, self.W, self.segments, self.T, self.S, self.B = s.multi, s.W, s.segments, s.T, s.S, s.B
         self.P, self.C = s.theta0.shape[1], s.theta0.shape[0]
@@ -374,6 +386,8 @@ class ChainEnsemble(object):
             self.launch_windows()           # static windows: written once, no draw
         if self.correlation is not None:
             self._cpm_alloc(pm, pv)
+        if self.sqmc:
+            self._sqmc_alloc(pm, pv)
         if self._mh:
             self._mh_init()
         if sampler == "pgibbs":
@@ -522,8 +536,8 @@ class ChainEnsemble(object):
                           subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
                           resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
                           Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None, correlation=None, centre=None,
-                          centre_repeats=1, centre_N=None):
+                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None, correlation=None, sqmc=False,
+                          centre=None, centre_repeats=1, centre_N=None):
         """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
         device is made here and nowhere else, so it runs (and is tested) without a GPU.
 
@@ -533,7 +547,8 @@ class ChainEnsemble(object):
         into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto;
         ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
         'pmmh' | 'pmala'); correlation (rho as a float, None unless the correlated pseudo-marginal filter is on); sampler =
-        'sgld_cv' alone: centre_repeats, centre_N (the particles of the centring launches: N unless given)."""
+        'sgld_cv' alone: centre_repeats, centre_N (the particles of the centring launches: N unless given); sqmc set alone:
+        sqmc = True (a namespace without it is today's)."""
         tau = None
         if sampler == "sgld_cv":
             ChainEnsemble._refuse_cv(observations, N, pf, kind, centre_repeats, centre_N)
@@ -545,6 +560,10 @@ class ChainEnsemble(object):
                                              buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
                                              kernel)
             correlation = float(correlation)
+        if sqmc:
+            ChainEnsemble._refuse_sqmc(sampler, pmmh_stat, correlation, model, observations, N, pf, subsequence_length,
+                                       buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
+                                       kernel)
         if sampler == "pgibbs":
             ChainEnsemble._refuse_chain_filter("pgibbs", model, observations, N, pf, subsequence_length, buffer_length, dtype,
                                                resampling, kind, minibatch_size, num_sequences, ess_threshold, kernel)
@@ -741,6 +760,8 @@ class ChainEnsemble(object):
         if sampler == "sgld_cv":        # (the other samplers' namespaces keep their fields)
             s.centre_repeats = 1 if kind == "marginal" else int(centre_repeats)
             s.centre_N = N if centre_N is None else int(centre_N)
+        if sqmc:
+            s.sqmc = True
         return s
 
     @staticmethod
@@ -786,6 +807,12 @@ class ChainEnsemble(object):
             whole="filters the whole series", window="runs one filter per chain and step", own="filter",
             resampling="resamples systematically in the order of the states, on a uniform it carries: resampling stays at its "
                        "default", inside="the sorted filter", particles="", max_n=_capi.CPM_MAX_N),
+        "sqmc": dict(
+            what="sqmc (PMMH on sequential quasi-Monte Carlo: the sorted filter on one randomised Sobol' point set per step) ",
+            garch="the sort orders a scalar state, GARCH's has two components", lists="filters one series",
+            whole="filters the whole series", window="runs one filter per chain and step", own="filter",
+            resampling="resamples in the order of the states on the first coordinate of its point set: resampling stays at its "
+                       "default", inside="the sorted filter", particles="", max_n=_capi.SQMC_MAX_N),
     }
 
     @staticmethod
@@ -847,6 +874,25 @@ class ChainEnsemble(object):
         if not 0.0 <= rho < 1.0:        # (false for a NaN as well)
             raise ValueError("correlation must lie in [0, 1) (rho of U' = rho U + sqrt(1 - rho^2) eps; 0: fresh normals at every "
                              "step), got {0}".format(correlation))
+
+    @staticmethod
+    def _refuse_sqmc(sampler, pmmh_stat, correlation, *shared):
+        """`sqmc`: not beside `correlation`, the sampler it belongs to, then the shared refusals (with pmmh_stat's ahead of N),
+        then the power of two."""
+        what = ChainEnsemble._CHAIN_FILTERS["sqmc"]["what"]
+        if correlation is not None:
+            raise NotImplementedError(what + "draws a fresh point set at every step and carries no normals: correlation stays "
+                                      "None, got correlation = {0}".format(correlation))
+        if sampler != "pmmh":
+            raise NotImplementedError(what + "belongs to sampler='pmmh', got sampler = '{0}'{1}".format(
+                sampler, " (pMALA would need the score on the point set: not built)" if sampler == "pmala" else ""))
+        ChainEnsemble._refuse_chain_filter("sqmc", *shared, also=[(
+            pmmh_stat not in (None, "none"), "computes the log-likelihood estimate alone: pmmh_stat stays at its default, got "
+                                             "pmmh_stat = '{0}'".format(pmmh_stat))])
+        N = int(shared[2])
+        if N & (N - 1):
+            raise NotImplementedError(what + "takes the first 2^m points of the Sobol' sequence, a (0, m, 2)-net: N must be a "
+                                      "power of two, got N = {0}".format(N))
 
     @staticmethod
     def _window_counts(observations, minibatch_size, num_sequences):
@@ -1021,6 +1067,8 @@ class ChainEnsemble(object):
             return self.launch_csmc(stream, traced=traced)
         if self.correlation is not None:    # the sorted, correlated filter: its own descriptors as well
             return self.launch_cpm(stream, traced=traced)
+        if self.sqmc:       # the sequential quasi-Monte Carlo filter: its own descriptors too
+            return self.launch_sqmc(stream, traced=traced)
         if self.ess_threshold:      # adaptive resampling: its own kernels, the family stated at launch level
             return self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.N, self._nl,
                                                    self.desc_dev.data_ptr(), self._stream(stream), traced=traced)
@@ -1114,6 +1162,19 @@ class ChainEnsemble(object):
                             0.0 if init else self.correlation, self.seed ^ 0x43504D4D, self.chain_offset,
                             self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
 
+    def launch_sqmc(self, stream=None, traced=False):
+        """sampler='pmmh' with sqmc: one sequential quasi-Monte Carlo filter per chain on theta_prop_dev (pfg_sqmc_device), the
+        estimate to out_dev[:, 4].  The init pass is the same launch at counter 0."""
+        self.ctx.sqmc_device(self.model, self.dtype, self.N, self.C, self.sqmc_desc_dev.data_ptr(), self.seed ^ 0x53514D43,
+                             self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
+
+    def _sqmc_alloc(self, prior_mean, prior_var):
+        """The pfg_sqmc_problem records (static: the step replays in hipGraphs).  An SQMC chain carries nothing beyond PMMH's
+        state."""
+        d, _ = self._chain_filter_records(_capi.SQMC_PROBLEM_DTYPE, self.theta_prop_dev, prior_mean, prior_var)
+        self._sqmc_desc = d
+        self.sqmc_desc_dev = self._upload_records(d)
+
     def _alloc_per_chain(self, make, kept, per_chain, sb, copies=1):
         """`copies` * C slabs of sb bytes in one uint8 tensor (make: torch.zeros | torch.empty); a refusal names what is kept,
         the size formula and the byte count."""
@@ -1126,8 +1187,8 @@ class ChainEnsemble(object):
                 kept, times, per_chain, self.C, sb, n, n / 1e9, str(e).splitlines()[0])) from e
 
     def _chain_filter_records(self, dtype, theta, prior_mean, prior_var):
-        """(d, idx): C records of a chain-filter descriptor (pfg_csmc_problem | pfg_cpm_problem) with what both have filled in
-        -- chain b reads row b of `theta` and the whole series, writes row b of out_dev -- and the chain indices as uint64."""
+        """(d, idx): C records of a chain-filter descriptor (pfg_csmc_problem | pfg_cpm_problem | pfg_sqmc_problem) with what all
+        have filled in -- chain b reads row b of `theta` and the whole series, writes row b of out_dev -- and the chain indices as uint64."""
         idx = np.arange(self.C, dtype=np.uint64)
         d = np.zeros(self.C, dtype=dtype)
         d["theta"] = theta.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
@@ -1327,6 +1388,8 @@ class ChainEnsemble(object):
         state.update((key, t.cpu().numpy()) for key, t in self._chain_state()[0])
         if self.correlation is not None:    # the current buffer only (the other one is a step's scratch), and what it belongs to
             state.update(aux=self.aux(), correlation=self.correlation, T=self.T)
+        if self.sqmc:       # (no state of its own: the setting alone, so that a plain PMMH checkpoint is what it was)
+            state.update(sqmc=True)
         return state
 
     def _chain_state(self):
@@ -1369,6 +1432,9 @@ class ChainEnsemble(object):
         if state.get("correlation", None) != self.correlation:          # (either side may be a plain PMMH chain: None)
             raise ValueError("checkpoint correlation = {0} does not match the ensemble ({1})".format(
                 state.get("correlation", None), self.correlation))
+        if bool(state.get("sqmc", False)) != self.sqmc:
+            raise ValueError("checkpoint sqmc = {0} does not match the ensemble ({1})".format(
+                bool(state.get("sqmc", False)), self.sqmc))
         if self.correlation is not None:
             shape = (self.C, self.T + 1, self.N + 1)
             if state.get("T", None) != self.T or tuple(np.shape(state["aux"])) != shape:

@@ -24,7 +24,7 @@ With h_i = (ll_i + logprior(theta_i)) - log q0(theta_i), ll_i the estimate chain
 
 Steps 1-5 and the accept are HIP kernels (csrc/pfg_smc.hip, csrc/pfg_chains.hip); the expensive part, the filter or Kalman
 launch, is the ensemble's, unchanged -- so every PMMH configuration the ensemble accepts runs here (GARCH, kind='marginal',
-stratified / systematic / adaptive resampling, N up to 16384, sequence lists), except `correlation`.  At phi = 1 the tempered
+stratified / systematic / adaptive resampling, N up to 16384, sequence lists), except `correlation` and `sqmc`.  At phi = 1 the tempered
 accept is PMMH's bit for bit and `ensemble` is a plain PMMH ChainEnsemble whose chains are posterior-distributed and whose
 proposal scale is the population's.
 
@@ -104,7 +104,8 @@ class TemperedPopulation(object):
       scale_factor: c of s_j = c sd_j (default 2.38 / sqrt(d))
       **ensemble_kwargs: forwarded to ChainEnsemble(sampler='pmmh', ...) untouched -- every refusal of a PMMH configuration is
                the ensemble's own.  proposal_scale, if given, is the scale of a slot until the population gives it one.
-    Refused here, by name: correlation (the normals would have to be gathered too: not built), a sampler other than 'pmmh',
+    Refused here, by name: correlation (the normals would have to be gathered too: not built), sqmc (its move is not routed
+    through the sequential quasi-Monte Carlo filter: not built), a sampler other than 'pmmh',
     C outside 2 .. 2^20, tau outside (0, 1), moves < 1, an init_sd <= 0, and a process that is one rank of several (the
     population interacts; a rank partition of it is not built).
 
@@ -156,6 +157,10 @@ class TemperedPopulation(object):
         if ensemble_kwargs.get("correlation", None) is not None:
             raise NotImplementedError(what + "resamples theta and the estimate across chains; with correlation the chains' "
                                       "normals would have to be gathered too, and that is not built: correlation stays None")
+        if ensemble_kwargs.get("sqmc", False):
+            raise NotImplementedError(what + "moves the population through its own accept step (pfg_smc_accept_device around the "
+                                      "ensemble's launch); routing that move through the sequential quasi-Monte Carlo filter is "
+                                      "not built: sqmc stays False")
         if ensemble_kwargs.get("sampler", "pmmh") != "pmmh":
             raise NotImplementedError(what + "moves the population by PMMH steps: sampler stays 'pmmh', got sampler = '{0}'".format(
                 ensemble_kwargs["sampler"]))
