@@ -2,6 +2,7 @@
 
 This is the only door from Python to the particle-filter kernels.  There is no CPU
 fallback: if the library is missing or no MI355X is visible the calls raise."""
+import collections
 import ctypes as C
 import gc
 import os
@@ -32,6 +33,7 @@ MAX_STAT, MAX_THETA, OUT_DOUBLES, MAX_PRED, STAMP_WORDS = 4, 4, 8, 16, 16
 MAX_DRAWN_SEQUENCES = 1024       # PFG_MAX_DRAWN_SEQUENCES: sequences a chain draws per step (num_sequences != -1)
 STATE_DIM = {"svm": 1, "garch": 2, "lgssm": 1}
 STAT_DIM = {"svm": 3, "garch": 4, "lgssm": 4}
+THETA_DIM = {"svm": 3, "garch": 4, "lgssm": 4}
 
 
 def ess_threshold_bits(tau):
@@ -46,72 +48,54 @@ def ess_threshold_from_bits(bits):
 def kalman_scratch_bytes(L):
     """pfg_dev_problem.scratch a PFG_SMOOTHER_KALMAN window of L = tL - t1 steps needs (include/pfgrad.h)."""
     return (16 * (int(L) + 1) + 255) // 256 * 256
-THETA_DIM = {"svm": 3, "garch": 4, "lgssm": 4}
+
 
 PFG_OK, PFG_ERR_INVALID, PFG_ERR_UNSUPPORTED, PFG_ERR_DEVICE, PFG_ERR_NOMEM, PFG_ERR_NUMERIC = 0, -1, -2, -3, -4, -5
 
 _dp = C.POINTER(C.c_double)
+_SCALAR = {"i4": C.c_int32, "u4": C.c_uint32, "i8": C.c_int64, "u8": C.c_uint64, "f8": C.c_double}
 
 
-class Problem(C.Structure):
-    _fields_ = [
-        ("model", C.c_int32), ("kernel", C.c_int32), ("smoother", C.c_int32), ("stat", C.c_int32),
-        ("dtype", C.c_int32), ("rng", C.c_int32),
-        ("N", C.c_int32), ("T", C.c_int32), ("t1", C.c_int32), ("tL", C.c_int32),
-        ("flags", C.c_uint32), ("reserved", C.c_int32),
-        ("lambduh", C.c_double), ("prior_mean", C.c_double), ("prior_var", C.c_double),
-        ("y", _dp), ("weights", _dp), ("theta", _dp),
-        ("z0", _dp), ("u", _dp), ("z", _dp),
-        ("seed", C.c_uint64), ("stream", C.c_uint64),
-        ("init_x", _dp), ("init_logw", _dp), ("init_stats", _dp),
-        ("Ntilde", C.c_int32), ("max_accept_reject", C.c_int32),
-        ("paris_idx_u", _dp), ("paris_acc_u", _dp), ("paris_man_u", _dp),
-        ("num_steps_ahead", C.c_int32), ("elementwise", C.c_int32),
-        ("pred_z", _dp),
-        ("paris_stream", _dp), ("paris_stream_len", C.c_int64),
-        ("paris_manual_threshold", C.c_int32), ("reserved2", C.c_int32),
-        ("step", C.c_uint64),
-    ]
+def _mirrors(name, fields):
+    """The two forms of one host struct of include/pfgrad.h, from its fields stated as the header declares them --
+    (scalar kind, names[, array length]), '*kind' a pointer to that scalar: the ctypes structure, and the aligned numpy
+    dtype (a pointer is a 'u8' address there) of the vectorised marshalling of large batches (Context._run_batch_plain)."""
+    c_fields, np_fields = [], []
+    for kind, names, *length in fields:
+        for n in names.split():
+            if kind[0] == "*":
+                c_fields.append((n, C.POINTER(_SCALAR[kind[1:]])))
+                np_fields.append((n, "u8"))
+            elif length:
+                c_fields.append((n, _SCALAR[kind] * length[0]))
+                np_fields.append((n, kind, (length[0],)))
+            else:
+                c_fields.append((n, _SCALAR[kind]))
+                np_fields.append((n, kind))
+    return type(name, (C.Structure,), {"_fields_": c_fields}), np.dtype(np_fields, align=True)
 
 
-class Result(C.Structure):
-    _fields_ = [
-        ("mean_stat", C.c_double * MAX_STAT), ("loglik", C.c_double),
-        ("x_T", _dp), ("logw_T", _dp), ("stats_T", _dp),
-        ("trace_x", _dp), ("trace_logw", _dp), ("trace_stats", _dp), ("trace_ll", _dp),
-        ("status", C.c_int32), ("paris_carry_back", C.c_int32),
-        ("trace_anc", C.POINTER(C.c_int32)),
-        ("pred", C.c_double * MAX_PRED),
-        ("rec_u", C.POINTER(C.c_uint32)), ("rec_z", _dp), ("rec_z0", _dp),
-        ("rec_ud", _dp),
-        ("ew_mean", _dp), ("ew_stats", _dp),
-        ("paris_consumed", C.c_int64),
-        ("trace_paris_J", C.POINTER(C.c_int32)),
-    ]
-
-
-# numpy mirrors of pfg_problem / pfg_result for the vectorised marshalling of large device-generator batches
-# (Context._run_batch_plain); layouts are asserted against the ctypes structures at import
-PROBLEM_DTYPE = np.dtype([
-    ("model", "i4"), ("kernel", "i4"), ("smoother", "i4"), ("stat", "i4"), ("dtype", "i4"), ("rng", "i4"),
-    ("N", "i4"), ("T", "i4"), ("t1", "i4"), ("tL", "i4"), ("flags", "u4"), ("reserved", "i4"),
-    ("lambduh", "f8"), ("prior_mean", "f8"), ("prior_var", "f8"),
-    ("y", "u8"), ("weights", "u8"), ("theta", "u8"), ("z0", "u8"), ("u", "u8"), ("z", "u8"),
-    ("seed", "u8"), ("stream", "u8"),
-    ("init_x", "u8"), ("init_logw", "u8"), ("init_stats", "u8"),
-    ("Ntilde", "i4"), ("max_accept_reject", "i4"),
-    ("paris_idx_u", "u8"), ("paris_acc_u", "u8"), ("paris_man_u", "u8"),
-    ("num_steps_ahead", "i4"), ("elementwise", "i4"), ("pred_z", "u8"),
-    ("paris_stream", "u8"), ("paris_stream_len", "i8"), ("paris_manual_threshold", "i4"), ("reserved2", "i4"),
-    ("step", "u8")], align=True)
-RESULT_DTYPE = np.dtype([
-    ("mean_stat", "f8", (MAX_STAT,)), ("loglik", "f8"),
-    ("x_T", "u8"), ("logw_T", "u8"), ("stats_T", "u8"),
-    ("trace_x", "u8"), ("trace_logw", "u8"), ("trace_stats", "u8"), ("trace_ll", "u8"),
-    ("status", "i4"), ("paris_carry_back", "i4"), ("trace_anc", "u8"),
-    ("pred", "f8", (MAX_PRED,)),
-    ("rec_u", "u8"), ("rec_z", "u8"), ("rec_z0", "u8"), ("rec_ud", "u8"), ("ew_mean", "u8"), ("ew_stats", "u8"),
-    ("paris_consumed", "i8"), ("trace_paris_J", "u8")], align=True)
+Problem, PROBLEM_DTYPE = _mirrors("Problem", (             # pfg_problem
+    ("i4", "model kernel smoother stat dtype rng N T t1 tL"), ("u4", "flags"), ("i4", "reserved"),
+    ("f8", "lambduh prior_mean prior_var"),
+    ("*f8", "y weights theta z0 u z"),
+    ("u8", "seed stream"),
+    ("*f8", "init_x init_logw init_stats"),
+    ("i4", "Ntilde max_accept_reject"),
+    ("*f8", "paris_idx_u paris_acc_u paris_man_u"),
+    ("i4", "num_steps_ahead elementwise"),
+    ("*f8", "pred_z paris_stream"), ("i8", "paris_stream_len"),
+    ("i4", "paris_manual_threshold reserved2"),
+    ("u8", "step")))
+Result, RESULT_DTYPE = _mirrors("Result", (                # pfg_result
+    ("f8", "mean_stat", MAX_STAT), ("f8", "loglik"),
+    ("*f8", "x_T logw_T stats_T trace_x trace_logw trace_stats trace_ll"),
+    ("i4", "status paris_carry_back"),
+    ("*i4", "trace_anc"),
+    ("f8", "pred", MAX_PRED),
+    ("*u4", "rec_u"), ("*f8", "rec_z rec_z0 rec_ud ew_mean ew_stats"),
+    ("i8", "paris_consumed"),
+    ("*i4", "trace_paris_J")))
 assert PROBLEM_DTYPE.itemsize == C.sizeof(Problem) and RESULT_DTYPE.itemsize == C.sizeof(Result)
 assert all(PROBLEM_DTYPE.fields[n][1] == getattr(Problem, n).offset for n, _ in Problem._fields_)
 assert all(RESULT_DTYPE.fields[n][1] == getattr(Result, n).offset for n, _ in Result._fields_)
@@ -222,21 +206,113 @@ def device_descriptors(n, *, theta, row, out, step_ctr, scratch, scratch_bytes, 
     return d
 
 
-EXPORTS = ("pfg_version", "pfg_struct_size", "pfg_create", "pfg_destroy", "pfg_last_error", "pfg_run", "pfg_run_batch",
-           "pfg_ctx_stream", "pfg_launch_device", "pfg_launch_device_smoother", "pfg_scratch_bytes", "pfg_variant_name", "pfg_synchronize",
-           "pfg_sgld_update_device", "pfg_sghmc_update_device", "pfg_imq_ksd", "pfg_sample_windows_device",
-           "pfg_last_variant", "pfg_legacy_streams", "pfg_host_register", "pfg_host_unregister",
-           "pfg_launch_device_traced", "pfg_last_traced", "pfg_launch_device_grid", "pfg_launch_device_grid_phase",
-           "pfg_launch_device_grid_smoother", "pfg_sgrld_update_device", "pfg_gibbs_update_device",
-           "pfg_sample_windows_multi_device", "pfg_reduce_windows_device", "pfg_scratch_bytes_smoother",
-           "pfg_launch_device_adaptive", "pfg_logprior_device", "pfg_pmmh_propose_device", "pfg_pmmh_accept_device",
-           "pfg_pmala_propose_device", "pfg_pmala_accept_device", "pfg_csmc_scratch_bytes", "pfg_csmc_device",
-           "pfg_pgibbs_update_device", "pfg_cpm_aux_bytes", "pfg_cpm_device", "pfg_cpm_commit_device", "pfg_sqmc_device",
-           "pfg_smc_scratch_bytes", "pfg_smc_logtarget_device", "pfg_smc_temper_device", "pfg_smc_gather_device",
-           "pfg_smc_scale_device", "pfg_smc_accept_device", "pfg_sgd_update_device", "pfg_adagrad_update_device",
-           "pfg_sgld_cv_update_device", "pfg_cv_accumulate_device")
+# ---- entry points (include/pfgrad.h) -----------------------------------------------------
+# A kind is how one sort of C argument or return value crosses the boundary: its ctypes type, which checks and converts
+# the Python value (an int is anything with __index__ and wraps to the type's width, a double anything with __float__,
+# None or 0 is a NULL pointer, a structure meets a pointer to it by reference), and for what ctypes cannot take as it is,
+# the conversion Context._call applies first.  Those are few and C-level: a step of a small ensemble is bound by these calls.
+_Kind = collections.namedtuple("_Kind", "ctype convert")
+
+
+class _Ids(dict):
+    """The ids of one enum by name; an id stands for itself (a bad one is the library's to refuse)."""
+
+    def __missing__(self, key):
+        if isinstance(key, int):
+            return key
+        raise KeyError(key)
+
+
+_ctx = _Kind(C.c_void_p, None)                      # the handle: Context._call passes its own
+_ctx_out = _Kind(C.POINTER(C.c_void_p), None)
+_model, _kernel, _dtype, _rng, _smoother = (_Kind(C.c_int, _Ids(ids).__getitem__)
+                                            for ids in (MODEL, KERNEL, DTYPE, RNG, SMOOTHER))
+_int = _Kind(C.c_int, None)
+_flag = _Kind(C.c_int, bool)                        # any truth value
+_f64 = _Kind(C.c_double, None)
+_u64 = _Kind(C.c_uint64, None)                      # seeds, chain ids and counters: masked to 64 bits
+_u32 = _Kind(C.c_uint32, None)
+_size = _Kind(C.c_size_t, None)
+_i64 = _Kind(C.c_int64, None)
+_addr = _Kind(C.c_void_p, None)                     # a device or host address as an int; None or 0 is NULL
+_stream = _Kind(C.c_void_p, None)                   # a hipStream_t as an int; 0 is HIP's default stream
+_hyper = _Kind(C.POINTER(PriorHyper), None)         # a PriorHyper; None is NULL
+_problem_p, _result_p = _Kind(C.POINTER(Problem), None), _Kind(C.POINTER(Result), None)
+_f64_p, _i32_p = _Kind(_dp, None), _Kind(C.POINTER(C.c_int32), None)
+_status = _Kind(C.c_int, None)                      # 0 or a negative PFG_ERR_*: Context._call hands it to _check
+_cstr = _Kind(C.c_char_p, None)
+_void = _Kind(None, None)
+
+# every exported function, in the header's order: name -> (return kind, argument kinds)
+_ENTRY_POINTS = {
+    "pfg_version": (_int, ()),
+    "pfg_struct_size": (_int, (_int,)),
+    "pfg_create": (_status, (_ctx_out, _int)),
+    "pfg_destroy": (_void, (_ctx,)),
+    "pfg_last_error": (_cstr, (_ctx,)),
+    "pfg_run": (_status, (_ctx, _problem_p, _result_p)),
+    "pfg_run_batch": (_status, (_ctx, _int, _problem_p, _result_p)),
+    "pfg_ctx_stream": (_addr, (_ctx,)),
+    "pfg_launch_device": (_status, (_ctx, _model, _kernel, _dtype, _rng, _int, _int, _addr, _stream)),
+    "pfg_launch_device_traced": (_status, (_ctx, _model, _kernel, _dtype, _rng, _smoother, _int, _int, _addr, _stream)),
+    "pfg_last_traced": (_int, (_ctx,)),
+    "pfg_launch_device_smoother": (_status, (_ctx, _model, _kernel, _dtype, _rng, _smoother, _int, _int, _addr, _stream)),
+    "pfg_launch_device_adaptive": (_status, (_ctx, _model, _kernel, _dtype, _rng, _int, _int, _addr, _stream, _flag)),
+    "pfg_launch_device_grid": (_status, (_ctx, _model, _kernel, _dtype, _rng, _int, _int, _int, _addr, _stream)),
+    "pfg_launch_device_grid_phase": (_status, (_ctx, _model, _kernel, _dtype, _rng, _int, _int, _int, _addr, _stream)),
+    "pfg_launch_device_grid_smoother": (_status, (_ctx, _model, _kernel, _dtype, _rng, _smoother, _int, _int, _int, _int,
+                                                  _addr, _stream)),
+    "pfg_sample_windows_device": (_status, (_ctx, _int, _addr, _addr, _addr, _int, _int, _int, _flag, _u64, _u64, _addr,
+                                            _stream)),
+    "pfg_sample_windows_multi_device": (_status, (_ctx, _int, _int, _addr, _addr, _int, _int, _addr, _addr, _addr, _addr,
+                                                  _int, _int, _flag, _u64, _u64, _addr, _stream)),
+    "pfg_reduce_windows_device": (_status, (_ctx, _int, _int, _int, _addr, _addr, _flag, _f64, _addr, _stream)),
+    "pfg_scratch_bytes": (_i64, (_model, _dtype, _rng, _int)),
+    "pfg_scratch_bytes_smoother": (_i64, (_model, _dtype, _rng, _smoother, _int)),
+    "pfg_variant_name": (_cstr, (_model, _kernel, _dtype, _rng, _int)),
+    "pfg_last_variant": (_cstr, (_ctx,)),
+    "pfg_synchronize": (_status, (_ctx,)),
+    "pfg_sgld_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _hyper, _f64, _f64, _u64, _u64, _addr, _stream)),
+    "pfg_sghmc_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _hyper, _f64, _f64, _f64, _u64, _u64,
+                                          _addr, _stream)),
+    "pfg_sgrld_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _hyper, _f64, _f64, _u64, _u64, _addr, _stream)),
+    "pfg_sgd_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _hyper, _f64, _f64, _addr, _stream)),
+    "pfg_adagrad_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _hyper, _f64, _f64, _addr, _stream)),
+    "pfg_sgld_cv_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _addr, _hyper, _f64, _f64, _u64, _u64,
+                                            _addr, _stream)),
+    "pfg_cv_accumulate_device": (_status, (_ctx, _int, _addr, _addr, _int, _int, _addr, _stream)),
+    "pfg_gibbs_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _hyper, _u64, _u64, _addr, _stream)),
+    "pfg_logprior_device": (_status, (_ctx, _model, _int, _addr, _hyper, _addr, _stream)),
+    "pfg_pmmh_propose_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _addr, _u64, _u64, _addr, _stream)),
+    "pfg_pmmh_accept_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _addr, _addr, _addr, _hyper, _flag,
+                                         _u64, _u64, _addr, _stream)),
+    "pfg_pmala_propose_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _addr, _addr, _hyper, _u64, _u64,
+                                           _addr, _stream)),
+    "pfg_pmala_accept_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _addr, _addr, _addr, _addr, _hyper,
+                                          _addr, _flag, _u64, _u64, _addr, _stream)),
+    "pfg_csmc_scratch_bytes": (_i64, (_int, _int)),
+    "pfg_csmc_device": (_status, (_ctx, _model, _dtype, _int, _int, _addr, _u64, _u64, _addr, _stream, _flag)),
+    "pfg_pgibbs_update_device": (_status, (_ctx, _model, _int, _addr, _addr, _hyper, _u64, _u64, _addr, _stream)),
+    "pfg_cpm_aux_bytes": (_i64, (_int, _int)),
+    "pfg_cpm_device": (_status, (_ctx, _model, _dtype, _int, _int, _addr, _f64, _u64, _u64, _addr, _stream, _flag)),
+    "pfg_cpm_commit_device": (_status, (_ctx, _int, _addr, _addr, _addr, _flag, _stream)),
+    "pfg_sqmc_device": (_status, (_ctx, _model, _dtype, _int, _int, _addr, _u64, _u64, _addr, _stream, _flag)),
+    "pfg_smc_scratch_bytes": (_i64, (_int,)),
+    "pfg_smc_logtarget_device": (_status, (_ctx, _model, _int, _addr, _addr, _hyper, _addr, _addr, _addr, _stream)),
+    "pfg_smc_temper_device": (_status, (_ctx, _int, _addr, _addr, _f64, _u64, _u64, _addr, _addr, _addr, _addr, _stream)),
+    "pfg_smc_gather_device": (_status, (_ctx, _int, _addr, _addr, _addr, _addr, _addr, _stream)),
+    "pfg_smc_scale_device": (_status, (_ctx, _int, _addr, _u32, _f64, _addr, _stream)),
+    "pfg_smc_accept_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _addr, _addr, _addr, _hyper, _addr, _addr,
+                                        _addr, _addr, _u64, _u64, _addr, _stream)),
+    "pfg_imq_ksd": (_status, (_ctx, _int, _int, _f64_p, _f64_p, _f64, _f64, _f64_p)),
+    "pfg_legacy_streams": (_status, (_addr, _i32_p, _i32_p, _f64_p, _int, _int, _addr, _addr, _addr, _int)),
+    "pfg_host_register": (_status, (_addr, _size)),
+    "pfg_host_unregister": (_status, (_addr,)),
+}
+EXPORTS = tuple(_ENTRY_POINTS)
 
 _lib = None
+_calls = {}     # name -> (function, ((position after the handle, conversion), ...), takes the handle, returns a status)
 
 
 class PfgError(RuntimeError):
@@ -271,149 +347,18 @@ def load_library():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    lib.pfg_version.restype = C.c_int
-    lib.pfg_struct_size.argtypes = [C.c_int]
-    lib.pfg_struct_size.restype = C.c_int
+    for name, (ret, kinds) in _ENTRY_POINTS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = ret.ctype, [k.ctype for k in kinds]
+        takes_handle = bool(kinds) and kinds[0] is _ctx         # (`is`: an address is the same pair of type and conversion)
+        converts = tuple((i, k.convert) for i, k in enumerate(kinds[takes_handle:]) if k.convert)
+        _calls[name] = (fn, converts, takes_handle, ret is _status)
     sizes = (C.sizeof(Problem), C.sizeof(Result), DEV_PROBLEM_DTYPE.itemsize, C.sizeof(PriorHyper), CSMC_PROBLEM_DTYPE.itemsize,
              CPM_PROBLEM_DTYPE.itemsize, SQMC_PROBLEM_DTYPE.itemsize)
     for which, mine in enumerate(sizes):
         if lib.pfg_struct_size(which) != mine:
             raise RuntimeError("ABI mismatch: struct {0} is {1} bytes in libpfgrad.so, {2} in the binding"
                                .format(which, lib.pfg_struct_size(which), mine))
-    lib.pfg_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-    lib.pfg_create.restype = C.c_int
-    lib.pfg_destroy.argtypes = [C.c_void_p]
-    lib.pfg_destroy.restype = None
-    lib.pfg_last_error.argtypes = [C.c_void_p]
-    lib.pfg_last_error.restype = C.c_char_p
-    lib.pfg_run.argtypes = [C.c_void_p, C.POINTER(Problem), C.POINTER(Result)]
-    lib.pfg_run.restype = C.c_int
-    lib.pfg_run_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Result)]
-    lib.pfg_run_batch.restype = C.c_int
-    lib.pfg_launch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p, C.c_void_p]
-    lib.pfg_launch_device.restype = C.c_int
-    lib.pfg_ctx_stream.argtypes = [C.c_void_p]
-    lib.pfg_ctx_stream.restype = C.c_void_p
-    lib.pfg_launch_device_smoother.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]
-    lib.pfg_launch_device_smoother.restype = C.c_int
-    lib.pfg_launch_device_traced.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]
-    lib.pfg_launch_device_traced.restype = C.c_int
-    lib.pfg_launch_device_grid.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]
-    lib.pfg_launch_device_grid.restype = C.c_int
-    lib.pfg_launch_device_grid_phase.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]
-    lib.pfg_launch_device_grid_phase.restype = C.c_int
-    lib.pfg_launch_device_grid_smoother.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_void_p]
-    lib.pfg_launch_device_grid_smoother.restype = C.c_int
-    lib.pfg_last_traced.argtypes = [C.c_void_p]
-    lib.pfg_last_traced.restype = C.c_int
-    lib.pfg_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.pfg_scratch_bytes.restype = C.c_int64
-    lib.pfg_variant_name.argtypes = [C.c_int] * 5
-    lib.pfg_variant_name.restype = C.c_char_p
-    lib.pfg_legacy_streams.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
-                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.pfg_legacy_streams.restype = C.c_int
-    lib.pfg_host_register.argtypes = [C.c_void_p, C.c_size_t]
-    lib.pfg_host_register.restype = C.c_int
-    lib.pfg_host_unregister.argtypes = [C.c_void_p]
-    lib.pfg_host_unregister.restype = C.c_int
-    lib.pfg_last_variant.argtypes = [C.c_void_p]
-    lib.pfg_last_variant.restype = C.c_char_p
-    lib.pfg_synchronize.argtypes = [C.c_void_p]
-    lib.pfg_synchronize.restype = C.c_int
-    lib.pfg_sgld_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                           C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_uint64,
-                                           C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_sgld_update_device.restype = C.c_int
-    lib.pfg_sghmc_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_double,
-                                            C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_sghmc_update_device.restype = C.c_int
-    lib.pfg_sgrld_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_uint64,
-                                            C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_sgrld_update_device.restype = C.c_int
-    lib.pfg_sgd_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PriorHyper),
-                                          C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-    lib.pfg_sgd_update_device.restype = C.c_int
-    lib.pfg_adagrad_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-    lib.pfg_adagrad_update_device.restype = C.c_int
-    lib.pfg_sgld_cv_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.POINTER(PriorHyper), C.c_double, C.c_double, C.c_uint64, C.c_uint64,
-                                              C.c_void_p, C.c_void_p]
-    lib.pfg_sgld_cv_update_device.restype = C.c_int
-    lib.pfg_cv_accumulate_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_void_p]
-    lib.pfg_cv_accumulate_device.restype = C.c_int
-    lib.pfg_gibbs_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.POINTER(PriorHyper), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_gibbs_update_device.restype = C.c_int
-    lib.pfg_pgibbs_update_device.argtypes = lib.pfg_gibbs_update_device.argtypes
-    lib.pfg_pgibbs_update_device.restype = C.c_int
-    lib.pfg_csmc_scratch_bytes.argtypes = [C.c_int, C.c_int]
-    lib.pfg_csmc_scratch_bytes.restype = C.c_int64
-    lib.pfg_csmc_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64,
-                                    C.c_void_p, C.c_void_p, C.c_int]
-    lib.pfg_csmc_device.restype = C.c_int
-    lib.pfg_cpm_aux_bytes.argtypes = [C.c_int, C.c_int]
-    lib.pfg_cpm_aux_bytes.restype = C.c_int64
-    lib.pfg_cpm_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_uint64,
-                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_int]
-    lib.pfg_cpm_device.restype = C.c_int
-    lib.pfg_cpm_commit_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.pfg_cpm_commit_device.restype = C.c_int
-    lib.pfg_sqmc_device.argtypes = lib.pfg_csmc_device.argtypes
-    lib.pfg_sqmc_device.restype = C.c_int
-    lib.pfg_smc_scratch_bytes.argtypes = [C.c_int]
-    lib.pfg_smc_scratch_bytes.restype = C.c_int64
-    lib.pfg_smc_logtarget_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PriorHyper),
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pfg_smc_logtarget_device.restype = C.c_int
-    lib.pfg_smc_temper_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_uint64,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.pfg_smc_temper_device.restype = C.c_int
-    lib.pfg_smc_gather_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
-    lib.pfg_smc_gather_device.restype = C.c_int
-    lib.pfg_smc_scale_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p]
-    lib.pfg_smc_scale_device.restype = C.c_int
-    lib.pfg_smc_accept_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(PriorHyper)] + \
-                                         [C.c_void_p] * 4 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_smc_accept_device.restype = C.c_int
-    lib.pfg_logprior_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(PriorHyper), C.c_void_p, C.c_void_p]
-    lib.pfg_logprior_device.restype = C.c_int
-    lib.pfg_pmmh_propose_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_pmmh_propose_device.restype = C.c_int
-    lib.pfg_pmmh_accept_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.POINTER(PriorHyper), C.c_int, C.c_uint64, C.c_uint64,
-                                           C.c_void_p, C.c_void_p]
-    lib.pfg_pmmh_accept_device.restype = C.c_int
-    lib.pfg_pmala_propose_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.POINTER(PriorHyper), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_pmala_propose_device.restype = C.c_int
-    lib.pfg_pmala_accept_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PriorHyper), C.c_void_p, C.c_int,
-                                            C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_pmala_accept_device.restype = C.c_int
-    lib.pfg_imq_ksd.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp]
-    lib.pfg_imq_ksd.restype = C.c_int
-    lib.pfg_sample_windows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                              C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p,
-                                              C.c_void_p]
-    lib.pfg_sample_windows_device.restype = C.c_int
-    lib.pfg_sample_windows_multi_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                                    C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.pfg_sample_windows_multi_device.restype = C.c_int
-    lib.pfg_reduce_windows_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                              C.c_double, C.c_void_p, C.c_void_p]
-    lib.pfg_reduce_windows_device.restype = C.c_int
-    lib.pfg_scratch_bytes_smoother.argtypes = [C.c_int] * 5
-    lib.pfg_scratch_bytes_smoother.restype = C.c_int64
-    lib.pfg_launch_device_adaptive.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int]
-    lib.pfg_launch_device_adaptive.restype = C.c_int
     _lib = lib
     return lib
 
@@ -497,6 +442,19 @@ class Context:
             if rc == PFG_ERR_INVALID:
                 raise ValueError(msg)
             raise PfgError(rc, msg)
+
+    def _call(self, name, *args):
+        """The entry point `name` on Python values, converted by the kinds of its row in _ENTRY_POINTS (the handle is
+        passed for a row that starts with one); a status goes through _check, any other result is returned."""
+        fn, converts, takes_handle, is_status = _calls[name]
+        if converts:
+            args = list(args)
+            for i, convert in converts:
+                args[i] = convert(args[i])
+        rc = fn(self.handle, *args) if takes_handle else fn(*args)
+        if is_status:
+            self._check(rc)
+        return rc
 
     # ---- host-buffer path ----------------------------------------------------------------
     def run_batch(self, problems, want_final=False, want_trace=False, want_draws=False, want_elementwise=False):
@@ -732,15 +690,13 @@ class Context:
     # ---- resident path ---------------------------------------------------------------------
     def stream(self):
         """The context's own hipStream_t (as an integer handle)."""
-        return self.lib.pfg_ctx_stream(self.handle) or 0
+        return self._call("pfg_ctx_stream") or 0
 
     GRID_PHASE_INIT, GRID_PHASE_FINISH = -2, -3
 
     def launch_device_grid_phase(self, model, kernel, dtype, rng, n_max, phase, B, dev_probs_ptr, stream_ptr=0):
         """One piece of a whole-GPU window: phase = GRID_PHASE_INIT, a timestep t >= 0, or GRID_PHASE_FINISH."""
-        self._check(self.lib.pfg_launch_device_grid_phase(
-            self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], int(n_max), int(phase), int(B),
-            C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_launch_device_grid_phase", model, kernel, dtype, rng, n_max, phase, B, dev_probs_ptr, stream_ptr)
 
     GRID_PHASE_ALL = -1
 
@@ -748,262 +704,176 @@ class Context:
         """The whole-GPU window (phase = GRID_PHASE_ALL) or one piece of it with the batch's smoother stated: 'nemeth' /
         'filter' as launch_device_grid[_phase]; 'poyiadjis_n' (every window NEMETH, lambduh = 1, score) runs the score-only
         twin of the device-generator timestep kernel."""
-        self._check(self.lib.pfg_launch_device_grid_smoother(
-            self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], SMOOTHER[smoother], int(n_max), int(T_max),
-            int(phase), int(B), C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_launch_device_grid_smoother", model, kernel, dtype, rng, smoother, n_max, T_max, phase, B,
+                   dev_probs_ptr, stream_ptr)
 
     def launch_device_smoother(self, model, kernel, dtype, rng, smoother, n_max, B, dev_probs_ptr, stream_ptr=0):
-        self._check(self.lib.pfg_launch_device_smoother(
-            self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], SMOOTHER[smoother], int(n_max),
-            int(B), C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_launch_device_smoother", model, kernel, dtype, rng, smoother, n_max, B, dev_probs_ptr, stream_ptr)
 
     def launch_device_traced(self, model, kernel, dtype, rng, smoother, n_max, B, dev_probs_ptr, stream_ptr=0):
         """The launch that honours the trace_* / rec_* buffers of the descriptors (pfg_launch_device_traced)."""
-        self._check(self.lib.pfg_launch_device_traced(
-            self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], SMOOTHER[smoother], int(n_max),
-            int(B), C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_launch_device_traced", model, kernel, dtype, rng, smoother, n_max, B, dev_probs_ptr, stream_ptr)
 
     def launch_device_adaptive(self, model, kernel, dtype, rng, n_max, B, dev_probs_ptr, stream_ptr=0, traced=False):
         """A batch of adaptive-resampling windows (descriptors with FLAG_ADAPTIVE_RESAMPLING and ess_threshold):
         pfg_launch_device_adaptive; traced: honour the trace_* / rec_* buffers."""
-        self._check(self.lib.pfg_launch_device_adaptive(
-            self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], int(n_max), int(B),
-            C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr)), int(bool(traced))))
+        self._call("pfg_launch_device_adaptive", model, kernel, dtype, rng, n_max, B, dev_probs_ptr, stream_ptr, traced)
 
     def last_traced(self):
-        return bool(self.lib.pfg_last_traced(self.handle))
+        return bool(self._call("pfg_last_traced"))
 
     def launch_device_grid(self, model, kernel, dtype, rng, n_max, T_max, B, dev_probs_ptr, stream_ptr=0):
         """Whole-GPU windows (N > 16384: one launch per timestep, pfg_launch_device_grid); T_max = the largest T."""
-        self._check(self.lib.pfg_launch_device_grid(
-            self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], int(n_max), int(T_max), int(B),
-            C.c_void_p(dev_probs_ptr), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_launch_device_grid", model, kernel, dtype, rng, n_max, T_max, B, dev_probs_ptr, stream_ptr)
 
     def launch_device(self, model, kernel, dtype, rng, n_max, B, dev_probs_ptr, stream_ptr=0):
         """stream_ptr: a hipStream_t handle used as is (0 = HIP's default stream, which is also
         torch's default `torch.cuda.current_stream().cuda_stream`)."""
-        self._check(self.lib.pfg_launch_device(self.handle, MODEL[model], KERNEL[kernel], DTYPE[dtype],
-                                               RNG[rng], int(n_max), int(B), C.c_void_p(dev_probs_ptr),
-                                               C.c_void_p(int(stream_ptr))))
+        self._call("pfg_launch_device", model, kernel, dtype, rng, n_max, B, dev_probs_ptr, stream_ptr)
 
     def sample_windows_device(self, B, dev_probs_ptr, y_ptr, weights_table_ptr, T, S, buffer, strict, seed,
                               chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
-        self._check(self.lib.pfg_sample_windows_device(
-            self.handle, int(B), C.c_void_p(dev_probs_ptr), C.c_void_p(y_ptr), C.c_void_p(weights_table_ptr or 0),
-            int(T), int(S), int(buffer), int(bool(strict)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr or 0), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_sample_windows_device", B, dev_probs_ptr, y_ptr, weights_table_ptr, T, S, buffer, strict, seed,
+                   chain_offset, step_ctr_ptr, stream_ptr)
 
     def sample_windows_multi_device(self, num_chains, n_seq, bounds_ptr, weight_offsets_ptr, num_sequences, M, dev_probs_ptr,
                                     seq_len_ptr, y_ptr, weights_ptr, S, buffer, strict, seed, chain_offset=0,
                                     step_ctr_ptr=None, stream_ptr=0):
         """pfg_sample_windows_multi_device: W = K_eff * M window descriptors per chain, chain-major (include/pfgrad.h)."""
-        self._check(self.lib.pfg_sample_windows_multi_device(
-            self.handle, int(num_chains), int(n_seq), C.c_void_p(bounds_ptr), C.c_void_p(weight_offsets_ptr or 0),
-            int(num_sequences), int(M), C.c_void_p(dev_probs_ptr), C.c_void_p(seq_len_ptr), C.c_void_p(y_ptr),
-            C.c_void_p(weights_ptr or 0), int(S), int(buffer), int(bool(strict)),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr or 0),
-            C.c_void_p(int(stream_ptr))))
+        self._call("pfg_sample_windows_multi_device", num_chains, n_seq, bounds_ptr, weight_offsets_ptr, num_sequences, M,
+                   dev_probs_ptr, seq_len_ptr, y_ptr, weights_ptr, S, buffer, strict, seed, chain_offset, step_ctr_ptr,
+                   stream_ptr)
 
     def reduce_windows_device(self, num_chains, K, M, win_outs_ptr, seq_len_ptr, rescale, T_total, outs_ptr, stream_ptr=0):
         """pfg_reduce_windows_device: [C*K*M][8] window records -> [C][8], in the reference's order (include/pfgrad.h)."""
-        self._check(self.lib.pfg_reduce_windows_device(
-            self.handle, int(num_chains), int(K), int(M), C.c_void_p(win_outs_ptr), C.c_void_p(seq_len_ptr or 0),
-            int(bool(rescale)), float(T_total), C.c_void_p(outs_ptr), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_reduce_windows_device", num_chains, K, M, win_outs_ptr, seq_len_ptr, rescale, T_total, outs_ptr,
+                   stream_ptr)
 
     def sgld_update_device(self, model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, seed,
                            chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
-        self._check(self.lib.pfg_sgld_update_device(
-            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper),
-            float(epsilon), float(Tscale), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
-            C.c_void_p(int(stream_ptr))))
+        self._call("pfg_sgld_update_device", model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, seed, chain_offset,
+                   step_ctr_ptr, stream_ptr)
 
     def sgrld_update_device(self, model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, seed,
                             chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
-        self._check(self.lib.pfg_sgrld_update_device(
-            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper),
-            float(epsilon), float(Tscale), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
-            C.c_void_p(int(stream_ptr))))
+        self._call("pfg_sgrld_update_device", model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, seed, chain_offset,
+                   step_ctr_ptr, stream_ptr)
 
     def sgd_update_device(self, model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, step_ctr_ptr=None, stream_ptr=0):
         """pfg_sgd_update_device: theta += eps (grad_logprior + ghat) / Tscale, then the projection; no draws."""
-        self._check(self.lib.pfg_sgd_update_device(
-            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper), float(epsilon),
-            float(Tscale), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_sgd_update_device", model, B, theta_ptr, outs_ptr, hyper, epsilon, Tscale, step_ctr_ptr, stream_ptr)
 
     def adagrad_update_device(self, model, B, theta_ptr, moment_ptr, outs_ptr, hyper, epsilon, Tscale, step_ctr_ptr=None,
                               stream_ptr=0):
         """pfg_adagrad_update_device: the SGD step on g / sqrt(G + 1e-9), G [B][MAX_THETA] += g g in place."""
-        self._check(self.lib.pfg_adagrad_update_device(
-            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(moment_ptr), C.c_void_p(outs_ptr),
-            C.byref(hyper), float(epsilon), float(Tscale), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
-            C.c_void_p(int(stream_ptr))))
+        self._call("pfg_adagrad_update_device", model, B, theta_ptr, moment_ptr, outs_ptr, hyper, epsilon, Tscale,
+                   step_ctr_ptr, stream_ptr)
 
     def sgld_cv_update_device(self, model, B, theta_ptr, outs_ptr, outs_centre_ptr, centre_grad_ptr, hyper, epsilon, Tscale,
                               seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
         """pfg_sgld_cv_update_device: the SGLD step on centre_grad + (outs - outs_centre) (include/pfgrad.h)."""
-        self._check(self.lib.pfg_sgld_cv_update_device(
-            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.c_void_p(outs_centre_ptr),
-            C.c_void_p(centre_grad_ptr), C.byref(hyper), float(epsilon), float(Tscale),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_sgld_cv_update_device", model, B, theta_ptr, outs_ptr, outs_centre_ptr, centre_grad_ptr, hyper,
+                   epsilon, Tscale, seed, chain_offset, step_ctr_ptr, stream_ptr)
 
     def cv_accumulate_device(self, B, outs_ptr, acc_ptr, repeat, num_repeats, step_ctr_ptr=None, stream_ptr=0):
         """pfg_cv_accumulate_device: repeat `repeat` of the mean over num_repeats records (include/pfgrad.h)."""
-        self._check(self.lib.pfg_cv_accumulate_device(
-            self.handle, int(B), C.c_void_p(outs_ptr), C.c_void_p(acc_ptr), int(repeat), int(num_repeats),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_cv_accumulate_device", B, outs_ptr, acc_ptr, repeat, num_repeats, step_ctr_ptr, stream_ptr)
 
     def gibbs_update_device(self, model, B, theta_ptr, outs_ptr, hyper, seed, chain_offset=0, step_ctr_ptr=None,
                             stream_ptr=0):
-        self._check(self.lib.pfg_gibbs_update_device(
-            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(outs_ptr), C.byref(hyper),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_gibbs_update_device", model, B, theta_ptr, outs_ptr, hyper, seed, chain_offset, step_ctr_ptr,
+                   stream_ptr)
 
     def pgibbs_update_device(self, model, B, theta_ptr, outs_ptr, hyper, seed, chain_offset=0, step_ctr_ptr=None,
                              stream_ptr=0):
         """pfg_pgibbs_update_device: the conjugate draw from the statistics of a conditional SMC path (SVM, LGSSM)."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_pgibbs_update_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(outs_ptr or 0),
-            C.byref(hyper) if hyper is not None else None,
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_pgibbs_update_device", model, B, theta_ptr, outs_ptr, hyper, seed, chain_offset, step_ctr_ptr,
+                   stream_ptr)
 
     def csmc_device(self, model, dtype, n_max, B, problems_ptr, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0,
                     traced=False):
         """pfg_csmc_device: one conditional SMC sweep with ancestor sampling per pfg_csmc_problem record (a device array)."""
-        m = model if isinstance(model, int) else MODEL[model]
-        d = dtype if isinstance(dtype, int) else DTYPE[dtype]
-        self._check(self.lib.pfg_csmc_device(
-            self.handle, m, d, int(n_max), int(B), C.c_void_p(problems_ptr or 0),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr)), int(bool(traced))))
+        self._call("pfg_csmc_device", model, dtype, n_max, B, problems_ptr, seed, chain_offset, step_ctr_ptr, stream_ptr,
+                   traced)
 
     def cpm_device(self, model, dtype, n_max, B, problems_ptr, rho, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0,
                    traced=False):
         """pfg_cpm_device: one sorted, correlated filter per pfg_cpm_problem record (a device array): U' = rho U + sqrt(1 -
         rho^2) eps into the chain's other buffer, out[4] the log-likelihood estimate on U'."""
-        m = model if isinstance(model, int) else MODEL[model]
-        d = dtype if isinstance(dtype, int) else DTYPE[dtype]
-        self._check(self.lib.pfg_cpm_device(
-            self.handle, m, d, int(n_max), int(B), C.c_void_p(problems_ptr or 0), C.c_double(float(rho)),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr)), int(bool(traced))))
+        self._call("pfg_cpm_device", model, dtype, n_max, B, problems_ptr, rho, seed, chain_offset, step_ctr_ptr, stream_ptr,
+                   traced)
 
     def cpm_commit_device(self, B, n_accept_ptr, seen_ptr, which_ptr, init, stream_ptr=0):
         """pfg_cpm_commit_device: a chain whose acceptance count moved (init: every chain) flips its buffer selector."""
-        self._check(self.lib.pfg_cpm_commit_device(
-            self.handle, int(B), C.c_void_p(n_accept_ptr or 0), C.c_void_p(seen_ptr or 0), C.c_void_p(which_ptr or 0),
-            int(bool(init)), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_cpm_commit_device", B, n_accept_ptr, seen_ptr, which_ptr, init, stream_ptr)
 
     def sqmc_device(self, model, dtype, n_max, B, problems_ptr, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0,
                     traced=False):
         """pfg_sqmc_device: one sequential quasi-Monte Carlo filter per pfg_sqmc_problem record (a device array): sorted
         particles on one randomised Sobol' point set per timestep, out[4] the log-likelihood estimate."""
-        m = model if isinstance(model, int) else MODEL[model]
-        d = dtype if isinstance(dtype, int) else DTYPE[dtype]
-        self._check(self.lib.pfg_sqmc_device(
-            self.handle, m, d, int(n_max), int(B), C.c_void_p(problems_ptr or 0),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr)), int(bool(traced))))
+        self._call("pfg_sqmc_device", model, dtype, n_max, B, problems_ptr, seed, chain_offset, step_ctr_ptr, stream_ptr,
+                   traced)
 
     def logprior_device(self, model, B, theta_ptr, hyper, logprior_ptr, stream_ptr=0):
         """pfg_logprior_device: logprior[b] = Prior.logprior of the raw row theta[b], up to a constant of the hyper-parameters."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_logprior_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.byref(hyper) if hyper is not None else None,
-            C.c_void_p(logprior_ptr or 0), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_logprior_device", model, B, theta_ptr, hyper, logprior_ptr, stream_ptr)
 
     def pmmh_propose_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, scale_ptr, seed, chain_offset=0,
                             step_ctr_ptr=None, stream_ptr=0):
         """pfg_pmmh_propose_device: theta_prop = theta + scale (.) z, or theta and valid = 0 outside the support."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_pmmh_propose_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
-            C.c_void_p(scale_ptr or 0), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_pmmh_propose_device", model, B, theta_ptr, theta_prop_ptr, valid_ptr, scale_ptr, seed, chain_offset,
+                   step_ctr_ptr, stream_ptr)
 
     def pmmh_accept_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, n_accept_ptr, hyper, init,
                            seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
         """pfg_pmmh_accept_device: the accept / reject step on out[4] (init: ll = out[4] only); bumps *step_ctr unless init."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_pmmh_accept_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
-            C.c_void_p(outs_ptr or 0), C.c_void_p(ll_ptr or 0), C.c_void_p(n_accept_ptr or 0),
-            C.byref(hyper) if hyper is not None else None, int(bool(init)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_pmmh_accept_device", model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, n_accept_ptr,
+                   hyper, init, seed, chain_offset, step_ctr_ptr, stream_ptr)
 
     def pmala_propose_device(self, model, B, theta_ptr, grad_ptr, theta_prop_ptr, valid_ptr, scale_ptr, hyper, seed,
                              chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
         """pfg_pmala_propose_device: theta_prop = theta + scale^2 / 2 (.) (grad_logprior + grad) + scale (.) z, or theta and
         valid = 0 outside the support."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_pmala_propose_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(grad_ptr or 0), C.c_void_p(theta_prop_ptr or 0),
-            C.c_void_p(valid_ptr or 0), C.c_void_p(scale_ptr or 0), C.byref(hyper) if hyper is not None else None,
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_pmala_propose_device", model, B, theta_ptr, grad_ptr, theta_prop_ptr, valid_ptr, scale_ptr, hyper,
+                   seed, chain_offset, step_ctr_ptr, stream_ptr)
 
     def pmala_accept_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, grad_ptr, n_accept_ptr,
                             hyper, scale_ptr, init, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
         """pfg_pmala_accept_device: the accept / reject step on out[4], out[0..3] and the two proposal densities (init:
         ll = out[4], grad = out[0..3] only); bumps *step_ctr unless init."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_pmala_accept_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
-            C.c_void_p(outs_ptr or 0), C.c_void_p(ll_ptr or 0), C.c_void_p(grad_ptr or 0), C.c_void_p(n_accept_ptr or 0),
-            C.byref(hyper) if hyper is not None else None, C.c_void_p(scale_ptr or 0), int(bool(init)),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(chain_offset)),
-            C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_pmala_accept_device", model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, grad_ptr,
+                   n_accept_ptr, hyper, scale_ptr, init, seed, chain_offset, step_ctr_ptr, stream_ptr)
 
     def smc_logtarget_device(self, model, B, theta_ptr, ll_ptr, hyper, q0_mean_ptr, q0_sd_ptr, h_ptr, stream_ptr=0):
         """pfg_smc_logtarget_device: h[b] = (ll[b] + logprior(theta[b])) - log q0(theta[b])."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_smc_logtarget_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(ll_ptr or 0),
-            C.byref(hyper) if hyper is not None else None, C.c_void_p(q0_mean_ptr or 0), C.c_void_p(q0_sd_ptr or 0),
-            C.c_void_p(h_ptr or 0), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_smc_logtarget_device", model, B, theta_ptr, ll_ptr, hyper, q0_mean_ptr, q0_sd_ptr, h_ptr, stream_ptr)
 
     def smc_temper_device(self, B, h_ptr, phi_ptr, ess_target, seed, stage, result_ptr, status_ptr, parent_ptr, scratch_ptr,
                           stream_ptr=0):
         """pfg_smc_temper_device: the next temperature, the evidence increment and the chains' parents (one workgroup)."""
-        self._check(self.lib.pfg_smc_temper_device(
-            self.handle, int(B), C.c_void_p(h_ptr or 0), C.c_void_p(phi_ptr or 0), C.c_double(float(ess_target)),
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(stage)), C.c_void_p(result_ptr or 0),
-            C.c_void_p(status_ptr or 0), C.c_void_p(parent_ptr or 0), C.c_void_p(scratch_ptr or 0), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_smc_temper_device", B, h_ptr, phi_ptr, ess_target, seed, stage, result_ptr, status_ptr, parent_ptr,
+                   scratch_ptr, stream_ptr)
 
     def smc_gather_device(self, B, parent_ptr, theta_ptr, ll_ptr, theta_tmp_ptr, ll_tmp_ptr, stream_ptr=0):
         """pfg_smc_gather_device: theta[b], ll[b] = theta[parent[b]], ll[parent[b]] through the two scratch arrays."""
-        self._check(self.lib.pfg_smc_gather_device(
-            self.handle, int(B), C.c_void_p(parent_ptr or 0), C.c_void_p(theta_ptr or 0), C.c_void_p(ll_ptr or 0),
-            C.c_void_p(theta_tmp_ptr or 0), C.c_void_p(ll_tmp_ptr or 0), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_smc_gather_device", B, parent_ptr, theta_ptr, ll_ptr, theta_tmp_ptr, ll_tmp_ptr, stream_ptr)
 
     def smc_scale_device(self, B, theta_ptr, slots, factor, scale_ptr, stream_ptr=0):
         """pfg_smc_scale_device: scale[j] = factor * sd_j of the population for every slot j in the bit mask `slots`."""
-        self._check(self.lib.pfg_smc_scale_device(
-            self.handle, int(B), C.c_void_p(theta_ptr or 0), C.c_uint32(int(slots)), C.c_double(float(factor)),
-            C.c_void_p(scale_ptr or 0), C.c_void_p(int(stream_ptr))))
+        self._call("pfg_smc_scale_device", B, theta_ptr, slots, factor, scale_ptr, stream_ptr)
 
     def smc_accept_device(self, model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, n_accept_ptr, hyper,
                           q0_mean_ptr, q0_sd_ptr, phi_ptr, log_alpha_ptr, seed, chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
         """pfg_smc_accept_device: pfg_pmmh_accept_device's step at the temperature *phi; bumps *step_ctr."""
-        m = model if isinstance(model, int) else MODEL[model]
-        self._check(self.lib.pfg_smc_accept_device(
-            self.handle, m, int(B), C.c_void_p(theta_ptr or 0), C.c_void_p(theta_prop_ptr or 0), C.c_void_p(valid_ptr or 0),
-            C.c_void_p(outs_ptr or 0), C.c_void_p(ll_ptr or 0), C.c_void_p(n_accept_ptr or 0),
-            C.byref(hyper) if hyper is not None else None, C.c_void_p(q0_mean_ptr or 0), C.c_void_p(q0_sd_ptr or 0),
-            C.c_void_p(phi_ptr or 0), C.c_void_p(log_alpha_ptr or 0), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None, C.c_void_p(int(stream_ptr))))
+        self._call("pfg_smc_accept_device", model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, n_accept_ptr,
+                   hyper, q0_mean_ptr, q0_sd_ptr, phi_ptr, log_alpha_ptr, seed, chain_offset, step_ctr_ptr, stream_ptr)
 
     def scratch_bytes(self, model, dtype, rng, N):
-        return int(self.lib.pfg_scratch_bytes(MODEL[model], DTYPE[dtype], RNG[rng], int(N)))
+        return self._call("pfg_scratch_bytes", model, dtype, rng, N)
 
     def scratch_bytes_smoother(self, model, dtype, rng, smoother, N):
         """Per-descriptor scratch of a pfg_launch_device_smoother batch of `smoother` windows (-1: above its maximum)."""
-        return int(self.lib.pfg_scratch_bytes_smoother(MODEL[model], DTYPE[dtype], RNG[rng], SMOOTHER[smoother], int(N)))
+        return self._call("pfg_scratch_bytes_smoother", model, dtype, rng, smoother, N)
 
     def scratch_bytes_adaptive(self, model, dtype, N):
         """Per-descriptor scratch of a pfg_launch_device_adaptive batch: 0 for N <= 1024, above it the large-N kernels' state,
@@ -1016,27 +886,23 @@ class Context:
         if x.ndim != 2 or x.shape != g.shape:
             raise ValueError("x and gradlogp dimensions do not match")
         out = C.c_double()
-        self._check(self.lib.pfg_imq_ksd(self.handle, x.shape[0], x.shape[1], _ptr(x), _ptr(g), float(c),
-                                         float(beta), C.byref(out)))
+        self._call("pfg_imq_ksd", x.shape[0], x.shape[1], _ptr(x), _ptr(g), c, beta, C.byref(out))
         return float(out.value)
 
     def sghmc_update_device(self, model, B, theta_ptr, momentum_ptr, outs_ptr, hyper, epsilon, alpha, Tscale, seed,
                             chain_offset=0, step_ctr_ptr=None, stream_ptr=0):
-        self._check(self.lib.pfg_sghmc_update_device(
-            self.handle, MODEL[model], int(B), C.c_void_p(theta_ptr), C.c_void_p(momentum_ptr), C.c_void_p(outs_ptr),
-            C.byref(hyper), float(epsilon), float(alpha), float(Tscale), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(chain_offset)), C.c_void_p(step_ctr_ptr) if step_ctr_ptr else None,
-            C.c_void_p(int(stream_ptr))))
+        self._call("pfg_sghmc_update_device", model, B, theta_ptr, momentum_ptr, outs_ptr, hyper, epsilon, alpha, Tscale,
+                   seed, chain_offset, step_ctr_ptr, stream_ptr)
 
     def variant_name(self, model, kernel, dtype, rng, n_max):
-        return self.lib.pfg_variant_name(MODEL[model], KERNEL[kernel], DTYPE[dtype], RNG[rng], int(n_max)).decode()
+        return self._call("pfg_variant_name", model, kernel, dtype, rng, n_max).decode()
 
     def last_variant(self):
         """Tag of the kernel variant the latest launch through this context ran."""
-        return self.lib.pfg_last_variant(self.handle).decode()
+        return self._call("pfg_last_variant").decode()
 
     def synchronize(self):
-        self._check(self.lib.pfg_synchronize(self.handle))
+        self._call("pfg_synchronize")
 
 
 _default_ctx = {}

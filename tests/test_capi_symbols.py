@@ -18,6 +18,137 @@ def declared_functions():
     return sorted(set(names))
 
 
+def declared_prototypes():
+    """name -> (return type, parameter types) of every pfg_* prototype of the header, as C spells them without `const`
+    and the parameter names; every pointer is '*'."""
+    src = open(os.path.join(ROOT, "include", "pfgrad.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+    def c_type(decl, named):
+        if "*" in decl:
+            return "char*" if "char" in decl else "*"
+        words = [w for w in decl.split() if w != "const"]
+        return " ".join(words[:-1] if named else words)
+    protos = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?(?:int|void|int64_t|char)\s*\*?)\s*(pfg_\w+)\s*\(([^)]*)\)\s*;",
+                                        src, flags=re.M):
+        params = [] if params.strip() == "void" else params.split(",")
+        protos[name] = (c_type(ret, False), [c_type(p, True) for p in params])
+    return protos
+
+
+C_SCALARS = {"int": ctypes.c_int, "double": ctypes.c_double, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
+             "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
+
+
+def is_pointer_type(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def test_binding_types_match_the_header_prototypes():
+    """Every prototype of include/pfgrad.h against the argtypes / restype the binding sets on the loaded library: the
+    arity, each parameter's class (int, double, uint64_t, uint32_t, int64_t, size_t, or a pointer -- which must meet a
+    ctypes pointer type or c_void_p, as an integer must meet its own ctypes integer) and the return type."""
+    if _build.is_stale():
+        _build.build_library()
+    lib = _capi.load_library()
+    protos = declared_prototypes()
+    assert len(protos) >= 54 and set(protos) == set(declared_functions()), sorted(protos)
+    returns = dict(C_SCALARS, void=None)
+    for name, (ret, params) in protos.items():
+        fn = getattr(lib, name)
+        argtypes = list(fn.argtypes or ())
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        for i, (c, t) in enumerate(zip(params, argtypes)):
+            if c == "*":
+                assert is_pointer_type(t), (name, i, c, t)
+            else:
+                assert t is C_SCALARS[c], (name, i, c, t)
+        if ret == "char*":
+            assert fn.restype is ctypes.c_char_p, (name, "return", fn.restype)
+        elif ret == "*":
+            assert fn.restype is ctypes.c_void_p, (name, "return", fn.restype)
+        else:
+            assert fn.restype is returns[ret], (name, "return", ret, fn.restype)
+
+
+ABI_STRUCTS = (("pfg_problem", "PROBLEM_DTYPE"), ("pfg_result", "RESULT_DTYPE"), ("pfg_dev_problem", "DEV_PROBLEM_DTYPE"),
+               ("pfg_prior_hyper", "PriorHyper"), ("pfg_csmc_problem", "CSMC_PROBLEM_DTYPE"),
+               ("pfg_cpm_problem", "CPM_PROBLEM_DTYPE"), ("pfg_sqmc_problem", "SQMC_PROBLEM_DTYPE"))
+ENUM_PREFIXES = (("MODEL", "PFG_MODEL_"), ("KERNEL", "PFG_KERNEL_"), ("SMOOTHER", "PFG_SMOOTHER_"), ("STAT", "PFG_STAT_"),
+                 ("DTYPE", "PFG_"), ("RNG", "PFG_RNG_"))
+
+
+def mirror_layout(mirror):
+    """(size, [(field, offset, size)]) of a numpy structured dtype or a ctypes structure."""
+    if isinstance(mirror, type) and issubclass(mirror, ctypes.Structure):
+        return ctypes.sizeof(mirror), [(n, getattr(mirror, n).offset, getattr(mirror, n).size) for n, _ in mirror._fields_]
+    return mirror.itemsize, [(n, mirror.fields[n][1], mirror.fields[n][0].itemsize) for n in mirror.names]
+
+
+def enumerators(table, prefix):
+    """C enumerator -> value behind one of the binding's name tables ("philox" is its alias of "device", not an enumerator)."""
+    return {prefix + key.upper(): value for key, value in getattr(_capi, table).items() if (table, key) != ("RNG", "philox")}
+
+
+def mirrored_values():
+    """name -> value of everything the binding restates from the header: the struct layouts (the field names are the
+    mirrors'), the constants and the enumerators; the keys are C expressions of type size_t or int."""
+    want = {}
+    for c_name, py_name in ABI_STRUCTS:
+        size, fields = mirror_layout(getattr(_capi, py_name))
+        want["sizeof({0})".format(c_name)] = size
+        for field, offset, width in fields:
+            want["offsetof({0}, {1})".format(c_name, field)] = offset
+            want["sizeof((({0} *)0)->{1})".format(c_name, field)] = width
+    for name in ("MAX_STAT", "MAX_THETA", "OUT_DOUBLES", "MAX_PRED", "STAMP_WORDS", "MAX_DRAWN_SEQUENCES", "SMC_RESULT_DOUBLES",
+                 "FLAG_GARCH_STATIONARY_PRIOR", "FLAG_PARIS_NO_ACCEPT_REJECT", "FLAG_PARIS_RAW_STREAM", "FLAG_PARIS_RAW_CARRY",
+                 "FLAG_ADAPTIVE_RESAMPLING"):
+        want["PFG_" + name] = getattr(_capi, name)
+    for name in ("GRID_PHASE_INIT", "GRID_PHASE_FINISH", "GRID_PHASE_ALL"):
+        want["PFG_" + name] = getattr(_capi.Context, name)
+    for name in ("PFG_OK", "PFG_ERR_INVALID", "PFG_ERR_UNSUPPORTED", "PFG_ERR_DEVICE", "PFG_ERR_NOMEM", "PFG_ERR_NUMERIC"):
+        want[name] = getattr(_capi, name)
+    for table, prefix in ENUM_PREFIXES:
+        want.update(enumerators(table, prefix))
+    return want
+
+
+def test_binding_layouts_constants_and_enums_match_the_header(tmp_path):
+    """A C99 program that includes pfgrad.h prints sizeof of the seven ABI structs, offsetof and the member size of every
+    field of their mirrors, every constant and every enumerator the binding restates; each must equal the Python side.
+    The fields are the mirrors', and a struct's sizeof must equal its mirror's size, so a field a mirror lacks shows too;
+    the header's enums must hold no enumerator the binding lacks."""
+    import shutil
+    import subprocess
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("gcc not available")
+    want = mirrored_values()
+    # the ctypes forms of pfg_problem / pfg_result (what pfg_run_batch is handed) lay out as their numpy forms do
+    assert mirror_layout(_capi.Problem) == mirror_layout(_capi.PROBLEM_DTYPE)
+    assert mirror_layout(_capi.Result) == mirror_layout(_capi.RESULT_DTYPE)
+    assert _capi.RNG["philox"] == _capi.RNG["device"]
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pfgrad.h")).read(), flags=re.S)
+    for table, prefix in ENUM_PREFIXES:
+        declared = set(re.findall(r"\b" + (r"PFG_F\d+" if table == "DTYPE" else prefix + r"\w+") + r"\b", header))
+        assert declared == set(enumerators(table, prefix)), (table, declared)
+    src = tmp_path / "abi_layout.c"
+    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"pfgrad.h\"\nint main(void) {\n" +
+                   "".join("    printf(\"%ld\\n\", (long)({0}));\n".format(expr) for expr in want) +
+                   "    return 0;\n}\n")
+    exe = str(tmp_path / "abi_layout")
+    res = subprocess.run([gcc, "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
+                          str(src), "-o", exe], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, (run.returncode, run.stderr)
+    got = [int(line) for line in run.stdout.split()]
+    assert len(got) == len(want)
+    wrong = {expr: (c_value, py_value) for (expr, py_value), c_value in zip(want.items(), got) if c_value != py_value}
+    assert not wrong, wrong          # expression -> (the header's value, the binding's)
+
+
 def test_header_declares_expected_entry_points():
     names = declared_functions()
     assert set(names) == set(_capi.EXPORTS), (names, _capi.EXPORTS)
