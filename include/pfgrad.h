@@ -268,13 +268,20 @@ typedef struct pfg_result {
     /* DEVICE rng + trace_x only (test instrumentation of the device-generator kernels): the random
      * inputs the kernel drew, so that a CPU oracle can replay the SAME launch deterministically.
      * rec_u [T*N]: the raw 32-bit word child i searched the resampling CDF with at step t;
-     * rec_z [T*N]: its standard normal (as widened to f64);  rec_z0 [N]: the x0 normals. */
+     * rec_z [T*N]: its standard normal (as widened to f64);  rec_z0 [N]: the x0 normals.  Every device-generator
+     * family that the launch plan picks writes rec_z and rec_z0: pf_reg_kernel, pf_big_kernel, the grid kernels and
+     * pf_mem_kernel's PaRIS and O(N^2) sweeps (paris_mem1024, n2_mem1024: 1024 < N <= 16384; a twin of the production
+     * instantiation that pfg_run_batch and pfg_launch_device_traced run when buffers are asked for).  pf_mem_kernel's plain
+     * sweep forced onto the device generator (PFGRAD_VARIANT=mem1024) records nothing.  The backward-sampling uniforms of
+     * PaRIS and the normals of the predictive statistic are recorded nowhere. */
     uint32_t *rec_u;
     double *rec_z, *rec_z0;
     double *rec_ud;     /* [T*N]: large-N device kernel (pf_big_kernel), whose resampling uniforms are not raw
                            generator words but SORTED uniforms built from exponential spacings: the uniform in
                            (0,1) child i searched the CDF with at step t (rec_u stays 0 there); the stratified,
-                           adaptive and systematic instantiations record the uniform of child i the same way */
+                           adaptive and systematic instantiations record the uniform of child i the same way, and
+                           so do pf_mem_kernel's PaRIS and O(N^2) sweeps on the device generator: (word + 0.5) / 2^32
+                           of child i's word, searched against the f64 CDF in particle order */
     /* pfg_problem.elementwise: ew_mean [3 (tL-t1)] = average_statistic of the elementwise run (required);
      * ew_stats [N * 3 (tL-t1)] = its per-particle statistics, row-major (optional) */
     double *ew_mean, *ew_stats;

@@ -138,6 +138,26 @@ def device_ancestors(logw, words, NT, PPT, cdf="fixed32"):
     return np.minimum((pos % PPT) * NT + pos // PPT, N - 1)
 
 
+def particle_order_ancestors(logw, u):
+    """Multinomial resampling as pf_mem_kernel lays it out on the DEVICE generator (a restatement of
+    csrc/pfg_mem_kernel.hpp phases B-E, not of the reference): the CDF runs in PARTICLE order,
+    p_i = exp(logw_i - max), inclusive running sum, times 1 / W with W the total; child i's ancestor
+    is the number of entries <= its own uniform u[i] in (0, 1), clamped to N - 1 -- np.random.choice's
+    searchsorted(cdf, u, 'right') on the same uniforms.
+    Returns (ancestors [N], gap [N]): gap_i = min over the CDF entries of |u_i - entry|.  The kernel's
+    weights go through its fast exp and its sum is a wave scan plus offsets, so a child whose gap is
+    of the order of that rounding may sit on the other side of the nearest entry there."""
+    logw = np.asarray(logw, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64)
+    N = logw.shape[0]
+    cs = np.cumsum(np.exp(logw - np.max(logw)))
+    cdf = cs * (1.0 / cs[-1])
+    pos = np.searchsorted(cdf, u, side="right")
+    below = np.where(pos > 0, u - cdf[np.maximum(pos - 1, 0)], np.inf)
+    above = np.where(pos < N, cdf[np.minimum(pos, N - 1)] - u, np.inf)
+    return np.minimum(pos, N - 1), np.minimum(below, above)
+
+
 def sample_x0(model, prior_mean, prior_var, z0):
     """kernels.py:83-100 (n=1), garch/kernels.py:7-18.  z0: (N,) standard normals.
     np.random.normal(loc, scale) is loc + scale*gauss."""
@@ -533,8 +553,8 @@ def pf_window(model, theta, y, N, z0, u, z, kernel=None, pf="poyiadjis_N",
             for i in range(N):
                 child_ll = prior_log_density(model, d, x, np.outer(np.ones(N), x_next[i]))
                 bw[i] = log_normalize(logw + child_ll)
-            idx = np.array([ii for _ in range(N) for ii in range(N)])
-            new_idx = np.array([ii for ii in range(N) for _ in range(N)])
+            idx = np.tile(np.arange(N), N)              # [ii for _ in range(N) for ii in range(N)]
+            new_idx = np.repeat(np.arange(N), N)        # [ii for ii in range(N) for _ in range(N)]
             if inside and stat == "score":
                 add = widen(score_statistic(model, d, x[idx], x_next[new_idx], y[t]), t)
             elif inside and stat == "suff":

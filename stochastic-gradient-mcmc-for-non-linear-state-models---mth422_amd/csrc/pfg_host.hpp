@@ -129,6 +129,7 @@ struct LaunchPlan {
     bool traced = true;          // the TRACE instantiation (pfg_last_traced)
     bool score1 = false;         // the score-only twin (PFG_SMOOTHER_POYIADJIS_N, see SCORE1 in pfg_reg_kernel.hpp)
     bool lw4 = false;
+    bool record = false;         // Paris / N2 on the large-N kernel, device generator: the twin that writes rec_z0 / rec_z / rec_ud
     int np2 = 0;                 // Big
     int kmax = 0, tiles = 0, t_max = 0, phase = -1;   // Grid
     bool cdf_single = false;     // Grid, REPLAY: the lone-workgroup CDF kernel

@@ -147,7 +147,12 @@ template <int MODEL, int KERNEL, typename REAL, int RNG, int MODE>
 int launch_paris(pfg_ctx *ctx, const LaunchPlan &p, int B, const pfg_dev_problem *dp, hipStream_t st) {
     if (p.nt == 256 && p.ppt == 1) return launch_one_t<MODEL, KERNEL, REAL, 256, 1, RNG, true, MODE>(ctx, p, B, dp, st);
     if (p.nt == 256) return launch_one_t<MODEL, KERNEL, REAL, 256, 4, RNG, true, MODE>(ctx, p, B, dp, st);
-    if (p.nt == pfg::MEM_NT) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, true>, pfg::MEM_NT, p, B, dp, st);
+    if (p.nt == pfg::MEM_NT) {
+        if (RNG != PFG_RNG_DEVICE || !p.record) return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, true>, pfg::MEM_NT, p, B, dp, st);
+        if constexpr (RNG == PFG_RNG_DEVICE)        // a traced launch: the twin that also writes out its draws (rec_z0, rec_z, rec_ud)
+            return launch_kernel(ctx, pfg::pf_mem_kernel<MODEL, KERNEL, REAL, RNG, /*PARIS*/ true, /*LW4*/ false, /*SCORE1*/ false, /*STRAT*/ false,
+                                                         /*ADAPT*/ false, /*RECORD*/ true>, pfg::MEM_NT, p, B, dp, st);
+    }
     if (p.nt == 64 && p.ppt == 2) return launch_one_t<MODEL, KERNEL, REAL, 64, 2, RNG, true, MODE>(ctx, p, B, dp, st);
     return fail(ctx, PFG_ERR_INVALID, "the launch plan names no PaRIS / O(N^2) kernel of this unit");
 }

@@ -92,10 +92,18 @@ __host__ __device__ inline size_t mem_kernel_lds_bytes(int N) {
 // wave 0 adds the slots beside its offset scan and broadcasts the total through LDS, and every wave makes the SAME comparison
 // of the same two LDS values scalar -- barrier 3 is skipped under it.  A step that keeps its particles builds no CDF and runs
 // no search: child i proposes from record i and its log-weight carries on (`keep` below).  A template argument, like STRAT.
+// RECORD (device generator, PARIS; what a traced launch of paris_mem1024 / n2_mem1024 runs): the twin that writes out the
+// draws it consumed -- rec_z0 at the x0 draw, rec_ud / rec_z at the per-child draw of the PaRIS and O(N^2) sweeps --, in
+// traced launches (trace_x), each store behind its own pointer.  Draws and arithmetic are the production instantiation's;
+// the stores are a twin and not a run-time branch because that instantiation sits at its register limit (128 VGPRs, 14
+// spilled): with the guarded stores in it, two more spill and the O(N^2) launch of N = 10000 is 0.55 % slower
+// (profiles/mem_record_ab.txt).  The plain sweeps record nothing: on the device generator they are a fallback the launch
+// plan never picks (PFGRAD_VARIANT=mem1024), and the stores tripled the spills of its N <= 4096 instantiation.
 template <int MODEL, int KERNEL, typename REAL, int RNG, bool PARIS = false, bool LW4 = false, bool SCORE1 = false, bool STRAT = false,
-          bool ADAPT = false>
+          bool ADAPT = false, bool RECORD = false>
 __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *__restrict__ probs) {
     static_assert(!(PARIS && LW4), "LW4 is a variant of the plain kernel");
+    static_assert(!RECORD || (RNG == PFG_RNG_DEVICE && PARIS), "the recording twin is a device-generator instantiation of the PaRIS kernel");
     static_assert(!ADAPT || (RNG == PFG_RNG_REPLAY && !PARIS && !SCORE1 && !STRAT), "the adaptive twin is a REPLAY instantiation of the plain kernel");
     static_assert(!STRAT || (RNG == PFG_RNG_REPLAY && !PARIS && !SCORE1), "the stratified twin is a REPLAY instantiation of the plain kernel");
     static_assert(!SCORE1 || LW4, "the score-only twin exists for the N <= 4096 variant");
@@ -190,6 +198,16 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
     LaneRng rng = {};
     if (RNG == PFG_RNG_DEVICE)
         rng = lane_rng_init(P.seed, P.stream, P.step_ctr ? *P.step_ctr : 0ull, (uint32_t)tid);
+    // RECORD: the uniform child i searched the CDF with at step t and its normal (pfg_result.rec_ud / rec_z), beside the x0
+    // normals below.  Lanes past N draw too (v: the child exists).  The backward-sampling uniforms are not recorded.
+    [[maybe_unused]] auto record_draw = [&](int t, int i, bool v, double u, REAL z) {
+        if constexpr (RECORD) {
+            if (P.trace_x && v) {
+                if (P.rec_ud) P.rec_ud[(size_t)t * N + i] = u;
+                if (P.rec_z) P.rec_z[(size_t)t * N + i] = (double)z;
+            }
+        }
+    };
 
     // ---- PaRIS, the reference's whole np.random stream in ONE launch (as pf_reg_kernel does for N <= 1024) ---------------
     // The N normals of a call are NumPy's legacy Gaussians -- Marsaglia's polar method on pairs of doubles, the second
@@ -296,7 +314,12 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
             } else {
                 double z;
                 if (RNG == PFG_RNG_REPLAY) z = (RAWCAP && raw) ? zbuf[i] : P.z0[i];
-                else { REAL a, b; mth.normal_pair(rng.next(), rng.next(), a, b); z = (double)a; }
+                else {
+                    REAL a, b;
+                    mth.normal_pair(rng.next(), rng.next(), a, b);
+                    z = (double)a;
+                    if constexpr (RECORD) { if (P.trace_x && P.rec_z0) P.rec_z0[i] = z; }   // (i < N: lanes past N have left the loop)
+                }
                 x[0] = (REAL)(P.prior_mean + sd * z);
             }
             if (LW4) {
@@ -724,7 +747,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
                 REAL z;
                 if (RAWCAP && raw) { u = paris_overflow ? 0.5 : P.paris_stream[cursor_u + ii]; z = (REAL)zbuf[ii]; }
                 else if (RNG == PFG_RNG_REPLAY) { u = uv[(size_t)t * N + ii]; z = (REAL)zv[(size_t)t * N + ii]; }
-                else { REAL zb; u = u01_32(rng.next()); mth.normal_pair(rng.next(), rng.next(), z, zb); }
+                else { REAL zb; u = u01_32(rng.next()); mth.normal_pair(rng.next(), rng.next(), z, zb); record_draw(t, i, v, u, z); }
                 const int a = search(u);
                 if (RNG == PFG_RNG_REPLAY && v) {
                     const double hi = cdf[cdf_phys(a)] - u;
@@ -1075,7 +1098,7 @@ __global__ __launch_bounds__(MEM_NT) void pf_mem_kernel(const pfg_dev_problem *_
                 double u;
                 REAL z;
                 if (RNG == PFG_RNG_REPLAY) { u = uv[(size_t)t * N + ii]; z = (REAL)zv[(size_t)t * N + ii]; }
-                else { REAL zb; u = u01_32(rng.next()); mth.normal_pair(rng.next(), rng.next(), z, zb); }
+                else { REAL zb; u = u01_32(rng.next()); mth.normal_pair(rng.next(), rng.next(), z, zb); record_draw(t, i, v, u, z); }
                 int pos = 0;
                 for (int step = np2 >> 1; step >= 1; step >>= 1) {
                     const int probe = step - 1 + (step >= 32 ? (step >> 5) - 1 : 0);

@@ -267,6 +267,8 @@ LaunchPlan make_plan(const PlanRequest &r) {
                 return refuse(p, PFG_ERR_UNSUPPORTED, pf + " is implemented for N <= 16384 (N = " + std::to_string(n_max) + ")");
             p.nt = pfg::MEM_NT;
             p.lds = mem_lds();
+            // both instantiations honour trace_* buffers; the draws are written by the twin a traced launch runs
+            p.record = traced && rng == PFG_RNG_DEVICE;
             break;
         }
         case Family::Systematic:

@@ -9,7 +9,9 @@ po.prior_log_density, po.log_normalize, po.score_statistic and po.sufficient_sta
 at a time; nothing of one recomputed step enters the next.  The proposal itself (x_{t+1} from its normal) is NOT checked
 here: that needs the recorded normals.
 
-`ancestor_law_z` is a z-score of one resampling step against the multinomial law.
+`ancestor_law_z` is a z-score of one resampling step against the multinomial law.  `ancestors_against_restatement` derives the
+ancestors of a unit that does record its resampling uniforms (pf_mem_kernel on the device generator) and counts the
+children that differ, inside and outside the exemption for uniforms that sit on a CDF entry.
 
 `forced_paris_steps` is the same for a PaRIS window (pf.py:183-258): the statistics of step t + 1 are the reference's rewiring
 mean_j(stats_t[J_ij] + weight_t h(x_t[J_ij], x_{t+1}[i])) over the Ntilde backward-sampled parents J the launch traced.
@@ -88,6 +90,38 @@ def ancestor_law_score(all_logw, all_anc):
     zs = [z for z in zs if z is not None]
     assert zs, "no step with varying weights"
     return abs(float(np.sum(zs))) / np.sqrt(len(zs)), len(zs)
+
+
+def ancestors_against_restatement(all_logw, ud, all_anc, gap_tol=1e-10):
+    """The traced ancestors of pf_mem_kernel's device-generator units against po.particle_order_ancestors on the traced
+    log-weights of step t and the uniforms the launch recorded (ud [T, N]) -> (wrong, exempt, flips).
+
+    exempt: children whose uniform lies within gap_tol of a CDF entry -- the device's weights go through its fast exp (below
+    3e-12 relative) and its sum is a wave scan plus offsets, so such a child may take either neighbour.  wrong: children
+    outside the exemption whose traced ancestor is not the restatement's, plus exempt ones further than one neighbour away.
+    flips: all children whose traced ancestor differs, exempt or not."""
+    wrong = exempt = flips = 0
+    for t in range(len(all_anc)):
+        ref, gap = po.particle_order_ancestors(all_logw[t], ud[t])
+        got = np.asarray(all_anc[t])
+        ex = gap < gap_tol
+        exempt += int(np.sum(ex))
+        wrong += int(np.sum((got != ref) & ~ex)) + int(np.sum(np.abs(got - ref)[ex] > 1))
+        flips += int(np.sum(got != ref))
+    return wrong, exempt, flips
+
+
+def recorded_draws_are_sound(o, T, N):
+    """What every traced device-generator launch of pf_mem_kernel must have recorded: finite normals, no row of them all
+    zero; uniforms in (0, 1) that are (word + 0.5) / 2^32 of a 32-bit word."""
+    z, z0, ud = o["rec_z"], o["rec_z0"], o["rec_ud"]
+    assert z.shape == (T, N) and z0.shape == (N,) and ud.shape == (T, N)
+    assert np.all(np.isfinite(z)) and np.all(np.isfinite(z0))
+    assert np.all(np.any(z != 0.0, axis=1)) and np.any(z0 != 0.0)
+    assert np.all(ud > 0.0) and np.all(ud < 1.0)
+    words = ud * 4294967296.0 - 0.5
+    assert np.all(words == np.round(words))
+    return True
 
 
 def forced_paris_step(model, kernel, d, x, logw, stats, anc, J, x_next, y_t, stat, inside, weight_t):

@@ -11,8 +11,12 @@ These units record no resampling words, so the ancestors themselves enter the re
 the trace instead (tests/helpers/forced_window.ancestor_law_score, shown to pass on the oracle's own multinomial ancestors
 and to fail on shifted ones by tests/test_forced_window_host.py).
 
-n2_mem1024 (N > 1024: the large-N kernel's O(N^2) sweep) records no normals either; it is checked teacher-forced from its
-own trace (tests/helpers/forced_window.forced_steps)."""
+n2_mem1024 (N > 1024: the large-N kernel's O(N^2) sweep) records its normals and, unlike the 256-thread units, the uniform
+every child searched the CDF with (rec_ud).  test_large_n_device_kernel_replayed_by_oracle DERIVES its ancestors from them
+(po.particle_order_ancestors on the traced log-weights, pinned to np.random.choice by tests/test_mem_resampling_host.py;
+exact but for children whose uniform sits within 1e-10 of a CDF entry) and replays the window as above -- x0, proposal and
+parent records included -- on every model, at every chunk edge of the unit.  test_large_n_device_kernel_teacher_forced
+stays: N = 1100 from the unit's own trace (tests/helpers/forced_window.forced_steps), x_{t+1} and ancestors as traced."""
 import os
 import sys
 
@@ -83,10 +87,61 @@ def test_256_thread_device_kernels_replayed_by_oracle(ctx, monkeypatch, variant,
     assert steps == T - 1 and score < 5.0, (score, steps)
 
 
+# n2_mem1024 replayed on its recorded draws: (N, T, model, kernel).  The unit works in chunks of 1024 particles and pads its
+# CDF to a power of two.  N = 1025: the second chunk holds one particle (every model); 2048: every chunk full, N is the
+# padded size (no sentinel entries), GARCH's two-component record; 2049: the third chunk holds one particle; 4097: five chunks.
+MEM_REPLAY_CASES = [(1025, 4) + mk for mk in CASES] + [(2048, 4, "garch", "optimal"), (2049, 4, "lgssm", "prior"),
+                                                        (4097, 3, "svm", "prior")]
+
+
+@pytest.mark.parametrize("stat", ["score", "suff"])
+@pytest.mark.parametrize("N,T,model,kernel", MEM_REPLAY_CASES)
+def test_large_n_device_kernel_replayed_by_oracle(ctx, monkeypatch, N, T, model, kernel, stat):
+    """n2_mem1024, window [1, T - 1) with weights.  The launch records rec_z0, rec_z and rec_ud; the production launch of
+    the same key returns the same mean_stat and loglik bit for bit.  The traced ancestors are the restatement's on the
+    traced log-weights and the recorded uniforms (a child whose uniform lies within 1e-10 of a CDF entry -- 30 times the
+    bound of the device's fast exp -- may take either neighbour; at most one such child per 10^4 draws, a condition and
+    not a measurement: a draw is exempt with probability about 2e-10 N).  po.pf_window(pf='poyiadjis_N2') replays the
+    window on the recorded normals at the tolerances of test_256_thread_device_kernels_replayed_by_oracle: this unit is
+    built with the same flags.  Up to N = 2049 the ancestors' law score runs as a sanity check."""
+    t1, tL = 1, T - 1
+    q = _device_problem(model, kernel, stat, N, T, t1, tL)
+    monkeypatch.delenv("PFGRAD_VARIANT", raising=False)
+    o = ctx.run_batch([q], want_trace=True, want_draws=True)[0]
+    assert ctx.last_variant() == "n2_mem1024"
+    plain = ctx.run_batch([dict(q)])[0]
+    assert ctx.last_variant() == "n2_mem1024"
+    assert np.array_equal(plain["mean_stat"], o["mean_stat"]) and plain["loglik"] == o["loglik"]
+    assert forced_window.recorded_draws_are_sound(o, T, N)
+    z, z0, anc = o["rec_z"], o["rec_z0"], o["all_ancestors"]
+    assert anc.shape == (T, N) and anc.min() >= 0 and anc.max() < N
+    wrong, exempt, flips = forced_window.ancestors_against_restatement(o["all_log_weights"], o["rec_ud"], anc, 1e-10)
+    print("ancestors restated n2_mem1024", model, kernel, N, stat, "exempt = {0} flips = {1} of {2} draws".format(exempt, flips, T * N))
+    assert wrong == 0 and exempt * 10 ** 4 <= T * N, (wrong, exempt, flips)
+    ref = po.pf_window(model, q["theta"], q["y"], N, z0, None, z, kernel=kernel, pf="poyiadjis_N2", stat=stat, t1=t1, tL=tL,
+                       weights=q["weights"], prior_mean=q["prior_mean"], prior_var=q["prior_var"], save_all=True,
+                       resampler=lambda t, logw: anc[t])
+    r, a = 1e-8, 1e-8
+    np.testing.assert_allclose(o["all_x_t"], ref["all_x_t"], rtol=r, atol=a)
+    np.testing.assert_allclose(o["all_log_weights"], ref["all_log_weights"], rtol=r, atol=a)
+    np.testing.assert_allclose(o["all_loglikelihood_estimate"], ref["all_loglikelihood_estimate"], rtol=r, atol=a)
+    assert o["all_statistics"].shape == ref["all_statistics"].shape
+    np.testing.assert_allclose(o["all_statistics"], ref["all_statistics"], rtol=r, atol=1e-7)
+    np.testing.assert_allclose(o["statistics"], ref["statistics"], rtol=r, atol=1e-7)
+    np.testing.assert_allclose(o["mean_stat"], ref["mean_statistic"], rtol=r, atol=1e-7)
+    np.testing.assert_allclose(o["loglik"], ref["loglikelihood_estimate"], rtol=r, atol=a)
+    assert np.all(o["all_statistics"][:t1 + 1] == 0.0) and np.all(np.any(o["all_statistics"][t1 + 1:] != 0.0, axis=(1, 2)))
+    if N <= 2049:
+        score, steps = forced_window.ancestor_law_score(o["all_log_weights"], anc)
+        print("ancestor law n2_mem1024", model, kernel, N, stat, score, steps)
+        assert steps == T - 1 and score < 5.0, (score, steps)
+
+
 @pytest.mark.parametrize("stat", ["score", "suff"])
 def test_large_n_device_kernel_teacher_forced(ctx, monkeypatch, stat):
-    """n2_mem1024, SVM prior, N = 1100, T = 3, window [1, 2) with a weight: the unit records no normals, so the PROPOSAL
-    ITSELF IS NOT CHECKED here (x_{t+1} is taken from the trace).  Everything downstream of it is: from the traced
+    """n2_mem1024, SVM prior, N = 1100, T = 3, window [1, 2) with a weight, teacher-forced: x_{t+1} and the ancestors are
+    taken from the trace here (test_large_n_device_kernel_replayed_by_oracle checks the proposal on the recorded normals
+    and derives the ancestors).  Everything downstream of the proposal is recomputed: from the traced
     particles, log-weights, statistics and ancestors of step t, forced_window.forced_steps recomputes the log-weights of
     step t + 1 (po.kernel_reweight) and the O(N^2) statistic recursion in float64 NumPy -- log-weights at rtol 1e-8,
     statistics at rtol 1e-8 / atol 1e-7 --, the running log-likelihood and the weighted mean follow from the traced
