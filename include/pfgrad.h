@@ -779,6 +779,26 @@ typedef struct pfg_sqmc_problem {
 int pfg_sqmc_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_sqmc_problem *problems, uint64_t seed,
                     uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced);
 
+/* EXTENSION (not in the reference): the two sorted filters with a score beside out[4] -- the drift of particle MALA on
+ * correlated or quasi-Monte Carlo chains (Nemeth, Sherlock and Fearnhead 2016, on the filters above).  The same kernels,
+ * instantiated with the score statistic: the same descriptors, keys, draws, sort, resampling, U' (pfg_cpm_score_device) and
+ * trace arrays, and out[4] is bit for bit what pfg_cpm_device / pfg_sqmc_device write for the same arguments.  Every particle
+ * carries alpha [H] (H = 3 SVM: [LRinv, LQinv, A]; 4 LGSSM: [LRinv, LQinv, C, A]) through the sort and the gather:
+ *   t = 0    alpha_i = add(x_{-1}^i -> x_0^i, y_0), the complete-data score increment of the move from x_{-1} (under
+ *            pfg_sqmc_score_device the parent at sorted position k)
+ *   t >= 1   alpha_r = lambduh alpha_parent(r) + (1 - lambduh) S_{t-1} + add(x_parent -> x_r, y_t), S_{t-1} = sum_i w_i alpha_i /
+ *            sum_i w_i under the weights the CDF of step t is built from.  lambduh == 1 is Poyiadjis' O(N) recursion and does
+ *            not read S; lambduh < 1 is the fixed-lag shrinkage of Nemeth, Sherlock and Fearnhead.
+ *   out      out[h] = S_{T-1}[h] for h < H, 0 for H <= h < 4 and for slots 5 .. 7; a degenerate chain: out[4] = -inf and every
+ *            other slot 0; a refused descriptor: a NaN record and no other store, as above.
+ * Shapes as above; the 256 x 4 units keep H * 1024 more doubles in LDS (alpha by particle).  Errors as pfg_cpm_device /
+ * pfg_sqmc_device, and PFG_ERR_INVALID for lambduh outside (0, 1]. */
+int pfg_cpm_score_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_cpm_problem *problems, double rho,
+                         double lambduh, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream,
+                         int traced);
+int pfg_sqmc_score_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_sqmc_problem *problems, double lambduh,
+                          uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced);
+
 /* EXTENSION (not in the reference): density-tempered SMC over B resident PMMH chains (Del Moral, Doucet and Jasra 2006; Duan
  * and Fulop 2015).  The chains are one interacting population that is carried from a Gaussian q0 -- the product over the
  * slots a PMMH proposal moves of N(q0_mean[j], q0_sd[j]^2), two DEVICE arrays of PFG_MAX_THETA doubles -- to the posterior

@@ -1,7 +1,8 @@
 // What the kernels that run one chain per lane or per workgroup share: the chain key of every draw (pfg_chains.hip,
 // pfg_csmc.hip, pfg_cpm.hip, pfg_sqmc.hip) and, for the filters with one workgroup per chain, f64, N <= 1024 (pfg_csmc.hip,
 // pfg_cpm.hip, pfg_sqmc.hip), the device pieces -- emission_logw, cdf_search, the descriptor check, the workgroup maximum and
-// CDF offsets, the sort by state of the two filters that resample in the order of the states -- and the host
+// CDF offsets, the sort by state of the two filters that resample in the order of the states and the way their score
+// instantiations carry a particle's additive statistic through that sort (stat_publish, stat_at, stat_advance) -- and the host
 // pieces: the entry point's argument check, the (model, traced, n_max) -> instantiation dispatch and the sizing helpers.
 // Each file keeps its tags, its LDS, its phase structure and what it does with a descriptor it refuses.
 #pragma once
@@ -169,6 +170,40 @@ __device__ __forceinline__ void sort_by_state(int N, int npad, const double *x, 
             }
         }
     }
+}
+
+// ---- the additive statistic of the two sorted filters (STAT = PFG_STAT_SCORE: Poyiadjis' O(N) recursion, with the fixed-lag
+// shrinkage of Nemeth, Sherlock and Fearnhead 2016 for lambduh < 1)
+// Every particle carries alpha [H] in registers beside (x, lw).  The sort moves (state, index) pairs only, so alpha goes to LDS
+// BY PARTICLE, sa[h * NMAX + i], in the phase that stores the keys (the barrier that orders those stores orders these), and
+// whoever needs the alpha at a sorted position reads it through si: the weighted sums S ride on block_cdf's K = 1 + H values,
+// a child gathers its parent's.  Both filters keep sa until the barrier that frees sx and the CDF.
+template <int NMAX, int PPT, int H>
+__device__ __forceinline__ void stat_publish(int N, const double (&alpha)[PPT][H], double *sa) {
+    const int i0 = threadIdx.x * PPT;
+#pragma unroll
+    for (int k = 0; k < PPT; ++k)
+        if (i0 + k < N) {
+#pragma unroll
+            for (int h = 0; h < H; ++h) sa[h * NMAX + i0 + k] = alpha[k][h];
+        }
+}
+// a [H] = the alpha of the particle at sorted position p < N.  An entry that names no particle has none, 0: a padding entry of
+// the bitonic network, or a slot the rank sort never wrote -- NaN states can leave either at p < N, and the chain is then
+// degenerate whatever is read here; the unsigned compare keeps the read inside sa all the same
+template <int NMAX, int H>
+__device__ __forceinline__ void stat_at(const double *sa, const int *si, int N, int p, double *a) {
+    const unsigned i = (unsigned)si[p];
+#pragma unroll
+    for (int h = 0; h < H; ++h) a[h] = i < (unsigned)N ? sa[h * NMAX + i] : 0.0;
+}
+// alpha_child = lambduh alpha_parent + (1 - lambduh) S + add; lambduh == 1 is the plain recursion and does not read S
+template <int H>
+__device__ __forceinline__ void stat_advance(double lambduh, const double *parent, const double *S, const double *add,
+                                             double *alpha) {
+#pragma unroll
+    for (int h = 0; h < H; ++h)
+        alpha[h] = lambduh == 1.0 ? parent[h] + add[h] : (lambduh * parent[h] + (1.0 - lambduh) * S[h]) + add[h];
 }
 
 }  // namespace pfg

@@ -30,6 +30,15 @@
 //                       systematic resampling on one uniform.  The smallest j with cdf[j] > target, clamped to N-1.
 //              move     child r gathers the state at sorted position j and takes particle_step with U'[t+1][r].
 //   out      out[4] = sum_t log((1 / N) sum_i w_t^i) with the Gaussian constants log g carries; every other slot 0.
+//   STAT     PFG_STAT_NONE: the above, what pfg_cpm_device launches.  PFG_STAT_SCORE (pfg_cpm_score_device: the drift of particle
+//            MALA on this filter) carries Poyiadjis' O(N) additive statistic through the sort and the gather: alpha [H] per
+//            particle in registers beside (x, lw), alpha = add(x_{-1} -> x_0, y_0) at t = 0 and, for the child r of the parent at
+//            sorted position j, alpha_r = lambduh alpha_j + (1 - lambduh) S + add(x_j -> x_r, y_t), S = sum_i w_i alpha_i / sum_i w_i
+//            under the weights of the CDF (lambduh == 1 does not read S: the plain recursion; lambduh < 1: the fixed-lag
+//            shrinkage of Nemeth, Sherlock and Fearnhead 2016).  alpha goes to LDS by particle with the keys (sa; pfg::stat_publish)
+//            and is read through si (pfg::stat_at); the sums of w alpha are block_cdf's values 1 .. H, so they cost no barrier.
+//            out[h] = S of the last step for h < H, 0 above and for a degenerate chain.  The weight arithmetic is the same
+//            instructions in the same order: out[4], U' and the trace arrays are bitwise STAT_NONE's.
 //   degenerate  a weight sum that is zero or not finite: out[4] = -inf, which pmmh_accept_kernel rejects; the rest of U' is
 //            still written (a finite array: NaN never enters U).  Every thread holds the same sum: the branch is uniform.
 //   refused  a NULL array, T < 1, N outside [2, the launch's shape], a prior variance that is not positive: a NaN record and
@@ -45,17 +54,20 @@ namespace {
 
 constexpr uint32_t kTagCpm = 0x43500000u;      // | column >> 2
 
-template <int MODEL, int NT, int PPT, bool TRACED>
-__global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restrict__ probs, double rho, uint64_t seed,
-                                                 uint64_t chain_offset, const uint64_t *__restrict__ step_ctr) {
+template <int MODEL, int NT, int PPT, bool TRACED, int STAT>
+__global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restrict__ probs, double rho, double lambduh,
+                                                 uint64_t seed, uint64_t chain_offset, const uint64_t *__restrict__ step_ctr) {
     static_assert(PPT == 2 || PPT == 4, "a thread's columns lie in one Philox draw");
-    constexpr int NMAX = NT * PPT, NW = NT / pfg::WAVE;
-    constexpr bool ONE_WAVE = NW == 1;
+    static_assert(STAT == PFG_STAT_NONE || STAT == PFG_STAT_SCORE, "out[4] alone, or the score beside it");
+    constexpr int NMAX = NT * PPT, NW = NT / pfg::WAVE, H = pfg::ModelDims<MODEL>::H;
+    constexpr bool ONE_WAVE = NW == 1, SCORE = STAT == PFG_STAT_SCORE;
+    constexpr int K = SCORE ? 1 + H : 1;        // what block_cdf sums: the weights, and the weighted alpha columns
     // sorted states; log-weights (by particle under the bitonic sort, by sorted position under the rank sort); the CDF in
     // sorted order; sorted position -> particle
     __shared__ double sx[NMAX], slw[NMAX], cdf[NMAX];
     __shared__ int si[NMAX];
-    __shared__ double red_max[1][NW], red_sum[1][NW], u_sh;
+    __shared__ double red_max[1][NW], red_sum[K][NW], u_sh;
+    __shared__ double sa[SCORE ? H * NMAX : 1];         // alpha by particle (pfg::stat_publish)
 
     const pfg_cpm_problem &P = probs[blockIdx.x];
     const int tid = threadIdx.x;
@@ -124,6 +136,9 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
 
     // ---- t = 0
     double x[PPT], lw[PPT], z[PPT];
+    double alpha[PPT][H], S[H];             // SCORE: the particles' statistics; the weighted mean of the step before
+#pragma unroll
+    for (int h = 0; h < H; ++h) S[h] = 0.0;
     {
         double zm1[PPT];
 #pragma unroll
@@ -134,10 +149,11 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             x[k] = 0.0; lw[k] = -INFINITY;
+#pragma unroll
+            for (int h = 0; h < H; ++h) alpha[k][h] = 0.0;
             if (i0 + k >= N) continue;
-            double add[pfg::ModelDims<MODEL>::H];
             const double xm1 = prior_mean + sd0 * zm1[k];
-            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, PFG_STAT_NONE>(c, mth, &xm1, y0, z[k], &x[k], lw[k], add);
+            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, STAT>(c, mth, &xm1, y0, z[k], &x[k], lw[k], alpha[k]);
         }
     }
 
@@ -172,6 +188,7 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
                 sx[i] = INFINITY; slw[i] = -INFINITY; si[i] = i;
             }
         }
+        if (SCORE && t < T) pfg::stat_publish<NMAX, PPT, H>(N, alpha, sa);
         pfg::block_max(red_max, &ma);
         if (ONE_WAVE) pfg::block_sync<NW>();      // the keys' stores before the sort's reads (256 x 4: block_max's barrier)
         // (S) the sort: the last step's weights need no order (their sum does not depend on it).  -DPFG_CPM_NO_SORT: a
@@ -188,7 +205,11 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
         }
 #endif
         // (B) the CDF in sorted order: a thread's running sums, one scan of the threads' totals
-        double cs[PPT], run = 0.0;
+        // SCORE: the sums of w alpha beside it, in the same order; lambduh == 1 reads them after the last step only
+        const bool want_S = SCORE && (t == T || lambduh != 1.0);
+        double cs[PPT], run[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) run[q] = 0.0;
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const int p = i0 + k;
@@ -200,17 +221,28 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
                     else { const int i = si[p]; l = i < N ? slw[i] : -INFINITY; }
                 }
                 w = mth.exp(l - ma);
+                if (want_S) {
+                    double a[H];
+                    if (t < T) pfg::stat_at<NMAX, H>(sa, si, N, p, a);
+#pragma unroll
+                    for (int h = 0; h < H; ++h) run[SCORE ? 1 + h : 0] += w * (t < T ? a[h] : alpha[k][h]);
+                }
             }
-            run += w;
-            cs[k] = run;
+            run[0] += w;
+            cs[k] = run[0];
         }
-        double off, W;
-        pfg::block_cdf(red_sum, &run, &off, &W);
+        double offs[K], tot[K];
+        pfg::block_cdf(red_sum, run, offs, tot, want_S);
+        const double off = offs[0], W = tot[0];
         // every thread holds the same W: the branch is uniform over the workgroup
         if (!(W > 0.0 && W < INFINITY)) { degenerate = true; break; }
         const double incr = (ma + ::log(W)) - logN;
         ll += incr;
         if (TRACED && P.trace_ll && tid == 0) P.trace_ll[t - 1] = incr;
+        if (want_S) {
+#pragma unroll
+            for (int h = 0; h < H; ++h) S[h] = tot[SCORE ? 1 + h : 0] / W;
+        }
         if (t == T) break;
 #pragma unroll
         for (int k = 0; k < PPT; ++k)
@@ -234,8 +266,10 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
                 if (j < N - 1 && !(cdf[j] > target)) j = pfg::cdf_search(cdf, N, target, j + 1);
             }
             const double xp = sx[j];
-            double add[pfg::ModelDims<MODEL>::H];
-            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, PFG_STAT_NONE>(c, mth, &xp, yt, z[k], &x[k], lw[k], add);
+            double add[H], ap[H];
+            if (SCORE) pfg::stat_at<NMAX, H>(sa, si, N, j, ap);
+            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, STAT>(c, mth, &xp, yt, z[k], &x[k], lw[k], add);
+            if (SCORE) pfg::stat_advance<H>(lambduh, ap, S, add, alpha[k]);
             if (TRACED && P.trace_anc) P.trace_anc[(size_t)t * N + r] = j;
         }
         pfg::block_sync<NW>();       // the sorted states and the CDF are free for the next step
@@ -243,7 +277,13 @@ __global__ __launch_bounds__(NT) void cpm_kernel(const pfg_cpm_problem *__restri
     // a degenerate chain: the rows of U' the loop did not reach (row t + 1 is written when step t begins)
     if (degenerate)
         for (int row = t + 2; row <= T; ++row) propose_row(row, z);
-    if (tid < PFG_OUT_DOUBLES) P.out[tid] = tid == 4 ? (degenerate ? -INFINITY : ll) : 0.0;
+    // out[h] = S_{T-1}[h], the weighted mean of the last step's statistics (a degenerate chain: 0)
+    double mine = 0.0;
+    if (SCORE && !degenerate) {
+#pragma unroll
+        for (int h = 0; h < H; ++h) mine = tid == h ? S[h] : mine;
+    }
+    if (tid < PFG_OUT_DOUBLES) P.out[tid] = tid == 4 ? (degenerate ? -INFINITY : ll) : mine;
 }
 
 // One lane per chain, after the accept step: a chain whose acceptance count moved (or every chain: init) now reads the
@@ -262,21 +302,41 @@ int64_t pfg_cpm_aux_bytes(int T, int N) {
     return round_up_256(((int64_t)T + 1) * ((int64_t)N + 1) * 8);          // U [T+1][N+1] f64
 }
 
-int pfg_cpm_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_cpm_problem *problems, double rho,
-                   uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
-    const int rc = check_chain_filter_launch(ctx, __func__, "the correlated filter is built for SVM and LGSSM (the sort orders a "
+namespace {
+
+// the two entry points: the checks, then the STAT instantiation of (model, traced, n_max)
+template <int STAT>
+int launch_cpm(pfg_ctx *ctx, const char *func, int model, int dtype, int n_max, int B, const pfg_cpm_problem *problems, double rho,
+               double lambduh, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
+    const int rc = check_chain_filter_launch(ctx, func, "the correlated filter is built for SVM and LGSSM (the sort orders a "
                                              "scalar state)", model, dtype, n_max, B, problems);
     if (rc != PFG_OK) return rc;
-    if (!(rho >= 0.0 && rho < 1.0)) return fail(ctx, PFG_ERR_INVALID, std::string(__func__) + ": rho must lie in [0, 1)");
+    if (!(rho >= 0.0 && rho < 1.0)) return fail(ctx, PFG_ERR_INVALID, std::string(func) + ": rho must lie in [0, 1)");
+    if (!(lambduh > 0.0 && lambduh <= 1.0)) return fail(ctx, PFG_ERR_INVALID, std::string(func) + ": lambduh must lie in (0, 1]");
     if (B == 0) return PFG_OK;
     PFG_HIP(ctx, hipSetDevice(ctx->device));
     dispatch_chain_filter(model, traced != 0, n_max, [&](auto m, auto nt, auto ppt, auto tr) {
-        hipLaunchKernelGGL((cpm_kernel<decltype(m)::value, decltype(nt)::value, decltype(ppt)::value, decltype(tr)::value>),
-                           dim3((unsigned)B), dim3(decltype(nt)::value), 0, (hipStream_t)hip_stream, problems, rho, seed,
+        hipLaunchKernelGGL((cpm_kernel<decltype(m)::value, decltype(nt)::value, decltype(ppt)::value, decltype(tr)::value, STAT>),
+                           dim3((unsigned)B), dim3(decltype(nt)::value), 0, (hipStream_t)hip_stream, problems, rho, lambduh, seed,
                            chain_offset, step_ctr);
     });
     PFG_HIP(ctx, hipGetLastError());
     return PFG_OK;
+}
+
+}  // namespace
+
+int pfg_cpm_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_cpm_problem *problems, double rho,
+                   uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
+    return launch_cpm<PFG_STAT_NONE>(ctx, __func__, model, dtype, n_max, B, problems, rho, 1.0, seed, chain_offset, step_ctr,
+                                     hip_stream, traced);
+}
+
+int pfg_cpm_score_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_cpm_problem *problems, double rho,
+                         double lambduh, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream,
+                         int traced) {
+    return launch_cpm<PFG_STAT_SCORE>(ctx, __func__, model, dtype, n_max, B, problems, rho, lambduh, seed, chain_offset, step_ctr,
+                                      hip_stream, traced);
 }
 
 int pfg_cpm_commit_device(pfg_ctx *ctx, int B, const uint64_t *n_accept, uint64_t *seen, int32_t *which, int init,

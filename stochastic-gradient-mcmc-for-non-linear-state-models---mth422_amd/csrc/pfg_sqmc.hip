@@ -25,6 +25,11 @@
 //            with u_(k) W for the smallest j with cdf[j] > target, clamped to N-1; it gathers the sorted state at j and moves
 //            with z of row t+1's point i(k).  No resampling after the last weight.
 //   out      out[4] = sum_t log((1 / N) sum_i w_t^i) with the Gaussian constants log g carries; every other slot 0.
+//   STAT     PFG_STAT_NONE: the above, what pfg_sqmc_device launches.  PFG_STAT_SCORE (pfg_sqmc_score_device) carries the O(N)
+//            additive statistic through the sort and the gather exactly as pfg_cpm.hip does (see there; the pieces are
+//            pfg::stat_publish, stat_at and stat_advance of pfg_chain_filter.hpp): at t = 0 the parent of the child at position k
+//            is the x_{-1} at sorted position k.  out[h] = the weighted mean of the last step's alpha for h < H; out[4] and the
+//            trace arrays are bitwise STAT_NONE's.
 //   degenerate  a weight sum that is zero or not finite: out[4] = -inf, which pmmh_accept_kernel rejects.  Every thread holds
 //            the same sum: the branch is uniform.
 //   refused  a NULL array, T < 1, N not a power of two in [2, the launch's shape], a prior variance that is not positive: a
@@ -61,16 +66,19 @@ __device__ __forceinline__ double grid52(uint32_t hi, uint32_t lo) {
 // each with a table of fp64 coefficients) took the kernels to 452 .. 490 VGPRs, one wave per SIMD
 __device__ __attribute__((noinline)) double inverse_normal_cdf(double v) { return ::normcdfinv(v); }
 
-template <int MODEL, int NT, int PPT, bool TRACED>
-__global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__restrict__ probs, uint64_t seed,
+template <int MODEL, int NT, int PPT, bool TRACED, int STAT>
+__global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__restrict__ probs, double lambduh, uint64_t seed,
                                                   uint64_t chain_offset, const uint64_t *__restrict__ step_ctr) {
-    constexpr int NMAX = NT * PPT, NW = NT / pfg::WAVE;
-    constexpr bool ONE_WAVE = NW == 1;
+    static_assert(STAT == PFG_STAT_NONE || STAT == PFG_STAT_SCORE, "out[4] alone, or the score beside it");
+    constexpr int NMAX = NT * PPT, NW = NT / pfg::WAVE, H = pfg::ModelDims<MODEL>::H;
+    constexpr bool ONE_WAVE = NW == 1, SCORE = STAT == PFG_STAT_SCORE;
+    constexpr int K = SCORE ? 1 + H : 1;        // what block_cdf sums: the weights, and the weighted alpha columns
     // sorted states; log-weights (by particle under the bitonic sort, by sorted position under the rank sort); the CDF in
     // sorted order; sorted position -> particle
     __shared__ double sx[NMAX], slw[NMAX], cdf[NMAX];
     __shared__ int si[NMAX];
-    __shared__ double red_max[1][NW], red_sum[1][NW];
+    __shared__ double red_max[1][NW], red_sum[K][NW];
+    __shared__ double sa[SCORE ? H * NMAX : 1];         // alpha by particle (pfg::stat_publish)
 
     const pfg_sqmc_problem &P = probs[blockIdx.x];
     const int tid = threadIdx.x;
@@ -97,8 +105,12 @@ __global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__rest
     auto point_of_rank = [&](const pfg::u32x4 &r, int k) -> uint32_t {
         return __brev((uint32_t)k ^ (r.x >> (32 - m))) >> (32 - m);
     };
-    // the particles (x, lw) into LDS as sort_by_state wants them, then the sort; sx is sorted afterwards
-    auto sort = [&](const double *x, const double *lw) {
+    double alpha[PPT][H], S[H];             // SCORE: the particles' statistics; the weighted mean of the step before
+#pragma unroll
+    for (int h = 0; h < H; ++h) S[h] = 0.0;
+    // the particles (x, lw) into LDS as sort_by_state wants them (SCORE, from t = 1 on: their alpha too), then the sort; sx
+    // is sorted afterwards
+    auto sort = [&](const double *x, const double *lw, bool with_alpha) {
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const int i = i0 + k;
@@ -107,6 +119,7 @@ __global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__rest
                 else { sx[i] = x[k]; slw[i] = lw[k]; si[i] = i; }
             }
         }
+        if (SCORE && with_alpha) pfg::stat_publish<NMAX, PPT, H>(N, alpha, sa);
         pfg::block_sync<NW>();
         pfg::sort_by_state<NT, PPT>(N, N, x, lw, cdf, sx, slw, si);
     };
@@ -124,16 +137,17 @@ __global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__rest
             xm1[k] = prior_mean + sd0 * zm1;
             if (TRACED && P.trace_z) P.trace_z[i0 + k] = zm1;
         }
-        sort(xm1, lw);
+        sort(xm1, lw, false);
         const double y0 = y[0];
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             x[k] = 0.0; lw[k] = -INFINITY; z[k] = 0.0;
+#pragma unroll
+            for (int h = 0; h < H; ++h) alpha[k][h] = 0.0;
             if (i0 + k >= N) continue;
-            double add[pfg::ModelDims<MODEL>::H];
             const double xp = sx[i0 + k];
             z[k] = point_z(r1, point_of_rank(r1, i0 + k));
-            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, PFG_STAT_NONE>(c, mth, &xp, y0, z[k], &x[k], lw[k], add);
+            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, STAT>(c, mth, &xp, y0, z[k], &x[k], lw[k], alpha[k]);
             if (TRACED && P.trace_z) P.trace_z[(size_t)N + i0 + k] = z[k];
             if (TRACED && P.trace_anc) P.trace_anc[i0 + k] = -1;
         }
@@ -166,9 +180,13 @@ __global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__rest
         }
         pfg::block_max(red_max, &ma);
         // (S) the sort: the last step's weights need no order (their sum does not depend on it)
-        if (t < T) sort(x, lw);
+        if (t < T) sort(x, lw, true);
         // (B) the CDF in sorted order: a thread's running sums, one scan of the threads' totals
-        double cs[PPT], run = 0.0;
+        // SCORE: the sums of w alpha beside it, in the same order; lambduh == 1 reads them after the last step only
+        const bool want_S = SCORE && (t == T || lambduh != 1.0);
+        double cs[PPT], run[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) run[q] = 0.0;
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const int p = i0 + k;
@@ -177,17 +195,28 @@ __global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__rest
                 double l = lw[k];           // the last step: particle order
                 if (t < T) l = ONE_WAVE ? slw[p] : slw[si[p]];
                 w = mth.exp(l - ma);
+                if (want_S) {
+                    double a[H];
+                    if (t < T) pfg::stat_at<NMAX, H>(sa, si, N, p, a);
+#pragma unroll
+                    for (int h = 0; h < H; ++h) run[SCORE ? 1 + h : 0] += w * (t < T ? a[h] : alpha[k][h]);
+                }
             }
-            run += w;
-            cs[k] = run;
+            run[0] += w;
+            cs[k] = run[0];
         }
-        double off, W;
-        pfg::block_cdf(red_sum, &run, &off, &W);
+        double offs[K], tot[K];
+        pfg::block_cdf(red_sum, run, offs, tot, want_S);
+        const double off = offs[0], W = tot[0];
         // every thread holds the same W: the branch is uniform over the workgroup
         if (!(W > 0.0 && W < INFINITY)) { degenerate = true; break; }
         const double incr = (ma + ::log(W)) - logN;
         ll += incr;
         if (TRACED && P.trace_ll && tid == 0) P.trace_ll[t - 1] = incr;
+        if (want_S) {
+#pragma unroll
+            for (int h = 0; h < H; ++h) S[h] = tot[SCORE ? 1 + h : 0] / W;
+        }
         if (t == T) break;
 #pragma unroll
         for (int k = 0; k < PPT; ++k)
@@ -211,30 +240,53 @@ __global__ __launch_bounds__(NT) void sqmc_kernel(const pfg_sqmc_problem *__rest
                 if (j < N - 1 && !(cdf[j] > target)) j = pfg::cdf_search(cdf, N, target, j + 1);
             }
             const double xp = sx[j];
-            double add[pfg::ModelDims<MODEL>::H];
-            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, PFG_STAT_NONE>(c, mth, &xp, yt, z[k], &x[k], lw[k], add);
+            double add[H], ap[H];
+            if (SCORE) pfg::stat_at<NMAX, H>(sa, si, N, j, ap);
+            pfg::particle_step<MODEL, PFG_KERNEL_PRIOR, STAT>(c, mth, &xp, yt, z[k], &x[k], lw[k], add);
+            if (SCORE) pfg::stat_advance<H>(lambduh, ap, S, add, alpha[k]);
             if (TRACED && P.trace_anc) P.trace_anc[(size_t)t * N + r] = j;
             if (TRACED && P.trace_z) P.trace_z[(size_t)(t + 1) * N + r] = z[k];
         }
         pfg::block_sync<NW>();       // the sorted states and the CDF are free for the next step
     }
-    if (tid < PFG_OUT_DOUBLES) P.out[tid] = tid == 4 ? (degenerate ? -INFINITY : ll) : 0.0;
+    // out[h] = S_{T-1}[h], the weighted mean of the last step's statistics (a degenerate chain: 0)
+    double mine = 0.0;
+    if (SCORE && !degenerate) {
+#pragma unroll
+        for (int h = 0; h < H; ++h) mine = tid == h ? S[h] : mine;
+    }
+    if (tid < PFG_OUT_DOUBLES) P.out[tid] = tid == 4 ? (degenerate ? -INFINITY : ll) : mine;
+}
+
+// the two entry points: the checks, then the STAT instantiation of (model, traced, n_max)
+template <int STAT>
+int launch_sqmc(pfg_ctx *ctx, const char *func, int model, int dtype, int n_max, int B, const pfg_sqmc_problem *problems,
+                double lambduh, uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
+    const int rc = check_chain_filter_launch(ctx, func, "the SQMC filter is built for SVM and LGSSM (the sort orders a "
+                                             "scalar state)", model, dtype, n_max, B, problems);
+    if (rc != PFG_OK) return rc;
+    if (!(lambduh > 0.0 && lambduh <= 1.0)) return fail(ctx, PFG_ERR_INVALID, std::string(func) + ": lambduh must lie in (0, 1]");
+    if (B == 0) return PFG_OK;
+    PFG_HIP(ctx, hipSetDevice(ctx->device));
+    dispatch_chain_filter(model, traced != 0, n_max, [&](auto m, auto nt, auto ppt, auto tr) {
+        hipLaunchKernelGGL((sqmc_kernel<decltype(m)::value, decltype(nt)::value, decltype(ppt)::value, decltype(tr)::value, STAT>),
+                           dim3((unsigned)B), dim3(decltype(nt)::value), 0, (hipStream_t)hip_stream, problems, lambduh, seed,
+                           chain_offset, step_ctr);
+    });
+    PFG_HIP(ctx, hipGetLastError());
+    return PFG_OK;
 }
 
 }  // namespace
 
 int pfg_sqmc_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_sqmc_problem *problems, uint64_t seed,
                     uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
-    const int rc = check_chain_filter_launch(ctx, __func__, "the SQMC filter is built for SVM and LGSSM (the sort orders a "
-                                             "scalar state)", model, dtype, n_max, B, problems);
-    if (rc != PFG_OK) return rc;
-    if (B == 0) return PFG_OK;
-    PFG_HIP(ctx, hipSetDevice(ctx->device));
-    dispatch_chain_filter(model, traced != 0, n_max, [&](auto m, auto nt, auto ppt, auto tr) {
-        hipLaunchKernelGGL((sqmc_kernel<decltype(m)::value, decltype(nt)::value, decltype(ppt)::value, decltype(tr)::value>),
-                           dim3((unsigned)B), dim3(decltype(nt)::value), 0, (hipStream_t)hip_stream, problems, seed, chain_offset,
-                           step_ctr);
-    });
-    PFG_HIP(ctx, hipGetLastError());
-    return PFG_OK;
+    return launch_sqmc<PFG_STAT_NONE>(ctx, __func__, model, dtype, n_max, B, problems, 1.0, seed, chain_offset, step_ctr, hip_stream,
+                                      traced);
+}
+
+int pfg_sqmc_score_device(pfg_ctx *ctx, int model, int dtype, int n_max, int B, const pfg_sqmc_problem *problems, double lambduh,
+                          uint64_t seed, uint64_t chain_offset, const uint64_t *step_ctr, void *hip_stream, int traced) {
+    return launch_sqmc<PFG_STAT_SCORE>(ctx, __func__, model, dtype, n_max, B, problems, lambduh, seed, chain_offset, step_ctr,
+                                       hip_stream, traced);
 }

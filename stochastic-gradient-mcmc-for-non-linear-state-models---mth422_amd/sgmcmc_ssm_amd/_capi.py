@@ -297,6 +297,8 @@ _ENTRY_POINTS = {
     "pfg_cpm_device": (_status, (_ctx, _model, _dtype, _int, _int, _addr, _f64, _u64, _u64, _addr, _stream, _flag)),
     "pfg_cpm_commit_device": (_status, (_ctx, _int, _addr, _addr, _addr, _flag, _stream)),
     "pfg_sqmc_device": (_status, (_ctx, _model, _dtype, _int, _int, _addr, _u64, _u64, _addr, _stream, _flag)),
+    "pfg_cpm_score_device": (_status, (_ctx, _model, _dtype, _int, _int, _addr, _f64, _f64, _u64, _u64, _addr, _stream, _flag)),
+    "pfg_sqmc_score_device": (_status, (_ctx, _model, _dtype, _int, _int, _addr, _f64, _u64, _u64, _addr, _stream, _flag)),
     "pfg_smc_scratch_bytes": (_i64, (_int,)),
     "pfg_smc_logtarget_device": (_status, (_ctx, _model, _int, _addr, _addr, _hyper, _addr, _addr, _addr, _stream)),
     "pfg_smc_temper_device": (_status, (_ctx, _int, _addr, _addr, _f64, _u64, _u64, _addr, _addr, _addr, _addr, _stream)),
@@ -813,6 +815,21 @@ class Context:
         particles on one randomised Sobol' point set per timestep, out[4] the log-likelihood estimate."""
         self._call("pfg_sqmc_device", model, dtype, n_max, B, problems_ptr, seed, chain_offset, step_ctr_ptr, stream_ptr,
                    traced)
+
+    def cpm_score_device(self, model, dtype, n_max, B, problems_ptr, rho, lambduh, seed, chain_offset=0, step_ctr_ptr=None,
+                         stream_ptr=0, traced=False):
+        """pfg_cpm_score_device: pfg_cpm_device's filter (the same U', the same out[4], bit for bit) with the score beside it:
+        out[0..H-1] the weighted mean of the particles' additive statistics, carried through the sort (lambduh = 1: Poyiadjis'
+        O(N) recursion; lambduh < 1: the fixed-lag shrinkage of Nemeth, Sherlock and Fearnhead)."""
+        self._call("pfg_cpm_score_device", model, dtype, n_max, B, problems_ptr, rho, lambduh, seed, chain_offset, step_ctr_ptr,
+                   stream_ptr, traced)
+
+    def sqmc_score_device(self, model, dtype, n_max, B, problems_ptr, lambduh, seed, chain_offset=0, step_ctr_ptr=None,
+                          stream_ptr=0, traced=False):
+        """pfg_sqmc_score_device: pfg_sqmc_device's filter (the same out[4], bit for bit) with the score beside it, as
+        cpm_score_device."""
+        self._call("pfg_sqmc_score_device", model, dtype, n_max, B, problems_ptr, lambduh, seed, chain_offset, step_ctr_ptr,
+                   stream_ptr, traced)
 
     def logprior_device(self, model, B, theta_ptr, hyper, logprior_ptr, stream_ptr=0):
         """pfg_logprior_device: logprior[b] = Prior.logprior of the raw row theta[b], up to a constant of the hyper-parameters."""

@@ -134,7 +134,18 @@ class ChainEnsemble(object):
                resampling and ess_threshold, N <= 16384, or kind 'marginal' (LGSSM, f64: the Kalman score and likelihood
                are exact, plain MALA); pmmh_stat is refused.  loglik(), score() and acceptance_rate() read the chains'
                estimates and acceptance, last_gradient_statistics() the estimates at the latest proposals; the init
-               pass is PMMH's and refuses a chain whose initial log-likelihood or score is not finite)
+               pass is PMMH's and refuses a chain whose initial log-likelihood or score is not finite) |
+               'pmala_sorted' (extension: 'pmala' on one of the two sorted filters, whose estimate is usable at N = 64 .. 128.
+               It takes exactly one of correlation=rho and sqmc=True (below); the launch is pfg_cpm_score_device or
+               pfg_sqmc_score_device -- the filter of sampler='pmmh' with that option, draw for draw and with the same
+               out[4], carrying Poyiadjis' O(N) score through the sort (pf='poyiadjis_N', the default) or its fixed-lag
+               shrinkage (pf='nemeth', lambduh in (0, 1], default 0.95).  The drift g-hat(theta, U) is a deterministic
+               function of theta and of the filter's draws U, and U -> U' is reversible with respect to their law, so with
+               q(theta' | theta, U) one way and q(theta | theta', U') the other the chain is exact on the extended target
+               for every N, rho and lambduh; no smoothness of the score in U is needed.  State: 'pmala's, and under
+               correlation the correlated chain's buffers and selector; propose, accept, commit, checkpoints and graphs
+               are theirs.  Refusals: the filter family's (SVM | LGSSM, f64, one whole series, kind 'pf', the prior kernel,
+               its own resampling, N <= 1024, a power of two under sqmc), pf = 'paris' | 'poyiadjis_N2', pmmh_stat)
                'pgibbs' (extension: particle Gibbs, Andrieu, Doucet and Holenstein 2010, model 'svm' | 'lgssm', dtype 'f64',
                2 <= N <= 1024, the whole series: a step is one conditional SMC sweep with ancestor sampling (Lindsten,
                Jordan and Schon 2014; pfg_csmc_device) that replaces each chain's latent path [T] -- the path is part of
@@ -326,7 +337,8 @@ class ChainEnsemble(object):
             self.moment_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
         self._cv = sampler == "sgld_cv"                 # every descriptor has a twin at the centre, in the same launch
         self.proposal_scale = s.proposal_scale
-        self._mh = sampler in ("pmmh", "pmala")         # a proposal, a launch on it, an accept step
+        self._mh = sampler in ("pmmh", "pmala", "pmala_sorted")         # a proposal, a launch on it, an accept step
+        self._pmala = sampler in ("pmala", "pmala_sorted")              # ... along a score, accepted on both proposal densities
         if self._mh:
             # the proposal the launch reads, its validity, each chain's current estimate and acceptance count
             self.theta_prop_dev = self.theta_dev.clone()
@@ -334,7 +346,7 @@ class ChainEnsemble(object):
             self.ll_dev = torch.zeros(C, dtype=torch.float64, device=dev)
             self.accept_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
             self.scale_dev = torch.from_numpy(s.proposal_scale).to(dev)
-        if sampler == "pmala":      # the score estimate each chain's current state was accepted with: out[0..3], verbatim
+        if self._pmala:     # the score estimate each chain's current state was accepted with: out[0..3], verbatim
             self.grad_cur_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
         # one weights row per window start of every sequence longer than S.  Single-window lists: every row times
         # T_total / T_sequence, the Seq sampler's rescaling of a one-sequence gradient, whole short sequences a row of it;
@@ -555,12 +567,17 @@ class ChainEnsemble(object):
         elif centre is not None or centre_N is not None or centre_repeats != 1:
             raise ValueError("centre, centre_repeats and centre_N belong to sampler='sgld_cv' (SGLD with control variates), got "
                              "sampler = '{0}'".format(sampler))
-        if correlation is not None:
+        if sampler == "pmala_sorted":
+            ChainEnsemble._refuse_pmala_sorted(pmmh_stat, correlation, sqmc, lambduh, model, observations, N, pf,
+                                               subsequence_length, buffer_length, dtype, resampling, kind, minibatch_size,
+                                               num_sequences, ess_threshold, kernel)
+            correlation = None if sqmc else float(correlation)
+        elif correlation is not None:
             ChainEnsemble._refuse_correlated(sampler, pmmh_stat, correlation, model, observations, N, pf, subsequence_length,
                                              buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
                                              kernel)
             correlation = float(correlation)
-        if sqmc:
+        if sqmc and sampler != "pmala_sorted":
             ChainEnsemble._refuse_sqmc(sampler, pmmh_stat, correlation, model, observations, N, pf, subsequence_length,
                                        buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
                                        kernel)
@@ -570,11 +587,11 @@ class ChainEnsemble(object):
         if ess_threshold is not None and ess_threshold != 0 and (kind != "pf" or sampler == "gibbs"):
             # (what else adaptive resampling is not built for: resolve_resampling, below)
             raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
-        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala", "pgibbs", "sgd", "adagrad", "sgld_cv"):
-            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'sgd', 'adagrad', 'sgld_cv', 'pgibbs', 'pmala', 'gibbs' or "
-                             "'pmmh'")
+        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala", "pmala_sorted", "pgibbs", "sgd", "adagrad", "sgld_cv"):
+            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'sgd', 'adagrad', 'sgld_cv', 'pgibbs', 'pmala_sorted', "
+                             "'pmala', 'gibbs' or 'pmmh'")
         scale = None
-        if sampler not in ("pmmh", "pmala"):
+        if sampler not in ("pmmh", "pmala", "pmala_sorted"):
             if proposal_scale is not None:
                 raise ValueError("proposal_scale is the random walk of sampler='pmmh', got sampler = '{0}'".format(sampler))
             if pmmh_stat is not None:
@@ -740,7 +757,7 @@ class ChainEnsemble(object):
             if N > 16384:
                 raise NotImplementedError("the multi-window path is built for N <= 16384 (one workgroup per window), "
                                           "got N = {0}".format(N))
-        if sampler in ("pmmh", "pmala"):
+        if sampler in ("pmmh", "pmala", "pmala_sorted"):
             # every step needs the likelihood of the whole data set: no window is drawn, nothing is rescaled
             whole = sampler + " needs the whole series in every step: "
             if segments is None and (S != -1 or int(buffer_length) != -1):
@@ -762,6 +779,8 @@ class ChainEnsemble(object):
             s.centre_N = N if centre_N is None else int(centre_N)
         if sqmc:
             s.sqmc = True
+        if sampler == "pmala_sorted":       # which sorted filter carries the score: 'cpm' (correlation) | 'sqmc'
+            s.sorted_score = "sqmc" if sqmc else "cpm"
         return s
 
     @staticmethod
@@ -817,11 +836,11 @@ class ChainEnsemble(object):
 
     @staticmethod
     def _refuse_chain_filter(family, model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind,
-                             minibatch_size, num_sequences, ess_threshold, kernel, also=()):
+                             minibatch_size, num_sequences, ess_threshold, kernel, also=(), score=False):
         """What sampler='pgibbs' and `correlation` are not built for, each refusal naming its reason: either is one kernel
         family with one workgroup per chain -- SVM and LGSSM, f64, the prior proposal, its own resampling at every step, the
         whole series, N <= 1024.  family: a key of _CHAIN_FILTERS.  also: (refused, reason) pairs of the family's own, checked
-        ahead of N."""
+        ahead of N.  score: the family's kernel carries the O(N) score (sampler='pmala_sorted'), so pf may be 'nemeth' as well."""
         f = ChainEnsemble._CHAIN_FILTERS[family]
         what = f["what"]
         if model == "garch":
@@ -840,7 +859,10 @@ class ChainEnsemble(object):
                                       "minibatch_size = {0}, num_sequences = {1}".format(M, K))
         if kind != "pf":
             raise NotImplementedError(what + "is a particle method: kind='pf', got kind = '{0}'".format(kind))
-        if pf != "poyiadjis_N":
+        if score and pf not in ("poyiadjis_N", "nemeth"):
+            raise NotImplementedError(what + "carries the O(N) score through its own {0}: pf = 'poyiadjis_N' | 'nemeth', got pf = "
+                                      "'{1}' (a PaRIS / O(N^2) score on the sorted filters is not built)".format(f["own"], pf))
+        if not score and pf != "poyiadjis_N":
             raise NotImplementedError(what + "runs its own {0}, no smoother: pf stays at its default, got pf = '{1}'".format(
                 f["own"], pf))
         if resampling != "multinomial":
@@ -893,6 +915,45 @@ class ChainEnsemble(object):
         if N & (N - 1):
             raise NotImplementedError(what + "takes the first 2^m points of the Sobol' sequence, a (0, m, 2)-net: N must be a "
                                       "power of two, got N = {0}".format(N))
+
+    @staticmethod
+    def _refuse_pmala_sorted(pmmh_stat, correlation, sqmc, lambduh, *shared):
+        """sampler='pmala_sorted': exactly one of `correlation` and `sqmc`, then the refusals of that filter's family
+        (_refuse_chain_filter, with pf = 'nemeth' admitted: the kernel carries the score), then rho's range or the power of two,
+        then lambduh's range."""
+        what = "sampler='pmala_sorted' (particle MALA along the score of a sorted filter) "
+        if (correlation is not None) == bool(sqmc):
+            raise ValueError(what + "takes exactly one of correlation=rho (the correlated filter) and sqmc=True (the sequential "
+                             "quasi-Monte Carlo filter), got {0}".format("both" if sqmc else "neither"))
+        if pmmh_stat is not None:
+            raise ValueError("pmmh_stat belongs to sampler='pmmh' (sampler='pmala_sorted' needs the score launch), got sampler = "
+                             "'pmala_sorted'")
+        kind = shared[8]
+        if kind in ("marginal", "complete"):
+            raise NotImplementedError(what + "drifts along a particle filter's score: kind='pf', got kind = '{0}' (sampler='pmala' "
+                                      "serves the exact Kalman score)".format(kind))
+        ChainEnsemble._refuse_chain_filter("sqmc" if sqmc else "correlation", *shared, score=True)
+        if sqmc:
+            N = int(shared[2])
+            if N & (N - 1):
+                raise NotImplementedError(ChainEnsemble._CHAIN_FILTERS["sqmc"]["what"] + "takes the first 2^m points of the Sobol' "
+                                          "sequence, a (0, m, 2)-net: N must be a power of two, got N = {0}".format(N))
+        else:
+            try:
+                rho = float(correlation)
+            except (TypeError, ValueError):
+                rho = float("nan")
+            if not 0.0 <= rho < 1.0:        # (false for a NaN as well)
+                raise ValueError("correlation must lie in [0, 1) (rho of U' = rho U + sqrt(1 - rho^2) eps; 0: fresh normals at "
+                                 "every step), got {0}".format(correlation))
+        if shared[3] == "nemeth" and lambduh is not None:
+            try:
+                lam = float(lambduh)
+            except (TypeError, ValueError):
+                lam = float("nan")
+            if not 0.0 < lam <= 1.0:
+                raise ValueError(what + "shrinks the score with lambduh in (0, 1] (1: the plain O(N) recursion), got {0}".format(
+                    lambduh))
 
     @staticmethod
     def _window_counts(observations, minibatch_size, num_sequences):
@@ -1108,8 +1169,8 @@ class ChainEnsemble(object):
 
     def launch_propose(self, stream=None):
         """sampler='pmmh': theta_prop_dev = theta_dev + proposal_scale (.) z, valid_dev (pfg_pmmh_propose_device).
-        sampler='pmala': the Langevin proposal along grad_cur_dev (pfg_pmala_propose_device)."""
-        if self.sampler == "pmala":
+        sampler='pmala' | 'pmala_sorted': the Langevin proposal along grad_cur_dev (pfg_pmala_propose_device)."""
+        if self._pmala:
             return self.ctx.pmala_propose_device(
                 self.model, self.C, self.theta_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
                 self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), self.hyper, *self._update_key(stream))
@@ -1118,15 +1179,17 @@ class ChainEnsemble(object):
 
     def launch_accept(self, stream=None, init=False):
         """sampler='pmmh': accept / reject on out_dev[:, 4] and the log-prior; bumps the counter (pfg_pmmh_accept_device).
-        sampler='pmala': the same with the two proposal densities, on out_dev[:, :5] (pfg_pmala_accept_device)."""
-        if self.sampler == "pmala":
-            return self.ctx.pmala_accept_device(
+        sampler='pmala' | 'pmala_sorted': the same with the two proposal densities, on out_dev[:, :5] (pfg_pmala_accept_device).
+        With correlation set, either ends in the commit."""
+        if self._pmala:
+            self.ctx.pmala_accept_device(
                 self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(), self.valid_dev.data_ptr(),
                 self.out_dev.data_ptr(), self.ll_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.accept_dev.data_ptr(),
                 self.hyper, self.scale_dev.data_ptr(), init, *self._update_key(stream))
-        self.ctx.pmmh_accept_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
-                                    self.valid_dev.data_ptr(), self.out_dev.data_ptr(), self.ll_dev.data_ptr(),
-                                    self.accept_dev.data_ptr(), self.hyper, init, *self._update_key(stream))
+        else:
+            self.ctx.pmmh_accept_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
+                                        self.valid_dev.data_ptr(), self.out_dev.data_ptr(), self.ll_dev.data_ptr(),
+                                        self.accept_dev.data_ptr(), self.hyper, init, *self._update_key(stream))
         if self.correlation is not None:    # a chain that accepted (init: every chain) now reads the buffer the filter wrote
             self.ctx.cpm_commit_device(self.C, self.accept_dev.data_ptr(), self.seen_dev.data_ptr(), self.which_dev.data_ptr(),
                                        init, self._stream(stream))
@@ -1147,7 +1210,7 @@ class ChainEnsemble(object):
         self.step_ctr.fill_(1)
         self.synchronize()
         finite, what = np.isfinite(self.ll_dev.cpu().numpy()), "log-likelihood"
-        if self.sampler == "pmala":     # ... and the score columns the drift reads
+        if self._pmala:     # ... and the score columns the drift reads
             used = self.grad_cur_dev.cpu().numpy()[:, list(_PMALA_SCORE_COLUMNS[self.model])]
             finite, what = finite & np.all(np.isfinite(used), axis=1), "log-likelihood or score"
         bad = np.flatnonzero(~finite)
@@ -1157,16 +1220,24 @@ class ChainEnsemble(object):
 
     def launch_cpm(self, stream=None, traced=False, init=False):
         """sampler='pmmh' with correlation: one sorted, correlated filter per chain on theta_prop_dev (pfg_cpm_device): U' = rho U +
-        sqrt(1 - rho^2) eps goes to the chain's other buffer, the estimate on U' to out_dev[:, 4].  init: rho = 0."""
-        self.ctx.cpm_device(self.model, self.dtype, self.N, self.C, self.cpm_desc_dev.data_ptr(),
-                            0.0 if init else self.correlation, self.seed ^ 0x43504D4D, self.chain_offset,
-                            self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
+        sqrt(1 - rho^2) eps goes to the chain's other buffer, the estimate on U' to out_dev[:, 4].  init: rho = 0.
+        sampler='pmala_sorted': the same filter with the score beside it, out_dev[:, :H] (pfg_cpm_score_device, lambduh)."""
+        rho, key = 0.0 if init else self.correlation, (self.seed ^ 0x43504D4D, self.chain_offset, self.step_ctr.data_ptr(),
+                                                       self._stream(stream))
+        if self.sampler == "pmala_sorted":
+            return self.ctx.cpm_score_device(self.model, self.dtype, self.N, self.C, self.cpm_desc_dev.data_ptr(), rho,
+                                             self.lambduh, *key, traced=traced)
+        self.ctx.cpm_device(self.model, self.dtype, self.N, self.C, self.cpm_desc_dev.data_ptr(), rho, *key, traced=traced)
 
     def launch_sqmc(self, stream=None, traced=False):
         """sampler='pmmh' with sqmc: one sequential quasi-Monte Carlo filter per chain on theta_prop_dev (pfg_sqmc_device), the
-        estimate to out_dev[:, 4].  The init pass is the same launch at counter 0."""
-        self.ctx.sqmc_device(self.model, self.dtype, self.N, self.C, self.sqmc_desc_dev.data_ptr(), self.seed ^ 0x53514D43,
-                             self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
+        estimate to out_dev[:, 4].  The init pass is the same launch at counter 0.
+        sampler='pmala_sorted': the same filter with the score beside it, out_dev[:, :H] (pfg_sqmc_score_device, lambduh)."""
+        key = (self.seed ^ 0x53514D43, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
+        if self.sampler == "pmala_sorted":
+            return self.ctx.sqmc_score_device(self.model, self.dtype, self.N, self.C, self.sqmc_desc_dev.data_ptr(), self.lambduh,
+                                              *key, traced=traced)
+        self.ctx.sqmc_device(self.model, self.dtype, self.N, self.C, self.sqmc_desc_dev.data_ptr(), *key, traced=traced)
 
     def _sqmc_alloc(self, prior_mean, prior_var):
         """The pfg_sqmc_problem records (static: the step replays in hipGraphs).  An SQMC chain carries nothing beyond PMMH's
@@ -1226,7 +1297,7 @@ class ChainEnsemble(object):
         """sampler='pmmh' with correlation: [C, T+1, N+1] the normals each chain holds, those its estimate loglik() was
         computed from."""
         if self.correlation is None:
-            raise ValueError("aux() belongs to sampler='pmmh' with correlation set")
+            raise ValueError("aux() belongs to sampler='pmmh' with correlation set (and sampler='pmala_sorted' with it)")
         rows = torch.arange(self.C, device=self.device)
         cur = self._aux_view()[self.which_dev.long() & 1, rows]
         return cur[:, :(self.T + 1) * (self.N + 1)].reshape(self.C, self.T + 1, self.N + 1).cpu().numpy()
@@ -1385,6 +1456,8 @@ class ChainEnsemble(object):
                      model=self.model, N=self.N, C=self.C, ess_threshold=self.ess_threshold)
         if self.sampler == "pgibbs":    # (the only checkpoints that name their sampler and T: load_state_dict)
             state.update(sampler="pgibbs", T=self.T)
+        if self.sampler == "pmala_sorted":      # (named, so that no other sampler takes its checkpoint; the smoother's lambduh)
+            state.update(sampler="pmala_sorted", lambduh=self.lambduh)
         state.update((key, t.cpu().numpy()) for key, t in self._chain_state()[0])
         if self.correlation is not None:    # the current buffer only (the other one is a step's scratch), and what it belongs to
             state.update(aux=self.aux(), correlation=self.correlation, T=self.T)
@@ -1401,7 +1474,7 @@ class ChainEnsemble(object):
         follow it.  scratch: what a step overwrites besides; _graph restores both after its eager step."""
         carried, scratch = [], [self.desc_dev]
         if self._mh:
-            grad = [("grad", self.grad_cur_dev)] if self.sampler == "pmala" else []
+            grad = [("grad", self.grad_cur_dev)] if self._pmala else []
             carried = [("ll", self.ll_dev)] + grad + [("n_accept", self.accept_dev)]
             scratch += [self.theta_prop_dev, self.valid_dev]
         if self.correlation is not None:
@@ -1420,7 +1493,8 @@ class ChainEnsemble(object):
     def load_state_dict(self, state):
         # only 'pgibbs' checkpoints name their sampler and T: a 'pgibbs' ensemble wants both, and no other sampler takes one
         # (it would drop the path silently)
-        keys = ("sampler", "T") if self.sampler == "pgibbs" else ("sampler",) if state.get("sampler", None) is not None else ()
+        keys = ("sampler", "T") if self.sampler == "pgibbs" else ("sampler", "lambduh") if self.sampler == "pmala_sorted" else \
+            ("sampler",) if state.get("sampler", None) is not None else ()
         for key in keys:
             if state.get(key, None) != getattr(self, key):
                 raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(
@@ -1510,7 +1584,7 @@ class ChainEnsemble(object):
     def score(self):
         """sampler='pmala': [C, h] score estimates the chains hold (score-column order, as last_gradient_statistics), each
         the one its current state was accepted with and its next proposal drifts along."""
-        if self.sampler != "pmala":
+        if not self._pmala:
             raise ValueError("score() belongs to sampler='pmala', this ensemble runs '{0}'".format(self.sampler))
         return self.grad_cur_dev[:, :_capi.STAT_DIM[self.model]].cpu().numpy()
 

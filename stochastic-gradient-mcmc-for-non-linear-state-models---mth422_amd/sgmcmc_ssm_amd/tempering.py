@@ -154,6 +154,10 @@ class TemperedPopulation(object):
         """The wrapper's own arguments -> a namespace (q0_mean, q0_sd [MAX_THETA], theta0 [C, P] the initial population,
         scale0 [MAX_THETA], ess_target, moves, scale_factor), or the refusal.  Needs no device."""
         what = "TemperedPopulation (density-tempered SMC over resident PMMH chains) "
+        if ensemble_kwargs.get("sampler", "pmmh") == "pmala_sorted":
+            raise NotImplementedError(what + "moves the population by PMMH steps; tempering the Langevin proposal of "
+                                      "sampler='pmala_sorted' (its score, and under correlation its normals, would have to be "
+                                      "gathered and tempered too) is not built: sampler stays 'pmmh'")
         if ensemble_kwargs.get("correlation", None) is not None:
             raise NotImplementedError(what + "resamples theta and the estimate across chains; with correlation the chains' "
                                       "normals would have to be gathered too, and that is not built: correlation stays None")
