@@ -17,15 +17,11 @@ Per-step semantics follow `SGMCMCSampler.sample_sgld` + `project_parameters`
 the device Philox generator, so trajectories are statistically, not bitwise, equivalent to
 the reference (bitwise parity is what the REPLAY mode of the Sampler classes is for).
 """
-import ctypes
-import types
-
 import numpy as np
 import torch
 
 from . import _capi
-from .particle_filters import resolve_resampling
-from .sgmcmc_sampler import random_subsequence_and_weights
+from .ensemble_settings import ACCESSORS, FILTERS, SAMPLERS, filter_family, resolve_settings, window_counts
 
 _MODELS = {}
 # the score columns pMALA's drift reads (LGSSM: not C's, column 2: C stays 1)
@@ -239,12 +235,25 @@ class ChainEnsemble(object):
                with W > 1, window_sampling='host' when windows are drawn, N > 16384.
 
     How it is put together (each decision is made in one place):
-      _resolve_settings: the arguments above -> kind, pf, N, lambduh, the descriptor smoother `_smoother` and the launch
-               smoother `_launch_smoother`, the stat, the PaRIS fields, M / K / W, the path (`_multi`: W descriptors per
-               chain, records in win_out_dev, a reduction before the update), S, B, `strict`, the sequence bounds, and
-               every refusal that needs no device.  Nothing is allocated before it returns.  pf='poyiadjis_N2' is
-               resolved there to the descriptor and launch smoother 'poyiadjis_n2' (lambduh = 1, the score); from then on
-               it takes the paths of the other smoothers unchanged.
+      ensemble_settings.SAMPLERS: one record per sampler -- the update rule launch_update runs, the propose / accept pair of
+               a step that has one (PMMH's or pMALA's) and whether the proposal drifts along the filter's score, whether every
+               descriptor has a twin ('sgld_cv'), what a chain carries beyond theta, the momentum and the counter as ordered
+               (checkpoint key, attribute) pairs, the keys that name the sampler in a checkpoint, what
+               last_gradient_statistics returns, the accessors that are its own, and the methods that allocate for it
+               (_mh_alloc, _adagrad_alloc) and run its init pass (_mh_init, _pgibbs_init, _cv_init).
+      ensemble_settings.FILTERS: one record per family of filter launch -- 'descriptors' (the pfg_dev_problem records of
+               `_desc` / desc_dev: launch_descriptors), 'csmc' (launch_csmc on csmc_desc_dev), 'cpm' (launch_cpm on
+               cpm_desc_dev) and 'sqmc' (launch_sqmc on sqmc_desc_dev): the library call and its score twin, the record
+               dtype, the salt of its key (seed ^ salt), the method that allocates what it carries and its static records
+               (_csmc_alloc, _cpm_alloc, _sqmc_alloc), what it carries and what it writes into a checkpoint, and the wording
+               of its refusals.  The constructor resolves (sampler, correlation, sqmc) to one family once (filter_family);
+               `_rule` and `_family` are the two records, and no other line asks which sampler this is.
+      _resolve_settings (ensemble_settings.resolve_settings): the arguments above -> kind, pf, N, lambduh, the descriptor
+               smoother `_smoother` and the launch smoother `_launch_smoother`, the stat, the PaRIS fields, M / K / W, the
+               path (`_multi`: W descriptors per chain, records in win_out_dev, a reduction before the update), S, B,
+               `strict`, the sequence bounds, and every refusal that needs no device.  Nothing is allocated before it returns.
+               pf='poyiadjis_N2' is resolved there to the descriptor and launch smoother 'poyiadjis_n2' (lambduh = 1, the
+               score); from then on it takes the paths of the other smoothers unchanged.
       _capi.device_descriptors: the static fields of the `_nd` = C (single-window) or C * W (multi-window, chain-major)
                records of `_desc`; stream ids chain_offset + c, or (chain_offset + c) * W + w.
       _weights_blocks: weights_dev, one row per window start of every sequence longer than S, with the offsets of the
@@ -254,22 +263,21 @@ class ChainEnsemble(object):
                y, T, t1, tL, weights from it -- a single series is a list of one sequence; a full single series has a
                null weights pointer, a whole short sequence of a list points at its row of T_total / T_k.
       _scratch_bytes: the scratch per descriptor of the resolved smoother.
-      launch_windows / launch_pf / launch_reduce / launch_update: the launches of a step on one stream (_stream);
-               _enqueue_step is the one sequence of them (windows, proposal, filter, reduction, update, each where the
-               sampler and the path have one), step / run / _graph drive it; _update_key keys every update rule.
-               sampler='pmmh' | 'pmala': launch_propose before launch_pf, launch_accept as the update; _mh_init is the init
-               pass of both.  With correlation set launch_pf is launch_cpm on the pfg_cpm_problem records (cpm_desc_dev, static:
-               _cpm_alloc), launch_accept ends in the commit that flips the selector of a chain that accepted, and _mh_init
-               runs the rho = 0 launch.  With sqmc set launch_pf is launch_sqmc on the pfg_sqmc_problem records (sqmc_desc_dev,
-               static: _sqmc_alloc), keyed seed ^ 0x53514D43; propose, accept and _mh_init are PMMH's.
-               sampler='pgibbs': launch_pf is launch_csmc on the pfg_csmc_problem records (csmc_desc_dev,
-               static), launch_update the conjugate draw; _pgibbs_init allocates path_dev, the counters and the scratch
-               and runs the init pass.
+      launch_windows / launch_propose / launch_pf / launch_reduce / launch_update: the launches of a step on one stream
+               (_stream); _enqueue_step is the one sequence of them -- the windows where `_window_draws` says who draws them,
+               then `_step`, the list the constructor builds once: the proposal if the sampler has one, the family's launch,
+               the reduction on the multi-window path, the update -- and step / run / _graph drive it; _update_key keys
+               every update rule.  launch_pf is the family's launch; a family with records of its own launches through
+               _launch_chain_filter, its score twin with lambduh where the sampler drifts along the score.  launch_update is
+               the record's rule, or launch_accept where the step has a pair; launch_accept ends in the commit that flips the
+               selector of a chain that accepted where the family keeps two buffers of normals ('cpm').  _init_launch is the
+               launch of every init pass: the family's launch with its init keywords (cpm: rho = 0; csmc: has_ref = 0), the
+               reduction, the accept step, counter 1.
                sampler='sgld_cv': _desc / desc_dev hold _nl = 2 * _nd records, the chains' and behind them their twins'
                (_cv_alloc); launch_windows and launch_reduce serve both halves, launch_pf launches them together, set_centre is
                the centring pass on centre_desc_dev.
-      _chain_state: what a chain of the sampler carries beyond theta, the momentum and the counter, and the scratch of a
-               step: the one list state_dict, load_state_dict and _graph's snapshot follow.
+      _chain_state: the sampler's carried pairs, then the family's, and the scratch of a step: the one list state_dict,
+               load_state_dict and _graph's snapshot follow.  _need: the one guard of the accessors.
     """
 
     def __init__(self, model, observations, parameters, num_chains=None, N=1000, pf="poyiadjis_N",
@@ -299,6 +307,14 @@ class ChainEnsemble(object):
         self.ess_threshold = s.ess_threshold        # None: resample at every step
         self.correlation = s.correlation            # None: plain PMMH, a fresh estimate per proposal
         self.sqmc = getattr(s, "sqmc", False)       # True: PMMH on the sequential quasi-Monte Carlo filter's estimate
+        # what the sampler is and which family of filter its step launches: the two records every later decision reads
+        rule = self._rule = SAMPLERS[sampler]
+        self._filter = filter_family(sampler, self.correlation, self.sqmc)
+        family = self._family = FILTERS[self._filter]
+        self._twins = rule.twins                    # every descriptor has a twin at the centre, in the same launch
+        self._accessors = frozenset(rule.accessors + family.accessors)
+        # ordered (checkpoint key, attribute) pairs: the sampler's, then the family's (_chain_state)
+        self._carries = rule.carries + family.carries
         self.window_sampling, self.partition_style, self.strict = window_sampling, partition_style, s.strict
         self._multi, self.W, self.segments, self.T, self.S, self.B = s.multi, s.W, s.segments, s.T, s.S, s.B
         self.P, self.C = s.theta0.shape[1], s.theta0.shape[0]
@@ -333,21 +349,9 @@ class ChainEnsemble(object):
         self.out_dev = torch.zeros((C, _capi.OUT_DOUBLES), dtype=torch.float64, device=dev)
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         self.momentum_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
-        if sampler == "adagrad":        # G, the running sum of squared scaled gradients, per variable
-            self.moment_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
-        self._cv = sampler == "sgld_cv"                 # every descriptor has a twin at the centre, in the same launch
         self.proposal_scale = s.proposal_scale
-        self._mh = sampler in ("pmmh", "pmala", "pmala_sorted")         # a proposal, a launch on it, an accept step
-        self._pmala = sampler in ("pmala", "pmala_sorted")              # ... along a score, accepted on both proposal densities
-        if self._mh:
-            # the proposal the launch reads, its validity, each chain's current estimate and acceptance count
-            self.theta_prop_dev = self.theta_dev.clone()
-            self.valid_dev = torch.ones(C, dtype=torch.int32, device=dev)
-            self.ll_dev = torch.zeros(C, dtype=torch.float64, device=dev)
-            self.accept_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
-            self.scale_dev = torch.from_numpy(s.proposal_scale).to(dev)
-        if self._pmala:     # the score estimate each chain's current state was accepted with: out[0..3], verbatim
-            self.grad_cur_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
+        if rule.alloc is not None:
+            getattr(self, rule.alloc)(s)
         # one weights row per window start of every sequence longer than S.  Single-window lists: every row times
         # T_total / T_sequence, the Seq sampler's rescaling of a one-sequence gradient, whole short sequences a row of it;
         # the multi-window path leaves that rescaling to the reduction
@@ -376,7 +380,7 @@ class ChainEnsemble(object):
         if self._multi:
             self.scratch_bytes_per_window = sb
         # the descriptors of one launch: the chains', and under 'sgld_cv' their twins' behind them
-        self._nl = 2 * self._nd if self._cv else self._nd
+        self._nl = 2 * self._nd if self._twins else self._nd
         self.scratch_dev = None
         if sb > 0:       # state in HBM (L2-resident), one slab per descriptor: the large-N kernel, paris_mem1024, Kalman messages
             self.scratch_dev = torch.empty(self._nl * sb, dtype=torch.uint8, device=dev)
@@ -385,27 +389,57 @@ class ChainEnsemble(object):
         # they are kept, C * 376 bytes, because the step, the graph snapshot and enable_stamps address _desc / desc_dev
         # without asking the sampler
         self._desc = _capi.device_descriptors(
-            self._nd, theta=self.theta_prop_dev if self._mh else self.theta_dev, row=chain, out=records, step_ctr=self.step_ctr, scratch=self.scratch_dev,
-            scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv, lambduh=self.lambduh, seed=self.seed, N=self.N,
-            smoother=s.smoother, stat=s.stat, flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0,
-            ess_threshold=s.ess_threshold, **s.paris)
-        if self._cv:
+            self._nd, theta=self.theta_dev if rule.propose is None else self.theta_prop_dev, row=chain, out=records,
+            step_ctr=self.step_ctr, scratch=self.scratch_dev, scratch_bytes=sb, stream=stream, prior_mean=pm, prior_var=pv,
+            lambduh=self.lambduh, seed=self.seed, N=self.N, smoother=s.smoother, stat=s.stat,
+            flags=_capi.FLAG_GARCH_STATIONARY_PRIOR if garch_stationary else 0, ess_threshold=s.ess_threshold, **s.paris)
+        if self._twins:
             self._cv_alloc(s, records, sb)
         if not self._multi:
             self._set_windows(first=True)
         self.desc_dev = torch.from_numpy(self._desc.view(np.uint8).reshape(self._nl, -1)).to(dev)
         if self._multi and not self._draws:
             self.launch_windows()           # static windows: written once, no draw
-        if self.correlation is not None:
-            self._cpm_alloc(pm, pv)
-        if self.sqmc:
-            self._sqmc_alloc(pm, pv)
-        if self._mh:
-            self._mh_init()
-        if sampler == "pgibbs":
-            self._pgibbs_init(pm, pv)
-        if self._cv:
-            self.set_centre(centre, s.centre_repeats)
+        # who draws a step's windows: nobody when they are static (a proposal is judged on the whole data set on either path)
+        if self._multi:
+            self._window_draws = "device" if self._draws else None
+        else:
+            self._window_draws = window_sampling if rule.propose is None else None
+        # the family's launch: launch_descriptors | launch_csmc | launch_cpm | launch_sqmc, with the score twin of a sorted
+        # filter where the sampler drifts along the score, under the family's key; then the launches of a step, in order
+        # (the class's functions, called with the ensemble: a bound method kept on the instance would be a reference cycle,
+        # and the buffers in HBM would wait for the garbage collector)
+        cls = type(self)
+        self._launch_filter = getattr(cls, "launch_" + self._filter)
+        if family.launch is not None:
+            self._filter_call = family.score if rule.score else family.launch
+            self._filter_score = (self.lambduh,) if rule.score else ()
+            self._filter_key = (self.seed ^ family.salt, self.chain_offset, self.step_ctr.data_ptr())
+        self._step = [launch for launch, has in ((cls.launch_propose, rule.propose is not None), (self._launch_filter, True),
+                                                 (cls.launch_reduce, self._multi), (cls.launch_update, True)) if has]
+        # what the family carries and its records, then the sampler's init pass
+        if family.alloc is not None:
+            getattr(self, family.alloc)(pm, pv)
+        if rule.init is not None:
+            s.centre = centre
+            getattr(self, rule.init)(s)
+
+    def _mh_alloc(self, s):
+        """What a step with a propose / accept pair needs beside theta: the proposal the launch reads, its validity, each
+        chain's current estimate and acceptance count; where the proposal drifts along the score, the score estimate each
+        chain's current state was accepted with (out[0..3], verbatim)."""
+        C, dev = self.C, self.device
+        self.theta_prop_dev = self.theta_dev.clone()
+        self.valid_dev = torch.ones(C, dtype=torch.int32, device=dev)
+        self.ll_dev = torch.zeros(C, dtype=torch.float64, device=dev)
+        self.accept_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
+        self.scale_dev = torch.from_numpy(s.proposal_scale).to(dev)
+        if self._rule.score:
+            self.grad_cur_dev = torch.zeros((C, _capi.MAX_THETA), dtype=torch.float64, device=dev)
+
+    def _adagrad_alloc(self, s):
+        """G, the running sum of squared scaled gradients, per variable."""
+        self.moment_dev = torch.zeros((self.C, _capi.MAX_THETA), dtype=torch.float64, device=self.device)
 
     # -- sampler='sgld_cv': the twins, the centre and its gradient -----------------------------------------------------
     _CENTRE_SEED = 0x43454E5452453031       # "CENTRE01": the centring launches draw under seed ^ this
@@ -467,8 +501,7 @@ class ChainEnsemble(object):
         An error in centre_gradient() enters every step of every chain with the same sign: a BIAS that does not average out
         over steps, unlike the window noise the control variate removes.  repeats and centre_N are the knobs (the error's
         variance falls as 1 / (repeats * centre_N)); with kind='marginal' there is no such error."""
-        if not self._cv:
-            raise ValueError("set_centre() belongs to sampler='sgld_cv', this ensemble runs '{0}'".format(self.sampler))
+        self._need("set_centre")
         R = self.centre_repeats if repeats is None else int(repeats)
         if self.kind == "marginal":
             R = 1
@@ -502,6 +535,10 @@ class ChainEnsemble(object):
         if bad.size:
             raise ValueError("sgld_cv: the centre gradient of chain {0} is not finite".format(int(bad[0]) + self.chain_offset))
 
+    def _cv_init(self, s):
+        """The init pass of sampler='sgld_cv', the constructor's last act: the centring launches at the centre it was given."""
+        self.set_centre(s.centre, s.centre_repeats)
+
     def _project_rows(self, t):
         """project_parameters on the rows of the device tensor t [*, MAX_THETA], in place (the rule of pfg_chains.hip's
         project_store: |A| <= 0.9999, a negative Cholesky factor reflected, LGSSM's C = 1; GARCH: its LRinv alone)."""
@@ -518,461 +555,34 @@ class ChainEnsemble(object):
 
     def centre(self):
         """sampler='sgld_cv': [C, P] the centres the chains' control variates are taken at."""
-        self._need_cv("centre")
+        self._need("centre")
         return self.theta_centre_dev[:, :self.P].cpu().numpy()
 
     def centre_gradient(self):
         """sampler='sgld_cv': [C, h] the whole-series score estimate at each chain's centre (score-column order, raw, without
         the prior), as last_gradient_statistics()[0]."""
-        self._need_cv("centre_gradient")
+        self._need("centre_gradient")
         return self.centre_grad_dev[:, :_capi.STAT_DIM[self.model]].cpu().numpy()
 
     def cv_statistics(self):
         """sampler='sgld_cv': (cur, centre), the [C, 8] records of the latest step's window at each chain's parameters and at
         its centre (multi-window path: the reduced records).  The step's gradient is centre_gradient() + (cur - centre)."""
-        self._need_cv("cv_statistics")
+        self._need("cv_statistics")
         return self.out_dev.cpu().numpy(), self.out_centre_dev.cpu().numpy()
 
     def moment(self):
         """sampler='adagrad': [C, P] the running sums of squared scaled gradients G."""
-        if self.sampler != "adagrad":
-            raise ValueError("moment() belongs to sampler='adagrad', this ensemble runs '{0}'".format(self.sampler))
+        self._need("moment")
         return self.moment_dev[:, :self.P].cpu().numpy()
 
-    def _need_cv(self, what):
-        if not self._cv:
-            raise ValueError("{0}() belongs to sampler='sgld_cv', this ensemble runs '{1}'".format(what, self.sampler))
+    def _need(self, what):
+        """Refuse the accessor `what` unless it is the sampler's or the filter family's own (the records' accessors)."""
+        if what not in self._accessors:
+            raise ValueError("{0}() belongs to {1}".format(what, ACCESSORS[what].format(self.sampler)))
 
-    @staticmethod
-    def _resolve_settings(model, observations, parameters=None, num_chains=None, N=1000, pf="poyiadjis_N", lambduh=None,
-                          subsequence_length=-1, buffer_length=-1, dtype="f64", partition_style=None,
-                          resampling="multinomial", sampler="sgld", window_sampling="host", kind="pf", num_samples=None,
-                          Ntilde=2, max_accept_reject=None, accept_reject=True, minibatch_size=None, num_sequences=None,
-                          ess_threshold=None, proposal_scale=None, pmmh_stat=None, kernel=None, correlation=None, sqmc=False,
-                          centre=None, centre_repeats=1, centre_N=None):
-        """The constructor's arguments -> the resolved settings (a namespace), or the refusal: every decision that needs no
-        device is made here and nowhere else, so it runs (and is tested) without a GPU.
-
-        kind, pf, N (kind='complete': num_samples), lambduh; smoother (what the descriptors say) and launch_smoother (what the
-        launch states: 'poyiadjis_n' for 'nemeth' with lambduh = 1); stat; paris (the descriptors' PaRIS fields, {} otherwise),
-        Ntilde, max_accept_reject; M, K, W, multi; S, B, strict; y (the concatenated series), T, segments ([K+1] offsets
-        into y, None for a single series), bounds (segments, or [0, T]); multi: draws, rescale; theta0 [C, P], proto;
-        ess_threshold (None unless adaptive resampling is on); proposal_scale ([MAX_THETA] doubles, None unless sampler =
-        'pmmh' | 'pmala'); correlation (rho as a float, None unless the correlated pseudo-marginal filter is on); sampler =
-        'sgld_cv' alone: centre_repeats, centre_N (the particles of the centring launches: N unless given); sqmc set alone:
-        sqmc = True (a namespace without it is today's)."""
-        tau = None
-        if sampler == "sgld_cv":
-            ChainEnsemble._refuse_cv(observations, N, pf, kind, centre_repeats, centre_N)
-        elif centre is not None or centre_N is not None or centre_repeats != 1:
-            raise ValueError("centre, centre_repeats and centre_N belong to sampler='sgld_cv' (SGLD with control variates), got "
-                             "sampler = '{0}'".format(sampler))
-        if sampler == "pmala_sorted":
-            ChainEnsemble._refuse_pmala_sorted(pmmh_stat, correlation, sqmc, lambduh, model, observations, N, pf,
-                                               subsequence_length, buffer_length, dtype, resampling, kind, minibatch_size,
-                                               num_sequences, ess_threshold, kernel)
-            correlation = None if sqmc else float(correlation)
-        elif correlation is not None:
-            ChainEnsemble._refuse_correlated(sampler, pmmh_stat, correlation, model, observations, N, pf, subsequence_length,
-                                             buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
-                                             kernel)
-            correlation = float(correlation)
-        if sqmc and sampler != "pmala_sorted":
-            ChainEnsemble._refuse_sqmc(sampler, pmmh_stat, correlation, model, observations, N, pf, subsequence_length,
-                                       buffer_length, dtype, resampling, kind, minibatch_size, num_sequences, ess_threshold,
-                                       kernel)
-        if sampler == "pgibbs":
-            ChainEnsemble._refuse_chain_filter("pgibbs", model, observations, N, pf, subsequence_length, buffer_length, dtype,
-                                               resampling, kind, minibatch_size, num_sequences, ess_threshold, kernel)
-        if ess_threshold is not None and ess_threshold != 0 and (kind != "pf" or sampler == "gibbs"):
-            # (what else adaptive resampling is not built for: resolve_resampling, below)
-            raise NotImplementedError("adaptive resampling (ess_threshold) needs a particle filter: kind='pf'")
-        if sampler not in ("sgld", "sghmc", "sgrld", "gibbs", "pmmh", "pmala", "pmala_sorted", "pgibbs", "sgd", "adagrad", "sgld_cv"):
-            raise ValueError("sampler must be 'sgld', 'sghmc', 'sgrld', 'sgd', 'adagrad', 'sgld_cv', 'pgibbs', 'pmala_sorted', "
-                             "'pmala', 'gibbs' or 'pmmh'")
-        scale = None
-        if sampler not in ("pmmh", "pmala", "pmala_sorted"):
-            if proposal_scale is not None:
-                raise ValueError("proposal_scale is the random walk of sampler='pmmh', got sampler = '{0}'".format(sampler))
-            if pmmh_stat is not None:
-                raise ValueError("pmmh_stat belongs to sampler='pmmh', got sampler = '{0}'".format(sampler))
-        else:
-            # particle marginal Metropolis-Hastings and particle MALA (extensions): what they are not built for is refused
-            # by name
-            if sampler == "pmala" and pmmh_stat is not None:
-                raise ValueError("pmmh_stat belongs to sampler='pmmh' (sampler='pmala' needs the score launch), got sampler = 'pmala'")
-            if proposal_scale is None:
-                raise ValueError("sampler='{0}' needs proposal_scale: a positive scalar or a length-P vector in raw-theta "
-                                 "units".format(sampler))
-            P = _capi.THETA_DIM[model]
-            ps = np.asarray(proposal_scale, dtype=np.float64).reshape(-1)
-            if ps.size not in (1, P) or not np.all(np.isfinite(ps)) or not np.all(ps > 0.0):
-                raise ValueError("proposal_scale must be a positive scalar or a positive vector of length {0}, got {1}".format(
-                    P, proposal_scale))
-            scale = np.zeros(_capi.MAX_THETA)
-            scale[:P] = ps
-            if kind == "complete":
-                raise NotImplementedError("sampler='{0}' accepts on a log-likelihood estimate: kind='pf' or kind='marginal' "
-                                          "(kind='complete' samples paths and has none)".format(sampler))
-            if kind == "pf" and pf not in ("poyiadjis_N", "nemeth"):
-                if sampler == "pmmh":
-                    raise NotImplementedError("sampler='pmmh' reads the filter's log-likelihood only: pf = 'poyiadjis_N' | "
-                                              "'nemeth' (the smoothing of pf = '{0}' would be thrown away)".format(pf))
-                raise NotImplementedError("sampler='pmala' drifts along the O(N) filter's score: pf = 'poyiadjis_N' | 'nemeth' "
-                                          "(the score of pf = '{0}' as the drift is not built)".format(pf))
-            if kind == "pf" and int(N) > 16384:
-                raise NotImplementedError("sampler='{0}' is built for N <= 16384 (no whole-GPU windows), got N = {1}".format(
-                    sampler, int(N)))
-            if pmmh_stat not in (None, "none", "score"):
-                raise ValueError("pmmh_stat must be None, 'none' or 'score'")
-        M, K, W = ChainEnsemble._window_counts(observations, minibatch_size, num_sequences)
-        if W > 1 and sampler == "gibbs":
-            raise NotImplementedError("sampler='gibbs' draws one FFBS path per chain and step: W = 1 window "
-                                      "(minibatch_size = num_sequences = 1), got W = {0}".format(W))
-        if W > 1 and kind != "pf":
-            raise NotImplementedError("kind='{0}' with W = {1} windows per chain and step is not built: "
-                                      "the multi-window path is kind='pf' only".format(kind, W))
-        explicit = minibatch_size is not None or num_sequences is not None
-        multi = W > 1 or (explicit and kind == "pf" and sampler not in ("gibbs", "pgibbs"))
-        if sampler == "sgrld" and model != "lgssm":           # sgmcmc_sampler.py:643-646: LGSSM alone has one
-            raise NotImplementedError("No Default Preconditioner for {0}: sampler='sgrld' is built for model 'lgssm'".format(
-                dict(svm="SVMSampler", garch="GARCHSampler").get(model, model)))
-        stat = "score"
-        if sampler == "pmmh" and kind == "pf":
-            stat = pmmh_stat or "none"      # the launch computes no statistic: PMMH reads out[4] alone
-        if sampler == "gibbs":
-            if model != "lgssm" or dtype != "f64":
-                raise NotImplementedError("sampler='gibbs' (FFBS paths, conjugate draws) is built for model 'lgssm', dtype 'f64'")
-            if isinstance(observations, (list, tuple)):
-                raise NotImplementedError("Gibbs over lists of sequences is not built")
-            if int(subsequence_length) != -1 or int(buffer_length) != -1:
-                raise NotImplementedError("sampler='gibbs' samples the path of the whole series: "
-                                          "subsequence_length = buffer_length = -1")
-            kind, num_samples, pf, stat = "complete", 1, "poyiadjis_N", "gibbs"      # one FFBS path per chain and step
-        if kind not in ("pf", "marginal", "complete"):
-            raise ValueError("kind must be 'pf', 'marginal' or 'complete'")
-        if kind == "marginal" and (model != "lgssm" or dtype != "f64"):
-            raise NotImplementedError("kind='marginal' (the exact Kalman score) is built for model 'lgssm', dtype 'f64'")
-        if kind == "complete":
-            if model != "lgssm" or dtype != "f64":
-                raise NotImplementedError("kind='complete' (FFBS paths) is built for model 'lgssm', dtype 'f64'")
-            if num_samples is None or int(num_samples) < 1:
-                raise ValueError("kind='complete' needs num_samples >= 1 paths per window")
-            N = int(num_samples)        # the paths of a window take the particles' place in the descriptors
-        N, Ntilde = int(N), int(Ntilde)
-        max_accept_reject = 0 if not accept_reject else (64 if max_accept_reject is None else max(0, int(max_accept_reject)))
-        # which smoother runs: the one decision the descriptors, the launch and the scratch sizing follow
-        lam, paris = 1.0, {}
-        if kind == "pf":
-            # the resampling scheme of a NEMETH window (particle_filters.SCHEMES); the other smoothers say below what they
-            # make of `resampling`, and only the threshold is judged for them
-            own = pf in ("poyiadjis_N", "nemeth")
-            nemeth, _, tau = resolve_resampling("nemeth" if own else pf, pf, resampling if own else "multinomial",
-                                                ess_threshold, N)
-        if kind != "pf":
-            if pf == "paris":
-                raise ValueError("pf='paris' needs kind='pf'")
-            if pf == "poyiadjis_N2":
-                raise ValueError("pf='poyiadjis_N2' needs kind='pf'")
-            if resampling == "stratified":
-                raise ValueError("resampling='stratified' needs kind='pf', got kind = '{0}'".format(kind))
-            smoother = {"marginal": "kalman", "complete": "kalman_ffbs"}[kind]
-        elif pf == "paris":
-            # PaRIS on the LDS-resident kernels (paris64x2 / paris256x1 / paris256x4): no per-chain scratch; the
-            # multi-window path also runs paris_mem1024 (1024 < N <= 16384, its state in the descriptors' scratch)
-            if N > 1024 and not multi:
-                raise NotImplementedError("ChainEnsemble(pf='paris') is built for N <= 1024 on the single-window path, "
-                                          "got N = {0}: pass minibatch_size / num_sequences for the multi-window path "
-                                          "(paris_mem1024, N <= 16384)".format(N))
-            if resampling != "multinomial":
-                raise ValueError("pf='paris' resamples multinomially, got resampling = {0}".format(resampling))
-            if Ntilde < 1:
-                raise ValueError("pf='paris' needs Ntilde >= 1")
-            smoother, paris = "paris", dict(Ntilde=Ntilde, max_accept_reject=max_accept_reject)
-        elif pf == "poyiadjis_N2":
-            # the Poyiadjis O(N^2) smoother on the LDS-resident kernels (n2_64x2 / n2_256x1 / n2_256x4): no per-chain
-            # scratch; the multi-window path also runs n2_mem1024 (1024 < N <= 16384, its state in the descriptors' scratch)
-            if N > 1024 and not multi:
-                raise NotImplementedError("ChainEnsemble(pf='poyiadjis_N2') is built for N <= 1024 on the single-window path, "
-                                          "got N = {0}: pass minibatch_size / num_sequences for the multi-window path "
-                                          "(n2_mem1024, N <= 16384)".format(N))
-            if resampling != "multinomial":
-                raise ValueError("pf='poyiadjis_N2' resamples multinomially, got resampling = {0}".format(resampling))
-            smoother = "poyiadjis_n2"
-        elif pf in ("poyiadjis_N", "nemeth"):
-            if pf == "nemeth":
-                lam = 0.95 if lambduh is None else float(lambduh)
-            smoother = nemeth           # 'nemeth', or what its resampling scheme makes of it
-        else:
-            raise ValueError("ChainEnsemble supports pf = 'poyiadjis_N' | 'nemeth' | 'paris' | 'poyiadjis_N2', got {0}".format(pf))
-        # every chain the Poyiadjis O(N) score (NEMETH, lambduh = 1, score): units with a twin specialised to it run that
-        # (their kernels answer NaN to a window that asks for another statistic: stat 'none' launches the general unit)
-        launch_smoother = "poyiadjis_n" if smoother == "nemeth" and lam == 1.0 and stat == "score" else smoother
-        if window_sampling not in ("host", "device"):
-            raise ValueError("window_sampling must be 'host' or 'device'")
-
-        segments = None
-        if isinstance(observations, (list, tuple)):
-            segs = [np.ascontiguousarray(o, dtype=np.float64).reshape(-1) for o in observations]
-            if len(segs) == 0 or min(len(o) for o in segs) == 0:
-                raise ValueError("every sequence needs at least one observation")
-            segments = np.concatenate([[0], np.cumsum([len(o) for o in segs])]).astype(np.int64)
-            y = np.concatenate(segs)
-        else:
-            y = np.ascontiguousarray(observations, dtype=np.float64).reshape(-1)
-        T = y.shape[0]
-        bounds = segments if segments is not None else np.array([0, T], dtype=np.int64)
-        proto = None
-        if isinstance(parameters, np.ndarray):
-            theta0 = np.ascontiguousarray(parameters, dtype=np.float64).reshape(-1, _capi.THETA_DIM[model])
-        else:
-            if num_chains is None:
-                raise ValueError("num_chains is required when `parameters` is a Parameters object")
-            theta0, proto = np.tile(parameters.theta(), (int(num_chains), 1)), parameters
-
-        S, B = int(subsequence_length), int(buffer_length)
-        if segments is not None and not multi:
-            if window_sampling != "host":
-                raise NotImplementedError("sequence lists use host-side window sampling (device-side: pass num_sequences, "
-                                          "the multi-window path)")
-            if S == -1:
-                S = int(np.max(np.diff(segments)))      # whole sequences
-        elif S == -1 or T - S <= 0:
-            S = -1
-        B = T if B == -1 else B
-        Tk = np.diff(bounds)
-        longer = (Tk > S) if S > 0 else np.zeros(len(Tk), dtype=bool)
-        strict = (partition_style or 'uniform') == 'strict'
-        # (single-window lists draw their strict starts from Tk // S blocks without asking for divisibility)
-        if strict and (multi or segments is None) and np.any(Tk[longer] % S != 0):
-            k = int(np.flatnonzero(longer & (Tk % max(S, 1) != 0))[0])
-            raise ValueError("S {0} does not evenly divide T {1}".format(S, int(Tk[k])))   # sgmcmc_sampler.py:1991-1993
-        draws = rescale = None
-        if multi:
-            rescale = segments is not None and K != -1
-            draws = rescale or bool(np.any(longer))
-            if draws and window_sampling != "device":
-                raise NotImplementedError("the W = {0} windows per chain and step are drawn on the device: "
-                                          "window_sampling='device'".format(W))
-            if N > 16384:
-                raise NotImplementedError("the multi-window path is built for N <= 16384 (one workgroup per window), "
-                                          "got N = {0}".format(N))
-        if sampler in ("pmmh", "pmala", "pmala_sorted"):
-            # every step needs the likelihood of the whole data set: no window is drawn, nothing is rescaled
-            whole = sampler + " needs the whole series in every step: "
-            if segments is None and (S != -1 or int(buffer_length) != -1):
-                raise NotImplementedError(whole + "subsequence_length = buffer_length = -1, got {0} / {1}".format(
-                    int(subsequence_length), int(buffer_length)))
-            if segments is not None and (not multi or K != -1 or int(subsequence_length) != -1 or M != 1 or draws or rescale):
-                raise NotImplementedError(whole + "a list of sequences takes num_sequences = -1, subsequence_length = -1, "
-                                          "buffer_length = 0 and minibatch_size 1 (every sequence whole, out[4] summed{0})".format(
-                                              ", the score columns too" if sampler == "pmala" else ""))
-            if multi and (M != 1 or draws or rescale):
-                raise NotImplementedError(whole + "minibatch_size = 1 (an average of log-likelihoods is no estimate of one)")
-        s = types.SimpleNamespace(
-            proposal_scale=scale, kind=kind, pf=pf, N=N, lambduh=lam, smoother=smoother, launch_smoother=launch_smoother, stat=stat, paris=paris,
-            Ntilde=Ntilde, max_accept_reject=max_accept_reject, M=M, K=K, W=W, multi=multi, S=S, B=B, strict=strict, y=y, T=T,
-            segments=segments, bounds=bounds, draws=draws, rescale=rescale, theta0=theta0, proto=proto, ess_threshold=tau,
-            correlation=correlation)
-        if sampler == "sgld_cv":        # (the other samplers' namespaces keep their fields)
-            s.centre_repeats = 1 if kind == "marginal" else int(centre_repeats)
-            s.centre_N = N if centre_N is None else int(centre_N)
-        if sqmc:
-            s.sqmc = True
-        if sampler == "pmala_sorted":       # which sorted filter carries the score: 'cpm' (correlation) | 'sqmc'
-            s.sorted_score = "sqmc" if sqmc else "cpm"
-        return s
-
-    @staticmethod
-    def _refuse_cv(observations, N, pf, kind, centre_repeats, centre_N):
-        """What sampler='sgld_cv' is not built for, each refusal naming its reason: the chain and its twin at the centre filter
-        one window of one series on the same draws, in one launch of one-workgroup kernels."""
-        what = "sampler='sgld_cv' (SGLD with control variates: every window is filtered at theta and at the centre) "
-        if isinstance(observations, (list, tuple)):
-            raise NotImplementedError(what + "centres on the whole-data gradient of one series: lists of sequences are not built")
-        if kind == "complete":
-            raise NotImplementedError(what + "needs a score that is a function of (theta, draws): kind='pf' or kind='marginal', "
-                                      "got kind = 'complete' (sampled FFBS paths as a control variate are not built)")
-        if kind == "pf" and pf in ("paris", "poyiadjis_N2"):
-            raise NotImplementedError(what + "runs the O(N) filters: pf = 'poyiadjis_N' | 'nemeth', got pf = '{0}' (a paired "
-                                      "PaRIS / O(N^2) launch is not built)".format(pf))
-        if kind == "pf" and int(N) > 16384:
-            raise NotImplementedError(what + "is built for N <= 16384 (no whole-GPU windows), got N = {0}".format(int(N)))
-        if kind == "marginal" and centre_N is not None:
-            raise ValueError(what + "with kind='marginal' centres on the exact Kalman gradient: centre_N has no particles to "
-                             "count, got centre_N = {0}".format(centre_N))
-        if centre_N is not None and not 1 <= int(centre_N) <= 16384:
-            raise NotImplementedError(what + "centres with one-workgroup launches: 1 <= centre_N <= 16384, got centre_N = {0}".format(
-                int(centre_N)))
-        try:
-            ok = int(centre_repeats) == centre_repeats and int(centre_repeats) >= 1
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(what + "needs centre_repeats >= 1 whole-series launches at the centre, got {0}".format(centre_repeats))
-
-    # What differs between the refusals of the two kernel families that run one workgroup per chain (_refuse_chain_filter):
-    # the prefix, the reason clause of each shared check, the largest N.
-    _CHAIN_FILTERS = {
-        "pgibbs": dict(
-            what="sampler='pgibbs' (conditional SMC with ancestor sampling, then the conjugate draw) ",
-            garch="GARCH's prior has no conjugate draw", lists="samples the path of one series",
-            whole="samples the path of the whole series", window="draws one path per chain and step", own="sweep",
-            resampling="resamples multinomially inside the conditional sweep", inside="the conditional sweep",
-            particles=" and needs a free particle beside the reference", max_n=_capi.CSMC_MAX_N),
-        "correlation": dict(
-            what="correlation (correlated pseudo-marginal PMMH: the sorted filter on normals the chain carries) ",
-            garch="the sort orders a scalar state, GARCH's has two components", lists="carries the normals of one series",
-            whole="filters the whole series", window="runs one filter per chain and step", own="filter",
-            resampling="resamples systematically in the order of the states, on a uniform it carries: resampling stays at its "
-                       "default", inside="the sorted filter", particles="", max_n=_capi.CPM_MAX_N),
-        "sqmc": dict(
-            what="sqmc (PMMH on sequential quasi-Monte Carlo: the sorted filter on one randomised Sobol' point set per step) ",
-            garch="the sort orders a scalar state, GARCH's has two components", lists="filters one series",
-            whole="filters the whole series", window="runs one filter per chain and step", own="filter",
-            resampling="resamples in the order of the states on the first coordinate of its point set: resampling stays at its "
-                       "default", inside="the sorted filter", particles="", max_n=_capi.SQMC_MAX_N),
-    }
-
-    @staticmethod
-    def _refuse_chain_filter(family, model, observations, N, pf, subsequence_length, buffer_length, dtype, resampling, kind,
-                             minibatch_size, num_sequences, ess_threshold, kernel, also=(), score=False):
-        """What sampler='pgibbs' and `correlation` are not built for, each refusal naming its reason: either is one kernel
-        family with one workgroup per chain -- SVM and LGSSM, f64, the prior proposal, its own resampling at every step, the
-        whole series, N <= 1024.  family: a key of _CHAIN_FILTERS.  also: (refused, reason) pairs of the family's own, checked
-        ahead of N.  score: the family's kernel carries the O(N) score (sampler='pmala_sorted'), so pf may be 'nemeth' as well."""
-        f = ChainEnsemble._CHAIN_FILTERS[family]
-        what = f["what"]
-        if model == "garch":
-            raise NotImplementedError(what + "is built for model 'svm' | 'lgssm': " + f["garch"])
-        if dtype != "f64":
-            raise NotImplementedError(what + "is built for dtype 'f64', got '{0}'".format(dtype))
-        if isinstance(observations, (list, tuple)):
-            raise NotImplementedError(what + f["lists"] + ": lists of sequences are not built")
-        if int(subsequence_length) != -1 or int(buffer_length) != -1:
-            raise NotImplementedError(what + f["whole"] + ": subsequence_length = buffer_length = -1, got {0} / {1}".format(
-                int(subsequence_length), int(buffer_length)))
-        M = 1 if minibatch_size is None else int(minibatch_size)
-        K = 1 if num_sequences is None else int(num_sequences)
-        if M != 1 or K != 1:
-            raise NotImplementedError(what + f["window"] + ": W = 1 window (minibatch_size = num_sequences = 1), got "
-                                      "minibatch_size = {0}, num_sequences = {1}".format(M, K))
-        if kind != "pf":
-            raise NotImplementedError(what + "is a particle method: kind='pf', got kind = '{0}'".format(kind))
-        if score and pf not in ("poyiadjis_N", "nemeth"):
-            raise NotImplementedError(what + "carries the O(N) score through its own {0}: pf = 'poyiadjis_N' | 'nemeth', got pf = "
-                                      "'{1}' (a PaRIS / O(N^2) score on the sorted filters is not built)".format(f["own"], pf))
-        if not score and pf != "poyiadjis_N":
-            raise NotImplementedError(what + "runs its own {0}, no smoother: pf stays at its default, got pf = '{1}'".format(
-                f["own"], pf))
-        if resampling != "multinomial":
-            raise NotImplementedError(what + f["resampling"] + ", got resampling = '{0}'".format(resampling))
-        if ess_threshold is not None and ess_threshold != 0:
-            raise NotImplementedError(what + "resamples at every step: adaptive resampling (ess_threshold) is not built inside " +
-                                      f["inside"])
-        if kernel not in (None, "prior"):
-            raise NotImplementedError(what + "proposes from the prior kernel, got kernel = '{0}'".format(kernel))
-        for refused, reason in also:
-            if refused:
-                raise NotImplementedError(what + reason)
-        if not 2 <= int(N) <= f["max_n"]:
-            raise NotImplementedError(what + "keeps one chain's particles in one workgroup{0}: 2 <= N <= {1}, got N = {2}".format(
-                f["particles"], f["max_n"], int(N)))
-
-    @staticmethod
-    def _refuse_correlated(sampler, pmmh_stat, correlation, *shared):
-        """`correlation`: the sampler it belongs to, then the shared refusals (with pmmh_stat's ahead of N), then rho's range."""
-        if sampler != "pmmh":
-            raise NotImplementedError(ChainEnsemble._CHAIN_FILTERS["correlation"]["what"] + "belongs to sampler='pmmh', got "
-                                      "sampler = '{0}'{1}".format(sampler, " (pMALA would need a score that is smooth in the "
-                                                                  "normals as well)" if sampler == "pmala" else ""))
-        ChainEnsemble._refuse_chain_filter("correlation", *shared, also=[(
-            pmmh_stat not in (None, "none"), "computes the log-likelihood estimate alone: pmmh_stat stays at its default, got "
-                                             "pmmh_stat = '{0}'".format(pmmh_stat))])
-        try:
-            rho = float(correlation)
-        except (TypeError, ValueError):
-            rho = float("nan")
-        if not 0.0 <= rho < 1.0:        # (false for a NaN as well)
-            raise ValueError("correlation must lie in [0, 1) (rho of U' = rho U + sqrt(1 - rho^2) eps; 0: fresh normals at every "
-                             "step), got {0}".format(correlation))
-
-    @staticmethod
-    def _refuse_sqmc(sampler, pmmh_stat, correlation, *shared):
-        """`sqmc`: not beside `correlation`, the sampler it belongs to, then the shared refusals (with pmmh_stat's ahead of N),
-        then the power of two."""
-        what = ChainEnsemble._CHAIN_FILTERS["sqmc"]["what"]
-        if correlation is not None:
-            raise NotImplementedError(what + "draws a fresh point set at every step and carries no normals: correlation stays "
-                                      "None, got correlation = {0}".format(correlation))
-        if sampler != "pmmh":
-            raise NotImplementedError(what + "belongs to sampler='pmmh', got sampler = '{0}'{1}".format(
-                sampler, " (pMALA would need the score on the point set: not built)" if sampler == "pmala" else ""))
-        ChainEnsemble._refuse_chain_filter("sqmc", *shared, also=[(
-            pmmh_stat not in (None, "none"), "computes the log-likelihood estimate alone: pmmh_stat stays at its default, got "
-                                             "pmmh_stat = '{0}'".format(pmmh_stat))])
-        N = int(shared[2])
-        if N & (N - 1):
-            raise NotImplementedError(what + "takes the first 2^m points of the Sobol' sequence, a (0, m, 2)-net: N must be a "
-                                      "power of two, got N = {0}".format(N))
-
-    @staticmethod
-    def _refuse_pmala_sorted(pmmh_stat, correlation, sqmc, lambduh, *shared):
-        """sampler='pmala_sorted': exactly one of `correlation` and `sqmc`, then the refusals of that filter's family
-        (_refuse_chain_filter, with pf = 'nemeth' admitted: the kernel carries the score), then rho's range or the power of two,
-        then lambduh's range."""
-        what = "sampler='pmala_sorted' (particle MALA along the score of a sorted filter) "
-        if (correlation is not None) == bool(sqmc):
-            raise ValueError(what + "takes exactly one of correlation=rho (the correlated filter) and sqmc=True (the sequential "
-                             "quasi-Monte Carlo filter), got {0}".format("both" if sqmc else "neither"))
-        if pmmh_stat is not None:
-            raise ValueError("pmmh_stat belongs to sampler='pmmh' (sampler='pmala_sorted' needs the score launch), got sampler = "
-                             "'pmala_sorted'")
-        kind = shared[8]
-        if kind in ("marginal", "complete"):
-            raise NotImplementedError(what + "drifts along a particle filter's score: kind='pf', got kind = '{0}' (sampler='pmala' "
-                                      "serves the exact Kalman score)".format(kind))
-        ChainEnsemble._refuse_chain_filter("sqmc" if sqmc else "correlation", *shared, score=True)
-        if sqmc:
-            N = int(shared[2])
-            if N & (N - 1):
-                raise NotImplementedError(ChainEnsemble._CHAIN_FILTERS["sqmc"]["what"] + "takes the first 2^m points of the Sobol' "
-                                          "sequence, a (0, m, 2)-net: N must be a power of two, got N = {0}".format(N))
-        else:
-            try:
-                rho = float(correlation)
-            except (TypeError, ValueError):
-                rho = float("nan")
-            if not 0.0 <= rho < 1.0:        # (false for a NaN as well)
-                raise ValueError("correlation must lie in [0, 1) (rho of U' = rho U + sqrt(1 - rho^2) eps; 0: fresh normals at "
-                                 "every step), got {0}".format(correlation))
-        if shared[3] == "nemeth" and lambduh is not None:
-            try:
-                lam = float(lambduh)
-            except (TypeError, ValueError):
-                lam = float("nan")
-            if not 0.0 < lam <= 1.0:
-                raise ValueError(what + "shrinks the score with lambduh in (0, 1] (1: the plain O(N) recursion), got {0}".format(
-                    lambduh))
-
-    @staticmethod
-    def _window_counts(observations, minibatch_size, num_sequences):
-        """(M, K, W): windows per sequence, sequences per step (-1 = all), windows per chain and step."""
-        M = 1 if minibatch_size is None else int(minibatch_size)
-        K = 1 if num_sequences is None else int(num_sequences)
-        if M < 1:
-            raise ValueError("minibatch_size must be >= 1, got {0}".format(M))
-        if not isinstance(observations, (list, tuple)):
-            if K != 1:
-                raise ValueError("a single series takes num_sequences = 1, got {0}".format(K))
-            return M, K, M
-        n_seq = len(observations)
-        if K != -1 and not 1 <= K <= n_seq:
-            raise ValueError("num_sequences must be -1 or in 1..{0} (the number of sequences), got {1}".format(n_seq, K))
-        if K > _capi.MAX_DRAWN_SEQUENCES:
-            raise NotImplementedError("num_sequences = {0}: at most {1} sequences are drawn per chain and step "
-                                      "(num_sequences = -1 takes them all)".format(K, _capi.MAX_DRAWN_SEQUENCES))
-        return M, K, M * (n_seq if K == -1 else K)
+    # the arguments -> the resolved settings or the refusal, without a device: ensemble_settings.py
+    _resolve_settings = staticmethod(resolve_settings)
+    _window_counts = staticmethod(window_counts)
 
     def _scratch_bytes(self, N=None, whole=False):
         """pfg_dev_problem.scratch bytes per descriptor of the resolved smoother; refuses what the library refuses.
@@ -1075,7 +685,7 @@ class ChainEnsemble(object):
         block, null without a table (a full single series).  Returns whether the descriptors changed.  sampler='sgld_cv': the
         twins (the records behind the chains') take their chains' windows."""
         changed = self._set_chain_windows(self._desc[:self.C], first)
-        if self._cv and (changed or first):
+        if self._twins and (changed or first):
             for f in ("y", "T", "t1", "tL", "weights"):
                 self._desc[f][self.C:] = self._desc[f][:self.C]
         return changed
@@ -1119,17 +729,17 @@ class ChainEnsemble(object):
         (score columns, loglik).
         traced=True runs the twin instantiation that honours trace_* / rec_* buffers a caller put into
         the descriptors (tests, diagnostics); the production launch ignores them.
-        The launch is the resolved one: the launch smoother (_resolve_settings), at most N particles (the Kalman score has
-        none: 1) in each of _nl descriptors (_nd, and under 'sgld_cv' the twins behind them: ONE launch, so a chain and its
-        twin run the same kernel instantiation)."""
+        The launch is the resolved family's (ensemble_settings.FILTERS): launch_descriptors, or the conditional sweep
+        (launch_csmc), the sorted, correlated filter (launch_cpm) or the sequential quasi-Monte Carlo filter (launch_sqmc) on
+        records of their own."""
         if traced and self.kind != "pf":
             raise ValueError("kind='{0}' has no particles to trace".format(self.kind))
-        if self.sampler == "pgibbs":    # the conditional sweep: its own descriptors (traced: the twin that fills their trace_*)
-            return self.launch_csmc(stream, traced=traced)
-        if self.correlation is not None:    # the sorted, correlated filter: its own descriptors as well
-            return self.launch_cpm(stream, traced=traced)
-        if self.sqmc:       # the sequential quasi-Monte Carlo filter: its own descriptors too
-            return self.launch_sqmc(stream, traced=traced)
+        return self._launch_filter(self, stream, traced=traced)
+
+    def launch_descriptors(self, stream=None, traced=False):
+        """The launch on the window descriptors: the launch smoother (_resolve_settings), at most N particles (the Kalman
+        score has none: 1) in each of _nl descriptors (_nd, and under 'sgld_cv' the twins behind them: ONE launch, so a chain
+        and its twin run the same kernel instantiation)."""
         if self.ess_threshold:      # adaptive resampling: its own kernels, the family stated at launch level
             return self.ctx.launch_device_adaptive(self.model, self.kernel, self.dtype, "device", self.N, self._nl,
                                                    self.desc_dev.data_ptr(), self._stream(stream), traced=traced)
@@ -1140,28 +750,11 @@ class ChainEnsemble(object):
                self.desc_dev.data_ptr(), self._stream(stream))
 
     def launch_update(self, stream=None):
-        theta, out = (self.model, self.C, self.theta_dev.data_ptr()), (self.out_dev.data_ptr(), self.hyper)
-        key = self._update_key(stream)
-        if self._mh:
-            self.launch_accept(stream)
-        elif self.sampler == "sgrld":
-            self.ctx.sgrld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
-        elif self.sampler == "gibbs":
-            self.ctx.gibbs_update_device(*theta, *out, *key)
-        elif self.sampler == "pgibbs":
-            self.ctx.pgibbs_update_device(*theta, *out, *key)
-        elif self.sampler == "sgd":
-            self.ctx.sgd_update_device(*theta, *out, self.epsilon, float(self.T), *key[2:])
-        elif self.sampler == "adagrad":
-            self.ctx.adagrad_update_device(*theta, self.moment_dev.data_ptr(), *out, self.epsilon, float(self.T), *key[2:])
-        elif self._cv:
-            self.ctx.sgld_cv_update_device(*theta, self.out_dev.data_ptr(), self.out_centre_dev.data_ptr(),
-                                           self.centre_grad_dev.data_ptr(), self.hyper, self.epsilon, float(self.T), *key)
-        elif self.sampler == "sghmc":
-            self.ctx.sghmc_update_device(*theta, self.momentum_dev.data_ptr(), *out, self.epsilon, self.friction,
-                                         float(self.T), *key)
-        else:
-            self.ctx.sgld_update_device(*theta, *out, self.epsilon, float(self.T), *key)
+        """The sampler's update rule (ensemble_settings.SAMPLERS); where the step has a propose / accept pair, the accept step."""
+        if self._rule.update is None:
+            return self.launch_accept(stream)
+        self._rule.update(self, (self.model, self.C, self.theta_dev.data_ptr()), (self.out_dev.data_ptr(), self.hyper),
+                          self._update_key(stream))
 
     def _update_key(self, stream):
         """What keys the draws of every update rule and says where it runs: seed, first chain id, the counter, the stream."""
@@ -1170,47 +763,36 @@ class ChainEnsemble(object):
     def launch_propose(self, stream=None):
         """sampler='pmmh': theta_prop_dev = theta_dev + proposal_scale (.) z, valid_dev (pfg_pmmh_propose_device).
         sampler='pmala' | 'pmala_sorted': the Langevin proposal along grad_cur_dev (pfg_pmala_propose_device)."""
-        if self._pmala:
-            return self.ctx.pmala_propose_device(
-                self.model, self.C, self.theta_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
-                self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), self.hyper, *self._update_key(stream))
-        self.ctx.pmmh_propose_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
-                                     self.valid_dev.data_ptr(), self.scale_dev.data_ptr(), *self._update_key(stream))
+        self._rule.propose(self, self._update_key(stream))
 
     def launch_accept(self, stream=None, init=False):
         """sampler='pmmh': accept / reject on out_dev[:, 4] and the log-prior; bumps the counter (pfg_pmmh_accept_device).
         sampler='pmala' | 'pmala_sorted': the same with the two proposal densities, on out_dev[:, :5] (pfg_pmala_accept_device).
         With correlation set, either ends in the commit."""
-        if self._pmala:
-            self.ctx.pmala_accept_device(
-                self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(), self.valid_dev.data_ptr(),
-                self.out_dev.data_ptr(), self.ll_dev.data_ptr(), self.grad_cur_dev.data_ptr(), self.accept_dev.data_ptr(),
-                self.hyper, self.scale_dev.data_ptr(), init, *self._update_key(stream))
-        else:
-            self.ctx.pmmh_accept_device(self.model, self.C, self.theta_dev.data_ptr(), self.theta_prop_dev.data_ptr(),
-                                        self.valid_dev.data_ptr(), self.out_dev.data_ptr(), self.ll_dev.data_ptr(),
-                                        self.accept_dev.data_ptr(), self.hyper, init, *self._update_key(stream))
-        if self.correlation is not None:    # a chain that accepted (init: every chain) now reads the buffer the filter wrote
+        self._rule.accept(self, init, self._update_key(stream))
+        if self._family.aux:            # a chain that accepted (init: every chain) now reads the buffer the filter wrote
             self.ctx.cpm_commit_device(self.C, self.accept_dev.data_ptr(), self.seen_dev.data_ptr(), self.which_dev.data_ptr(),
                                        init, self._stream(stream))
 
-    def _mh_init(self):
-        """The init pass of sampler='pmmh' | 'pmala', the constructor's last act: the launch at the initial parameters, ll_dev =
-        its out[4] (pmala: grad_cur_dev = its out[0..3] as well).  It consumes counter value 0 -- the counter is 1 afterwards,
-        step s (from 0) draws with s + 1 -- so that no step's particle filter repeats the draws the initial estimate was
-        made with."""
-        self.theta_prop_dev.copy_(self.theta_dev)
-        if self.correlation is not None:    # fresh normals: rho = 0 reads no buffer
-            self.launch_cpm(init=True)
-        else:
-            self.launch_pf()
+    def _init_launch(self):
+        """The launch of an init pass at the initial parameters.  It consumes counter value 0 -- the counter is 1 afterwards,
+        step s (from 0) draws with s + 1 -- so that no step's filter repeats the draws the initial state was made with."""
+        self._launch_filter(self, **self._family.init)
         if self._multi:
             self.launch_reduce()
-        self.launch_accept(init=True)
+        if self._rule.accept is not None:
+            self.launch_accept(init=True)
         self.step_ctr.fill_(1)
         self.synchronize()
+
+    def _mh_init(self, s):
+        """The init pass of sampler='pmmh' | 'pmala' | 'pmala_sorted', the constructor's last act: the launch at the initial
+        parameters (the correlated filter: at rho = 0, fresh normals, no buffer is read), ll_dev = its out[4] (along a score:
+        grad_cur_dev = its out[0..3] as well)."""
+        self.theta_prop_dev.copy_(self.theta_dev)
+        self._init_launch()
         finite, what = np.isfinite(self.ll_dev.cpu().numpy()), "log-likelihood"
-        if self._pmala:     # ... and the score columns the drift reads
+        if self._rule.score:        # ... and the score columns the drift reads
             used = self.grad_cur_dev.cpu().numpy()[:, list(_PMALA_SCORE_COLUMNS[self.model])]
             finite, what = finite & np.all(np.isfinite(used), axis=1), "log-likelihood or score"
         bad = np.flatnonzero(~finite)
@@ -1218,33 +800,28 @@ class ChainEnsemble(object):
             raise ValueError("{0}: the initial {1} of chain {2} is not finite".format(self.sampler, what,
                                                                                    int(bad[0]) + self.chain_offset))
 
+    def _launch_chain_filter(self, desc, stream, traced, *before_key):
+        """One launch of the family that runs one workgroup per chain on its own records `desc`: the filter, or its score
+        twin with lambduh (sampler='pmala_sorted'), under the family's key (seed ^ its salt)."""
+        getattr(self.ctx, self._filter_call)(self.model, self.dtype, self.N, self.C, desc.data_ptr(), *before_key,
+                                             *self._filter_score, *self._filter_key, self._stream(stream), traced=traced)
+
     def launch_cpm(self, stream=None, traced=False, init=False):
         """sampler='pmmh' with correlation: one sorted, correlated filter per chain on theta_prop_dev (pfg_cpm_device): U' = rho U +
         sqrt(1 - rho^2) eps goes to the chain's other buffer, the estimate on U' to out_dev[:, 4].  init: rho = 0.
         sampler='pmala_sorted': the same filter with the score beside it, out_dev[:, :H] (pfg_cpm_score_device, lambduh)."""
-        rho, key = 0.0 if init else self.correlation, (self.seed ^ 0x43504D4D, self.chain_offset, self.step_ctr.data_ptr(),
-                                                       self._stream(stream))
-        if self.sampler == "pmala_sorted":
-            return self.ctx.cpm_score_device(self.model, self.dtype, self.N, self.C, self.cpm_desc_dev.data_ptr(), rho,
-                                             self.lambduh, *key, traced=traced)
-        self.ctx.cpm_device(self.model, self.dtype, self.N, self.C, self.cpm_desc_dev.data_ptr(), rho, *key, traced=traced)
+        self._launch_chain_filter(self.cpm_desc_dev, stream, traced, 0.0 if init else self.correlation)
 
     def launch_sqmc(self, stream=None, traced=False):
         """sampler='pmmh' with sqmc: one sequential quasi-Monte Carlo filter per chain on theta_prop_dev (pfg_sqmc_device), the
         estimate to out_dev[:, 4].  The init pass is the same launch at counter 0.
         sampler='pmala_sorted': the same filter with the score beside it, out_dev[:, :H] (pfg_sqmc_score_device, lambduh)."""
-        key = (self.seed ^ 0x53514D43, self.chain_offset, self.step_ctr.data_ptr(), self._stream(stream))
-        if self.sampler == "pmala_sorted":
-            return self.ctx.sqmc_score_device(self.model, self.dtype, self.N, self.C, self.sqmc_desc_dev.data_ptr(), self.lambduh,
-                                              *key, traced=traced)
-        self.ctx.sqmc_device(self.model, self.dtype, self.N, self.C, self.sqmc_desc_dev.data_ptr(), *key, traced=traced)
+        self._launch_chain_filter(self.sqmc_desc_dev, stream, traced)
 
-    def _sqmc_alloc(self, prior_mean, prior_var):
-        """The pfg_sqmc_problem records (static: the step replays in hipGraphs).  An SQMC chain carries nothing beyond PMMH's
-        state."""
-        d, _ = self._chain_filter_records(_capi.SQMC_PROBLEM_DTYPE, self.theta_prop_dev, prior_mean, prior_var)
-        self._sqmc_desc = d
-        self.sqmc_desc_dev = self._upload_records(d)
+    def launch_csmc(self, stream=None, traced=False, init=False):
+        """sampler='pgibbs': one conditional SMC sweep with ancestor sampling per chain (pfg_csmc_device): path_dev is replaced,
+        the new paths' statistics land in out_dev.  init: the descriptors with has_ref = 0, an unconditional sweep."""
+        self._launch_chain_filter(self._csmc_init_desc_dev if init else self.csmc_desc_dev, stream, traced)
 
     def _alloc_per_chain(self, make, kept, per_chain, sb, copies=1):
         """`copies` * C slabs of sb bytes in one uint8 tensor (make: torch.zeros | torch.empty); a refusal names what is kept,
@@ -1257,11 +834,11 @@ class ChainEnsemble(object):
             raise MemoryError("{0}: {1}C * {2} = {1}{3} * {4} = {5} bytes ({6:.2f} GB) could not be allocated ({7})".format(
                 kept, times, per_chain, self.C, sb, n, n / 1e9, str(e).splitlines()[0])) from e
 
-    def _chain_filter_records(self, dtype, theta, prior_mean, prior_var):
-        """(d, idx): C records of a chain-filter descriptor (pfg_csmc_problem | pfg_cpm_problem | pfg_sqmc_problem) with what all
+    def _chain_filter_records(self, theta, prior_mean, prior_var):
+        """(d, idx): C records of the family's descriptor (pfg_csmc_problem | pfg_cpm_problem | pfg_sqmc_problem) with what all
         have filled in -- chain b reads row b of `theta` and the whole series, writes row b of out_dev -- and the chain indices as uint64."""
         idx = np.arange(self.C, dtype=np.uint64)
-        d = np.zeros(self.C, dtype=dtype)
+        d = np.zeros(self.C, dtype=self._family.dtype)
         d["theta"] = theta.data_ptr() + idx * np.uint64(8 * _capi.MAX_THETA)
         d["y"] = self.y_dev.data_ptr()
         d["out"] = self.out_dev.data_ptr() + idx * np.uint64(8 * _capi.OUT_DOUBLES)
@@ -1271,10 +848,16 @@ class ChainEnsemble(object):
     def _upload_records(self, d):
         return torch.from_numpy(d.view(np.uint8).reshape(len(d), -1)).to(self.device)
 
+    def _sqmc_alloc(self, prior_mean, prior_var):
+        """The pfg_sqmc_problem records (static: the step replays in hipGraphs).  An SQMC chain carries nothing beyond PMMH's
+        state."""
+        self._sqmc_desc, _ = self._chain_filter_records(self.theta_prop_dev, prior_mean, prior_var)
+        self.sqmc_desc_dev = self._upload_records(self._sqmc_desc)
+
     def _cpm_alloc(self, prior_mean, prior_var):
         """The state of a correlated chain beyond PMMH's: two buffers of normals per chain (aux_dev, [2][C] slabs of
         pfg_cpm_aux_bytes(T, N) bytes), the selector which_dev, the acceptance count seen_dev the selector was last moved at, and
-        the pfg_cpm_problem records (static: the step replays in hipGraphs).  _mh_init fills the first buffer."""
+        the pfg_cpm_problem records (static: the step replays in hipGraphs).  The init pass fills the first buffer."""
         C, T, N, dev = self.C, self.T, self.N, self.device
         sb = self._aux_bytes = _capi.cpm_aux_bytes(T, N)
         self.aux_dev = self._alloc_per_chain(torch.zeros, "correlation keeps two buffers of normals per chain in HBM",
@@ -1282,7 +865,7 @@ class ChainEnsemble(object):
         self.which_dev = torch.zeros(C, dtype=torch.int32, device=dev)
         self.which_dev.fill_(1)          # the init pass writes buffer 0 and commits: every chain then reads buffer 0
         self.seen_dev = torch.zeros(C, dtype=torch.int64, device=dev)        # (the library's uint64 counts)
-        d, idx = self._chain_filter_records(_capi.CPM_PROBLEM_DTYPE, self.theta_prop_dev, prior_mean, prior_var)
+        d, idx = self._chain_filter_records(self.theta_prop_dev, prior_mean, prior_var)
         d["u0"] = self.aux_dev.data_ptr() + idx * np.uint64(sb)
         d["u1"] = self.aux_dev.data_ptr() + (idx + np.uint64(C)) * np.uint64(sb)
         d["which"] = self.which_dev.data_ptr() + idx * np.uint64(4)
@@ -1296,30 +879,21 @@ class ChainEnsemble(object):
     def aux(self):
         """sampler='pmmh' with correlation: [C, T+1, N+1] the normals each chain holds, those its estimate loglik() was
         computed from."""
-        if self.correlation is None:
-            raise ValueError("aux() belongs to sampler='pmmh' with correlation set (and sampler='pmala_sorted' with it)")
+        self._need("aux")
         rows = torch.arange(self.C, device=self.device)
         cur = self._aux_view()[self.which_dev.long() & 1, rows]
         return cur[:, :(self.T + 1) * (self.N + 1)].reshape(self.C, self.T + 1, self.N + 1).cpu().numpy()
 
-    def launch_csmc(self, stream=None, traced=False, init=False):
-        """sampler='pgibbs': one conditional SMC sweep with ancestor sampling per chain (pfg_csmc_device): path_dev is replaced,
-        the new paths' statistics land in out_dev.  init: the descriptors with has_ref = 0, an unconditional sweep."""
-        desc = self._csmc_init_desc_dev if init else self.csmc_desc_dev
-        self.ctx.csmc_device(self.model, self.dtype, self.N, self.C, desc.data_ptr(), self.seed ^ 0x43534D43, self.chain_offset,
-                             self.step_ctr.data_ptr(), self._stream(stream), traced=traced)
-
-    def _pgibbs_init(self, prior_mean, prior_var):
-        """The state and the init pass of sampler='pgibbs', the constructor's last act: path_dev [C, T], the counters, the
-        scratch and the pfg_csmc_problem records (static: the step replays in hipGraphs), then one sweep with has_ref = 0 at
-        the initial parameters for the first paths.  It consumes counter value 0: the counter is 1 afterwards."""
+    def _csmc_alloc(self, prior_mean, prior_var):
+        """The state of sampler='pgibbs': path_dev [C, T], the counters, the scratch and the pfg_csmc_problem records (static:
+        the step replays in hipGraphs), with a copy at has_ref = 0 for the init pass."""
         C, T, N, dev = self.C, self.T, self.N, self.device
         self.path_dev = torch.zeros((C, T), dtype=torch.float64, device=dev)
         self.ndeg_dev = torch.zeros(C, dtype=torch.int64, device=dev)       # (the library's uint64 counts)
         sb = _capi.csmc_scratch_bytes(T, N)
         self.csmc_scratch_dev = self._alloc_per_chain(torch.empty, "sampler='pgibbs' keeps every chain's particle history in HBM",
                                                       "pfg_csmc_scratch_bytes(T, N)", sb)
-        d, idx = self._chain_filter_records(_capi.CSMC_PROBLEM_DTYPE, self.theta_dev, prior_mean, prior_var)
+        d, idx = self._chain_filter_records(self.theta_dev, prior_mean, prior_var)
         d["path"] = self.path_dev.data_ptr() + idx * np.uint64(8 * T)
         d["scratch"] = self.csmc_scratch_dev.data_ptr() + idx * np.uint64(sb)
         d["n_degenerate"] = self.ndeg_dev.data_ptr() + idx * np.uint64(8)
@@ -1329,9 +903,11 @@ class ChainEnsemble(object):
         d0 = d.copy()
         d0["has_ref"] = 0
         self._csmc_init_desc_dev = self._upload_records(d0)
-        self.launch_csmc(init=True)
-        self.step_ctr.fill_(1)
-        self.synchronize()
+
+    def _pgibbs_init(self, s):
+        """The init pass of sampler='pgibbs', the constructor's last act: one sweep with has_ref = 0 at the initial parameters
+        for the first paths."""
+        self._init_launch()
         bad = np.flatnonzero(self.ndeg_dev.cpu().numpy() != 0)
         if bad.size:
             raise ValueError("pgibbs: the particle weights of chain {0} degenerated in the init pass (no first path)".format(
@@ -1344,7 +920,7 @@ class ChainEnsemble(object):
         weights = self.weights_dev.data_ptr() if self.weights_dev is not None else 0
         # sampler='sgld_cv': the twins' records are sampled again under the chains' key, so they hold the chains' windows
         halves = [(self.desc_dev.data_ptr(), self.seq_len_dev.data_ptr() if self._multi else 0)]
-        if self._cv:
+        if self._twins:
             halves.append((self.desc_dev.data_ptr() + self._nd * self.desc_dev.shape[1],
                            self.twin_seq_len_dev.data_ptr() if self._multi else 0))
         for desc, seq_len in halves:
@@ -1363,30 +939,21 @@ class ChainEnsemble(object):
         """Multi-window path: the C * W window records -> the C records the update reads (pfg_reduce_windows_device)."""
         self.ctx.reduce_windows_device(self.C, self.K_eff, self.M, self.win_out_dev.data_ptr(), self.seq_len_dev.data_ptr(),
                                        self._rescale, float(self.T), self.out_dev.data_ptr(), self._stream(stream))
-        if self._cv:        # the twins' window records -> out_centre_dev
+        if self._twins:        # the twins' window records -> out_centre_dev
             self.ctx.reduce_windows_device(self.C, self.K_eff, self.M, self.twin_out_dev.data_ptr(),
                                            self.twin_seq_len_dev.data_ptr(), self._rescale, float(self.T),
                                            self.out_centre_dev.data_ptr(), self._stream(stream))
 
     def _enqueue_step(self):
-        """One step: the windows if there are any to draw, the proposal if the sampler has one, the filter, the reduction
-        on the multi-window path, the update."""
-        # who draws them: nobody when they are static ('pmmh' | 'pmala' read the whole data set on either path)
-        if self._multi:
-            draws = "device" if self._draws else None
-        else:
-            draws = None if self._mh else self.window_sampling
-        if draws == "device":
+        """One step: the windows if there are any to draw, then `_step`: the proposal if the sampler has one, the filter,
+        the reduction on the multi-window path, the update."""
+        if self._window_draws == "device":
             self.launch_windows()
-        elif draws == "host" and self.steps_done > 0 and self._set_windows():
+        elif self._window_draws == "host" and self.steps_done > 0 and self._set_windows():
             self.desc_dev.copy_(torch.from_numpy(self._desc.view(np.uint8).reshape(self._nl, -1)),
                                 non_blocking=True)
-        if self._mh:
-            self.launch_propose()
-        self.launch_pf()
-        if self._multi:
-            self.launch_reduce()
-        self.launch_update()
+        for launch in self._step:
+            launch(self)
 
     def step(self, num_steps=1):
         """num_steps x (the sampler's step + project_parameters) for every chain.  Asynchronous."""
@@ -1454,76 +1021,49 @@ class ChainEnsemble(object):
                      step_ctr=int(self.step_ctr.item()), steps_done=int(self.steps_done),
                      seed=self.seed, chain_offset=self.chain_offset,
                      model=self.model, N=self.N, C=self.C, ess_threshold=self.ess_threshold)
-        if self.sampler == "pgibbs":    # (the only checkpoints that name their sampler and T: load_state_dict)
-            state.update(sampler="pgibbs", T=self.T)
-        if self.sampler == "pmala_sorted":      # (named, so that no other sampler takes its checkpoint; the smoother's lambduh)
-            state.update(sampler="pmala_sorted", lambduh=self.lambduh)
+        # what names the sampler and the filter family (load_state_dict), then what a chain carries
+        state.update((key, getattr(self, key)) for key in self._rule.names)
+        state.update((key, getattr(self, attr)) for key, attr in self._family.checkpoint)
         state.update((key, t.cpu().numpy()) for key, t in self._chain_state()[0])
-        if self.correlation is not None:    # the current buffer only (the other one is a step's scratch), and what it belongs to
-            state.update(aux=self.aux(), correlation=self.correlation, T=self.T)
-        if self.sqmc:       # (no state of its own: the setting alone, so that a plain PMMH checkpoint is what it was)
-            state.update(sqmc=True)
+        if self._family.aux:        # the current buffer only (the other one is a step's scratch)
+            state["aux"] = self.aux()
         return state
 
     def _chain_state(self):
-        """(carried, scratch).  carried: what a chain of this sampler carries beyond theta, the momentum and the counter, as
-        ordered (checkpoint key, tensor) pairs -- the estimates a 'pmmh' | 'pmala' chain was accepted with and its
-        acceptance count, the buffer selector of a correlated 'pmmh' chain and the count it was last moved at (its normals
-        travel as 'aux'), the path of a 'pgibbs' chain and how often its sweep degenerated, the moment of an 'adagrad' chain,
-        the centre, its gradient and the counter of the centring launches of an 'sgld_cv' chain.  state_dict and load_state_dict
-        follow it.  scratch: what a step overwrites besides; _graph restores both after its eager step."""
-        carried, scratch = [], [self.desc_dev]
-        if self._mh:
-            grad = [("grad", self.grad_cur_dev)] if self._pmala else []
-            carried = [("ll", self.ll_dev)] + grad + [("n_accept", self.accept_dev)]
-            scratch += [self.theta_prop_dev, self.valid_dev]
-        if self.correlation is not None:
-            # the selector names the chain's current buffer and a step writes the other one only, so restoring the selector
-            # restores the buffer: _graph copies these two, state_dict and load_state_dict move the current buffer as 'aux'
-            carried += [("which", self.which_dev), ("seen", self.seen_dev)]
-        if self.sampler == "pgibbs":
-            carried = [("path", self.path_dev), ("n_degenerate", self.ndeg_dev)]
-        if self.sampler == "adagrad":
-            carried = [("moment", self.moment_dev)]
-        if self._cv:    # (a step moves none of the three; they travel with the checkpoint)
-            carried = [("centre", self.theta_centre_dev), ("centre_gradient", self.centre_grad_dev),
-                       ("centre_ctr", self.centre_ctr_dev)]
+        """(carried, scratch).  carried: what a chain carries beyond theta, the momentum and the counter, as ordered
+        (checkpoint key, tensor) pairs: the sampler's record's, then the filter family's (ensemble_settings: `carries`).
+        state_dict and load_state_dict follow it.  scratch: what a step overwrites besides; _graph restores both after its
+        eager step."""
+        carried = [(key, getattr(self, attr)) for key, attr in self._carries]
+        scratch = [self.desc_dev] + ([self.theta_prop_dev, self.valid_dev] if self._rule.propose is not None else [])
         return carried, scratch
 
     def load_state_dict(self, state):
-        # only 'pgibbs' checkpoints name their sampler and T: a 'pgibbs' ensemble wants both, and no other sampler takes one
-        # (it would drop the path silently)
-        keys = ("sampler", "T") if self.sampler == "pgibbs" else ("sampler", "lambduh") if self.sampler == "pmala_sorted" else \
-            ("sampler",) if state.get("sampler", None) is not None else ()
-        for key in keys:
-            if state.get(key, None) != getattr(self, key):
-                raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(
-                    key, state.get(key, None), getattr(self, key)))
+        # a checkpoint that names its sampler is taken by that sampler alone ('pgibbs': another would drop the path silently),
+        # and a sampler that names itself wants its names; correlation and sqmc are compared whoever wrote the checkpoint
+        # (either side may be a plain PMMH chain: None, False), ess_threshold likewise (checkpoints from before the option: None)
+        def same(key, got):
+            if got != getattr(self, key):
+                raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(key, got, getattr(self, key)))
+        for key in self._rule.names or (("sampler",) if state.get("sampler", None) is not None else ()):
+            same(key, state.get(key, None))
         for key in ("model", "N", "C", "seed", "chain_offset"):
-            if state[key] != getattr(self, key):
-                raise ValueError("checkpoint {0} = {1} does not match the ensemble ({2})".format(
-                    key, state[key], getattr(self, key)))
-        if state.get("correlation", None) != self.correlation:          # (either side may be a plain PMMH chain: None)
-            raise ValueError("checkpoint correlation = {0} does not match the ensemble ({1})".format(
-                state.get("correlation", None), self.correlation))
-        if bool(state.get("sqmc", False)) != self.sqmc:
-            raise ValueError("checkpoint sqmc = {0} does not match the ensemble ({1})".format(
-                bool(state.get("sqmc", False)), self.sqmc))
-        if self.correlation is not None:
+            same(key, state[key])
+        same("correlation", state.get("correlation", None))
+        same("sqmc", bool(state.get("sqmc", False)))
+        if self._family.aux:
             shape = (self.C, self.T + 1, self.N + 1)
             if state.get("T", None) != self.T or tuple(np.shape(state["aux"])) != shape:
                 raise ValueError("checkpoint T = {0}, aux {1} does not match the ensemble (T = {2}, aux {3})".format(
                     state.get("T", None), tuple(np.shape(state["aux"])), self.T, shape))
-        if state.get("ess_threshold", None) != self.ess_threshold:      # (checkpoints from before the option: None)
-            raise ValueError("checkpoint ess_threshold = {0} does not match the ensemble ({1})".format(
-                state.get("ess_threshold", None), self.ess_threshold))
+        same("ess_threshold", state.get("ess_threshold", None))
         self.theta_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["theta"])))
         self.momentum_dev.copy_(torch.from_numpy(np.ascontiguousarray(state["momentum"])))
         self.step_ctr.fill_(int(state["step_ctr"]))
         for key, t in self._chain_state()[0]:
             dtype = {torch.int64: np.int64, torch.int32: np.int32}.get(t.dtype, np.float64)
             t.copy_(torch.from_numpy(np.ascontiguousarray(state[key], dtype=dtype)))
-        if self.correlation is not None:    # into the buffer each chain's selector (just loaded) names
+        if self._family.aux:        # into the buffer each chain's selector (just loaded) names
             flat = torch.from_numpy(np.ascontiguousarray(state["aux"], dtype=np.float64).reshape(self.C, -1)).to(self.device)
             view, rows = self._aux_view(), torch.arange(self.C, device=self.device)
             view[self.which_dev.long() & 1, rows, :flat.shape[1]] = flat
@@ -1568,55 +1108,41 @@ class ChainEnsemble(object):
         the latest FFBS paths (PFG_STAT_GIBBS: sum_{t>=1} x_{t-1}^2, x_t x_{t-1}, x_t^2; sum_t x_t^2, y_t x_t, y_t^2;
         T) and None: a sampled path has no log-likelihood estimate.  Multi-window path: the REDUCED records
         (pfg_reduce_windows_device); window_statistics() has the windows'."""
-        out = self.out_dev.cpu().numpy()
-        if self.sampler in ("gibbs", "pgibbs"):     # (pgibbs: the statistics of the latest conditional SMC paths)
-            return out[:, :7], None
-        if self.sampler == "pmmh":      # no score is computed: (None, the log-likelihood estimates at the latest PROPOSALS)
-            return None, out[:, 4]
-        return out[:, :_capi.STAT_DIM[self.model]], out[:, 4]       # (sampler='pmala': at the latest PROPOSALS)
+        return self._rule.statistics(self.out_dev.cpu().numpy(), _capi.STAT_DIM[self.model])
 
     def loglik(self):
         """sampler='pmmh' | 'pmala': [C] log-likelihood estimates the chains hold, each the one its current state was
         accepted with."""
-        self._need_pmmh("loglik")
+        self._need("loglik")
         return self.ll_dev.cpu().numpy()
 
     def score(self):
         """sampler='pmala': [C, h] score estimates the chains hold (score-column order, as last_gradient_statistics), each
         the one its current state was accepted with and its next proposal drifts along."""
-        if not self._pmala:
-            raise ValueError("score() belongs to sampler='pmala', this ensemble runs '{0}'".format(self.sampler))
+        self._need("score")
         return self.grad_cur_dev[:, :_capi.STAT_DIM[self.model]].cpu().numpy()
 
     def path(self):
         """sampler='pgibbs': [C, T] latent paths the chains hold."""
-        self._need_pgibbs("path")
+        self._need("path")
         return self.path_dev.cpu().numpy()
 
     def suff_stats(self):
         """sampler='pgibbs': [C, 7] statistics of the latest paths, as last_gradient_statistics()[0] (SVM: the three transition
         sums, sum_t y_t^2 exp(-x_t), 0, 0, T)."""
-        self._need_pgibbs("suff_stats")
+        self._need("suff_stats")
         return self.out_dev[:, :7].cpu().numpy()
 
     def n_degenerate(self):
         """sampler='pgibbs': [C] sweeps in which a chain kept its path because its weights degenerated."""
-        self._need_pgibbs("n_degenerate")
+        self._need("n_degenerate")
         return self.ndeg_dev.cpu().numpy()
-
-    def _need_pgibbs(self, what):
-        if self.sampler != "pgibbs":
-            raise ValueError("{0}() belongs to sampler='pgibbs', this ensemble runs '{1}'".format(what, self.sampler))
 
     def acceptance_rate(self):
         """sampler='pmmh' | 'pmala': [C] accepted proposals / steps done (nan before the first step)."""
-        self._need_pmmh("acceptance_rate")
+        self._need("acceptance_rate")
         n = self.accept_dev.cpu().numpy().astype(np.float64)
         return n / self.steps_done if self.steps_done else np.full(self.C, np.nan)
-
-    def _need_pmmh(self, what):
-        if not self._mh:
-            raise ValueError("{0}() belongs to sampler='pmmh' (and 'pmala'), this ensemble runs '{1}'".format(what, self.sampler))
 
     def window_statistics(self):
         """Multi-window path: the latest launch's [C, W, 8] window records and [C, W] sequence lengths."""

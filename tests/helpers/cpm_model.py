@@ -27,7 +27,7 @@ import pmmh_model as pm
 from chain_filter_model import EDGE_REL, LD, PM, PV, SEED, THETA, Key, case_theta_y, consts, logw, search  # noqa: F401
 
 TAG_CPM = 0x43500000
-CPM_SEED_XOR = 0x43504D4D           # ChainEnsemble keys the filter's eps with seed ^ this (ensemble.py, launch_cpm)
+CPM_SEED_XOR = 0x43504D4D           # ChainEnsemble keys the filter's eps with seed ^ this (ensemble_settings.py, FILTERS["cpm"].salt)
 U_MAX = 1.0 - 2.0 ** -53
 
 _erfc = np.vectorize(math.erfc, otypes=[np.float64])

@@ -24,7 +24,7 @@ import keyed_draws as kd
 from chain_filter_model import EDGE_REL, LD, PM, PV, SEED, THETA, Key, case_theta_y, consts, logw, search  # noqa: F401
 
 TAG_PARTICLE, TAG_ANCESTOR, TAG_FINAL = 0x43530000, 0x43531000, 0x43532000
-CSMC_SEED_XOR = 0x43534D43          # ChainEnsemble keys the sweep with seed ^ this (ensemble.py, launch_csmc)
+CSMC_SEED_XOR = 0x43534D43          # ChainEnsemble keys the sweep with seed ^ this (ensemble_settings.py, FILTERS["csmc"].salt)
 EDGE_SHARE = 0.01                   # a recorded index may be the neighbour on a CDF edge (EDGE_REL): at most this share of a case
 
 

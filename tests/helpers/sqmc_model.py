@@ -29,7 +29,7 @@ import pmmh_model as pm
 from chain_filter_model import EDGE_REL, LD, PM, PV, SEED, THETA, Key, case_theta_y, consts, logw, search  # noqa: F401
 
 TAG_SQMC = 0x53510000
-SQMC_SEED_XOR = 0x53514D43          # ChainEnsemble keys the filter's shifts with seed ^ this (ensemble.py, launch_sqmc)
+SQMC_SEED_XOR = 0x53514D43          # ChainEnsemble keys the filter's shifts with seed ^ this (ensemble_settings.py, FILTERS["sqmc"].salt)
 U32 = np.uint64(0xFFFFFFFF)
 
 

@@ -2,7 +2,11 @@
 the descriptor records after construction and after each of three steps (pointers as (buffer, byte offset)), the resident
 window tables, the resolved sizes and flags, and the arguments of every library call of the steps.  Recorded by
 tests/golden/make_ensemble_golden.py before the host side was restructured; equality everywhere -- these are integers,
-host-computed doubles and Philox-derived integers."""
+host-computed doubles and Philox-derived integers.
+
+tests/golden/ensemble_samplers.npz does the same for the samplers and chain filters that came later (SAMPLER_CASES), with
+the constructor's library calls, the chain-filter records, the checkpoint's keys, its round trip and the checkpoints a
+sampler refuses; recorded before the samplers and filters were stated in two tables."""
 import json
 import os
 import sys
@@ -16,10 +20,19 @@ import make_ensemble_golden as maker  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
+def _load(path):
+    z = np.load(path, allow_pickle=False)
+    return z, json.loads(str(z["meta"]))
+
+
 @pytest.fixture(scope="module")
 def golden():
-    z = np.load(maker.FIXTURE, allow_pickle=False)
-    return z, json.loads(str(z["meta"]))
+    return _load(maker.FIXTURE)
+
+
+@pytest.fixture(scope="module")
+def sampler_golden():
+    return _load(maker.SAMPLER_FIXTURE)
 
 
 def test_fixture_covers_the_cases(golden):
@@ -28,11 +41,16 @@ def test_fixture_covers_the_cases(golden):
     assert meta["columns"] == maker._columns() and meta["buffers"] == list(maker.BUFFERS)
 
 
-@pytest.mark.parametrize("case", maker.CASES, ids=[c[0] for c in maker.CASES])
-def test_device_sees_the_recorded_inputs(golden, case):
-    name = case[0]
+def test_sampler_fixture_covers_the_cases(sampler_golden):
+    from sgmcmc_ssm_amd import _capi
+    _, meta = sampler_golden
+    assert sorted(meta["cases"]) == sorted(c[0] for c in maker.SAMPLER_CASES)
+    assert meta["columns"] == maker._columns() and meta["buffers"] == list(maker.SAMPLER_BUFFERS)
+    assert meta["record_columns"] == {attr.lstrip("_"): maker._columns(getattr(_capi, dtype)) for attr, dtype in maker.RECORDS}
+
+
+def _compare(golden, name, arrays, info):
     z, meta = golden
-    arrays, info = maker.record_case(case)
     want = dict(meta["cases"][name])
     assert sorted(arrays) == sorted(k.split("/", 1)[1] for k in z.files if k.startswith(name + "/"))
     desc = z[name + "/desc"]
@@ -48,3 +66,15 @@ def test_device_sees_the_recorded_inputs(golden, case):
     assert len(calls) == len(want_calls)
     for got, ref in zip(calls, want_calls):
         assert got == ref
+
+
+@pytest.mark.parametrize("case", maker.CASES, ids=[c[0] for c in maker.CASES])
+def test_device_sees_the_recorded_inputs(golden, case):
+    _compare(golden, case[0], *maker.record_case(case))
+
+
+@pytest.mark.parametrize("case", maker.SAMPLER_CASES, ids=[c[0] for c in maker.SAMPLER_CASES])
+def test_device_sees_the_recorded_sampler_inputs(sampler_golden, case):
+    arrays, info = maker.record_sampler_case(case)
+    assert info["round_trip"] is True
+    _compare(sampler_golden, case[0], arrays, info)
