@@ -850,6 +850,45 @@ int pfg_smc_accept_device(pfg_ctx *ctx, int model, int B, double *theta, const d
                           const double *q0_mean, const double *q0_sd, const double *phi, double *log_alpha, uint64_t seed,
                           uint64_t chain_offset, uint64_t *step_ctr, void *hip_stream);
 
+/* EXTENSION (not in the reference): SMC^2 over B resident PMMH chains (Chopin, Jacob and Papaspiliopoulos 2013; Fulop and Li
+ * 2013) -- the sequential form of the population above.  The chains take the observations chunk by chunk; every chain keeps
+ * its filter's particle system as one row of row_doubles = N (NS + 1) doubles, x [N][NS] then logw [N] (what final_x /
+ * final_logw of a pfg_dev_problem write and init_x / init_logw read), a running log-weight and the sum of its chunks'
+ * estimates.  A stage is: the warm-started launch on the chunk, pfg_seq_reweight_device, and where that resampled
+ * pfg_seq_gather_device, pfg_smc_scale_device and PMMH steps on the prefix (pfg_pmmh_propose_device, a launch from scratch,
+ * pfg_pmmh_accept_device, pfg_seq_adopt_device).  Everything is f64 and a pure function of the inputs and (seed, stage); all
+ * arrays are DEVICE memory.
+ *
+ * pfg_seq_reweight_device: one workgroup of 1024 threads over logw [B] (in and out) and incr[b * incr_stride] (the chunk's
+ * estimates: column 4 of the records with stride PFG_OUT_DOUBLES, or any array with stride 1).  v_b = (logw_b - max logw) +
+ * incr_b, a logw or incr of -inf being a zero weight; record [PFG_SEQ_RECORD_DOUBLES] = {the evidence increment v_max +
+ * log(sum e^(v_b - v_max) / sum e^(logw_b - max logw)), ESS = (sum e^(v - v_max))^2 / sum e^(2 (v - v_max)), resampled (0 | 1),
+ * the uniform u, v_max, W = sum e^(v - v_max), max logw, 0}.  ESS < ess_target B: parent[r] the smallest j with cdf[j] >
+ * ((r + u) / B) W, B - 1 when there is none (cdf, pfg_smc_scratch_bytes(B) bytes of scratch: the running sum of e^(v - v_max) in
+ * chain order; u keyed as pfg_smc_temper_device keys its own) and logw = 0.  Otherwise parent = identity and logw = v - v_max.
+ * *status = 0, or 1: no v is finite, 2: some logw or incr is NaN or +inf, 4: B is not in 2 .. 2^20 -- and then NOTHING but
+ * *status is stored (the call itself returns PFG_OK: the status word is the population's channel).  PFG_ERR_INVALID: a NULL
+ * argument, incr_stride < 0, ess_target outside (0, 1] (1 resamples whenever the weights are not all equal).
+ *
+ * pfg_seq_gather_device: row b of dst = row parent[b] of src (src != dst, [B][row_doubles] each), one workgroup per row, 16
+ * bytes per lane and access; theta[b] = theta[parent[b]] and ll[b] = ll[parent[b]] through theta_tmp [B][PFG_MAX_THETA] and
+ * ll_tmp [B] as pfg_smc_gather_device moves them.  A parent outside [0, B) leaves the chain as it is (its own row is copied).
+ *
+ * pfg_seq_adopt_device: one workgroup per chain, after pfg_pmmh_accept_device: if (n_accept[b] != seen[b]) { row b of cur =
+ * row b of fresh; seen[b] = n_accept[b]; } -- pfg_cpm_commit_device's rule with a copy in place of the selector flip; every
+ * other row of cur is untouched.
+ *
+ * gather and adopt: PFG_ERR_INVALID for B outside 2 .. 2^20, row_doubles < 1 or B row_doubles > 2^40, a NULL argument, or the
+ * two row arrays being the same. */
+#define PFG_SEQ_RECORD_DOUBLES 8
+int pfg_seq_reweight_device(pfg_ctx *ctx, int B, double *logw, const double *incr, int64_t incr_stride, double ess_target,
+                            uint64_t seed, uint64_t stage, double *record, int32_t *status, int32_t *parent, void *scratch,
+                            void *hip_stream);
+int pfg_seq_gather_device(pfg_ctx *ctx, int B, const int32_t *parent, int64_t row_doubles, const double *src, double *dst,
+                          double *theta, double *theta_tmp, double *ll, double *ll_tmp, void *hip_stream);
+int pfg_seq_adopt_device(pfg_ctx *ctx, int B, const uint64_t *n_accept, uint64_t *seen, int64_t row_doubles, double *cur,
+                         const double *fresh, void *hip_stream);
+
 /* Inverse-multiquadric kernel Stein discrepancy of K points x[K][d] with score estimates
  * g[K][d] (HOST pointers, d <= 8): sqrt(sum_{i,j} k0(x_i,x_j)) / K for
  * k(x,y) = (c^2 + |x-y|^2)^(-beta) -- IMQ_KSD of sgmcmc_ssm/trace_metric_functions.py:20-81

@@ -8,7 +8,8 @@ of resident chains (csrc/pfg_chains.hip), the conditional SMC sweep of particle 
 (csrc/pfg_csmc.hip), the sorted, correlated filter of correlated pseudo-marginal PMMH (csrc/pfg_cpm.hip), the sequential
 quasi-Monte Carlo filter of SQMC PMMH (csrc/pfg_sqmc.hip) -- those four share the chain key, and the three filters their device
 and host pieces (the two sorted ones their sort), through csrc/pfg_chain_filter.hpp --, the population
-kernels of density-tempered SMC over PMMH chains (csrc/pfg_smc.hip: the workgroup reductions of the same header), their window
+kernels of density-tempered SMC over PMMH chains (csrc/pfg_smc.hip: the workgroup reductions of the same header) and of SMC^2
+over them (csrc/pfg_seq.hip: reweight, row gather, adopt; its argument checks in csrc/pfg_seq_checks.hpp), their window
 samplers and window reduction (csrc/pfg_windows.hip), the elementwise-statistics pass (csrc/pfg_elementwise.hip) and the IMQ KSD
 (csrc/pfg_ksd.hip).  The units are compiled to objects in parallel and linked into one shared library."""
 import os
@@ -24,10 +25,10 @@ INCLUDE = os.path.join(REPO, "include")
 LIB_PATH = os.path.join(CSRC, "libpfgrad.so")
 _UNITS = ["svm_prior", "garch_prior", "garch_optimal", "lgssm_prior", "lgssm_optimal"]
 SOURCES = ["pfgrad.hip", "pfg_plan.hip", "pfg_legacy_rng.hip"] + ["pfg_inst_{0}_{1}.hip".format(u, r) for u in _UNITS for r in ("device", "replay")] + \
-          ["pfg_kalman.hip", "pfg_ffbs.hip", "pfg_chains.hip", "pfg_csmc.hip", "pfg_cpm.hip", "pfg_sqmc.hip", "pfg_smc.hip", "pfg_windows.hip", "pfg_elementwise.hip", "pfg_ksd.hip"]
+          ["pfg_kalman.hip", "pfg_ffbs.hip", "pfg_chains.hip", "pfg_csmc.hip", "pfg_cpm.hip", "pfg_sqmc.hip", "pfg_smc.hip", "pfg_seq.hip", "pfg_windows.hip", "pfg_elementwise.hip", "pfg_ksd.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("pfg_device.hpp", "pfg_math.hpp", "pfg_models.hpp", "pfg_reg_kernel.hpp", "pfg_reg_traits.hpp",
                                            "pfg_mem_kernel.hpp", "pfg_big_kernel.hpp", "pfg_grid_kernel.hpp", "pfg_grid_dev_kernel.hpp", "pfg_grid_cdf.hpp", "pfg_host.hpp",
-                                           "pfg_launch.hpp", "pfg_kalman.hpp", "pfg_chain_filter.hpp")] + \
+                                           "pfg_launch.hpp", "pfg_kalman.hpp", "pfg_chain_filter.hpp", "pfg_seq_checks.hpp")] + \
           [os.path.join(INCLUDE, "pfgrad.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 

@@ -162,6 +162,7 @@ SQMC_PROBLEM_DTYPE = np.dtype([
 SQMC_MAX_N = 1024                                   # and a power of two
 SMC_MIN_CHAINS, SMC_MAX_CHAINS = 2, 1 << 20        # a tempered population (pfg_smc_temper_device: one workgroup)
 SMC_RESULT_DOUBLES = 8                              # PFG_SMC_RESULT_DOUBLES
+SEQ_RECORD_DOUBLES = 8                              # PFG_SEQ_RECORD_DOUBLES
 # the theta slots a PMMH proposal moves (pfg_chains.hip: moves), as pfg_smc_scale_device's bit mask
 PMMH_MOVING_SLOTS = {"svm": 0b0111, "lgssm": 0b1101, "garch": 0b1111}
 
@@ -306,6 +307,9 @@ _ENTRY_POINTS = {
     "pfg_smc_scale_device": (_status, (_ctx, _int, _addr, _u32, _f64, _addr, _stream)),
     "pfg_smc_accept_device": (_status, (_ctx, _model, _int, _addr, _addr, _addr, _addr, _addr, _addr, _hyper, _addr, _addr,
                                         _addr, _addr, _u64, _u64, _addr, _stream)),
+    "pfg_seq_reweight_device": (_status, (_ctx, _int, _addr, _addr, _i64, _f64, _u64, _u64, _addr, _addr, _addr, _addr, _stream)),
+    "pfg_seq_gather_device": (_status, (_ctx, _int, _addr, _i64, _addr, _addr, _addr, _addr, _addr, _addr, _stream)),
+    "pfg_seq_adopt_device": (_status, (_ctx, _int, _addr, _addr, _i64, _addr, _addr, _stream)),
     "pfg_imq_ksd": (_status, (_ctx, _int, _int, _f64_p, _f64_p, _f64, _f64, _f64_p)),
     "pfg_legacy_streams": (_status, (_addr, _i32_p, _i32_p, _f64_p, _int, _int, _addr, _addr, _addr, _int)),
     "pfg_host_register": (_status, (_addr, _size)),
@@ -884,6 +888,23 @@ class Context:
         """pfg_smc_accept_device: pfg_pmmh_accept_device's step at the temperature *phi; bumps *step_ctr."""
         self._call("pfg_smc_accept_device", model, B, theta_ptr, theta_prop_ptr, valid_ptr, outs_ptr, ll_ptr, n_accept_ptr,
                    hyper, q0_mean_ptr, q0_sd_ptr, phi_ptr, log_alpha_ptr, seed, chain_offset, step_ctr_ptr, stream_ptr)
+
+    def seq_reweight_device(self, B, logw_ptr, incr_ptr, incr_stride, ess_target, seed, stage, record_ptr, status_ptr, parent_ptr,
+                            scratch_ptr, stream_ptr=0):
+        """pfg_seq_reweight_device: the chains' running weights times the chunk's estimates, the evidence increment, the ESS
+        and, below the target, the chains' parents (one workgroup)."""
+        self._call("pfg_seq_reweight_device", B, logw_ptr, incr_ptr, incr_stride, ess_target, seed, stage, record_ptr, status_ptr,
+                   parent_ptr, scratch_ptr, stream_ptr)
+
+    def seq_gather_device(self, B, parent_ptr, row_doubles, src_ptr, dst_ptr, theta_ptr, theta_tmp_ptr, ll_ptr, ll_tmp_ptr,
+                          stream_ptr=0):
+        """pfg_seq_gather_device: row b of dst = row parent[b] of src; theta and ll by parent through the two scratch arrays."""
+        self._call("pfg_seq_gather_device", B, parent_ptr, row_doubles, src_ptr, dst_ptr, theta_ptr, theta_tmp_ptr, ll_ptr,
+                   ll_tmp_ptr, stream_ptr)
+
+    def seq_adopt_device(self, B, n_accept_ptr, seen_ptr, row_doubles, cur_ptr, fresh_ptr, stream_ptr=0):
+        """pfg_seq_adopt_device: a chain whose acceptance count moved copies its row fresh -> cur and takes the count."""
+        self._call("pfg_seq_adopt_device", B, n_accept_ptr, seen_ptr, row_doubles, cur_ptr, fresh_ptr, stream_ptr)
 
     def scratch_bytes(self, model, dtype, rng, N):
         return self._call("pfg_scratch_bytes", model, dtype, rng, N)
